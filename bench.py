@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - simulated-hours per wall-second of the soilFluxes3D water time step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload C4|C3|C2] [--forcing F20|F60]
+    python bench.py --gpus N --steps K --warmup W [--workload C4|C3|C2] [--forcing F20|F60] [--dump-outputs DIR] [--full]
 
 A "step" is one simulated hour of the synthetic tilted-plane catchment of SURVEY.md 8d
 (default workload C4 = 512x512x20 nodes, forcing F20 = 20 mm of rain in hour 0): the hourly
@@ -13,17 +13,28 @@ are timed, with the hour's sinks already resident in HBM (sf3d_synchronize() upl
 before the clock starts); a barrier + device synchronize brackets the timed region and the MAX
 over ranks is reported.  `value` = K simulated hours / that time.
 
-The timed region is repeated (default: at least 3 times and until 1.5 s have been timed, at most 15; --reps fixes the count), each time from
-the initial state - rewound through the API, not rebuilt, so that the repetitions keep the GPU busy back to back - and the MEDIAN elapsed time
-is reported (all repetitions in `repeats_s`).  `headline_6h` repeats `value` with its elapsed time (kept for readers of earlier rounds' lines).
+A plain run times the K hours once (`ms_per_step` = their time / K).  With --full (or --reps R) the timed region is repeated (--full
+default: at least 3 times and until 1.5 s have been timed, at most 15; --reps fixes the count), each time from the initial state - rewound
+through the API, not rebuilt, so that the repetitions keep the GPU busy back to back - and the MEDIAN elapsed time is reported (all
+repetitions in `repeats_s`).  `headline_6h` repeats `value` with its elapsed time (kept for readers of earlier rounds' lines).
 `inclusive_value` puts the hourly sink/source upload (host -> HBM) inside the clock; it is never `value`.
 `python bench.py --gpus N` without a launcher spawns its own N ranks (fresh child processes, before anything touches the
 GPU) and relays rank 0's line.
 
-Extra objects on the JSON line: `roofline` (dominant kernel, algorithmic bytes per launch over
-its HIP-event duration measured on the solver's own stream) and `cpu_baseline` (rank 0, N=1:
-the unmodified reference built in oracle/_ref - or the oracle port when it cannot be loaded -
-on a bounded sample of the same workload, on the host cores of this box).
+A plain run does only what the headline needs: set-up, warm-up, the timed hours, the outputs (--dump-outputs) and the line.
+Everything else runs with --full only (N = 1; for N > 1 the first-contact checks and the episode check against the stored single-GPU
+values are part of the set-up and always run):
+  * `parity`: hour 0 of C2 F20 against the unmodified reference's stored vector, before anything is timed;
+  * `roofline`: dominant kernel, algorithmic bytes per launch over its HIP-event duration measured on the solver's own stream (HIP
+    events on every 8th computeStep of the first repetition; --time-all-kernels asks for them in a plain run too);
+  * `f60_hour0` and `legs`: C4 F60 hour 0, config 5 (water; + heat) and config 3 F60, timed after the C4 line;
+  * `cpu_baseline` (rank 0, N=1): the unmodified reference built in oracle/_ref - or the oracle port when it cannot be loaded - on a
+    bounded sample of the same workload, on the host cores of this box.
+
+--dump-outputs DIR writes what the timed path computed in its last timed hour, as float64 .npy files: per-node total potential, water
+content, degree of saturation and boundary water flow (+ temperature with --heat) over a fixed, seeded sample of at most
+DUMP_SAMPLE_NODES nodes (`node_index.npy` names them; every node when the grid is smaller), the accepted time steps of that hour and
+the water storage.  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -80,6 +91,43 @@ def log(*a):
 
 
 EPISODE_HOURS = 6           # "C4: F20 6 sim-h for the headline number"
+DUMP_SAMPLE_NODES = 1_300_000      # --dump-outputs: at most 6 per-node float64 files (index, 4 water fields, temperature) = 62.4 MB
+DUMP_SEED = 20261016
+
+
+def dump_outputs(sf, model, heat, dts, world, rank, owner, allgather, out_dir):
+    """--dump-outputs: the state the timed path left after its last timed hour (see the module docstring).  Collective for N > 1: every
+    rank contributes the sampled nodes it owns (`owner`: the owner map of a strip-cut model, None when every rank holds the whole one)."""
+    n = model.n
+    if n > DUMP_SAMPLE_NODES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_NODES, replace=False))
+    else:
+        idx = np.arange(n)
+    fields = {"total_potential": sf.total_potential, "water_content": sf.water_content, "degree_of_saturation": sf.degree_of_saturation,
+              "boundary_water_flow": sf.boundary_water_flow}
+    if heat is not None:
+        fields["temperature"] = sf.temperature
+    vals = {name: get(0, n)[idx] for name, get in fields.items()}
+    if owner is not None:
+        mine = owner[idx] == rank
+        parts = allgather({name: v[mine] for name, v in vals.items()} | {"_mask": mine})
+        if rank != 0:
+            return
+        for name in vals:
+            v = np.empty(idx.size)
+            for part in parts:
+                v[part["_mask"]] = part[name]
+            vals[name] = v
+    elif rank != 0:
+        return
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "node_index.npy", idx.astype(np.float64))
+    for name, v in vals.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(v, dtype=np.float64))
+    np.save(d / "dt_last_step.npy", np.asarray(dts, dtype=np.float64))
+    np.save(d / "water_storage.npy", np.asarray([sf.lib.sf3d_get_water_storage()], dtype=np.float64))
+    log(f"[bench] outputs of the last timed hour written to {d} ({idx.size} of {n} nodes)")
 
 
 def run_hours(sf, cm, model, forcing, hours, per_step=None, hour_starts=None, heat=None, per_hour=None, inclusive=None, rewind=None,
@@ -347,12 +395,17 @@ def main():
     ap.add_argument("--no-f60", action="store_true", help="skip the C4 F60 hour-0 leg (runoff regime, SURVEY 8d)")
     ap.add_argument("--no-kernel-timing", action="store_true", help="no HIP events (no roofline object): batches replay from hipGraphs")
     ap.add_argument("--time-all-kernels", action="store_true", help="HIP-event timing of every node kernel (adds ~5%% overhead)")
-    ap.add_argument("--reps", type=int, default=0, help="repetitions of the timed region, each from the initial state (rewound, not rebuilt); the median is reported; 0 = at least 3 and as many as it takes to time 1.5 s (at most 15)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region, each from the initial state (rewound, not rebuilt); the median is reported; 0 = at least 3 and as many as it takes to time 1.5 s (at most 15); default 1, with --full 0")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU baseline; 0 = min(32, CPUs the container may use: affinity and cgroup quota)")
     ap.add_argument("--no-extra-legs", action="store_true", help="default C4 line only: skip the config-5 (Ravone project, water; + heat) and config-3 (F60, runoff regime) legs timed after it")
     ap.add_argument("--write-episode-checks", default=None, metavar="PATH", help="one GPU, C4 F20: write storage and per-strip H checksums (2 / 4 / 8 strips) after hour 5 of the first episode - what an N > 1 line is held to (tests/golden/c4_f20_episode_checks.json)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline too: the reference-vector parity check, the roofline (HIP-event kernel timing), "
+                    "repeated timed regions, the C4 F60 hour and the other BASELINE configs, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last timed hour to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 0 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -405,12 +458,15 @@ def main():
     sf.check(sf.lib.sf3d_set_device(device), "set_device")
     shard = (rank, world, allgather_bytes) if world > 1 else None
 
-    # before anything is timed: the path this line measures against the unmodified reference's own vector (about a second)
+    # before anything is timed: the path this line measures against the unmodified reference's own vector (about a second; --full, or
+    # N > 1, where the first contact decides which exchange the timed path uses)
     first_contact = None
-    try:
-        ok, parity_msg = reference_vector_check(sf, cm, rank, world, allgather_bytes)
-    except Exception as e:  # noqa: BLE001
-        ok, parity_msg = False, f"the run itself failed: {e}"
+    ok, parity_msg = True, None
+    if args.full or world > 1:
+        try:
+            ok, parity_msg = reference_vector_check(sf, cm, rank, world, allgather_bytes)
+        except Exception as e:  # noqa: BLE001
+            ok, parity_msg = False, f"the run itself failed: {e}"
     if world > 1:
         fails = [x.decode() for x in allgather_bytes(b"" if ok else f"rank {rank}: {parity_msg}".encode()) if x]
         if fails and os.environ.get("SF3D_RESIDENT_SWEEP") != "0":
@@ -449,13 +505,17 @@ def main():
                 sf.lib.sf3d_clean()
             else:
                 log(f"[bench] rank {rank}: paired pass with record hand-over: {msg2}")
-    log(f"[bench] rank {rank}: {'parity ok' if ok else 'PARITY FAILURE'}: {parity_msg}")
+    if parity_msg is not None:
+        log(f"[bench] rank {rank}: {'parity ok' if ok else 'PARITY FAILURE'}: {parity_msg}")
     if world > 1:
         ok = all(x == b"1" for x in allgather_bytes(b"1" if ok else b"0"))
     if not ok:
         log(f"[bench] rank {rank}: the product does not reproduce tests/golden/c2_f20.npz on this node - no line is printed")
         sys.exit(5)
-    parity = {"c2_f20_hour0_vs_reference_vector": "bit-identical (H, Se of every owned node, accepted time steps)" + (f", {world} strips" if world > 1 else "")}
+    if parity_msg is not None:
+        parity = {"c2_f20_hour0_vs_reference_vector": "bit-identical (H, Se of every owned node, accepted time steps)" + (f", {world} strips" if world > 1 else "")}
+    else:
+        parity = {"c2_f20_hour0_vs_reference_vector": "not checked in this run (--full checks it)"}
     if first_contact:
         parity["note"] = first_contact
 
@@ -536,9 +596,10 @@ def main():
         run_hours(sf, cm, model, args.forcing, args.warmup, heat=heat)
         fresh()
 
-    # HIP events around the dominant kernel only, on every 8th computeStep (mode 2); --time-all-kernels
+    # HIP events around the dominant kernel only, on every 8th computeStep (mode 2, --full); --time-all-kernels
     # instruments every node kernel of every step (eager launches, ~6 % slower)
-    sf.check(sf.lib.sf3d_kernel_timing(0 if args.no_kernel_timing else (1 if args.time_all_kernels else 2)), "kernel_timing")
+    timing_mode = 0 if args.no_kernel_timing else (1 if args.time_all_kernels else (2 if args.full else 0))
+    sf.check(sf.lib.sf3d_kernel_timing(timing_mode), "kernel_timing")
     # the state at the end of the first complete episode (hour 5 of repetition 0), read outside the clock: what an N > 1 line is held to
     episode_end = {}
     want_checks = args.workload == "C4" and args.forcing == "F20" and not args.heat and not args.lineal and args.steps >= EPISODE_HOURS and (world > 1 or args.write_episode_checks)
@@ -548,7 +609,7 @@ def main():
             episode_end["H"] = sf.total_potential(0, model.n)
             episode_end["storage"] = float(sf.lib.sf3d_get_water_storage())
 
-    reps = max(1, args.reps) if args.reps > 0 else 3          # --reps 0: at least 3, and as many as it takes to time >= 1.5 s (<= 15)
+    reps = args.reps if args.reps > 0 else 3          # --reps 0: at least 3, and as many as it takes to time >= 1.5 s (<= 15)
     rep_elapsed, rep_incl, rep_episodes, episode_work = [], [], [], None      # (rep_episodes: every complete 6-hour episode of every repetition)
     per_step, hour_starts, c0, work0, heat_work0 = [], [], None, None, None
     rep = 0
@@ -589,6 +650,8 @@ def main():
         if rep == 0 and args.reps <= 0 and vals[0] > 0:          # (the maximum over the ranks: the same decision on every rank)
             reps = int(min(15, max(3, np.ceil(1.5 / vals[0]))))
         rep += 1
+        if rep == reps:
+            last_dts = [dt for (tq, dt) in ps if tq >= hs_[-1]] if hs_ else []      # the accepted steps of the last timed hour
     order = sorted(range(reps), key=lambda k: rep_elapsed[k])
     med = order[reps // 2]
     elapsed, elapsed_incl = rep_elapsed[med], rep_incl[med]
@@ -597,6 +660,9 @@ def main():
     if not np.isfinite(tw):     # computeStep keeps returning a dt after stepNan, like the reference: such a run measures nothing
         raise RuntimeError(f"rank {rank}: the state is not finite after the timed steps (total water content {tw}): invalid run")
     sf.lib.sf3d_kernel_timing(0)
+    if args.dump_outputs:
+        dump_outputs(sf, model, heat, last_dts, world, rank, sf.owner_map(world, model.n) if shard is not None else None, allgather_bytes,
+                     args.dump_outputs)
 
     checks_file = ROOT / "tests" / "golden" / "c4_f20_episode_checks.json"
     if episode_end and args.write_episode_checks and world == 1:
@@ -647,7 +713,7 @@ def main():
 
     work = {k: c1[k] - c0[k] for k in c1}
     f60 = None
-    if world == 1 and args.workload == "C4" and args.forcing == "F20" and not args.heat and not args.lineal and not args.no_f60:
+    if args.full and world == 1 and args.workload == "C4" and args.forcing == "F20" and not args.heat and not args.lineal and not args.no_f60:
         # "C4: F20 6 sim-h for the headline number plus F60 hour 0 only" - the runoff-regime figure, timed here so that it
         # is on the driver's line: hour 0 of the 60 mm forcing from the initial state (76 steps incl. the Courant rejections), median of 3
         f60_s, f60_work = [], None
@@ -666,7 +732,7 @@ def main():
     # project from the committed fixtures: water, hour 0, median of 3; with coupled heat, hour 0, once) and config 3 (256x256x15, F60:
     # the runoff regime, hour 0 + the dry hour after it).  Each with its work counters and its dominant kernel's event-timed average.
     legs = None
-    if world == 1 and args.workload == "C4" and args.forcing == "F20" and not args.heat and not args.lineal and not args.no_extra_legs and not args.no_f60:
+    if args.full and world == 1 and args.workload == "C4" and args.forcing == "F20" and not args.heat and not args.lineal and not args.no_extra_legs and not args.no_f60:
         legs = {}
 
         def leg(name, m2, hours_plan, reps2, heat2=None, what=""):
@@ -746,7 +812,7 @@ def main():
             log(f"[bench] extra legs stopped: {e}")
             legs["error"] = str(e)[:300]
     # dominant kernel by measured device time
-    dom = max(stats, key=lambda k: stats[k][1]) if stats else None      # k_sweep unless --time-all-kernels finds another
+    dom = max(stats, key=lambda k: stats[k][1]) if stats and timing_mode else None      # k_sweep unless --time-all-kernels finds another
     roofline = None
     # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes (separate --pmc runs
     # of this same command, corrected per MI355X_MICROARCH.md: 2 x FETCH_SIZE + WRITE_SIZE); bench.py
@@ -837,7 +903,7 @@ def main():
                             "traffic": run_traffic if w_ is episode_work else None,
                             "traffic_frac": (run_traffic / el_ / 1e9 / HBM_PEAK_GBS) if (run_traffic and w_ is episode_work) else None}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.heat:      # the baseline leg drives the water-only set-up
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.heat:      # the baseline leg drives the water-only set-up
         try:
             cpu = cpu_baseline(cm, capi, model, args.forcing, args.workload,
                                (hour_starts[0], per_step) if hour_starts else None, budget_s=args.cpu_budget,
@@ -873,8 +939,10 @@ def main():
         "timed_region": {"hours": args.steps, "elapsed_s": elapsed, "hours_per_s": args.steps / elapsed, "per_hour_s_last_rep": ph,
                          "note": "all K timed hours (median repetition): complete episodes plus the first K mod 6 hours of one more"},
         "inclusive_value": args.steps / elapsed_incl if elapsed_incl > 0 else None,
-        "value_timing": f"median of {reps} repetitions of the timed region; repetition 0 carries the HIP-event sampling of the dominant kernel "
-                        f"(every 8th computeStep launched eagerly), the others replay hipGraphs uninstrumented; repetition 0 took {rep_elapsed[0]:.4f} s",
+        "value_timing": (f"median of {reps} repetitions of the timed region; repetition 0 carries the HIP-event sampling of the dominant kernel "
+                         f"(every 8th computeStep launched eagerly), the others replay hipGraphs uninstrumented; repetition 0 took {rep_elapsed[0]:.4f} s"
+                         if timing_mode == 2 and reps > 1 else
+                         f"median of {reps} repetition(s) of the timed region" + (", HIP-event kernel timing on in repetition 0" if timing_mode else ", no kernel timing")),
         "f60_hour0": f60,
         "legs": legs,                  # config 5 (water; + heat) and config 3 F60 on the same line: builder-run lines under profiles/ until round 5
         "parity": parity,              # checked before the timed region (exit 5 and no line on a mismatch)

@@ -81,6 +81,14 @@ def build_v1_alias(force: bool = False) -> Path:
 REFERENCE = Path("/root/reference")
 
 
+def _present(p: Path) -> bool:
+    """p exists and this user may look at it (a reference tree behind a directory the user cannot enter counts as absent)"""
+    try:
+        return p.exists()
+    except OSError:
+        return False
+
+
 def build_v2_demo(force: bool = False) -> Path:
     """tests/v2_caller_demo.cpp: a C++ caller of the soilFluxes3D::v2 API linked against the shim.  With the reference
     mounted it is compiled against the reference's OWN soilFluxes3D.h (the caller-side header of bin/CRITERIA3D);
@@ -90,7 +98,7 @@ def build_v2_demo(force: bool = False) -> Path:
     build_shim()
     if force or _stale(demo, [dsrc, SHIM_LIB]):
         ref_inc = REFERENCE / "agrolib" / "soilFluxes3D"
-        if (ref_inc / "soilFluxes3D.h").exists():
+        if _present(ref_inc / "soilFluxes3D.h"):
             inc = ["-DSF3D_USE_REFERENCE_HEADER", f"-I{ref_inc}", f"-I{REFERENCE / 'agrolib' / 'mathFunctions'}"]
         else:
             inc = [f"-I{ROOT / 'shim'}"]
@@ -111,7 +119,7 @@ def build_static_dropin(force: bool = False):
     main.cpp:81) linked against that archive the way the .pro change says.  Needs the reference headers and Qt: returns None
     elsewhere (the GPU box runs the prebuilt demo)."""
     ref_inc = REFERENCE / "agrolib" / "soilFluxes3D"
-    if not (ref_inc / "soilFluxes3D.h").exists() or not (QT_INC / "QtCore").exists() or not QT_CORE.exists():
+    if not _present(ref_inc / "soilFluxes3D.h") or not (QT_INC / "QtCore").exists() or not QT_CORE.exists():
         return None
     src = ROOT / "shim" / "sf3d_cxx_shim.cpp"
     obj = ROOT / "shim" / "sf3d_cxx_shim_static.o"

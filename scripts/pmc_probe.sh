@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --no-cpu-baseline --steps 1 --warmup 0 --no-kernel-timing > /dev/null 2> $OUT/err.log
+rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 1 --warmup 0 --no-kernel-timing > /dev/null 2> $OUT/err.log
 cd $ROOT
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections, re

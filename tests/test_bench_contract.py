@@ -71,10 +71,10 @@ import pytest
 
 @pytest.mark.gpu
 def test_bench_runs_and_prints_one_json_line():
-    """a short real run (C2, one simulated hour, CPU baseline on a 3 s budget): exactly one JSON line on stdout"""
+    """a short real run (C2, one simulated hour, CPU baseline on a 3 s budget; --full: roofline and CPU baseline): exactly one JSON line on stdout"""
     import subprocess
     import sys
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "C2", "--steps", "1", "--warmup", "1", "--cpu-budget", "3"],
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "C2", "--steps", "1", "--warmup", "1", "--cpu-budget", "3", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -84,6 +84,35 @@ def test_bench_runs_and_prints_one_json_line():
     assert line["roofline"]["bound"] == "hbm" and line["roofline"]["kernel"] == "k_sweep_resident"      # (C2's rows fit on chip: all iterations of an approximation in one launch)
     assert line["cpu_baseline"] is not None and line["cpu_baseline"]["kind"] == "reference" and line["cpu_baseline"]["value"] > 0
     assert line["config"]["work"]["accepted"] == 22          # C2 F20 hour 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_once_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps hours once, measures nothing else, and --dump-outputs writes what the timed path
+    computed: one hour of C2 F20 after the warm-up (the model rebuilt) is hour 0 from the initial state - the reference's own vector
+    (tests/golden/c2_f20.npz) bit for bit"""
+    import subprocess
+    import sys
+    import numpy as np
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "C2", "--steps", "1", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 1 and line["warmup"] == 1 and len(line["repeats_s"]) == 1 and line["config"]["work"]["accepted"] == 22
+    assert line["value"] > 0 and abs(line["ms_per_step"] - line["repeats_s"][0] * 1e3) < 1e-9 * line["ms_per_step"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["legs"] is None and line["f60_hour0"] is None
+    g = np.load(ROOT / "tests" / "golden" / "c2_f20.npz")
+    n0 = int(g["steps_per_hour"][0])
+    dump = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert set(dump) == {"node_index", "total_potential", "water_content", "degree_of_saturation", "boundary_water_flow", "dt_last_step", "water_storage"}
+    assert all(a.dtype == np.float64 for a in dump.values())
+    assert np.array_equal(dump["node_index"], np.arange(64 * 64 * 10))      # (C2 is smaller than the sample: every node)
+    assert np.array_equal(dump["dt_last_step"], g["dts"][:n0])
+    assert np.array_equal(dump["total_potential"], g["H_h0"]) and np.array_equal(dump["degree_of_saturation"], g["Se_h0"])
+    assert dump["water_storage"].shape == (1,) and dump["water_storage"][0] > 0
 
 
 def _run_shared_gpu_bench(cmd, env):
@@ -112,7 +141,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     env = dict(os.environ, SF3D_BENCH_SHARE_GPU="1")
     p = _run_shared_gpu_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                "--master-port", "29631", str(ROOT / "bench.py"), "--gpus", "2", "--workload", "C2", "--steps", "1", "--warmup", "0",
-                               "--no-cpu-baseline"], env)
+                               "--no-cpu-baseline", "--full"], env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -148,7 +177,7 @@ def test_bench_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SF3D_BENCH_SHARE_GPU"] = "1"
     p = _run_shared_gpu_bench([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--workload", "C2", "--steps", "6", "--warmup", "0", "--reps", "2",
-                               "--no-cpu-baseline"], env)
+                               "--no-cpu-baseline", "--full"], env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -176,7 +205,7 @@ def test_bench_value_is_the_six_hour_episode_whatever_steps_is():
     out = {}
     for steps, warm in ((20, 5), (6, 1)):
         p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "C2", "--steps", str(steps), "--warmup", str(warm), "--reps", "3",
-                            "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                            "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-2000:]
         out[steps] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     a, b = out[20], out[6]
