@@ -141,6 +141,7 @@ struct LocalModel {
     std::vector<int32_t> g2l;
     Partition part;                  /* local indices */
     Partition gpart;                 /* global indices: what sf3d_dist_owner / sf3d_dist_halo answer from once M is trimmed */
+    uint64_t gen = 0;                /* counts the builds of L (the output maps' column table follows the local numbering) */
 };
 LocalModel LM;
 int distRank = 0, distWorld = 1;
@@ -167,6 +168,7 @@ sf3d_error_t buildLocal()
                         "build must stage the whole one-cell ring of columns around the strip\n", distRank, gp.missingFrom, gp.missingTo);
     if (e != SF3D_OK) return e;
     LM.trimmed = false;
+    ++LM.gen;
     std::vector<uint8_t> in(M.N, 0);
     for (uint32_t i = 0; i < M.N; ++i) if (gp.owner[i] == distRank) in[i] = 1;
     for (int p = 0; p < distWorld; ++p) for (uint32_t i : gp.recv[p]) in[i] = 1;
@@ -367,6 +369,8 @@ template <class T> void reset(std::vector<T>& v, size_t n) { v.assign(n, T()); }
 /* (ONE statement - an else-if chain closed by an empty else - so that it stays whole under an unbraced if) */
 #define NEED_NODE_D(i) if ((i) >= M.N) return errValue(SF3D_INDEX_ERROR); else if (skippedByTrim(i)) return (double)SF3D_NODATA; else (void)0
 
+void mapsClear();                               /* sf3d_maps_api.inc: what include/sf3d_maps.h set belongs to one model */
+
 }  // namespace
 
 extern "C" {
@@ -375,6 +379,7 @@ const char* sf3d_backend_name(void) { return "hip"; }
 
 sf3d_error_t sf3d_clean(void)                                       /* soilFluxes3D.cpp:218-304 */
 {
+    mapsClear();
     if (!M.initialized) return SF3D_OK;
     dev().release();
     M = HostModel();
@@ -1160,3 +1165,5 @@ sf3d_error_t sf3d_device_norm_sum(uint32_t count, const double* x, uint32_t bloc
 sf3d_error_t sf3d_device_pow(uint32_t count, const double* x, const double* y, double* out) { return (count && (!x || !y || !out)) ? SF3D_PARAMETER_ERROR : dev().device_pow(count, x, y, out); }
 
 } /* extern "C" */
+
+#include "sf3d_maps_api.inc"

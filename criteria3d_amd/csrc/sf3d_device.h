@@ -397,7 +397,29 @@ struct DevView {
     HeatDev heat;
 };
 
+/* ---- output maps (sf3d_maps.inc, include/sf3d_maps.h): one thread per raster cell walks its column of nodes ---- */
+struct MapGeo {         /* per soil class: what computeFactorOfSafety reads of the class's horizon (project3D.cpp:2614-2721) */
+    double cohesion;    /* effective cohesion [kPa] */
+    double tanFriction; /* tan(frictionAngle * DEG_TO_RAD), host libm */
+    double bulkDensity; /* [g cm-3] */
+    double present;     /* 0: no sf3d_set_horizon_geotechnics entry for the class */
+};
+struct MapView {
+    const int32_t* col;                 /* [nLayers][nCells] node of the cell in the layer (device numbering), -1 = none */
+    const double* thick;                /* [nLayers] layer thickness [m] */
+    const double* slope;                /* [2][nCells] tanAngle, sin(2 slopeAngle) (host libm); null until sf3d_set_cell_slopes */
+    const MapGeo* geo;                  /* [soil classes] */
+    const double *H, *Se, *z, *pond, *lflowSum;
+    const uint16_t* cls;
+    const SoilDev* soils;
+    uint32_t N, ns, nCells, nLayers, lay0, lay1, wrc;   /* layers [lay0, lay1) are written, layer l at out + (l - lay0) * nCells */
+    int32_t var;
+    float flag;
+    float* out;
+    int* missing;                       /* set to 1 by a cell whose factor of safety needs a class without geotechnics */
+};
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
-enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_COUNT };
+enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 
 #endif

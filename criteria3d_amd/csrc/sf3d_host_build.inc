@@ -21,7 +21,7 @@ template <class F> void parallel_for(uint32_t n, F f)
     for (auto& t : th) t.join();
 }
 
-const char* kKernelNames[KID_COUNT] = {"k_props", "k_assemble", "k_sweep", "k_post", "k_restore", "k_accept", "k_sweep_pair", "k_sweep_resident"};
+const char* kKernelNames[KID_COUNT] = {"k_props", "k_assemble", "k_sweep", "k_post", "k_restore", "k_accept", "k_sweep_pair", "k_sweep_resident", "k_output_map"};
 
 }  // namespace
 
@@ -117,6 +117,20 @@ static void res_launch(int K, int NW, bool dist, uint32_t blocks, uint32_t lds, 
 }
 
 __global__ void k_dist_ping(DistView d, unsigned long long token, long long timeoutTicks, int* out);
+
+/* output maps (sf3d_maps.inc): device copies of what include/sf3d_maps.h set, uploaded by the first map call after a change and freed with
+ * the model (release) - a rebuilt model may number its nodes differently */
+struct MapsCache {
+    int32_t* col = nullptr; double* thick = nullptr; double* slope = nullptr; MapGeo* geo = nullptr; float* out = nullptr; int* missing = nullptr;
+    size_t colCap = 0, thickCap = 0, slopeCap = 0, geoCap = 0, outCap = 0;
+    uint64_t colVer = 0, slopeVer = 0;          /* versions of MapsInput that are on the device (0: none) */
+    std::vector<MapGeo> geoHost;
+    void free_all()
+    {
+        for (void* q : {(void*)col, (void*)thick, (void*)slope, (void*)geo, (void*)out, (void*)missing}) if (q) (void)hipFree(q);
+        *this = MapsCache();
+    }
+};
 
 struct DeviceSolver::Impl {
     int device = -1;
@@ -236,6 +250,7 @@ struct DeviceSolver::Impl {
     std::vector<hipEvent_t> freeEvents;
     uint64_t launches[KID_COUNT] = {0};
     double ms[KID_COUNT] = {0};
+    MapsCache maps;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the
@@ -293,6 +308,7 @@ sf3d_error_t DeviceSolver::release()
     for (void* p : I.allocs) hipFree(p);
     I.allocs.clear();
     g_deviceBytes = 0;
+    I.maps.free_all();
     if (I.comm && I.pCommDestroy) { I.pCommDestroy(I.comm); I.comm = nullptr; }
     I.rcclMode = false; I.rcclMine = I.rcclGathered = nullptr;
     for (void* p : I.peerMaps) hipIpcCloseMemHandle(p);

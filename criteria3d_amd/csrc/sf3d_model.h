@@ -134,6 +134,19 @@ struct DistBlob {
                                       * records - used only if EVERY rank says so (a rank on single sweeps puts plain values and needs two exchanges per two iterations) */
 };
 
+/* what include/sf3d_maps.h set, in the numbering of the model the device works on (sf3d_api.cpp hands it over per map call; the device
+ * uploads a part only when its version differs from the one it holds) */
+struct MapsInput {
+    uint32_t nCells = 0, nLayers = 0;
+    const int32_t* col = nullptr;      /* [nLayers][nCells] node or -1 */
+    const double* thick = nullptr;     /* [nLayers] */
+    uint64_t colVer = 0;
+    const double* slope = nullptr;     /* [2][nCells] tanAngle, sin(2 slopeAngle); null until set */
+    uint64_t slopeVer = 0;
+    const MapGeo* geo = nullptr;       /* [soil classes] */
+    uint32_t nGeo = 0;
+};
+
 /* The device half.  All methods return an sf3d_error_t; HIP failures map to SF3D_SOLVER_ERROR
  * and leave a message retrievable with last_error(). */
 class DeviceSolver {
@@ -182,6 +195,9 @@ public:
     sf3d_error_t device_pow(uint32_t n, const double* x, const double* y, double* out);   /* test hook: the property kernels' pow */
     sf3d_error_t device_norm_sum(uint32_t n, const double* x, uint32_t blocks, int assoc, double* out);   /* test hook: the sweep kernels' double-double norm sum */
     uint64_t device_bytes() const;               /* bytes of device memory the model's arrays take (sum of the allocations) */
+    /* output maps (sf3d_maps.inc): variable `var` of criteria3DVariable on layer `layer` (-1: all) of the accepted state -> out (floats);
+     * *missing = 1 when a factor of safety needed a soil class without geotechnics */
+    sf3d_error_t output_map(HostModel& m, const ParamsHost& p, const MapsInput& in, int var, int layer, float flag, float* out, int* missing);
 
 private:
     DeviceSolver() = default;

@@ -45,3 +45,4 @@
 #include "sf3d_phases.inc"
 #include "sf3d_host_build.inc"
 #include "sf3d_host_step.inc"
+#include "sf3d_maps.inc"

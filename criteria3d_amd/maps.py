@@ -1,0 +1,297 @@
+"""Output maps of the application on the device (include/sf3d_maps.h, criteria3d_amd/csrc/sf3d_maps.inc): per-layer maps of every
+variable `getCriteria3DVar` serves, the infinite-slope factor of safety, the minimum factor of safety and the average degree of
+saturation of a column - what `Project3D::computeCriteria3DMap` (src/project3D/project3D.cpp:1896-1948), `computeMinimumFoS`
+(:2128-2157), `computeAvgDegreeOfSaturation` (:2076-2125) and `computeFactorOfSafety` (:2614-2721) compute after each hour - and the
+hourly output-point values of `Crit3DProject::appendCriteria3DOutputValue` (bin/CRITERIA3D/criteria3DProject.cpp:3305-3336).
+
+Two halves:
+  * the binding (`bind`, `set_output`, `output_maps`, `output_point_values`, `write_map`): the maps are computed by the HIP kernel
+    k_output_map from the state the device holds; only the float maps cross the bus.  A missing kernel or library is an error.
+  * `restate_*`: the reference's loops over per-node getter values, in numpy with the reference's operation order (elementwise IEEE
+    + - x / only; tan / sin through python's `math`, the C library).  They are the yardstick of tests/test_gpu_output_maps.py (evaluated on
+    the ORACLE's getters) and the host path scripts/output_maps_timing.py measures against; not used by the binding.
+
+The reference loops restated here are Qt application code (not buildable here) and are not pinned against compiled reference code."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import capi
+from .project3d import DEG_TO_RAD, EPSILON, GRAVITY, NODATA, soil_layer_index
+
+# criteria3DVariable (agrolib/meteo/meteo.h:110-114)
+(VOLUMETRIC_WATER_CONTENT, WATER_TOTAL_POTENTIAL, WATER_MATRIC_POTENTIAL, AVAILABLE_WATER_CONTENT, DEGREE_OF_SATURATION,
+ AVG_DEGREE_OF_SATURATION, SOIL_TEMPERATURE, SOIL_SURFACE_MOISTURE, BOTTOM_DRAINAGE, WATER_DEFICIT, WATER_INFLOW, WATER_OUTFLOW,
+ FACTOR_OF_SAFETY, MINIMUM_FACTOR_OF_SAFETY, SURFACE_POND, MIN_VOLUMETRIC_WATER_CONTENT, MAX_VOLUMETRIC_WATER_CONTENT) = range(17)
+# per-layer variables served through getCriteria3DVar (project3D.cpp:2756-2804)
+LAYER_VARIABLES = (VOLUMETRIC_WATER_CONTENT, WATER_TOTAL_POTENTIAL, WATER_MATRIC_POTENTIAL, AVAILABLE_WATER_CONTENT, DEGREE_OF_SATURATION,
+                   WATER_DEFICIT, WATER_INFLOW, WATER_OUTFLOW, SURFACE_POND, MIN_VOLUMETRIC_WATER_CONTENT, MAX_VOLUMETRIC_WATER_CONTENT)
+COLUMN_VARIABLES = (MINIMUM_FACTOR_OF_SAFETY, AVG_DEGREE_OF_SATURATION)
+FIELD_CAPACITY = 3.0                     # project3D.cpp:2793 (TODO of the reference: not read from the horizon)
+
+pf32 = C.POINTER(C.c_float)
+pi32 = C.POINTER(C.c_int32)
+# name -> (restype, argtypes): every symbol include/sf3d_maps.h declares
+SIGNATURES = {
+    "sf3d_set_output_columns": (capi.u8, [capi.u32, capi.u32, pi32, capi.pd]),
+    "sf3d_set_horizon_geotechnics": (capi.u8, [capi.u16, capi.u16, capi.f64, capi.f64, capi.f64]),
+    "sf3d_set_cell_slopes": (capi.u8, [capi.u32, pf32, capi.i32]),
+    "sf3d_compute_output_map": (capi.u8, [capi.i32, capi.i32, capi.f32, pf32]),
+}
+
+
+def bind(sf: capi.SF3D) -> capi.SF3D:
+    """attach the signatures of include/sf3d_maps.h to a loaded product library (AttributeError if a symbol is missing)"""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(sf.lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return sf
+
+
+# ------------------------------------------------------------------------------------------------ binding
+
+def columns(model) -> tuple[np.ndarray, np.ndarray]:
+    """the column table of a project model (Project3D::indexMap: meta["index"], [nz, ny, nx], -1 = no node) as [nz][ny * nx] int32 and the
+    layer thicknesses [nz] (layer 0 = surface, 0 m)"""
+    idx = np.asarray(model.meta["index"])
+    nz = idx.shape[0]
+    return np.ascontiguousarray(idx.reshape(nz, -1), dtype=np.int32), np.array([0.0] + list(model.meta["layers"]), dtype=np.float64)
+
+
+def set_output(sf: capi.SF3D, model, increase_slope: bool = False) -> None:
+    """the three setters for a model of project3d.project_model: column table, geotechnics of every (soil, horizon) of the soil list,
+    cell slopes"""
+    bind(sf)
+    col, thick = columns(model)
+    nz, nc = col.shape
+    sf.check(sf.lib.sf3d_set_output_columns(nc, nz, col.ctypes.data_as(pi32), thick.ctypes.data_as(capi.pd)), "set_output_columns")
+    for si, hi, coh, fri, bd in model.meta["geotechnics"]:
+        sf.check(sf.lib.sf3d_set_horizon_geotechnics(si, hi, coh, fri, bd), f"set_horizon_geotechnics({si}, {hi})")
+    set_slopes(sf, model, increase_slope)
+
+
+def set_slopes(sf: capi.SF3D, model, increase_slope: bool) -> None:
+    slope = np.ascontiguousarray(np.asarray(model.meta["slope"], dtype=np.float32).ravel())
+    sf.check(sf.lib.sf3d_set_cell_slopes(slope.size, slope.ctypes.data_as(pf32), int(bool(increase_slope))), "set_cell_slopes")
+
+
+def output_maps(sf: capi.SF3D, model, variable: int, layers=None, flag: float = NODATA) -> np.ndarray:
+    """-> float32 [layers, rows, cols] of `variable` on the accepted state (layers None: every layer; an int or a list of layers; the
+    whole-column variables give one map).  Cells without a node and NODATA values hold `flag`."""
+    idx = np.asarray(model.meta["index"])
+    nz, ny, nx = idx.shape
+    if variable in COLUMN_VARIABLES:
+        out = np.empty((1, ny, nx), np.float32)
+        sf.check(sf.lib.sf3d_compute_output_map(variable, -1, flag, out.ctypes.data_as(pf32)), f"compute_output_map({variable})")
+        return out
+    if layers is None:
+        out = np.empty((nz, ny, nx), np.float32)
+        sf.check(sf.lib.sf3d_compute_output_map(variable, -1, flag, out.ctypes.data_as(pf32)), f"compute_output_map({variable})")
+        return out
+    layers = [layers] if np.isscalar(layers) else list(layers)
+    out = np.empty((len(layers), ny, nx), np.float32)
+    for k, layer in enumerate(layers):
+        sf.check(sf.lib.sf3d_compute_output_map(variable, int(layer), flag, out[k].ctypes.data_as(pf32)), f"compute_output_map({variable}, {layer})")
+    return out
+
+
+def row_col_from_xy(header: dict, x: float, y: float) -> tuple[int, int]:
+    """gis::getRowColFromXY (agrolib/gis/gis.cpp:741-745)"""
+    inv = 1.0 / float(header["cellsize"])
+    nrows = int(header["nrows"])
+    row = (nrows - 1) -int(math.floor((y - float(header["yllcorner"])) * inv))
+    col = int(math.floor((x - float(header["xllcorner"])) * inv))
+    return row, col
+
+
+def output_point_values(maps: np.ndarray, points_xy, depths_cm, model, flag: float = NODATA) -> np.ndarray:
+    """Crit3DProject::appendCriteria3DOutputValue (criteria3DProject.cpp:3305-3336) for every output point over all-layer maps of one
+    variable (output_maps(.., layers=None)): depth [cm] -> getSoilLayerIndex -> the map's value at the point's cell; NODATA where the
+    layer or the node does not exist.  -> float32 [points, depths].  Depths must be > 0 cm, as the application's depth lists are (layer 0
+    of the maps holds the water level in mm and the flag for the factor of safety, not the getter's value)."""
+    if any(int(d) <= 0 for d in depths_cm):
+        raise ValueError("output depths must be > 0 cm")
+    thick = [0.0] + list(model.meta["layers"])
+    centre = list(model.meta["centre"])
+    hdr = dict(model.meta["header"])
+    hdr.setdefault("nrows", maps.shape[1])
+    out = np.full((len(points_xy), len(depths_cm)), np.float32(NODATA), np.float32)
+    for p, (x, y) in enumerate(points_xy):
+        row, col = row_col_from_xy(hdr, x, y)
+        if not (0 <= row < maps.shape[1] and 0 <= col < maps.shape[2]):
+            continue
+        for k, d in enumerate(depths_cm):
+            layer = soil_layer_index(thick, centre, int(d) * 0.01)
+            if layer == int(NODATA):
+                continue
+            v = maps[layer, row, col]
+            if v != np.float32(flag):
+                out[p, k] = v
+    return out
+
+
+def write_map(path, map2d: np.ndarray, model, flag: float = NODATA) -> None:
+    """one map as an ESRI float grid (.flt + .hdr) on the model's raster (esri.write_grid)"""
+    from . import esri
+    hdr = dict(model.meta["header"])
+    hdr["nodata"] = flag
+    esri.write_grid(path, np.asarray(map2d, np.float32), hdr)
+
+
+# ------------------------------------------------------------------------------------------------ restatements (test yardstick / host path)
+
+GETTERS = {          # variable -> per-node getter of include/sf3d.h it reads (getCriteria3DVar, project3D.cpp:2756-2804)
+    VOLUMETRIC_WATER_CONTENT: "sf3d_get_node_water_content",
+    MIN_VOLUMETRIC_WATER_CONTENT: "sf3d_get_node_minimum_water_content",
+    MAX_VOLUMETRIC_WATER_CONTENT: "sf3d_get_node_maximum_water_content",
+    AVAILABLE_WATER_CONTENT: "sf3d_get_node_available_water_content",
+    WATER_TOTAL_POTENTIAL: "sf3d_get_node_total_potential",
+    WATER_MATRIC_POTENTIAL: "sf3d_get_node_matric_potential",
+    DEGREE_OF_SATURATION: "sf3d_get_node_degree_of_saturation",
+    WATER_INFLOW: "sf3d_get_node_sum_lateral_water_flow_in",
+    WATER_OUTFLOW: "sf3d_get_node_sum_lateral_water_flow_out",
+    WATER_DEFICIT: "sf3d_get_node_water_deficit",
+    SURFACE_POND: "sf3d_get_node_pond",
+}
+SCALE_1000 = (WATER_INFLOW, WATER_OUTFLOW, SURFACE_POND)
+
+
+def node_getter_values(sf: capi.SF3D, n: int, variables=tuple(GETTERS)) -> dict:
+    """variable -> float64 [n]: the per-node getter of every node, called one node at a time as the application does"""
+    out = {}
+    for var in variables:
+        fn = getattr(sf.lib, GETTERS[var])
+        if var == WATER_DEFICIT:
+            out[var] = np.array([fn(i, FIELD_CAPACITY) for i in range(n)], np.float64)
+        else:
+            out[var] = np.array([fn(i) for i in range(n)], np.float64)
+    return out
+
+
+def criteria3d_var(var: int, getter: np.ndarray) -> np.ndarray:
+    """getCriteria3DVar (project3D.cpp:2756-2810) over per-node getter values: the x 1000 of inflow / outflow / pond, then the sentinels
+    INDEX_ERROR, MEMORY_ERROR, TOPOGRAPHY_ERROR, MISSING_DATA_ERROR -> NODATA"""
+    v = np.asarray(getter, np.float64)
+    if var in SCALE_1000:
+        v = v * 1000
+    return np.where((v == -1111.0) | (v == -2222.0) | (v == -3333.0) | (v == -9999.0), NODATA, v)
+
+
+def restate_layer_map(index: np.ndarray, var: int, layer: int, getter: np.ndarray, flag: float = NODATA) -> np.ndarray:
+    """computeCriteria3DMap for a getCriteria3DVar variable (project3D.cpp:1913-1945) -> float32 [rows, cols]"""
+    idx = index[layer]
+    out = np.full(idx.shape, np.float32(flag), np.float32)
+    has = idx >= 0
+    v = criteria3d_var(var, getter)[idx[has]]
+    ok = v != NODATA
+    if var == VOLUMETRIC_WATER_CONTENT and layer == 0:
+        v = np.where(ok, v * 1000, v)
+    vals = np.full(v.shape, np.float32(flag), np.float32)
+    vals[ok] = v[ok].astype(np.float32)
+    out[has] = vals
+    return out
+
+
+def slope_terms(slope_deg: np.ndarray, increase_slope: bool) -> tuple[np.ndarray, np.ndarray]:
+    """tanAngle and sin(2 slopeAngle) of computeFactorOfSafety (project3D.cpp:2638-2650) per cell, through the C library"""
+    sd = np.asarray(slope_deg, np.float32).astype(np.float64).ravel()
+    tan_a, sin2 = np.empty(sd.size), np.empty(sd.size)
+    for k, s in enumerate(sd.tolist()):
+        if increase_slope:
+            s = min(s * 1.5, 89.)
+        angle = max(s * DEG_TO_RAD, EPSILON)
+        tan_a[k] = max(EPSILON, math.tan(angle))
+        sin2[k] = math.sin(2 * angle)
+    return tan_a.reshape(np.shape(slope_deg)), sin2.reshape(np.shape(slope_deg))
+
+
+def node_geotechnics(model) -> dict:
+    """per node (NaN on surface nodes): effective cohesion, tan(friction angle), bulk density of the node's (soil, horizon)"""
+    table = {(si, hi): (coh, math.tan(fri * DEG_TO_RAD), bd) for si, hi, coh, fri, bd in model.meta["geotechnics"]}
+    n, ns = model.n, model.ns
+    hz = model.horizon_index if model.horizon_index is not None else np.zeros(n - ns, np.uint16)
+    out = {k: np.full(n, np.nan) for k in ("cohesion", "tan_friction", "bulk_density")}
+    for key, (coh, tf, bd) in table.items():
+        sel = ns + np.nonzero((model.soil_index == key[0]) & (hz == key[1]))[0]
+        out["cohesion"][sel], out["tan_friction"][sel], out["bulk_density"][sel] = coh, tf, bd
+    return out
+
+
+def restate_factor_of_safety(index: np.ndarray, thick, layer: int, tan_a: np.ndarray, sin2: np.ndarray, geo: dict, wc: np.ndarray,
+                             dos: np.ndarray, mpot: np.ndarray) -> np.ndarray:
+    """computeFactorOfSafety(row, col, layer) (project3D.cpp:2614-2721) on every cell -> float64 [rows, cols] of the float it returns
+    (NODATA where the node does not exist).  wc / dos / mpot: getNodeWaterContent / DegreeOfSaturation / MatricPotential of every node."""
+    idx = index[layer]
+    out = np.full(idx.shape, NODATA)
+    has = idx >= 0
+    n = idx[has]
+    ta, s2 = tan_a[has], sin2[has]
+    tan_f = geo["tan_friction"][n]
+    friction_effect = tan_f / ta
+    saturation = dos[n]
+    bad = (saturation == -2222.0) | (saturation == -1111.0)
+    mp = mpot[n] * GRAVITY
+    matric = np.where(mp < 0.0, mp, 0.0)                          # std::min(0.0, x)
+    suction_stress = matric * saturation
+    weight_sum = np.zeros(n.size)
+    s0 = index[0][has]
+    sw = np.where(s0 >= 0, wc[np.maximum(s0, 0)], 0.0)
+    add = (s0 >= 0) & (sw > 0)
+    weight_sum[add] += sw[add] * GRAVITY
+    for l in range(1, layer + 1):
+        nl = index[l][has]
+        ok = nl >= 0
+        nn = nl[ok]
+        unit_weight = (geo["bulk_density"][nn] + wc[nn]) * GRAVITY
+        weight_sum[ok] += unit_weight * thick[l]
+    root_cohesion = 0.
+    cohesion_effect = 2 * (geo["cohesion"][n] + root_cohesion) / (weight_sum * s2)
+    suction_effect = (suction_stress * (ta + 1 / ta) * tan_f) / weight_sum
+    fos = (friction_effect + cohesion_effect - suction_effect).astype(np.float32).astype(np.float64)
+    out[has] = np.where(bad, NODATA, fos)
+    return out
+
+
+def restate_fos_map(index, thick, layer, tan_a, sin2, geo, wc, dos, mpot, flag: float = NODATA) -> np.ndarray:
+    """computeCriteria3DMap(factorOfSafety, layer) -> float32 [rows, cols] (layer 0: the flag, the device's documented deviation)"""
+    if layer == 0:
+        return np.full(index[0].shape, np.float32(flag), np.float32)
+    v = restate_factor_of_safety(index, thick, layer, tan_a, sin2, geo, wc, dos, mpot)
+    return np.where(v == NODATA, np.float32(flag), v.astype(np.float32)).astype(np.float32)
+
+
+def restate_minimum_fos(index, thick, tan_a, sin2, geo, wc, dos, mpot, flag: float = NODATA) -> np.ndarray:
+    """computeMinimumFoS (project3D.cpp:2128-2157) -> float32 [rows, cols]"""
+    minimum = np.full(index[0].shape, NODATA)
+    for l in range(1, index.shape[0]):
+        v = restate_factor_of_safety(index, thick, l, tan_a, sin2, geo, wc, dos, mpot)
+        take = ~(np.abs(v - NODATA) < EPSILON) & ((np.abs(minimum - NODATA) < EPSILON) | (v < minimum))
+        minimum = np.where(take, v, minimum)
+    return np.where(np.abs(minimum - NODATA) < EPSILON, np.float32(flag), minimum.astype(np.float32)).astype(np.float32)
+
+
+def restate_avg_degree_of_saturation(index, thick, wc, wc_min, wc_max, flag: float = NODATA) -> np.ndarray:
+    """computeAvgDegreeOfSaturation (project3D.cpp:2076-2125), its (sumWC - thetaR) / (thetaS - thetaR) of thickness-weighted sums as
+    written -> float32 [rows, cols]"""
+    shape = index[0].shape
+    theta_s, theta_r, sum_wc = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+    vwc_all = criteria3d_var(VOLUMETRIC_WATER_CONTENT, wc)
+    tr_all = criteria3d_var(MIN_VOLUMETRIC_WATER_CONTENT, wc_min)
+    ts_all = criteria3d_var(MAX_VOLUMETRIC_WATER_CONTENT, wc_max)
+    for l in range(1, index.shape[0]):
+        nl = index[l]
+        ok = nl >= 0
+        nn = np.maximum(nl, 0)
+        vwc = vwc_all[nn]
+        ok &= ~(np.abs(vwc - NODATA) < EPSILON)
+        sum_wc = np.where(ok, sum_wc + vwc * thick[l], sum_wc)
+        theta_r = np.where(ok, theta_r + tr_all[nn] * thick[l], theta_r)
+        theta_s = np.where(ok, theta_s + ts_all[nn] * thick[l], theta_s)
+    out = np.full(shape, np.float32(flag), np.float32)
+    sel = (index[0] >= 0) & (sum_wc > 0)
+    out[sel] = ((sum_wc[sel] - theta_r[sel]) / (theta_s[sel] - theta_r[sel])).astype(np.float32)
+    return out

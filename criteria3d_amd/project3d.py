@@ -250,7 +250,104 @@ def horizon_index(soil: dict, depth: float) -> int:
     return int(NODATA)
 
 
+# ------------------------------------------------------------------------------------------------ geotechnics (slope stability)
+# The USCS classification and the geotechnics fall-back below are restated from agrolib/soil and are NOT pinned against compiled
+# reference code (oracle/ holds no recipe for them): tests/test_output_maps_host.py checks every branch on hand-made horizons and the
+# Ravone database's values.
+
+def geotechnics_classes(rows) -> list:
+    """loadGeotechnicsParameters (soilDbTools.cpp:38-78): rows (id_class, USCS_code, effective_cohesion, friction_angle) of table
+    geotechnics -> list indexed by id_class of dict(code, effective_cohesion [kPa], friction_angle [deg]); NODATA where getValue fails
+    (Crit3DGeotechnicsClass defaults, soil.cpp:148-152).  The table must hold 18 rows."""
+    if len(rows) != 18:
+        raise ValueError("Table geotechnics: wrong number of soil classes (must be 18).")
+    out = [dict(code=None, effective_cohesion=NODATA, friction_angle=NODATA) for _ in range(19)]
+    for (cid, code, coh, fri) in rows:
+        out[int(cid)] = dict(code=code, effective_cohesion=db_double(coh), friction_angle=db_double(fri))
+    return out
+
+
+def uscs_class(coarse: float, sand: float, silt: float, clay: float, class_name_usda: str, organic_matter: float) -> int:
+    """soil::getUSCSClass (soil.cpp:325-397): coarse fragments and organic matter as fractions [0-1], sand / silt / clay in %, the
+    USDA class name as the van_genuchten table spells it ('clayloam', 'silty clayloam', 'sandy clayloam', ...)"""
+    coarse_fraction = coarse + (sand / 100) * (1 - coarse)
+    fine_fraction = (clay + silt) / 100 * (1 - coarse)
+    name, om = class_name_usda, organic_matter
+    if coarse_fraction > 0.5:
+        gravels_fraction = 0.66 * coarse
+        if gravels_fraction / coarse_fraction > 0.5:                     # GRAVELS
+            return 1 if fine_fraction < 0.12 else 3                      # GW / GM
+        if name == "sand":                                               # SANDS
+            return 8                                                     # SP
+        if name in ("sandy loam", "loamy sand"):
+            return 9                                                     # SM
+        if name in ("sandy clayloam", "sandy clay"):
+            return 10                                                    # SC
+        return 9
+    if name == "loam":                                                   # FINE grained soils
+        return 16 if om > 0.2 else 12                                    # OL / SC-CL
+    if name in ("clayloam", "silty clayloam"):
+        return 16 if om > 0.2 else 14                                    # OL / CL
+    if name in ("silt", "silt loam"):
+        if om > 0.2:
+            return 16
+        return 12 if clay >= 20 else 13                                  # SC-CL / ML
+    if name in ("clay", "silty clay"):
+        return 17 if om > 0.2 else 15                                    # OH / CH
+    return 16 if om > 0.2 else 13
+
+
+def horizon_geotechnics(row: dict, h: dict, textures, classes) -> dict:
+    """soil::setHorizon's slope-stability part (soil.cpp:986-1007) for a horizon set_horizon accepted: `row` is convert_horizon_row's
+    output plus the horizon's effective_cohesion / friction_angle through db_double (NODATA when NULL or ''), `h` set_horizon's horizon.
+    An explicit database value wins; otherwise the USCS class's row of the geotechnics table; otherwise NODATA.
+    -> dict(class_uscs, effective_cohesion, friction_angle)"""
+    sand, silt, clay = row["sand"], row["silt"], row["clay"]                 # texture as setHorizon stores it (:868-877)
+    if (not is_equal(sand, NODATA) and not is_equal(silt, NODATA) and not is_equal(clay, NODATA)
+            and (sand + silt + clay) <= 1.01):
+        sand *= 100; silt *= 100; clay *= 100
+    cls = uscs_class(h["coarse"], sand, silt, clay, textures[h["class_usda"]]["name"], h["organic_matter"])
+    out = dict(class_uscs=cls, effective_cohesion=NODATA, friction_angle=NODATA)
+    for key in ("effective_cohesion", "friction_angle"):
+        v = row.get(key, NODATA)
+        if v != NODATA:
+            out[key] = v
+        elif 1 <= cls <= 18:
+            out[key] = classes[cls][key]
+    return out
+
+
+def add_geotechnics(soils, horizon_rows, vg_rows, geotechnics_rows, horizon_geo) -> None:
+    """loadSoil with the slope-stability fields (soilDbTools.cpp:361-367 + soil.cpp:986-1007) over load_all_soils' list: every horizon
+    dict gains class_uscs, effective_cohesion and friction_angle.  horizon_rows: as for load_all_soils; horizon_geo: soil_code -> list of
+    (horizon_nr, effective_cohesion, friction_angle) as sqlite holds them (tests/golden/ravone_geotechnics.json)."""
+    textures = texture_classes(vg_rows)
+    classes = geotechnics_classes(geotechnics_rows)
+    for s in soils:
+        geo = {int(r[0]): r for r in horizon_geo.get(s["code"], [])}
+        for raw, h in zip(horizon_rows[s["code"]], s["horizons"]):
+            row = convert_horizon_row(raw)
+            g = geo.get(row["horizon_nr"], (None, None, None))
+            row["effective_cohesion"], row["friction_angle"] = db_double(g[1]), db_double(g[2])
+            h.update(horizon_geotechnics(row, h, textures, classes))
+
+
 # ------------------------------------------------------------------------------------------------ layers
+
+def soil_layer_bottom(thickness, centre, i: int) -> float:
+    """Project3D::getSoilLayerBottom (project3D.cpp:1757-1760): lower depth of layer i [m]"""
+    return centre[i] + thickness[i] * 0.5
+
+
+def soil_layer_index(thickness, centre, depth: float) -> int:
+    """Project3D::getSoilLayerIndex (project3D.cpp:1764-1776): first layer whose bottom is at or below `depth` [m]; NODATA when none"""
+    if len(thickness) == 0 or depth < 0:
+        return int(NODATA)
+    for layer in range(len(thickness)):
+        if depth <= soil_layer_bottom(thickness, centre, layer):
+            return layer
+    return int(NODATA)
+
 
 def soil_layers(depth: float, min_thickness: float = 0.02, max_thickness: float = 0.10, max_thickness_depth: float = 0.40):
     """Project3D::setSoilLayers + setLayersDepth (project3D.cpp:1568-1661) -> (thickness[nrLayers], centre depth[nrLayers]),
@@ -558,6 +655,10 @@ def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> M
                 continue
             soil_table.append((si, hi, soil_property_args(h)))
 
+    # what computeFactorOfSafety reads of each (soil, horizon) (project3D.cpp:2645-2702): the output maps' sf3d_set_horizon_geotechnics
+    geotechnics = [(si, hi, soils[si]["horizons"][hi].get("effective_cohesion", NODATA), soils[si]["horizons"][hi].get("friction_angle", NODATA),
+                    soils[si]["horizons"][hi]["bulk_density"]) for si, hi, _ in soil_table]
+
     # setCrit3DNodeSoil :1164-1238: horizon holding the layer's centre depth; surface: land unit + current pond
     hz_of = np.full((len(soils) + 1, nz), -1, np.int64)
     for k in np.unique(soil_index[soil_index >= 0]):
@@ -587,7 +688,8 @@ def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> M
                 link_to=cand_to[mask].astype(np.uint32), link_dir=cand_dir[mask], link_area=cand_area[mask],
                 soil_index=node_soil.astype(np.uint16), soils=[], psi0_surface=psi_surface, psi0_soil=par.initial_water_potential,
                 lv_ratio=par.conductivity_horiz_vert_ratio, numerics=numerics, cell_area=area, shape=(nx, ny, nz),
-                meta=dict(kind="project", layers=thick[1:], index=index, cell=cell, depth=depth, header=dict(inp.header)),
+                meta=dict(kind="project", layers=thick[1:], index=index, cell=cell, depth=depth, header=dict(inp.header),
+                          centre=centre, slope=slope_deg, geotechnics=geotechnics),
                 horizon_index=node_hz.astype(np.uint16), soil_table=soil_table, surface_index=su.astype(np.uint16),
                 surface_roughness=[float(u["roughness"]) for u in units], pond_node=pond)
     return mdl
@@ -604,6 +706,10 @@ def load_project_fixture(path) -> ProjectInputs:
     dem, hdr = esri.load_dem_fixture(path.parent / "ravone_dem_519x1208.npz")
     tables = json.loads(str(z["tables_json"]))
     soils = load_all_soils([tuple(r) for r in tables["soils"]], tables["horizons"], [tuple(r) for r in tables["van_genuchten"]])
+    geo_path = path.parent / "ravone_geotechnics.json"                  # the geotechnics table and the horizons' slope-stability columns
+    if geo_path.exists():
+        geo = json.loads(geo_path.read_text())
+        add_geotechnics(soils, tables["horizons"], [tuple(r) for r in tables["van_genuchten"]], geo["geotechnics"], geo["horizons"])
     units = [dict(id=r[0], id_landuse=r[3], id_crop=r[4], roughness=r[5], pond=r[6]) for r in tables["land_units"]]
     return ProjectInputs(dem=dem, soil_map=z["soil_map"].astype(np.float32), land_use=z["land_use"].astype(np.float32),
                          header=hdr, soils=soils, land_units=units, meta=dict(name="Ravone"))

@@ -1,0 +1,222 @@
+"""Output maps, the parts that need no GPU: the C entry points of include/sf3d_maps.h are exported by the product library and match the
+binding table, the geotechnics of the soil database (getUSCSClass, the fall-back of setHorizon), the layer stack the output depth lists
+map through, the restated factor of safety against closed-form values, and the resources of the new kernel (no scratch, full occupancy)."""
+import json
+import math
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import build, capi, maps
+from criteria3d_amd import project3d as p3
+
+ROOT = Path(__file__).resolve().parent.parent
+GOLDEN = ROOT / "tests" / "golden"
+
+
+def test_maps_header_and_binding_table_agree():
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_maps.h").read_text(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(sf3d_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(maps.SIGNATURES)
+    assert not set(declared) & set(capi.SIGNATURES)          # sf3d.h (the drop-in ABI the oracle exports too) is unchanged
+
+
+def test_product_library_exports_the_map_entry_points():
+    lib = build.build_product()
+    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert set(maps.SIGNATURES) <= names
+
+
+def test_variable_numbers_are_the_applications():
+    src = (ROOT / "include" / "sf3d_maps.h").read_text()
+    for name, value in [("VOLUMETRIC_WATER_CONTENT", 0), ("AVG_DEGREE_OF_SATURATION", 5), ("WATER_DEFICIT", 9), ("FACTOR_OF_SAFETY", 12),
+                        ("MINIMUM_FACTOR_OF_SAFETY", 13), ("SURFACE_POND", 14), ("MAX_VOLUMETRIC_WATER_CONTENT", 16)]:
+        assert re.search(rf"SF3D_MAP_{name} = {value}\b", src), name
+        assert getattr(maps, name) == value
+
+
+# ------------------------------------------------------------------------------------------------ USCS and the geotechnics fall-back
+
+@pytest.mark.parametrize("coarse, sand, silt, clay, name, om, want", [
+    (0.9, 5, 5, 2, "sand", 0.01, 1),                 # gravels, few fines: GW
+    (0.7, 5, 40, 55, "clay", 0.01, 3),              # gravels, fines >= 12 %: GM
+    (0.0, 90, 5, 5, "sand", 0.01, 8),               # sands: SP
+    (0.0, 80, 10, 10, "sandy loam", 0.01, 9),       # SM
+    (0.0, 80, 10, 10, "loamy sand", 0.01, 9),
+    (0.0, 60, 5, 35, "sandy clayloam", 0.01, 10),   # SC
+    (0.0, 60, 0, 40, "sandy clay", 0.01, 10),
+    (0.0, 85, 10, 5, "loam", 0.01, 9),              # sands, other name: SM (default)
+    (0.0, 40, 40, 20, "loam", 0.01, 12),            # fine: SC-CL
+    (0.0, 40, 40, 20, "loam", 0.3, 16),             # OL
+    (0.0, 30, 35, 35, "clayloam", 0.01, 14),        # CL
+    (0.0, 10, 55, 35, "silty clayloam", 0.25, 16),
+    (0.0, 10, 70, 20, "silt loam", 0.01, 12),       # clay >= 20: SC-CL
+    (0.0, 10, 80, 10, "silt", 0.01, 13),            # ML
+    (0.0, 10, 80, 10, "silt", 0.5, 16),
+    (0.0, 10, 30, 60, "clay", 0.01, 15),            # CH
+    (0.0, 5, 50, 45, "silty clay", 0.3, 17),        # OH
+    (0.0, 45, 35, 20, "other", 0.01, 13),           # fine default: ML
+    (0.0, 45, 35, 20, "other", 0.21, 16),
+])
+def test_uscs_class_every_branch(coarse, sand, silt, clay, name, om, want):
+    assert p3.uscs_class(coarse, sand, silt, clay, name, om) == want
+
+
+def _fixture():
+    z = np.load(GOLDEN / "ravone_project.npz", allow_pickle=False)
+    tables = json.loads(str(z["tables_json"]))
+    geo = json.loads((GOLDEN / "ravone_geotechnics.json").read_text())
+    return tables, geo
+
+
+def test_geotechnics_table_of_the_fixture():
+    _, geo = _fixture()
+    classes = p3.geotechnics_classes(geo["geotechnics"])
+    assert [c["code"] for c in classes[1:]] == ["GW", "GP", "GM", "GC", "GM-GL", "GC-CL", "SW", "SP", "SM", "SC", "SM-SL", "SC-CL", "ML",
+                                                 "CL", "CH", "OL", "OH", "MH"]
+    assert min(c["effective_cohesion"] for c in classes[1:]) == 0 and max(c["effective_cohesion"] for c in classes[1:]) == 25
+    assert min(c["friction_angle"] for c in classes[1:]) == 22 and max(c["friction_angle"] for c in classes[1:]) == 40
+    with pytest.raises(ValueError):
+        p3.geotechnics_classes(geo["geotechnics"][:17])
+
+
+def test_every_ravone_horizon_takes_its_uscs_class_row():
+    tables, geo = _fixture()
+    # the database holds no explicit value: NULL (1 767) or '' (23) in both columns
+    vals = [v for rows in geo["horizons"].values() for r in rows for v in r[1:]]
+    assert len(vals) == 2 * 1790 and all(v in (None, "") for v in vals)
+    assert sum(1 for rows in geo["horizons"].values() for r in rows if r[1] == "") == 23
+    vg = [tuple(r) for r in tables["van_genuchten"]]
+    soils = p3.load_all_soils([tuple(r) for r in tables["soils"]], tables["horizons"], vg)
+    p3.add_geotechnics(soils, tables["horizons"], vg, geo["geotechnics"], geo["horizons"])
+    classes = p3.geotechnics_classes(geo["geotechnics"])
+    n = 0
+    for s in soils:
+        for h in s["horizons"]:
+            assert 1 <= h["class_uscs"] <= 18
+            assert h["effective_cohesion"] == classes[h["class_uscs"]]["effective_cohesion"]
+            assert h["friction_angle"] == classes[h["class_uscs"]]["friction_angle"]
+            n += 1
+    assert n > 1600
+
+
+def test_explicit_database_values_win_over_the_class_table():
+    tables, geo = _fixture()
+    textures = p3.texture_classes([tuple(r) for r in tables["van_genuchten"]])
+    classes = p3.geotechnics_classes(geo["geotechnics"])
+    raw = dict(horizon_nr=1, upper_depth=0, lower_depth=30, sand=30, silt=35, clay=35, coarse_fragment=0, organic_matter=1.5,
+               bulk_density=1.3, theta_sat="", k_sat="")
+    row = p3.convert_horizon_row(raw)
+    ok, h = p3.set_horizon(row, textures)
+    assert ok and textures[h["class_usda"]]["name"] == "clayloam"
+    for coh, fri, want in [(p3.db_double("12.5"), p3.db_double(None), (12.5, 27.0)), (p3.db_double(""), p3.db_double(31), (20.0, 31.0)),
+                           (p3.db_double(None), p3.db_double(None), (20.0, 27.0)), (0.0, 0.0, (0.0, 0.0))]:
+        g = p3.horizon_geotechnics(dict(row, effective_cohesion=coh, friction_angle=fri), h, textures, classes)
+        assert g["class_uscs"] == 14 and (g["effective_cohesion"], g["friction_angle"]) == want
+
+
+# ------------------------------------------------------------------------------------------------ layers and depth lists
+
+def test_soil_layer_index_on_the_ravone_layer_stack():
+    thick, centre = p3.soil_layers(0.95)
+    assert len(thick) == 14 and thick[0] == 0.0
+    assert p3.soil_layer_index(thick, centre, -0.01) == int(p3.NODATA)
+    assert p3.soil_layer_index([], [], 0.1) == int(p3.NODATA)
+    assert p3.soil_layer_index(thick, centre, 0.0) == 0
+    assert p3.soil_layer_index(thick, centre, 1.0) == int(p3.NODATA)
+    for layer in range(1, len(thick)):
+        top, bottom = centre[layer] - thick[layer] * 0.5, p3.soil_layer_bottom(thick, centre, layer)
+        assert p3.soil_layer_index(thick, centre, bottom) == layer
+        assert p3.soil_layer_index(thick, centre, (top + bottom) / 2) == layer
+    # the depth lists of an output section, in cm (Project3D::setVariableDepth): 2 cm is the first soil layer's bottom
+    got = [p3.soil_layer_index(thick, centre, d * 0.01) for d in (1, 2, 3, 10, 30, 50, 80, 94)]
+    assert got == sorted(got) and got[0] == got[1] == 1 and got[2] == 2 and got[-1] == len(thick) - 1
+
+
+def test_output_point_values_follow_the_depth_list():
+    thick, centre = p3.soil_layers(0.95)
+    nz, ny, nx = len(thick), 3, 4
+    hdr = dict(xllcorner=1000.0, yllcorner=2000.0, cellsize=5.0, nrows=ny, ncols=nx)
+
+    class M:                                                    # the model attributes output_point_values reads
+        meta = dict(layers=thick[1:], centre=centre, header=hdr)
+    mp = np.arange(nz * ny * nx, dtype=np.float32).reshape(nz, ny, nx)
+    mp[3, 0, 1] = p3.NODATA
+    pts = [(1000.0 + 5.0 * 1 + 2.5, 2000.0 + 5.0 * 2 + 0.1), (999.0, 2000.0)]      # row 0 col 1; outside the grid
+    out = maps.output_point_values(mp, pts, [2, 5, 96], M)
+    l5 = p3.soil_layer_index(thick, centre, 0.05)
+    assert out[0, 0] == mp[1, 0, 1] and out[0, 1] == (p3.NODATA if l5 == 3 else mp[l5, 0, 1]) and out[0, 2] == np.float32(p3.NODATA)
+    assert np.all(out[1] == np.float32(p3.NODATA))
+    with pytest.raises(ValueError):
+        maps.output_point_values(mp, pts, [0], M)
+
+
+# ------------------------------------------------------------------------------------------------ the factor of safety, restated
+
+def test_factor_of_safety_restatement_on_one_column_against_closed_form():
+    # one cell, surface node 0 with 4 mm of water, soil nodes 1..3 of 0.1 m
+    index = np.array([0, 1, 2, 3]).reshape(4, 1, 1)
+    thick = [0.0, 0.1, 0.1, 0.1]
+    wc = np.array([0.004, 0.30, 0.35, 0.40])
+    dos = np.array([0.0, 0.6, 0.8, 1.0])
+    mpot = np.array([0.004, -2.0, -0.5, 0.3])                  # the bottom node saturated (psi > 0: no suction)
+    geo = dict(cohesion=np.array([np.nan, 5.0, 5.0, 20.0]), tan_friction=np.array([np.nan] + [math.tan(30 * p3.DEG_TO_RAD)] * 3),
+               bulk_density=np.array([np.nan, 1.3, 1.4, 1.5]))
+    slope = 25.0
+    tan_a, sin2 = maps.slope_terms(np.array([[slope]], np.float32), False)
+    angle = slope * p3.DEG_TO_RAD
+    assert tan_a[0, 0] == math.tan(angle) and sin2[0, 0] == math.sin(2 * angle)
+    g = p3.GRAVITY
+    for layer in (1, 2, 3):
+        w = 0.004 * g + sum((geo["bulk_density"][l] + wc[l]) * g * thick[l] for l in range(1, layer + 1))
+        tf = geo["tan_friction"][layer]
+        suction = min(0.0, mpot[layer] * g) * dos[layer]
+        want = tf / math.tan(angle) + 2 * geo["cohesion"][layer] / (w * math.sin(2 * angle)) \
+            - suction * (math.tan(angle) + 1 / math.tan(angle)) * tf / w
+        got = maps.restate_factor_of_safety(index, thick, layer, tan_a, sin2, geo, wc, dos, mpot)[0, 0]
+        assert got == float(np.float32(got)) and abs(got - want) <= 1e-6 * abs(want), (layer, got, want)
+    # a cohesionless, dry, flat-topped column: FoS = tan(phi) / tan(slope)
+    geo0 = dict(geo, cohesion=np.zeros(4))
+    got = maps.restate_factor_of_safety(index, thick, 1, tan_a, sin2, geo0, wc, dos, np.zeros(4))[0, 0]
+    assert got == float(np.float32(math.tan(30 * p3.DEG_TO_RAD) / math.tan(angle)))
+    # increaseSlope: x 1.5, capped at 89 degrees; a flat cell is clamped to EPSILON
+    t, s = maps.slope_terms(np.array([25.0, 70.0, 0.0], np.float32), True)
+    assert t[0] == math.tan(37.5 * p3.DEG_TO_RAD) and t[1] == math.tan(89 * p3.DEG_TO_RAD) and t[2] == max(p3.EPSILON, math.tan(p3.EPSILON))
+    # the minimum over layers >= 1, and the missing-node flag
+    mn = maps.restate_minimum_fos(index, thick, tan_a, sin2, geo, wc, dos, mpot)
+    per = [maps.restate_factor_of_safety(index, thick, l, tan_a, sin2, geo, wc, dos, mpot)[0, 0] for l in (1, 2, 3)]
+    assert mn[0, 0] == np.float32(min(per))
+    hole = index.copy(); hole[2] = -1
+    assert maps.restate_fos_map(hole, thick, 2, tan_a, sin2, geo, wc, dos, mpot, flag=-1.0)[0, 0] == -1.0
+    # the average degree of saturation as written: (sum theta dz - sum thetaR dz) / (sum thetaS dz - sum thetaR dz)
+    wmin, wmax = np.array([-1111.0, 0.05, 0.05, 0.05]), np.array([-1111.0, 0.45, 0.45, 0.45])
+    avg = maps.restate_avg_degree_of_saturation(index, thick, wc, wmin, wmax)
+    sw = sum(wc[l] * 0.1 for l in (1, 2, 3)); sr = sum(0.05 * 0.1 for _ in range(3)); ss = sum(0.45 * 0.1 for _ in range(3))
+    assert avg[0, 0] == np.float32((sw - sr) / (ss - sr))
+
+
+# ------------------------------------------------------------------------------------------------ kernel resources
+
+LLVM = Path("/opt/rocm/lib/llvm/bin")
+
+
+def test_output_map_kernel_has_no_scratch_and_full_occupancy(tmp_path):
+    if not (LLVM / "llvm-objdump").exists() or not (LLVM / "llvm-readelf").exists():
+        pytest.skip("no llvm-objdump / llvm-readelf in this image")
+    lib = build.build_product()
+    so = tmp_path / "libsf3d_hip.so"
+    shutil.copy(lib, so)
+    subprocess.run([str(LLVM / "llvm-objdump"), "--offloading", str(so)], check=True, capture_output=True, cwd=tmp_path)
+    co = [p for p in tmp_path.iterdir() if "gfx950" in p.name]
+    notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co[0])], check=True, capture_output=True, text=True).stdout
+    blk = [b for b in re.split(r"\n  - \.agpr_count:", notes)[1:] if re.search(r"\.name:\s+_Z12k_output_map7MapView\b", b)]
+    assert len(blk) == 1
+    g = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", blk[0]).group(1))
+    assert g("private_segment_fixed_size") == 0
+    assert g("vgpr_count") <= 64                     # 8 waves per SIMD: a streaming kernel keeps full occupancy
+    assert g("group_segment_fixed_size") * 8 <= 160 * 1024        # 8 blocks of 256 threads per CU
