@@ -370,14 +370,10 @@ template <class T> void reset(std::vector<T>& v, size_t n) { v.assign(n, T()); }
 #define NEED_NODE_D(i) if ((i) >= M.N) return errValue(SF3D_INDEX_ERROR); else if (skippedByTrim(i)) return (double)SF3D_NODATA; else (void)0
 
 void mapsClear();                               /* sf3d_maps_api.inc: what include/sf3d_maps.h set belongs to one model */
+void snowClear();                               /* sf3d_snow_api.inc: the snow maps belong to the raster - sf3d_clean frees them, sf3d_initialize keeps them */
 
-}  // namespace
-
-extern "C" {
-
-const char* sf3d_backend_name(void) { return "hip"; }
-
-sf3d_error_t sf3d_clean(void)                                       /* soilFluxes3D.cpp:218-304 */
+/* the model's part of sf3d_clean */
+sf3d_error_t cleanModel()
 {
     mapsClear();
     if (!M.initialized) return SF3D_OK;
@@ -387,9 +383,21 @@ sf3d_error_t sf3d_clean(void)                                       /* soilFluxe
     return SF3D_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+const char* sf3d_backend_name(void) { return "hip"; }
+
+sf3d_error_t sf3d_clean(void)                                       /* soilFluxes3D.cpp:218-304 */
+{
+    snowClear();
+    return cleanModel();
+}
+
 sf3d_error_t sf3d_initialize(uint32_t n, uint32_t ns, uint8_t nLat, int w, int h, int s, sf3d_heat_save_t saveMode)   /* :49-178 */
 {
-    sf3d_error_t c = sf3d_clean();
+    sf3d_error_t c = cleanModel();
     if (c != SF3D_OK) return c;
     M.water = w != 0; M.heat = h != 0; M.solutes = s != 0;
     { const char* ce = getenv("SF3D_COMPAT_STALE_LINK_FLOW"); M.compat = ce && ce[0] == '1'; }
@@ -1167,3 +1175,4 @@ sf3d_error_t sf3d_device_pow(uint32_t count, const double* x, const double* y, d
 } /* extern "C" */
 
 #include "sf3d_maps_api.inc"
+#include "sf3d_snow_api.inc"

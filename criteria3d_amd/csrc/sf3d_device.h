@@ -419,6 +419,24 @@ struct MapView {
     int* missing;                       /* set to 1 by a cell whose factor of safety needs a class without geotechnics */
 };
 
+/* ---- hourly snow model (sf3d_snow.inc, include/sf3d_snow.h): one thread per raster cell ---- */
+struct SnowParamsDev {  /* Crit3DSnowParameters (src/snow/snow.h:29-43) and the hour's clear-sky transmissivity */
+    double skinThickness, soilAlbedo, snowVegetationHeight, snowWaterHoldingCapacity, tempMaxWithSnow, tempMinWithRain, snowSurfaceDampingDepth;
+    double clearSky;
+};
+/* the device block of the snow maps: SNOW_MAPS maps of nCells floats */
+enum { SNOW_MAP_STATE = 0, SNOW_MAP_OUT = 7, SNOW_MAP_IN = 13, SNOW_MAP_DEM = 21, SNOW_MAPS = 22 };
+struct SnowView {
+    float* st[7];                       /* SWE, ice, liquid water, internal energy, surface energy, surface temperature, age of snow */
+    float* out[6];                      /* snowfall, snowmelt, delta SWE, sensible heat, latent heat, liquid water to the soil surface */
+    const float* in[8];                 /* air temperature, precipitation, relative humidity, wind, global / beam radiation, transmissivity, surface water (null: 0) */
+    const float* dem;
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    uint32_t nCells;
+    float flag;
+    SnowParamsDev p;
+};
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 

@@ -132,6 +132,9 @@ struct MapsCache {
     }
 };
 
+/* hourly snow model (sf3d_snow.inc): the maps of include/sf3d_snow.h; they belong to the raster and stay when the model is released */
+struct SnowCache { float* base = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0; double lastMs = 0.; };
+
 struct DeviceSolver::Impl {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -251,6 +254,7 @@ struct DeviceSolver::Impl {
     uint64_t launches[KID_COUNT] = {0};
     double ms[KID_COUNT] = {0};
     MapsCache maps;
+    SnowCache snow;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the
@@ -351,7 +355,7 @@ static void fill_params(Ctrl& c, const ParamsHost& p)
     c.lineal = p.lineal ? 1u : 0u;
 }
 
-sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
+sf3d_error_t DeviceSolver::ensure_device()
 {
     if (!impl_) impl_ = new Impl();
     Impl& I = *impl_;
@@ -375,6 +379,13 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
     }
     HIP_TRY(hipSetDevice(I.device));
     if (!I.stream) HIP_TRY(hipStreamCreateWithFlags(&I.stream, hipStreamNonBlocking));
+    return SF3D_OK;
+}
+
+sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
+{
+    { const sf3d_error_t e = ensure_device(); if (e != SF3D_OK) return e; }
+    Impl& I = *impl_;
     if ((I.linksPending[0] || I.linksPending[1]) && (m.graphDirty || m.stateDirty || m.flowSumsDirty || !built_)) { HIP_TRY(hipStreamSynchronize(I.stream2)); I.linksPending[0] = I.linksPending[1] = false; }
     if (!I.hostCtrl) HIP_TRY(hipHostMalloc((void**)&I.hostCtrl, sizeof(Ctrl), hipHostMallocDefault));
 

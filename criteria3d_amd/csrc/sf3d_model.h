@@ -198,6 +198,15 @@ public:
     /* output maps (sf3d_maps.inc): variable `var` of criteria3DVariable on layer `layer` (-1: all) of the accepted state -> out (floats);
      * *missing = 1 when a factor of safety needed a soil class without geotechnics */
     sf3d_error_t output_map(HostModel& m, const ParamsHost& p, const MapsInput& in, int var, int layer, float flag, float* out, int* missing);
+    /* hourly snow model (sf3d_snow.inc): SNOW_MAPS float maps of nCells on the device, independent of the node model (release() keeps
+     * them); map = index into the block (SNOW_MAP_*) */
+    sf3d_error_t ensure_device();                /* device choice and the solver's stream, without a model */
+    sf3d_error_t snow_alloc(uint32_t nCells);
+    sf3d_error_t snow_upload(int map, const float* src);
+    sf3d_error_t snow_download(int map, float* dst);
+    sf3d_error_t snow_hour(const float* const in[8], const SnowParamsDev& p, float flag, const uint8_t* mine);
+    sf3d_error_t snow_free();
+    double snow_kernel_ms() const;
 
 private:
     DeviceSolver() = default;

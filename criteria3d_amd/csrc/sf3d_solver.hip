@@ -46,3 +46,4 @@
 #include "sf3d_host_build.inc"
 #include "sf3d_host_step.inc"
 #include "sf3d_maps.inc"
+#include "sf3d_snow.inc"

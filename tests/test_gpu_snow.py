@@ -1,0 +1,252 @@
+"""The hourly snow model on the device (include/sf3d_snow.h, k_snow_hour) against the compiled-reference pin tests/golden/snow_brooks.npz:
+all thirteen maps after every checkpoint hour bit for bit, zero cells excluded; the same run interrupted at hour 48 through get_state /
+set_state and through the application's snow/ state folder; the solver does not notice the calls; a melt hour's liquid water drives the
+product and the oracle to the same state; two ranks sharing the GPU merge to the single-rank maps; the error codes."""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import capi, catchment as cm, maps, snow
+from tests import tolerances
+from tests.scenarios import ravone_project_model
+from tests.snow_cases import melt_forcing
+
+pytestmark = pytest.mark.gpu
+ROOT = Path(__file__).resolve().parent.parent
+PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
+WINDOW = (980, 1108, 300, 428)          # the 128 x 128 project window of the output-map tests
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def pin():
+    z = np.load(PIN)
+    return {k: z[k] for k in z.files}
+
+
+def _need_glibc_set(product):
+    if product.lib.sf3d_libm_set() != 1:
+        pytest.skip("this build evaluates the 0.50-ulp routines, not the C library's bits (-DSF3D_LIBM_GLIBC=0): bit identity with the compiled reference is not its contract")
+
+
+def _meteo(pin, h):
+    m = {n: pin["inputs"][h, k] for k, n in enumerate(snow.INPUT)}
+    m["clearSkyTransmissivity"] = float(pin["clear_sky"])
+    return m
+
+
+def _start(product, pin):
+    flag = float(pin["flag"])
+    snow.initialize(product, pin["dem"], flag)
+    edit = pin["swe_edit"]
+    swe = snow.get_state(product, "swe")
+    snow.set_state(product, "swe", np.where(edit == np.float32(flag), swe, edit))      # the hand-edited SWE map of the pin, no reset
+    edit = pin["surface_temp_edit"]
+    snow.set_state(product, "surfaceTemp", np.where(edit == np.float32(flag), snow.get_state(product, "surfaceTemp"), edit))
+
+
+def _compare(product, pin, k, what):
+    names = [str(n) for n in pin["map_names"]]
+    got = snow.all_maps(product)
+    for j, n in enumerate(names):
+        want = pin["maps"][k][j]
+        bad = _bits(got[n]) != _bits(want)
+        print(f"{what} hour {int(pin['checkpoints'][k])} {n}: {int(bad.sum())} cells differ")
+        assert not bad.any(), (what, int(pin["checkpoints"][k]), n, int(bad.sum()), got[n][bad][:4], want[bad][:4])
+
+
+def test_initial_maps_equal_the_reference(product, pin):
+    snow.initialize(product, pin["dem"], float(pin["flag"]))
+    got = snow.all_maps(product)
+    for j, n in enumerate(str(n) for n in pin["map_names"][:12]):
+        assert np.array_equal(_bits(got[n]), _bits(pin["initial"][j])), n
+    snow.clean(product)
+
+
+def test_all_thirteen_maps_equal_the_pin_at_every_checkpoint(product, pin):
+    _need_glibc_set(product)
+    _start(product, pin)
+    cps = [int(c) for c in pin["checkpoints"]]
+    for h in range(int(cps[-1])):
+        snow.compute_hour(product, _meteo(pin, h))
+        if h + 1 in cps:
+            _compare(product, pin, cps.index(h + 1), "uninterrupted")
+    snow.clean(product)
+
+
+@pytest.mark.parametrize("how", ["get_set_state", "state_directory"])
+def test_interrupted_run_equals_the_uninterrupted_one(product, pin, tmp_path, how):
+    _need_glibc_set(product)
+    _start(product, pin)
+    for h in range(48):
+        snow.compute_hour(product, _meteo(pin, h))
+    header = dict(xllcorner=0.0, yllcorner=0.0, cellsize=4.0, nodata=float(pin["flag"]))
+    if how == "get_set_state":
+        saved = {n: snow.get_state(product, n) for n in snow.STATE}
+    else:
+        d = snow.save_snow_state(product, tmp_path, header)
+        assert sorted(p.name for p in d.iterdir()) == sorted(f"{s}{e}" for s in snow.STATE_FILES.values() for e in (".flt", ".hdr"))
+    snow.clean(product)
+    snow.initialize(product, pin["dem"], float(pin["flag"]))
+    if how == "get_set_state":
+        for n, v in saved.items():
+            snow.set_state(product, n, v)
+    else:
+        snow.load_snow_state(product, tmp_path)
+    cps = [int(c) for c in pin["checkpoints"]]
+    for h in range(48, 96):
+        snow.compute_hour(product, _meteo(pin, h))
+        if h + 1 in cps:
+            _compare(product, pin, cps.index(h + 1), how)
+    snow.clean(product)
+
+
+def test_snow_calls_leave_the_solver_untouched(product, pin):
+    """C2 in its F20 hour, a snow hour between every two computeSteps: H, Se and the work counters of the run without"""
+    def run(with_snow):
+        m = cm.catchment_model(64, 64, 10)
+        product.check(product.lib.sf3d_reset_solver_state(), "reset")
+        cm.build(product, m, threads=1)
+        if with_snow:
+            _start(product, pin)
+        product.set_sink_source_bulk(0, np.full(m.ns, cm.rain_rate(20.0, m.cell_area)))
+        t, k = 0.0, 0
+        while t < 3600.0:
+            dt = product.lib.sf3d_compute_step(3600.0 - t)
+            assert dt > 0.0
+            t += dt
+            if with_snow:
+                snow.compute_hour(product, _meteo(pin, k % 96))
+                if k % 5 == 0:
+                    snow.get_output(product, "liquid")
+            k += 1
+        s, c = cm.snapshot(product, m), product.counters()
+        if with_snow:
+            assert np.count_nonzero(snow.get_state(product, "swe") > 0) > 0
+        product.lib.sf3d_clean()
+        return s, c
+    (s0, c0), (s1, c1) = run(False), run(True)
+    assert np.array_equal(s0["H"], s1["H"]) and np.array_equal(s0["Se"], s1["Se"])
+    assert c0 == c1
+
+
+def test_snow_state_survives_sf3d_initialize_and_goes_with_sf3d_clean(product, pin):
+    _start(product, pin)
+    snow.compute_hour(product, _meteo(pin, 0))
+    before = snow.get_state(product, "surfaceTemp")
+    m = cm.catchment_model(16, 16, 4)
+    product.check(product.lib.sf3d_reset_solver_state(), "reset")
+    cm.build(product, m, threads=1)                                   # sf3d_initialize inside
+    assert np.array_equal(_bits(snow.get_state(product, "surfaceTemp")), _bits(before))
+    product.lib.sf3d_clean()
+    out = np.empty(before.size, np.float32)
+    assert product.lib.sf3d_snow_get_state(0, out.size, out.ctypes.data_as(snow.pf32)) == capi.MEMORY_ERROR
+
+
+def test_melt_hour_drives_product_and_oracle_to_the_same_state(product, oracle):
+    m = ravone_project_model(WINDOW)
+    idx = np.asarray(m.meta["index"])[0]
+    flag = -9999.0
+    dem = np.where(idx >= 0, m.z[np.maximum(idx, 0)], flag).astype(np.float32)
+    snow.initialize(product, dem, flag)
+    for met in melt_forcing(dem.shape, dem, flag):
+        snow.compute_hour(product, met)
+    liquid, melt = snow.get_output(product, "liquid"), snow.get_output(product, "snowMelt")
+    assert np.count_nonzero(melt[idx >= 0] > 0) > 0.9 * np.count_nonzero(idx >= 0)
+    assert np.all(liquid[idx < 0] == np.float32(flag))
+    q = snow.surface_sources(m, liquid, flag)
+    assert np.count_nonzero(q) == np.count_nonzero((idx >= 0) & (liquid > 0)) and np.all(q[m.ns:] == 0)
+    snow.clean(product)
+    snaps = []
+    for sf in (product, oracle):
+        sf.check(sf.lib.sf3d_reset_solver_state(), "reset")
+        cm.build(sf, m, threads=16)
+        cm.run_hour_sinks(sf, m, q, max_steps=150)
+        snaps.append(cm.snapshot(sf, m))
+        sf.lib.sf3d_clean()
+    tolerances.assert_water_nodes(snaps[0]["H"], snaps[1]["H"], "H after the melt hour")
+    tolerances.assert_water_nodes(snaps[0]["Se"], snaps[1]["Se"], "Se after the melt hour")
+
+
+def test_two_ranks_merge_to_the_single_rank_maps(product, tmp_path):
+    world, port, hours = 2, 29761, 16
+    outs = [tmp_path / f"snow_r{r}.npz" for r in range(world)]
+    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
+    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_snow_worker.py"), str(r), str(world), str(port), str(hours), str(outs[r])],
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
+    logs = []
+    for pr in procs:
+        try:
+            o, _ = pr.communicate(timeout=300)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        logs.append(o)
+    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
+    ranks = [np.load(o) for o in outs]
+    m = ravone_project_model((980, 1060, 330, 420))
+    idx = np.asarray(m.meta["index"])[0]
+    flag = -9999.0
+    dem = np.where(idx >= 0, m.z[np.maximum(idx, 0)], flag).astype(np.float32)
+    snow.initialize(product, dem, flag)
+    for met in melt_forcing(dem.shape, dem, flag)[:hours]:
+        snow.compute_hour(product, met)
+    single = snow.all_maps(product)
+    snow.clean(product)
+    owner = np.full(m.n, 255, np.int64)
+    for r, res in enumerate(ranks):
+        owner[res["owner"] == r] = r
+    cell_owner = np.where(idx >= 0, owner[np.maximum(idx, 0)], 255)
+    assert set(np.unique(cell_owner[idx >= 0])) == {0, 1}
+    for n in snow.OUTPUT:
+        merged = np.full(dem.shape, np.float32(flag), np.float32)
+        for r, res in enumerate(ranks):
+            assert np.all(res[n][cell_owner != r] == np.float32(flag)), (n, r)       # another rank's cells: the flag
+            merged[cell_owner == r] = res[n][cell_owner == r]
+        assert np.array_equal(_bits(merged), _bits(single[n])), n
+    for n in snow.STATE:
+        for r, res in enumerate(ranks):
+            mine = cell_owner == r
+            assert np.array_equal(_bits(res[n][mine]), _bits(single[n][mine])), (n, r)
+            assert np.array_equal(_bits(res[n][~mine]), _bits(ranks[r]["initial_" + n][~mine])), (n, r)      # untouched elsewhere
+
+
+def test_error_paths(product, pin):
+    snow.bind(product)
+    lib = product.lib
+    n = pin["dem"].size
+    buf = np.zeros(n, np.float32)
+    p = buf.ctypes.data_as(snow.pf32)
+    lib.sf3d_snow_clean()
+    seven = [p] * 7
+    assert lib.sf3d_snow_get_state(0, n, p) == capi.MEMORY_ERROR                                    # before initialise
+    assert lib.sf3d_snow_set_state(0, n, p) == capi.MEMORY_ERROR
+    assert lib.sf3d_snow_get_output(0, n, p) == capi.MEMORY_ERROR
+    assert lib.sf3d_snow_compute_hour(n, *seven, None, 0.75) == capi.MEMORY_ERROR
+    assert lib.sf3d_snow_reset() == capi.MEMORY_ERROR
+    assert lib.sf3d_snow_initialize(0, 4, p, -9999.0, None) == capi.PARAMETER_ERROR
+    assert lib.sf3d_snow_initialize(4, 4, None, -9999.0, None) == capi.PARAMETER_ERROR
+    assert lib.sf3d_snow_default_parameters(None) == capi.PARAMETER_ERROR
+    snow.initialize(product, pin["dem"], float(pin["flag"]))
+    assert lib.sf3d_snow_get_state(0, n - 1, p) == capi.PARAMETER_ERROR                             # wrong size
+    assert lib.sf3d_snow_set_state(0, n + 1, p) == capi.PARAMETER_ERROR
+    assert lib.sf3d_snow_compute_hour(n // 2, *seven, None, 0.75) == capi.PARAMETER_ERROR
+    assert lib.sf3d_snow_get_state(0, n, None) == capi.PARAMETER_ERROR                              # null pointer
+    assert lib.sf3d_snow_compute_hour(n, *seven[:6], None, None, 0.75) == capi.PARAMETER_ERROR
+    assert lib.sf3d_snow_get_state(7, n, p) == capi.INDEX_ERROR
+    assert lib.sf3d_snow_get_output(6, n, p) == capi.INDEX_ERROR
+    assert lib.sf3d_snow_set_state(-1, n, p) == capi.INDEX_ERROR
+    assert lib.sf3d_snow_get_state(0, n, p) == capi.OK
+    with pytest.raises(ValueError):
+        snow.set_state(product, "swe", np.zeros((3, 3), np.float32))
+    assert lib.sf3d_snow_clean() == capi.OK
+    assert lib.sf3d_snow_get_state(0, n, p) == capi.MEMORY_ERROR                                    # after clean
+    assert lib.sf3d_snow_compute_hour(n, *seven, None, 0.75) == capi.MEMORY_ERROR

@@ -1,0 +1,172 @@
+"""The hourly snow model, the parts that need no GPU: the C entry points of include/sf3d_snow.h and the binding table, the error codes a
+call gives before a raster exists, the fixture (a pin of the compiled reference) is not vacuous, the python restatement of the point
+model equals it bit for bit over all 96 hours, the per-node sources of assignPrecipitation, the snow/ state folder."""
+import re
+import subprocess
+from pathlib import Path
+from types import SimpleNamespace
+
+import numpy as np
+
+from criteria3d_amd import build, capi, esri, snow
+
+ROOT = Path(__file__).resolve().parent.parent
+PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def test_snow_header_and_binding_table_agree():
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_snow.h").read_text(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(sf3d_snow_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(snow.SIGNATURES)
+    assert not set(declared) & set(capi.SIGNATURES)          # sf3d.h (the drop-in ABI) is unchanged
+    for k, n in enumerate(("SWE", "ICE_CONTENT", "LW_CONTENT", "INTERNAL_ENERGY", "SURFACE_ENERGY", "SURFACE_TEMP", "AGE_OF_SNOW")):
+        assert re.search(rf"SF3D_SNOW_{n} = {k}\b", text) and getattr(snow, n) == k
+    for k, n in enumerate(("SNOW_FALL", "SNOW_MELT", "DELTA_SWE", "SENSIBLE_HEAT", "LATENT_HEAT", "LIQUID_WATER")):
+        assert re.search(rf"SF3D_SNOW_OUT_{n} = {k}\b", text) and getattr(snow, n) == k
+
+
+def test_product_library_exports_the_snow_entry_points():
+    lib = build.build_product()
+    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert set(snow.SIGNATURES) <= names
+
+
+def test_error_codes_without_a_raster_and_default_parameters():
+    sf = snow.bind(capi.load_product())
+    buf = np.zeros(16, np.float32)
+    p = buf.ctypes.data_as(snow.pf32)
+    assert sf.lib.sf3d_snow_get_state(0, 16, p) == capi.MEMORY_ERROR
+    assert sf.lib.sf3d_snow_set_state(0, 16, p) == capi.MEMORY_ERROR
+    assert sf.lib.sf3d_snow_get_output(0, 16, p) == capi.MEMORY_ERROR
+    assert sf.lib.sf3d_snow_reset() == capi.MEMORY_ERROR
+    assert sf.lib.sf3d_snow_compute_hour(16, p, p, p, p, p, p, p, None, 0.75) == capi.MEMORY_ERROR
+    assert sf.lib.sf3d_snow_set_parameters(None) == capi.MEMORY_ERROR
+    assert sf.lib.sf3d_snow_initialize(0, 4, p, -9999.0, None) == capi.PARAMETER_ERROR
+    assert sf.lib.sf3d_snow_initialize(4, 4, None, -9999.0, None) == capi.PARAMETER_ERROR
+    assert sf.lib.sf3d_snow_clean() == capi.OK
+    par = snow.Parameters()
+    assert sf.lib.sf3d_snow_default_parameters(par) == capi.OK
+    assert {n: getattr(par, n) for n in snow.PARAMETER_NAMES} == snow.DEFAULT_PARAMETERS
+    assert sf.lib.sf3d_snow_kernel_ms() == 0.0
+
+
+def test_the_pin_is_not_vacuous():
+    z = np.load(PIN)
+    dem, flag = z["dem"], z["flag"]
+    assert dem.shape[0] <= 48 and dem.shape[1] <= 64 and PIN.stat().st_size < 1 << 20
+    valid = dem != flag
+    nv = int(valid.sum())
+    assert 0 < nv < dem.size                                  # the window holds flag cells
+    names = [str(n) for n in z["map_names"]]
+    assert names == list(snow.STATE + snow.OUTPUT) and [str(n) for n in z["input_names"]] == list(snow.INPUT)
+    assert list(z["checkpoints"]) == [1, 24, 48, 72, 96] and z["inputs"].shape[0] == 96 and z["inputs"].dtype == np.float32
+    maps = z["maps"]
+    assert np.isfinite(maps).all() and np.isfinite(z["inputs"]).all()
+    swe, melt = maps[:, names.index("swe")], maps[:, names.index("snowMelt")]
+    assert max(int(((s > 0) & valid).sum()) for s in swe) * 4 >= nv
+    assert max(int(((s > 0) & valid).sum()) for s in melt) * 10 >= nv
+    assert int(((swe[-1] == 0) & valid).sum()) * 10 >= nv       # snow-free again at the end
+    arms = dict(zip((str(n) for n in z["arm_names"]), (int(c) for c in z["arm_counts"])))
+    assert len(arms) >= 30 and all(c > 0 for c in arms.values()), {k: c for k, c in arms.items() if c == 0}
+    for must in ("free water (> 100 mm)", "invalid point", "re-seeding a hand-edited SWE", "precipitation: mixed", "refreeze", "melt",
+                 "soil energy check: energy averaged", "cloud cover default (flag)", "dew point: no humidity (flag or 0)"):
+        assert arms[must] > 0, must
+    assert int(z["snow_water_equivalent_enum"]) == snow.SNOW_WATER_EQUIVALENT_ENUM
+    assert dict(zip(snow.PARAMETER_NAMES, z["parameters"])) == snow.DEFAULT_PARAMETERS
+
+
+def test_restatement_equals_the_compiled_reference_for_all_96_hours():
+    z = np.load(PIN)
+    dem, flag, inp = z["dem"], float(z["flag"]), z["inputs"]
+    names = [str(n) for n in z["map_names"]]
+    cps = [int(c) for c in z["checkpoints"]]
+    init = snow.restate_reset(np.where(dem == np.float32(flag), np.float32(flag), np.float32(0)), flag)
+    for k, n in enumerate(names[:12]):
+        assert np.array_equal(_bits(init[n]), _bits(z["initial"][k])), n
+    state = {n: init[n] for n in snow.STATE}
+    edit = z["swe_edit"]
+    state["swe"] = np.where(edit == np.float32(flag), state["swe"], edit)
+    edit = z["surface_temp_edit"]
+    state["surfaceTemp"] = np.where(edit == np.float32(flag), state["surfaceTemp"], edit)
+    for h in range(96):
+        meteo = {n: inp[h, k] for k, n in enumerate(snow.INPUT)}
+        meteo["clearSkyTransmissivity"] = float(z["clear_sky"])
+        state = snow.restate_snow_hour(state, meteo, dem, flag)
+        if h + 1 in cps:
+            want = z["maps"][cps.index(h + 1)]
+            for k, n in enumerate(names):
+                bad = _bits(state[n]) != _bits(want[k])
+                assert not bad.any(), (h + 1, n, int(bad.sum()))
+
+
+def test_point_model_by_hand():
+    """cases small enough to follow with a pencil"""
+    p = snow.DEFAULT_PARAMETERS
+    soil = (0.0, 0.0, 0.0, 1927.8, 189.0, 5.0, snow.NODATA)
+    # free water and a missing input: NODATA, the internal energy stays, the melt getter gives 0
+    for inp in ((1.0, 0.0, 50.0, 1.0, 0.0, 0.0, 0.5, 150.0), (snow.NODATA, 0.0, 50.0, 1.0, 0.0, 0.0, 0.5, 0.0)):
+        s, o = snow.snow_point(soil, inp, 0.75, p)
+        assert s == (snow.NODATA, snow.NODATA, snow.NODATA, 1927.8, snow.NODATA, snow.NODATA, snow.NODATA)
+        assert o == (snow.NODATA, 0.0, snow.NODATA, snow.NODATA, snow.NODATA)
+    # computeSnowFall: all snow at -0.5, the linear mix at 0.75 (half), all rain at 2
+    for t, want in ((-0.5, 4.0), (0.75, 2.0), (2.0, 0.0)):
+        _, o = snow.snow_point(soil, (t, 4.0, 50.0, 1.0, 0.0, 0.0, 0.5, 0.0), 0.75, p)
+        assert o[0] == want
+    assert snow.t_dew_from_rel_hum(0.0, 5.0) == snow.NODATA and snow.t_dew_from_rel_hum(snow.NODATA, 5.0) == snow.NODATA
+    assert abs(snow.t_dew_from_rel_hum(100.0, 5.0) - 5.0) < 1e-9
+    # Campbell 1977 over snow at 1 m/s: ln(10.001 / 0.001) ln(2.0002 / 0.0002) / 0.41^2
+    import math
+    assert snow.aerodynamic_resistance(True, 10, 1.0, 1.0) == math.log((10 + 0.001) / 0.001) * math.log((2 + 0.0002) / 0.0002) / (0.41 * 0.41 * 1.0)
+    assert snow.aerodynamic_resistance(True, 10, 0.0, 1.0) == snow.aerodynamic_resistance(True, 10, 0.05, 1.0)
+    assert snow.aerodynamic_resistance(False, 10, 50.0, 1.0) == snow.aerodynamic_resistance(False, 10, 10.0, 1.0)
+
+
+def test_surface_sources_by_hand():
+    flag = -9999.0
+    index = np.array([[[0, 1, -1], [2, 3, 4]]])                # one layer: five surface nodes, one cell outside
+    model = SimpleNamespace(n=7, ns=5, meta=dict(index=index, cell=4.0))
+    liquid = np.array([[2.5, 0.0, 3.0], [flag, -0.25, np.float32(0.1)]], np.float32)
+    q = snow.surface_sources(model, liquid, flag)
+    assert q.shape == (7,) and q.dtype == np.float64
+    assert q[0] == 16.0 * (2.5 / 1000.0) / 3600.0               # area * (mm / 1000.) / 3600.
+    assert q[4] == 16.0 * (float(np.float32(0.1)) / 1000.0) / 3600.0      # the float map value, widened
+    assert q[1] == 0.0 and q[2] == 0.0 and q[3] == 0.0        # 0 mm, the flag, a negative balance: no source
+    assert np.all(q[5:] == 0.0)                                # soil nodes
+    try:
+        snow.surface_sources(model, liquid[:1], flag)
+        raise AssertionError("shape mismatch accepted")
+    except ValueError:
+        pass
+
+
+def test_state_directory_round_trip(tmp_path):
+    # the binding's get_state / set_state over a dict
+    z = np.load(PIN)
+    names = [str(n) for n in z["map_names"]]
+    maps = {n: z["maps"][2][names.index(n)] for n in snow.STATE}
+    got = {}
+    sf = SimpleNamespace(_snow_shape=z["dem"].shape, check=lambda code, what="": None,
+                         lib=SimpleNamespace(sf3d_snow_get_state=None, sf3d_snow_set_state=None))
+    def get_state(which, size, ptr):
+        np.ctypeslib.as_array(ptr, shape=(size,))[:] = maps[snow.STATE[which]].ravel()
+        return 0
+    def set_state(which, size, ptr):
+        got[snow.STATE[which]] = np.ctypeslib.as_array(ptr, shape=(size,)).copy().reshape(z["dem"].shape)
+        return 0
+    sf.lib.sf3d_snow_get_state, sf.lib.sf3d_snow_set_state = get_state, set_state
+    header = dict(xllcorner=683768.0, yllcorner=4928326.0, cellsize=4.0, nodata=-9999.0)
+    d = snow.save_snow_state(sf, tmp_path, header)
+    assert d == tmp_path / "snow"
+    assert sorted(p.name for p in d.iterdir()) == sorted(f"{s}{e}" for s in ("SWE", "AgeOfSnow", "SnowSurfaceTemp", "IceContent", "LWContent",
+                                                                            "InternalEnergy", "SurfaceInternalEnergy") for e in (".flt", ".hdr"))
+    grid, hdr = esri.read_grid(d / "SWE")
+    assert hdr["cellsize"] == 4.0 and hdr["nodata"] == -9999.0 and np.array_equal(_bits(grid), _bits(maps["swe"]))
+    snow.load_snow_state(sf, tmp_path)
+    assert sorted(got) == sorted(snow.STATE)
+    for n in snow.STATE:
+        assert np.array_equal(_bits(got[n]), _bits(maps[n])), n
