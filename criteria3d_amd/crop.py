@@ -1,0 +1,372 @@
+"""The hourly reference evapotranspiration and the daily crop maps of the application on the device (include/sf3d_crop.h,
+criteria3d_amd/csrc/sf3d_crop.inc): what `Crit3DProject::runModelHour` (bin/CRITERIA3D/criteria3DProject.cpp:2130-2153) does between the
+snow model and the solver - `computeET0PMMap` (agrolib/project/meteoMaps.cpp:238-271) over `ET0_Penman_hourly`
+(agrolib/meteo/meteo.cpp:550-609), `updateDailyTemperatures` (:1994-2018) - and once a day `dailyUpdateCropMaps` (:576-640): degree days
+and `Crit3DCrop::computeSimpleLAI` (agrolib/crop/crop.cpp:161-224, development.cpp:117-154).
+
+Three parts:
+  * the binding (`bind`, `initialize`, `compute_hour`, `daily_update`, `get_state` ...): the maps live on the device, k_et0_hour advances
+    them by one hour and k_crop_day by one day; a missing kernel or library is an error;
+  * the application's state as a `crop/` folder of ESRI float grids (`save_crop_state` / `load_crop_state`) for a resumed run;
+  * `restate_et0_hour`, `restate_daily_temperatures`, `restate_crop_day` (and `restate_degree_days`): the point models on whole maps in
+    numpy, with the reference's operation order and the C library's exp / log / pow (python's `math`) - the checker of the CPU tests
+    against the compiled-reference pin (tests/golden/crop_et0.npz) and the host figure of scripts/crop_timing.py.  A checker, never a
+    fallback."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from pathlib import Path
+
+import numpy as np
+
+from . import capi, esri
+
+NODATA = -9999.0
+EPSILON = 0.00001                               # commonConstants.h:252
+CLEAR_SKY_TRANSMISSIVITY_DEFAULT = 0.75         # solarRadiation/radiationDefinitions.h:33
+MAX_UNITS = 64                                  # SF3D_CROP_MAX_UNITS
+
+# state maps (degreeDaysMap, laiMap, dailyTminMap, dailyTmaxMap), in the order of include/sf3d_crop.h
+STATE = ("degreeDays", "lai", "dailyTmin", "dailyTmax")
+(DEGREE_DAYS, LAI, DAILY_TMIN, DAILY_TMAX) = range(4)
+MAPS = STATE + ("et0",)
+INPUT = ("airT", "relHum", "windInt", "globalRad", "transmissivity")
+KERNEL_ET0_HOUR, KERNEL_CROP_DAY = 0, 1
+STATE_FILES = {"degreeDays": "degreeDays", "lai": "LAI", "dailyTmin": "dailyTmin", "dailyTmax": "dailyTmax"}
+
+# speciesType (agrolib/crop/crop.h:14)
+(HERBACEOUS_ANNUAL, HERBACEOUS_PERENNIAL, HORTICULTURAL, GRASS, TREE, FALLOW, FALLOW_ANNUAL, BARESOIL) = range(8)
+UNIT_INT_FIELDS = ("type", "isCrop", "sowingDoy", "plantCycle")
+UNIT_DOUBLE_FIELDS = ("LAImin", "LAImax", "LAIgrass", "LAIcurve_a", "LAIcurve_b", "thermalThreshold", "upperThermalThreshold", "degreeDaysIncrease",
+                      "degreeDaysDecrease", "degreeDaysEmergence")
+UNIT_FIELDS = UNIT_INT_FIELDS + UNIT_DOUBLE_FIELDS
+
+
+class Unit(C.Structure):
+    """sf3d_crop_unit_t"""
+    _fields_ = [(n, C.c_int32) for n in UNIT_INT_FIELDS] + [(n, C.c_double) for n in UNIT_DOUBLE_FIELDS]
+
+
+pf32 = C.POINTER(C.c_float)
+pi32 = C.POINTER(C.c_int32)
+punit = C.POINTER(Unit)
+# name -> (restype, argtypes): every symbol include/sf3d_crop.h declares
+SIGNATURES = {
+    "sf3d_crop_initialize": (capi.u8, [capi.u32, capi.u32, pf32, capi.f32, pi32, capi.u32, punit, capi.f64]),
+    "sf3d_crop_set_state": (capi.u8, [capi.i32, capi.u32, pf32]),
+    "sf3d_crop_get_state": (capi.u8, [capi.i32, capi.u32, pf32]),
+    "sf3d_crop_get_et0": (capi.u8, [capi.u32, pf32]),
+    "sf3d_crop_set_degree_days": (capi.u8, [capi.u32, pf32, capi.i32]),
+    "sf3d_crop_compute_hour": (capi.u8, [capi.u32, pf32, pf32, pf32, pf32, pf32, capi.f32]),
+    "sf3d_crop_daily_update": (capi.u8, [capi.i32, capi.i32]),
+    "sf3d_crop_kernel_ms": (capi.f64, [capi.i32]),
+    "sf3d_crop_clean": (capi.u8, []),
+}
+
+
+def bind(sf: capi.SF3D) -> capi.SF3D:
+    """attach the signatures of include/sf3d_crop.h to a loaded product library (AttributeError if a symbol is missing)"""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(sf.lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return sf
+
+
+# ------------------------------------------------------------------------------------------------ binding
+
+def _f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if shape is not None and a.shape != tuple(shape):
+        raise ValueError(f"map of shape {a.shape}, the crop raster is {tuple(shape)}")
+    return a
+
+
+def unit_array(units):
+    """list of dicts (UNIT_FIELDS) -> ctypes array of sf3d_crop_unit_t"""
+    arr = (Unit * max(len(units), 1))()
+    for k, u in enumerate(units):
+        for n in UNIT_INT_FIELDS:
+            setattr(arr[k], n, int(u[n]))
+        for n in UNIT_DOUBLE_FIELDS:
+            setattr(arr[k], n, float(u[n]))
+    return arr
+
+
+def initialize(sf: capi.SF3D, dem, unit_index, units, latitude: float, flag: float = NODATA) -> None:
+    """initializeCropMaps on the raster `dem` [rows, cols]: the four state maps and ET0 hold the flag.  unit_index: the land-unit (= crop)
+    index per cell, negative where there is none; units: list of dicts with UNIT_FIELDS, one per land unit."""
+    bind(sf)
+    dem = _f32(dem)
+    idx = np.ascontiguousarray(unit_index, dtype=np.int32)
+    if idx.shape != dem.shape:
+        raise ValueError(f"unit index of shape {idx.shape}, the DEM is {dem.shape}")
+    sf._crop_shape = dem.shape
+    sf.check(sf.lib.sf3d_crop_initialize(dem.shape[0], dem.shape[1], dem.ctypes.data_as(pf32), float(flag), idx.ctypes.data_as(pi32), len(units),
+                                         unit_array(units), float(latitude)), "crop_initialize")
+
+
+def _index(which, names) -> int:
+    return names.index(which) if isinstance(which, str) else int(which)
+
+
+def set_state(sf: capi.SF3D, which, values) -> None:
+    v = _f32(values, sf._crop_shape)
+    sf.check(sf.lib.sf3d_crop_set_state(_index(which, STATE), v.size, v.ctypes.data_as(pf32)), f"crop_set_state({which})")
+
+
+def get_state(sf: capi.SF3D, which) -> np.ndarray:
+    out = np.empty(sf._crop_shape, np.float32)
+    sf.check(sf.lib.sf3d_crop_get_state(_index(which, STATE), out.size, out.ctypes.data_as(pf32)), f"crop_get_state({which})")
+    return out
+
+
+def get_et0(sf: capi.SF3D) -> np.ndarray:
+    out = np.empty(sf._crop_shape, np.float32)
+    sf.check(sf.lib.sf3d_crop_get_et0(out.size, out.ctypes.data_as(pf32)), "crop_get_et0")
+    return out
+
+
+def all_maps(sf: capi.SF3D) -> dict:
+    """the four state maps and ET0, by name"""
+    d = {n: get_state(sf, n) for n in STATE}
+    d["et0"] = get_et0(sf)
+    return d
+
+
+def set_degree_days(sf: capi.SF3D, degree_days, current_doy: int) -> None:
+    """initializeCropFromDegreeDays: degree days where the map holds a value, LAI from them"""
+    v = _f32(degree_days, sf._crop_shape)
+    sf.check(sf.lib.sf3d_crop_set_degree_days(v.size, v.ctypes.data_as(pf32), int(current_doy)), "crop_set_degree_days")
+
+
+def compute_hour(sf: capi.SF3D, meteo: dict | None, clear_sky: float = CLEAR_SKY_TRANSMISSIVITY_DEFAULT) -> None:
+    """one hour of ET0 and daily extremes on the device.  meteo: the float maps "airT", "relHum", "windInt", "globalRad",
+    "transmissivity"; None: the maps the last snow.compute_hour left on the device (nothing is uploaded)."""
+    n = int(np.prod(sf._crop_shape))
+    if meteo is None:
+        ptrs = [pf32()] * 5
+    else:
+        maps = [_f32(meteo[k], sf._crop_shape) for k in INPUT]
+        ptrs = [m.ctypes.data_as(pf32) for m in maps]
+    sf.check(sf.lib.sf3d_crop_compute_hour(n, *ptrs, float(clear_sky)), "crop_compute_hour")
+
+
+def daily_update(sf: capi.SF3D, date_doy: int, current_doy: int | None = None) -> None:
+    """dailyUpdateCropMaps for the date with day of year `date_doy` (current_doy: getCurrentDate().dayOfYear(), the same by default)"""
+    sf.check(sf.lib.sf3d_crop_daily_update(int(date_doy), int(date_doy if current_doy is None else current_doy)), "crop_daily_update")
+
+
+def kernel_ms(sf: capi.SF3D, which: int) -> float:
+    return float(sf.lib.sf3d_crop_kernel_ms(int(which)))
+
+
+def clean(sf: capi.SF3D) -> None:
+    sf.check(sf.lib.sf3d_crop_clean(), "crop_clean")
+
+
+def save_crop_state(sf: capi.SF3D, directory, header: dict) -> Path:
+    """<directory>/crop/{degreeDays, LAI, dailyTmin, dailyTmax}.flt/.hdr"""
+    d = Path(directory) / "crop"
+    d.mkdir(parents=True, exist_ok=True)
+    for name, stem in STATE_FILES.items():
+        esri.write_grid(d / stem, get_state(sf, name), header)
+    return d
+
+
+def load_crop_state(sf: capi.SF3D, directory) -> None:
+    """the four maps of <directory>/crop onto the device (the raster must be initialised with the same DEM)"""
+    d = Path(directory) / "crop"
+    for name, stem in STATE_FILES.items():
+        grid, _ = esri.read_grid(d / stem)
+        set_state(sf, name, grid)
+
+
+# ------------------------------------------------------------------------------------------------ restatement (checker)
+
+_exp = np.frompyfunc(math.exp, 1, 1)
+_log = np.frompyfunc(math.log, 1, 1)
+_pow = np.frompyfunc(math.pow, 2, 1)
+
+
+def _lib(fn, *a):
+    """the C library's function, element by element (numpy's own exp / log / pow are other algorithms)"""
+    return fn(*a).astype(np.float64)
+
+
+def _eq(a, b):
+    """isEqual (basicMath.h:25-29) on arrays: both operands widened to double"""
+    return np.abs(np.asarray(a).astype(np.float64) - np.float64(b)) < EPSILON
+
+
+def et0_penman_hourly(height, normalized_transmissivity, global_irradiance, air_temp, air_hum, wind_speed10):
+    """ET0_Penman_hourly (meteo.cpp:550-609) on float64 arrays, the helpers of physics.cpp inlined in the reference's order"""
+    es = 611 * _lib(_exp, 17.502 * air_temp / (air_temp + 240.97)) / 1000.
+    ea = air_hum * es / 100.0
+    emissivity = 0.34 - 0.14 * np.sqrt(ea)
+    t_air_k = air_temp + 273.15
+    sigma = 5.670373E-8 * 3600.
+    cf = 1.35 * np.where(normalized_transmissivity < 1, normalized_transmissivity, 1.0) - 0.35
+    cloud_factor = np.where(0 > cf, 0.0, cf)
+    net_lw = cloud_factor * emissivity * sigma * _lib(_pow, t_air_k, 4.0)
+    net_sw = 3600 * global_irradiance
+    net_radiation = (1 - 0.23) * net_sw - net_lw
+    day = net_radiation > 0
+    g = np.where(day, 0.1 * net_radiation, 0.5 * net_radiation)
+    cd = np.where(day, 0.24, 0.96)
+    delta = 4098. * es / ((237.3 + air_temp) * (237.3 + air_temp))
+    pressure = 101325. * _lib(_pow, 1 + height * 0.0065 / 293.16, np.float64(- 9.80665 / (0.0065 * 287.058))) / 1000.
+    lam = 2501000. - 2369.2 * air_temp
+    gamma = 1013. * pressure / (0.622 * lam)
+    wind_speed2 = wind_speed10 * 0.748
+    denominator = delta + gamma * (1 + cd * wind_speed2)
+    first = delta * (net_radiation - g) / (lam * denominator)
+    second = (gamma * (37 / t_air_k) * wind_speed2 * (es - ea)) / denominator
+    s = first + second
+    return np.where(s > 0, s, 0.0)
+
+
+def restate_et0_hour(dem, meteo: dict, flag: float = NODATA, clear_sky: float = CLEAR_SKY_TRANSMISSIVITY_DEFAULT) -> np.ndarray:
+    """computeET0PMMap (meteoMaps.cpp:238-271): a cell is a DEM cell when int(height) != int(flag); the five inputs by isEqual;
+    transmissivity / clearSky divided in float -> the float ET0 map (the flag elsewhere)"""
+    dem = np.asarray(dem, np.float32)
+    f32 = np.float32(flag)
+    fl = float(f32)
+    airT, rh, wind, glob, trans = (np.asarray(meteo[k], np.float32) for k in INPUT)
+    ok = np.trunc(dem.astype(np.float64)).astype(np.int64) != int(fl)
+    for m in (glob, trans, airT, rh, wind):
+        ok &= ~_eq(m, fl)
+    out = np.full(dem.shape, f32, np.float32)
+    if ok.any():
+        nt = (trans[ok] / np.float32(clear_sky)).astype(np.float64)
+        d = lambda a: a[ok].astype(np.float64)
+        out[ok] = et0_penman_hourly(d(dem), nt, d(glob), d(airT), d(rh), d(wind)).astype(np.float32)
+    return out
+
+
+def restate_daily_temperatures(tmin, tmax, air_t, flag: float = NODATA):
+    """updateDailyTemperatures (criteria3DProject.cpp:1994-2018) -> (tmin, tmax), new float arrays; no look at the DEM"""
+    tmin, tmax, air_t = (np.asarray(a, np.float32) for a in (tmin, tmax, air_t))
+    fl = float(np.float32(flag))
+    has = ~_eq(air_t, fl)
+    new_min = np.where(_eq(tmin, fl), air_t, np.where(air_t < tmin, air_t, tmin))
+    new_max = np.where(_eq(tmax, fl), air_t, np.where(tmax < air_t, air_t, tmax))
+    return np.where(has, new_min, tmin).astype(np.float32), np.where(has, new_max, tmax).astype(np.float32)
+
+
+def is_sowing_crop(u) -> bool:
+    return int(u["type"]) in (HERBACEOUS_ANNUAL, HORTICULTURAL)
+
+
+def is_inside_typical_cycle(u, doy: int) -> bool:
+    """Crit3DCrop::isInsideTypicalCycle (crop.cpp:314-344): C's remainder keeps the sign of the dividend"""
+    days = int(math.fmod(doy - int(u["sowingDoy"]), 365))
+    if days >= 0:
+        return days < int(u["plantCycle"])
+    return (doy + 365 - int(u["sowingDoy"])) < int(u["plantCycle"])
+
+
+def lai_criteria(u, dd):
+    """leafDevelopment::getLAICriteria (development.cpp:132-154) on a float64 array"""
+    c4 = 15.0 if int(u["type"]) == TREE else 9.0
+    lmin, lmax, inc = float(u["LAImin"]), float(u["LAImax"]), float(u["degreeDaysIncrease"])
+    out = np.empty(dd.shape, np.float64)
+    rising = dd <= inc
+    if rising.any():
+        out[rising] = lmin + (lmax - lmin) / (1 + _lib(_exp, float(u["LAIcurve_a"]) + float(u["LAIcurve_b"]) * dd[rising]))
+    if (~rising).any():
+        dec = float(u["degreeDaysDecrease"])
+        out[~rising] = lmin + (lmax - lmin) / (1 + _lib(_pow, 10 * ((dd[~rising] - inc) / (dec if dec > 1. else 1.)) / c4, 4.0))
+    return out
+
+
+def simple_lai(u, dd, latitude: float, current_doy: int):
+    """Crit3DCrop::computeSimpleLAI (crop.cpp:177-224) on a float64 array of degree days"""
+    dd = np.asarray(dd, np.float64)
+    lai = np.zeros(dd.shape, np.float64)
+    if is_sowing_crop(u):
+        em = float(u["degreeDaysEmergence"])
+        on = ~(dd < em)
+        if on.any():
+            lai[on] = lai_criteria(u, dd[on] - em)
+        return lai
+    on = dd > 0
+    lai[:] = float(u["LAImin"])
+    if on.any():
+        lai[on] = lai_criteria(u, dd[on])
+    if int(u["type"]) == TREE:
+        if latitude > 0:
+            start = 305
+            leaf_fall = current_doy >= start
+        else:
+            start = 120
+            leaf_fall = current_doy >= start and current_doy < 182
+        if leaf_fall:                                        # getLAISenescence(LAImin, LAImax * 0.75, days), development.cpp:117-129
+            days = current_doy - start
+            if days > 30:
+                lai[:] = float(u["LAImin"])
+            else:
+                a = math.log(max(float(u["LAImax"]) * 0.75, 0.1))
+                b = (math.log(max(float(u["LAImin"]), 0.01)) - a) / 30
+                lai[:] = math.exp(a + b * days)
+        lai = lai + float(u["LAIgrass"])
+    return lai
+
+
+def _crop_cells(dem, unit_index, units, fl):
+    idx = np.asarray(unit_index)
+    is_crop = np.array([bool(int(u["isCrop"])) for u in units] + [False])
+    return ~_eq(np.asarray(dem, np.float32), fl) & (idx >= 0) & is_crop[np.where(idx >= 0, idx, len(units))]
+
+
+def restate_degree_days(dem, unit_index, units, latitude: float, degree_days, current_doy: int, flag: float = NODATA) -> dict:
+    """initializeCropFromDegreeDays (criteria3DProject.cpp:524-573) -> the four state maps"""
+    f32 = np.float32(flag)
+    fl = float(f32)
+    src = np.asarray(degree_days, np.float32)
+    idx = np.asarray(unit_index)
+    st = {n: np.full(src.shape, f32, np.float32) for n in STATE}
+    cells = _crop_cells(dem, unit_index, units, fl) & ~_eq(src, fl)
+    st["degreeDays"][cells] = src[cells]
+    for k, u in enumerate(units):
+        m = cells & (idx == k)
+        if m.any():
+            st["lai"][m] = simple_lai(u, src[m].astype(np.float64), latitude, current_doy).astype(np.float32)
+    return st
+
+
+def restate_crop_day(state: dict, dem, unit_index, units, latitude: float, date_doy: int, current_doy: int | None = None, flag: float = NODATA) -> dict:
+    """dailyUpdateCropMaps (criteria3DProject.cpp:576-640): state = the four maps by name -> the four maps after the day (new arrays);
+    the degree days accumulate in float, as the application's map does"""
+    current_doy = date_doy if current_doy is None else current_doy
+    f32 = np.float32(flag)
+    fl = float(f32)
+    dd, lai, tmin, tmax = (np.array(state[n], np.float32) for n in STATE)
+    idx = np.asarray(unit_index)
+    if date_doy == (182 if latitude < 0 else 1):
+        dd[:] = f32
+        lai[:] = f32
+    cells = _crop_cells(dem, unit_index, units, fl) & ~_eq(tmin, fl) & ~_eq(tmax, fl)
+    for k, u in enumerate(units):
+        m = cells & (idx == k)
+        if not m.any():
+            continue
+        tn, tx = tmin[m].astype(np.float64), tmax[m].astype(np.float64)
+        # getDailyDegreeIncrease, crop.cpp:161-174
+        nodata = _eq(tn, NODATA) | _eq(tx, NODATA)
+        if is_sowing_crop(u) and not is_inside_typical_cycle(u, current_doy):
+            inc = np.zeros(tn.shape)
+        else:
+            upper = float(u["upperThermalThreshold"])
+            tmed = (tn + np.where(upper < tx, upper, tx)) * 0.5
+            v = tmed - float(u["thermalThreshold"])
+            inc = np.where(v < 0., 0., v)
+        m2 = m.copy()
+        m2[m] = ~nodata
+        inc32 = inc[~nodata].astype(np.float32)
+        old = dd[m2]
+        new = np.where(_eq(old, fl), inc32, (old + inc32).astype(np.float32)).astype(np.float32)
+        dd[m2] = new
+        lai[m2] = simple_lai(u, new.astype(np.float64), latitude, current_doy).astype(np.float32)
+    return {"degreeDays": dd, "lai": lai, "dailyTmin": np.full(dd.shape, f32, np.float32), "dailyTmax": np.full(dd.shape, f32, np.float32)}

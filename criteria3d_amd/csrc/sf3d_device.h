@@ -437,6 +437,28 @@ struct SnowView {
     SnowParamsDev p;
 };
 
+/* ---- hourly reference ET0, daily extremes and daily crop maps (sf3d_crop.inc, include/sf3d_crop.h): one thread per raster cell ---- */
+#define CROP_MAX_UNITS 64               /* SF3D_CROP_MAX_UNITS: the crop table of k_crop_day sits in LDS, 96 B per land unit */
+struct CropUnitDev {    /* sf3d_crop_unit_t: the fields of Crit3DCrop that getDailyDegreeIncrease / computeSimpleLAI read, and isCrop of the land unit */
+    int32_t type, isCrop, sowingDoy, plantCycle;
+    double LAImin, LAImax, LAIgrass, LAIcurve_a, LAIcurve_b, thermalThreshold, upperThermalThreshold, degreeDaysIncrease, degreeDaysDecrease, degreeDaysEmergence;
+};
+/* the device block of the crop maps: CROP_MAPS maps of nCells 4-byte values (the crop index is int32) */
+enum { CROP_MAP_STATE = 0, CROP_MAP_ET0 = 4, CROP_MAP_IN = 5, CROP_MAP_DEM = 10, CROP_MAP_INDEX = 11, CROP_MAPS = 12 };
+struct CropView {
+    float* st[4];                       /* degree days, LAI, daily minimum and maximum air temperature */
+    float* et0;
+    const float* in[5];                 /* air temperature, relative humidity, wind, global radiation, transmissivity (this block's, or the snow block's) */
+    const float* dem;
+    const int32_t* index;               /* land unit = crop index per cell, -1: none */
+    const CropUnitDev* units;
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    uint32_t nCells, nUnits;
+    float flag, clearSky;
+    double latitude;
+    int dateDoy, currentDoy;
+};
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 

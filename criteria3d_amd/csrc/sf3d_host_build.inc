@@ -133,7 +133,9 @@ struct MapsCache {
 };
 
 /* hourly snow model (sf3d_snow.inc): the maps of include/sf3d_snow.h; they belong to the raster and stay when the model is released */
-struct SnowCache { float* base = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0; double lastMs = 0.; };
+struct SnowCache { float* base = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0; double lastMs = 0.; bool hourDone = false; };
+/* hourly ET0 and daily crop maps (sf3d_crop.inc): the maps of include/sf3d_crop.h and the crop table; as the snow maps, they belong to the raster */
+struct CropCache { float* base = nullptr; CropUnitDev* units = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0, nUnits = 0; double lastMs[2] = {0., 0.}; };
 
 struct DeviceSolver::Impl {
     int device = -1;
@@ -255,6 +257,7 @@ struct DeviceSolver::Impl {
     double ms[KID_COUNT] = {0};
     MapsCache maps;
     SnowCache snow;
+    CropCache crop;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the

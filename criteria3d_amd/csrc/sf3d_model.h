@@ -207,6 +207,16 @@ public:
     sf3d_error_t snow_hour(const float* const in[8], const SnowParamsDev& p, float flag, const uint8_t* mine);
     sf3d_error_t snow_free();
     double snow_kernel_ms() const;
+    /* hourly ET0 / daily crop maps (sf3d_crop.inc): CROP_MAPS maps of nCells on the device and the crop table, independent of the node
+     * model as the snow maps are; in == nullptr: k_et0_hour reads the five maps the last snow_hour left in the snow block */
+    sf3d_error_t crop_alloc(uint32_t nCells, const CropUnitDev* units, uint32_t nUnits);
+    sf3d_error_t crop_upload(int map, const void* src);
+    sf3d_error_t crop_download(int map, float* dst);
+    bool crop_snow_inputs_ready(uint32_t nCells) const;
+    sf3d_error_t crop_hour(const float* const in[5], float clearSky, float flag, const uint8_t* mine);
+    sf3d_error_t crop_day(int dateDoy, int currentDoy, double latitude, float flag, const uint8_t* mine);
+    sf3d_error_t crop_free();
+    double crop_kernel_ms(int which) const;
 
 private:
     DeviceSolver() = default;

@@ -332,6 +332,7 @@ sf3d_error_t DeviceSolver::snow_hour(const float* const in[8], const SnowParamsD
     SNOW_TRY(hipGetLastError());
     if (I.timing) SNOW_TRY(hipEventRecord(ev[1], I.stream));
     SNOW_TRY(hipStreamSynchronize(I.stream));              /* the caller's input maps are free again on return */
+    S.hourDone = true;                                     /* the input maps of this hour stay in the block (sf3d_crop_compute_hour may read them) */
     S.lastMs = 0.;
     if (I.timing) {
         float ms = 0.f;

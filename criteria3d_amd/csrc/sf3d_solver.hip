@@ -47,3 +47,4 @@
 #include "sf3d_host_step.inc"
 #include "sf3d_maps.inc"
 #include "sf3d_snow.inc"
+#include "sf3d_crop.inc"

@@ -528,6 +528,75 @@ def window(inp: ProjectInputs, r0: int, r1: int, c0: int, c1: int) -> ProjectInp
                          meta=dict(inp.meta, window=(r0, r1, c0, c1)))
 
 
+def land_unit_index(inp: ProjectInputs) -> np.ndarray:
+    """land-unit index per cell (getLandUnitIndexRowCol :1476-1492), -1 outside the DEM and where the land-use map names no unit"""
+    dem = np.asarray(inp.dem, np.float32)
+    flag = float(inp.header.get("nodata", NODATA))
+    valid = np.abs(dem.astype(np.float64) - flag) >= EPSILON
+    units = inp.land_units
+    if len(units) <= 1:
+        return np.where(valid, 0, -1)
+    unit_index = np.full(dem.shape, -1, np.int64)
+    lu = np.asarray(inp.land_use)
+    for k, u in enumerate(units):
+        m = valid & (lu.astype(np.int64) == int(u["id"])) & (unit_index < 0)
+        unit_index[m] = k
+    return unit_index
+
+
+# ------------------------------------------------------------------------------------------------ crop database
+
+CROP_TYPES = {"herbaceous": 0, "herbaceous_perennial": 1, "horticultural": 2, "grass": 3, "fallow": 5, "annual_fallow": 6, "fallow_annual": 6,
+              "tree": 4, "fruit_tree": 4, "bare": 7, "bare_soil": 7}      # getCropType (agrolib/crop/crop.cpp:902-925); anything else: herbaceous
+
+
+def is_crop(id_crop) -> bool:
+    """Project3D::isCrop (project3D.cpp:1526-1537) of a land unit's id_crop: empty or BARE is no crop"""
+    s = "" if id_crop is None else str(id_crop).upper()
+    return not (s == "" or s == "BARE")
+
+
+def _db_int(v) -> int:
+    """QVariant::toInt: NULL, '' or text that is not a number -> 0"""
+    d = db_double(v)
+    return 0 if d == NODATA and not isinstance(v, (int, float)) else int(d)
+
+
+def _db_float(v) -> float:
+    """QVariant::toDouble: NULL, '' or text that is not a number -> 0"""
+    d = db_double(v)
+    return 0.0 if d == NODATA and not isinstance(v, (int, float)) else d
+
+
+def crop_table(crop_rows, land_units) -> list:
+    """the crop list of the project, indexed like the land-unit list: for every land unit the fields of its `crop` row (joined on
+    land_units.id_crop) that getDailyDegreeIncrease and computeSimpleLAI read, converted as loadCropParameters does
+    (agrolib/crop/cropDbTools.cpp:25-131), plus id_crop and isCrop.  crop_rows: dicts keyed by the columns of the `crop` table.  A unit
+    that is no crop (empty id or BARE) gets a zero entry; a crop id without a row is an error, as in the application."""
+    by_id = {}
+    for r in crop_rows:
+        by_id.setdefault(str(r["id_crop"]), r)
+    out = []
+    for u in land_units:
+        cid = u.get("id_crop")
+        entry = dict(id_crop="" if cid is None else str(cid), isCrop=int(is_crop(cid)), type=7, sowingDoy=int(NODATA), plantCycle=0, LAImin=0.0, LAImax=0.0,
+                     LAIgrass=0.0, LAIcurve_a=0.0, LAIcurve_b=0.0, thermalThreshold=0.0, upperThermalThreshold=0.0, degreeDaysIncrease=0.0,
+                     degreeDaysDecrease=0.0, degreeDaysEmergence=0.0)
+        if entry["isCrop"]:
+            r = by_id.get(entry["id_crop"])
+            if r is None:
+                raise ValueError(f"Missing crop: {entry['id_crop']}")
+            sowing, grass = db_double(r["sowing_doy"]), db_double(r["lai_grass"])
+            entry.update(type=CROP_TYPES.get(str(r["type"]).lower(), 0), sowingDoy=int(sowing), plantCycle=_db_int(r["plant_cycle_max_duration"]),
+                         LAImin=_db_float(r["lai_min"]), LAImax=_db_float(r["lai_max"]), LAIgrass=0.0 if grass == NODATA else grass,
+                         LAIcurve_a=_db_float(r["lai_curve_factor_a"]), LAIcurve_b=_db_float(r["lai_curve_factor_b"]),
+                         thermalThreshold=_db_float(r["thermal_threshold"]), upperThermalThreshold=_db_float(r["upper_thermal_threshold"]),
+                         degreeDaysIncrease=float(_db_int(r["degree_days_lai_increase"])), degreeDaysDecrease=float(_db_int(r["degree_days_lai_decrease"])),
+                         degreeDaysEmergence=float(_db_int(r["degree_days_emergence"])))
+        out.append(entry)
+    return out
+
+
 def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> Model:
     """The solver model `Project3D::initialize3DModel` builds (project3D.cpp:456-616), as arrays for the bulk ABI:
     setSoilIndexMap :708-755, computation depth :494-515, setSoilLayers / setLayersDepth :1568-1661, setIndexMaps :758-818,
@@ -554,15 +623,7 @@ def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> M
         if k is not None:
             soil_index[valid & (sm == sid)] = k
 
-    # land-unit index per cell (getLandUnitIndexRowCol :1476-1492)
-    if len(units) <= 1:
-        unit_index = np.where(valid, 0, -1)
-    else:
-        unit_index = np.full(dem.shape, -1, np.int64)
-        lu = np.asarray(inp.land_use)
-        for k, u in enumerate(units):
-            m = valid & (lu.astype(np.int64) == int(u["id"])) & (unit_index < 0)
-            unit_index[m] = k
+    unit_index = land_unit_index(inp)
 
     # computation depth :494-515
     if par.compute_all_soil_depth:

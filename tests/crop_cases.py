@@ -1,0 +1,123 @@
+"""What tests/test_crop_host.py, tests/test_gpu_crop.py and scripts/multirank_crop_worker.py share (no tests here): the pin
+tests/golden/crop_et0.npz decoded, its calendar replayed on a backend (the numpy restatement or the device), a small forcing."""
+from pathlib import Path
+
+import numpy as np
+
+from criteria3d_amd import crop
+
+PIN = Path(__file__).resolve().parent / "golden" / "crop_et0.npz"
+OP_HOUR, OP_DAY, OP_SET_STATE, OP_CHECKPOINT, OP_SET_DEGREE_DAYS, OP_LATITUDE = 1, 2, 3, 4, 5, 6
+
+
+def load_pin():
+    z = np.load(PIN)
+    p = {k: z[k] for k in z.files}
+    flag = np.float32(p["flag"])
+    steps = p["input_steps"].astype(np.float32).reshape(1, 5, 1, 1)
+    codes = p["input_codes"]
+    p["inputs"] = np.where(codes == -32768, flag, codes.astype(np.float32) * steps).astype(np.float32)      # exact: the steps are powers of two
+    names = [str(n) for n in p["unit_fields"]]
+    p["unit_list"] = [dict(zip(names, row)) for row in p["units"]]
+    return p
+
+
+def meteo(pin, h):
+    return {n: pin["inputs"][h, k] for k, n in enumerate(crop.INPUT)}
+
+
+class Restated:
+    """the numpy restatement behind the interface the replay drives"""
+    def __init__(self, pin):
+        self.dem, self.flag, self.idx, self.units = pin["dem"], float(pin["flag"]), pin["unit_index"], pin["unit_list"]
+        self.clear_sky = float(pin["clear_sky"])
+
+    def initialize(self, latitude):
+        self.latitude = latitude
+        self.m = {n: np.full(self.dem.shape, np.float32(self.flag), np.float32) for n in crop.MAPS}
+
+    def hour(self, met):
+        self.m["et0"] = crop.restate_et0_hour(self.dem, met, self.flag, self.clear_sky)
+        self.m["dailyTmin"], self.m["dailyTmax"] = crop.restate_daily_temperatures(self.m["dailyTmin"], self.m["dailyTmax"], met["airT"], self.flag)
+
+    def day(self, date_doy, current_doy):
+        self.m.update(crop.restate_crop_day(self.m, self.dem, self.idx, self.units, self.latitude, date_doy, current_doy, self.flag))
+
+    def set_state(self, name, values):
+        self.m[name] = np.array(values, np.float32)
+
+    def set_degree_days(self, values, doy):
+        self.m.update(crop.restate_degree_days(self.dem, self.idx, self.units, self.latitude, values, doy, self.flag))
+
+    def maps(self):
+        return dict(self.m)
+
+
+class Device:
+    """the product library behind the same interface"""
+    def __init__(self, sf, pin):
+        self.sf, self.pin = sf, pin
+
+    def initialize(self, latitude):
+        p = self.pin
+        crop.initialize(self.sf, p["dem"], p["unit_index"], p["unit_list"], latitude, float(p["flag"]))
+
+    def hour(self, met):
+        crop.compute_hour(self.sf, met, float(self.pin["clear_sky"]))
+
+    def day(self, date_doy, current_doy):
+        crop.daily_update(self.sf, date_doy, current_doy)
+
+    def set_state(self, name, values):
+        crop.set_state(self.sf, name, values)
+
+    def set_degree_days(self, values, doy):
+        crop.set_degree_days(self.sf, values, doy)
+
+    def maps(self):
+        return crop.all_maps(self.sf)
+
+
+def replay(pin, backend, at_checkpoint, interrupt=None, first_op=0):
+    """the pin's calendar on `backend`; at_checkpoint(k, maps) at the k-th checkpoint; interrupt(op_number, backend) before every operation.
+    A change of latitude re-initialises the raster and carries the four state maps over, as the generator's driver keeps its maps."""
+    k = 0
+    for n, (op, a, b) in enumerate(pin["ops"]):
+        op, a, b = int(op), int(a), int(b)
+        if interrupt is not None and n >= first_op:
+            interrupt(n, backend)
+        if op == OP_LATITUDE:
+            keep = backend.maps() if n > 0 else None
+            backend.initialize(a / 100.0)
+            if keep is not None:
+                for name in crop.STATE:
+                    backend.set_state(name, keep[name])
+        elif op == OP_HOUR:
+            backend.hour(meteo(pin, a))
+        elif op == OP_DAY:
+            backend.day(a, b)
+        elif op == OP_SET_STATE:
+            backend.set_state(crop.MAPS[a], pin["set_maps"][b])
+        elif op == OP_SET_DEGREE_DAYS:
+            backend.set_degree_days(pin["set_maps"][b], a)
+        elif op == OP_CHECKPOINT:
+            at_checkpoint(k, backend.maps())
+            k += 1
+    return k
+
+
+def small_forcing(shape, dem, flag, hours=5):
+    """a few daytime hours on any raster: every cell with a DEM value gets inputs, two cells lack one"""
+    valid = np.abs(dem.astype(np.float64) - float(np.float32(flag))) >= 1e-5
+    out = []
+    for h in range(hours):
+        f = lambda v: np.where(valid, np.float32(v), np.float32(flag)).astype(np.float32)
+        ramp = (np.arange(dem.size, dtype=np.float32).reshape(shape) % 13) * np.float32(0.25)
+        m = dict(airT=f(12.0 + 2.0 * h) + np.where(valid, ramp, 0).astype(np.float32), relHum=f(60.0 - 3.0 * h), windInt=f(2.0 + 0.5 * h),
+                 globalRad=f(100.0 * h), transmissivity=f(0.5 + 0.05 * h))
+        v = np.argwhere(valid)
+        if len(v) > 2:
+            m["airT"][tuple(v[1])] = np.float32(flag)
+            m["windInt"][tuple(v[2])] = np.float32(flag)
+        out.append(m)
+    return out
