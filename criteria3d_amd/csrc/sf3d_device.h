@@ -459,6 +459,72 @@ struct CropView {
     int dateDoy, currentDoy;
 };
 
+/* ---- root length / depth / density maps (sf3d_root.inc, include/sf3d_root.h): one thread per raster cell, the density vectors in a keyed table ---- */
+#define ROOT_MAX_SOILS 1024             /* SF3D_ROOT_MAX_SOILS */
+#define ROOT_MAX_LAYERS 64              /* SF3D_ROOT_MAX_LAYERS */
+#define ROOT_MAX_ATOMS 1024             /* SF3D_ROOT_MAX_ATOMS: int(totalDepth * 100) + 1 */
+struct RootUnitDev {    /* sf3d_root_unit_t: what computeRootLength3D / computeRootDensity3D read of Crit3DCrop and Crit3DRoot */
+    int32_t rootShape, growth, isRootStatic, degreeDaysRootGrowth;
+    double shapeDeformation, rootDepthMin, rootDepthMax, degreeDaysEmergence;
+};
+struct RootView {       /* k_root_cell, k_root_gather */
+    const float* dem;
+    const float* dd;                    /* degree days: this block's copy or the crop block's state map */
+    const int32_t* cropIndex;
+    const int32_t* soilIndex;
+    double* length;
+    double* depth;
+    int32_t* first;
+    int32_t* last;
+    int32_t* key;                       /* row of the density table, -1: not computed */
+    const RootUnitDev* units;
+    const double* soilDepth;            /* totalDepth per soil */
+    const int32_t* soilMaxN;            /* round(totalDepth / 0.01): the largest number of rooted atoms a cell of the soil can ask for */
+    const int32_t* pairRow;             /* [unit * nSoils + soil]: first table row of the pair (its rows: 0 .. soilMaxN rooted atoms), -1: the pair does not occur */
+    const int32_t* rowLayers;           /* [2 * row]: firstRootLayer, lastRootLayer */
+    const double* table;                /* [layer * nRows + row] */
+    double* out;                        /* k_root_gather: [layer - layer0][cell] */
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    uint32_t nCells, nUnits, nSoils, nRows, nrLayers, layer0, layerCount;
+    float flag;
+};
+struct RootTableView {  /* k_root_table: one thread per row = (unit, soil, number of rooted atoms) */
+    const RootUnitDev* units;
+    const double* soilDepth;
+    const double* layerDepth;
+    const double* layerThickness;
+    const double* layerFrac;            /* [soil * nrLayers + layer]: getSoilFraction() of the layer's horizon, < 0: getHorizonIndex finds none */
+    const double* lunette;              /* triangular: lunette[0 .. m-1] of m rooted atoms at m (m - 1) / 2 */
+    const int32_t* rowUnit;
+    const int32_t* rowSoil;
+    const int32_t* rowN;
+    double* table;
+    int32_t* rowLayers;
+    uint32_t nRows, nrLayers, lunetteMax;
+};
+
+struct RootSetup {      /* what sf3d_root_initialize hands to DeviceSolver::root_alloc: host pointers */
+    uint32_t nCells, nUnits, nSoils, nrLayers, nRows, lunetteMax;
+    const float* dem;
+    const int32_t* cropIndex;
+    const int32_t* soilIndex;
+    const RootUnitDev* units;
+    const double* soilDepth;
+    const int32_t* soilMaxN;
+    const int32_t* pairRow;
+    const double* layerDepth;
+    const double* layerThickness;
+    const double* layerFrac;
+    const double* lunette;
+    const int32_t* rowUnit;
+    const int32_t* rowSoil;
+    const int32_t* rowN;
+    float flag;
+};
+/* the per-cell block of the root maps: two double maps, then seven maps of 4-byte values */
+enum { ROOT_MAP_LENGTH = 0, ROOT_MAP_DEPTH = 1, ROOT_MAP_DEM = 2, ROOT_MAP_DD = 3, ROOT_MAP_CROP = 4, ROOT_MAP_SOIL = 5, ROOT_MAP_FIRST = 6, ROOT_MAP_LAST = 7,
+       ROOT_MAP_KEY = 8, ROOT_MAPS = 9, ROOT_MAP_WORDS = 11 };
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 

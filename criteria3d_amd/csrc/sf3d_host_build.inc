@@ -137,6 +137,18 @@ struct SnowCache { float* base = nullptr; uint8_t* mine = nullptr; uint32_t nCel
 /* hourly ET0 and daily crop maps (sf3d_crop.inc): the maps of include/sf3d_crop.h and the crop table; as the snow maps, they belong to the raster */
 struct CropCache { float* base = nullptr; CropUnitDev* units = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0, nUnits = 0; double lastMs[2] = {0., 0.}; };
 
+/* root maps (sf3d_root.inc): the maps of include/sf3d_root.h, the tables and the density table; they belong to the raster too */
+struct RootCache {
+    char* cells = nullptr;              /* ROOT_MAP_WORDS x nCells 4-byte words: the per-cell maps */
+    char* tables = nullptr;             /* units, soils, layer grid, lunette, rows, the density table: one block */
+    double* out = nullptr;              /* the gathered density maps, allocated by the first getter: nrLayers x nCells */
+    uint8_t* mine = nullptr;
+    size_t off[16] = {0};               /* offsets of the tables in `tables` */
+    uint32_t nCells = 0, nUnits = 0, nSoils = 0, nRows = 0, nrLayers = 0, lunetteMax = 0;
+    bool computed = false;
+    double lastMs[3] = {0., 0., 0.};
+};
+
 struct DeviceSolver::Impl {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -258,6 +270,7 @@ struct DeviceSolver::Impl {
     MapsCache maps;
     SnowCache snow;
     CropCache crop;
+    RootCache root;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the

@@ -217,6 +217,16 @@ public:
     sf3d_error_t crop_day(int dateDoy, int currentDoy, double latitude, float flag, const uint8_t* mine);
     sf3d_error_t crop_free();
     double crop_kernel_ms(int which) const;
+    /* root length / depth / density maps (sf3d_root.inc): the per-cell maps, the tables and the keyed density table, independent of the
+     * node model as the snow and crop maps are; dd == nullptr: k_root_cell reads the degree-day map of the crop block */
+    sf3d_error_t root_alloc(const RootSetup& setup);
+    sf3d_error_t root_compute(const float* dd, float flag, const uint8_t* mine);
+    bool root_crop_degree_days_ready(uint32_t nCells) const;
+    sf3d_error_t root_download(int map, void* dst);
+    sf3d_error_t root_density(int layer, double* dst, float flag);
+    sf3d_error_t root_free();
+    double root_kernel_ms(int which) const;
+    uint32_t root_table_rows() const;
 
 private:
     DeviceSolver() = default;

@@ -48,3 +48,4 @@
 #include "sf3d_maps.inc"
 #include "sf3d_snow.inc"
 #include "sf3d_crop.inc"
+#include "sf3d_root.inc"

@@ -597,6 +597,59 @@ def crop_table(crop_rows, land_units) -> list:
     return out
 
 
+ROOT_SHAPES = {"cylinder": 0, "cardioid": 1, "gamma function": 2}        # rootDistributionType (agrolib/crop/root.h:11)
+ROOT_GROWTHS = {"linear": 0, "exponential": 1, "logistic": 2}             # rootGrowthType (root.h:14)
+ROOT_STATIC_TYPES = (1, 3, 5, 4)                                          # isRootStatic (crop.cpp:359-365): perennial, grass, fallow, tree
+
+
+def root_distribution_type(v) -> int:
+    """a crop row's root_shape: a name through root::getRootDistributionTypeFromString (root.cpp:101-118), a number (what
+    loadCropParameters reads, cropDbTools.cpp:64) through getRootDistributionType (root.cpp:69-82: 1 cylinder, 4 cardioid, 5 gamma);
+    anything else is a cardioid in both"""
+    if isinstance(v, str) and v.strip() and not v.strip().lstrip("+-").replace(".", "", 1).isdigit():
+        return ROOT_SHAPES.get(v, 1)
+    return {1: 0, 4: 1, 5: 2}.get(_db_int(v), 1)
+
+
+def root_growth_type(v) -> int:
+    """a crop row's root growth name; the reference's crop table has no such column and Crit3DRoot::clear leaves LOGISTIC
+    (root.cpp:50), which is what a missing, empty or unknown value gives"""
+    return ROOT_GROWTHS.get(str(v).strip().lower(), 2) if v is not None else 2
+
+
+def root_table(crop_rows, land_units) -> list:
+    """the root units of the project, indexed like the land-unit list (beside crop_table): the fields of Crit3DCrop / Crit3DRoot that
+    computeRootLength3D and computeRootDensity3D read, converted as loadCropParameters does (cropDbTools.cpp:63-83: a missing
+    degree_days_root_increase is degree_days_lai_increase), and isRootStatic() of the unit.  A unit that is no crop gets a zero entry."""
+    by_id = {}
+    for r in crop_rows:
+        by_id.setdefault(str(r["id_crop"]), r)
+    out = []
+    for u in land_units:
+        cid = u.get("id_crop")
+        entry = dict(id_crop="" if cid is None else str(cid), isCrop=int(is_crop(cid)), rootShape=1, growth=2, isRootStatic=0, degreeDaysRootGrowth=0,
+                     shapeDeformation=0.0, rootDepthMin=0.0, rootDepthMax=0.0, degreeDaysEmergence=0.0)
+        if entry["isCrop"]:
+            r = by_id.get(entry["id_crop"])
+            if r is None:
+                raise ValueError(f"Missing crop: {entry['id_crop']}")
+            growth_dd = db_double(r.get("degree_days_root_increase"))
+            entry.update(rootShape=root_distribution_type(r.get("root_shape")), growth=root_growth_type(r.get("root_growth")),
+                         isRootStatic=int(CROP_TYPES.get(str(r["type"]).lower(), 0) in ROOT_STATIC_TYPES),
+                         degreeDaysRootGrowth=_db_int(r["degree_days_lai_increase"]) if growth_dd == NODATA else int(growth_dd),
+                         shapeDeformation=_db_float(r["root_shape_deformation"]), rootDepthMin=_db_float(r["root_depth_zero"]),
+                         rootDepthMax=_db_float(r["root_depth_max"]), degreeDaysEmergence=float(_db_int(r["degree_days_emergence"])))
+        out.append(entry)
+    return out
+
+
+def soil_root_table(soils) -> list:
+    """the soils of load_all_soils as the root module takes them, same index: totalDepth and per horizon upperDepth, lowerDepth and
+    getSoilFraction() = 1.0 - coarseFragments (soil.h:162)"""
+    return [dict(totalDepth=float(s["total_depth"]), upperDepth=[float(h["upper"]) for h in s["horizons"]], lowerDepth=[float(h["lower"]) for h in s["horizons"]],
+                 soilFraction=[1.0 - float(h["coarse"]) for h in s["horizons"]]) for s in soils]
+
+
 def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> Model:
     """The solver model `Project3D::initialize3DModel` builds (project3D.cpp:456-616), as arrays for the bulk ABI:
     setSoilIndexMap :708-755, computation depth :494-515, setSoilLayers / setLayersDepth :1568-1661, setIndexMaps :758-818,

@@ -1,0 +1,374 @@
+"""Root depth and root density maps on the device (include/sf3d_root.h, criteria3d_amd/csrc/sf3d_root.inc): the two calls
+`Project3D::assignTranspiration` makes for every crop cell, every hour (src/project3D/project3D.cpp:2487-2498) -
+`Crit3DCrop::computeRootLength3D` (agrolib/crop/crop.cpp:651-691, over `root::getRootLengthDD`, agrolib/crop/root.cpp:139-170) and
+`root::computeRootDensity3D` (root.cpp:505-633, over `cardioidDistribution` / `cylindricalDistribution`, root.cpp:255-364).
+
+Two parts:
+  * the binding (`bind`, `initialize`, `compute`, `get_length`, `get_density` ...): k_root_table builds the density vector of every
+    (land unit, soil, number of rooted atoms) key once, k_root_cell computes the root length of every cell and its key every hour,
+    k_root_gather serves the density maps; a missing kernel or library is an error;
+  * `restate_root_length`, `restate_root_density` (and `restate_root_maps`, `lunette`): the two functions in plain Python doubles with
+    the reference's operation order and the C library's exp / atan2 (python's `math`) - the checker of the CPU tests against the
+    compiled-reference pin (tests/golden/root_density.npz) and the host figure of scripts/root_timing.py.  A checker, never a fallback."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import capi
+
+NODATA = -9999.0
+EPSILON = 0.00001                               # commonConstants.h:252
+PI = 3.1415926535898                            # commonConstants.h:249
+MAX_UNITS = 64                                  # SF3D_CROP_MAX_UNITS
+MAX_SOILS = 1024                                # SF3D_ROOT_MAX_SOILS
+MAX_HORIZONS = 16                               # SF3D_ROOT_MAX_HORIZONS
+MAX_LAYERS = 64                                 # SF3D_ROOT_MAX_LAYERS
+MAX_ATOMS = 1024                                # SF3D_ROOT_MAX_ATOMS
+CYLINDER, CARDIOID, GAMMA = 0, 1, 2             # rootDistributionType (agrolib/crop/root.h:11)
+LINEAR, EXPONENTIAL, LOGISTIC = 0, 1, 2         # rootGrowthType (root.h:14)
+KERNEL_CELL, KERNEL_TABLE, KERNEL_GATHER = 0, 1, 2
+
+UNIT_INT_FIELDS = ("rootShape", "growth", "isRootStatic", "degreeDaysRootGrowth")
+UNIT_DOUBLE_FIELDS = ("shapeDeformation", "rootDepthMin", "rootDepthMax", "degreeDaysEmergence")
+UNIT_FIELDS = UNIT_INT_FIELDS + UNIT_DOUBLE_FIELDS
+
+
+class Unit(C.Structure):
+    """sf3d_root_unit_t"""
+    _fields_ = [(n, C.c_int32) for n in UNIT_INT_FIELDS] + [(n, C.c_double) for n in UNIT_DOUBLE_FIELDS]
+
+
+class Soil(C.Structure):
+    """sf3d_root_soil_t"""
+    _fields_ = [("totalDepth", C.c_double), ("nrHorizons", C.c_int32), ("reserved", C.c_int32), ("upperDepth", C.c_double * MAX_HORIZONS),
+                ("lowerDepth", C.c_double * MAX_HORIZONS), ("soilFraction", C.c_double * MAX_HORIZONS)]
+
+
+pf32 = C.POINTER(C.c_float)
+pf64 = C.POINTER(C.c_double)
+pi32 = C.POINTER(C.c_int32)
+punit = C.POINTER(Unit)
+psoil = C.POINTER(Soil)
+# name -> (restype, argtypes): every symbol include/sf3d_root.h declares
+SIGNATURES = {
+    "sf3d_root_initialize": (capi.u8, [capi.u32, capi.u32, pf32, capi.f32, capi.u32, pf64, pf64, pi32, pi32, capi.u32, punit, capi.u32, psoil]),
+    "sf3d_root_compute": (capi.u8, [capi.u32, pf32]),
+    "sf3d_root_get_length": (capi.u8, [capi.u32, pf64]),
+    "sf3d_root_get_depth": (capi.u8, [capi.u32, pf64]),
+    "sf3d_root_get_layers": (capi.u8, [capi.u32, pi32, pi32]),
+    "sf3d_root_get_density": (capi.u8, [capi.i32, capi.u32, pf64]),
+    "sf3d_root_get_keys": (capi.u8, [capi.u32, pi32]),
+    "sf3d_root_table_rows": (capi.u32, []),
+    "sf3d_root_kernel_ms": (capi.f64, [capi.i32]),
+    "sf3d_root_clean": (capi.u8, []),
+}
+
+
+def bind(sf: capi.SF3D) -> capi.SF3D:
+    """attach the signatures of include/sf3d_root.h to a loaded product library (AttributeError if a symbol is missing)"""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(sf.lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return sf
+
+
+# ------------------------------------------------------------------------------------------------ binding
+
+def unit_array(units):
+    """list of dicts (UNIT_FIELDS) -> ctypes array of sf3d_root_unit_t"""
+    arr = (Unit * max(len(units), 1))()
+    for k, u in enumerate(units):
+        for n in UNIT_INT_FIELDS:
+            setattr(arr[k], n, int(u[n]))
+        for n in UNIT_DOUBLE_FIELDS:
+            setattr(arr[k], n, float(u[n]))
+    return arr
+
+
+def soil_array(soils):
+    """list of dicts (totalDepth, upperDepth[], lowerDepth[], soilFraction[]: project3d.soil_root_table) -> ctypes array of
+    sf3d_root_soil_t; a soil with more than MAX_HORIZONS horizons keeps its count (the library refuses it) and its first MAX_HORIZONS"""
+    arr = (Soil * max(len(soils), 1))()
+    for k, s in enumerate(soils):
+        arr[k].totalDepth = float(s["totalDepth"])
+        arr[k].nrHorizons = len(s["upperDepth"])
+        for h in range(min(len(s["upperDepth"]), MAX_HORIZONS)):
+            arr[k].upperDepth[h], arr[k].lowerDepth[h], arr[k].soilFraction[h] = float(s["upperDepth"][h]), float(s["lowerDepth"][h]), float(s["soilFraction"][h])
+    return arr
+
+
+def initialize(sf: capi.SF3D, dem, crop_index, soil_index, units, soils, layer_depth, layer_thickness, flag: float = NODATA) -> None:
+    """the raster `dem` [rows, cols], the land-unit (= crop) and soil index per cell (negative: none), the root units (dicts with
+    UNIT_FIELDS), the soils (project3d.soil_root_table) and the layer grid (layer 0: the surface); builds the density table"""
+    bind(sf)
+    dem = np.ascontiguousarray(dem, np.float32)
+    ci = np.ascontiguousarray(crop_index, np.int32)
+    si = np.ascontiguousarray(soil_index, np.int32)
+    if ci.shape != dem.shape or si.shape != dem.shape:
+        raise ValueError(f"index maps of shape {ci.shape} / {si.shape}, the DEM is {dem.shape}")
+    ld = np.ascontiguousarray(layer_depth, np.float64)
+    lt = np.ascontiguousarray(layer_thickness, np.float64)
+    if ld.shape != lt.shape or ld.ndim != 1:
+        raise ValueError("layer depth and thickness differ in length")
+    sf._root_shape, sf._root_layers = dem.shape, len(ld)
+    sf.check(sf.lib.sf3d_root_initialize(dem.shape[0], dem.shape[1], dem.ctypes.data_as(pf32), float(flag), len(ld), ld.ctypes.data_as(pf64),
+                                         lt.ctypes.data_as(pf64), ci.ctypes.data_as(pi32), si.ctypes.data_as(pi32), len(units), unit_array(units),
+                                         len(soils), soil_array(soils)), "root_initialize")
+
+
+def compute(sf: capi.SF3D, degree_days=None) -> None:
+    """root length, depth, layers and density key of every cell from a float degree-day map; None: the degree-day map of the crop block
+    on the device (crop.initialize on the same raster), nothing is uploaded"""
+    n = int(np.prod(sf._root_shape))
+    if degree_days is None:
+        sf.check(sf.lib.sf3d_root_compute(n, pf32()), "root_compute")
+        return
+    v = np.ascontiguousarray(degree_days, np.float32)
+    if v.shape != tuple(sf._root_shape):
+        raise ValueError(f"map of shape {v.shape}, the root raster is {tuple(sf._root_shape)}")
+    sf.check(sf.lib.sf3d_root_compute(n, v.ctypes.data_as(pf32)), "root_compute")
+
+
+def get_length(sf: capi.SF3D) -> np.ndarray:
+    out = np.empty(sf._root_shape, np.float64)
+    sf.check(sf.lib.sf3d_root_get_length(out.size, out.ctypes.data_as(pf64)), "root_get_length")
+    return out
+
+
+def get_depth(sf: capi.SF3D) -> np.ndarray:
+    out = np.empty(sf._root_shape, np.float64)
+    sf.check(sf.lib.sf3d_root_get_depth(out.size, out.ctypes.data_as(pf64)), "root_get_depth")
+    return out
+
+
+def get_layers(sf: capi.SF3D):
+    """(firstRootLayer, lastRootLayer) int32 maps"""
+    first, last = np.empty(sf._root_shape, np.int32), np.empty(sf._root_shape, np.int32)
+    sf.check(sf.lib.sf3d_root_get_layers(first.size, first.ctypes.data_as(pi32), last.ctypes.data_as(pi32)), "root_get_layers")
+    return first, last
+
+
+def get_density(sf: capi.SF3D, layer: int = -1) -> np.ndarray:
+    """the root density of one layer [rows, cols] or (layer = -1) of all layers [layer, rows, cols]"""
+    shape = tuple(sf._root_shape) if layer >= 0 else (sf._root_layers,) + tuple(sf._root_shape)
+    out = np.empty(shape, np.float64)
+    sf.check(sf.lib.sf3d_root_get_density(int(layer), int(np.prod(sf._root_shape)), out.ctypes.data_as(pf64)), f"root_get_density({layer})")
+    return out
+
+
+def get_keys(sf: capi.SF3D) -> np.ndarray:
+    """the row of the density table every cell reads (-1: not computed): one per (land unit, soil, number of rooted atoms)"""
+    out = np.empty(sf._root_shape, np.int32)
+    sf.check(sf.lib.sf3d_root_get_keys(out.size, out.ctypes.data_as(pi32)), "root_get_keys")
+    return out
+
+
+def all_maps(sf: capi.SF3D) -> dict:
+    first, last = get_layers(sf)
+    return dict(length=get_length(sf), depth=get_depth(sf), first=first, last=last, density=get_density(sf, -1))
+
+
+def table_rows(sf: capi.SF3D) -> int:
+    return int(sf.lib.sf3d_root_table_rows())
+
+
+def kernel_ms(sf: capi.SF3D, which: int) -> float:
+    return float(sf.lib.sf3d_root_kernel_ms(int(which)))
+
+
+def clean(sf: capi.SF3D) -> None:
+    sf.check(sf.lib.sf3d_root_clean(), "root_clean")
+
+
+# ------------------------------------------------------------------------------------------------ restatement (checker)
+
+# std::log of a constant: folded by the pin build's compiler (the generator's library_calls names no log), the same values here
+INI_LOG = math.log(9.)
+FIL_LOG = math.log(1 / 0.99 - 1)
+LOG_02 = math.log(0.2)
+LOG_005 = math.log(0.05)
+
+
+def _round_int(x: float) -> int:
+    """int(round(x)) with C's round: half away from zero"""
+    f = math.floor(abs(x))
+    r = f + 1 if abs(x) - f >= 0.5 else f                  # exact: |x| - floor|x| is representable
+    return int(r) if x >= 0 else -int(r)
+
+
+def restate_root_length(unit: dict, degree_days: float, total_depth: float):
+    """Crit3DCrop::computeRootLength3D (crop.cpp:651-691) over root::getRootLengthDD (root.cpp:139-170) -> (currentRootLength, rootDepth)"""
+    dmin, dmax, ddg = float(unit["rootDepthMin"]), float(unit["rootDepthMax"]), float(int(unit["degreeDaysRootGrowth"]))
+    actual = dmax if abs(total_depth - NODATA) < EPSILON else (total_depth if total_depth < dmax else dmax)
+    dd = float(degree_days)
+    if int(unit["isRootStatic"]):
+        length = actual - dmin
+    elif dd <= 0:
+        length = 0.0
+    elif dd > ddg:
+        length = actual - dmin
+    else:
+        dd = dd if dd > 1.0 else 1.0
+        if dd <= 1:
+            length = 0.0
+        else:
+            max_len = actual - dmin
+            if int(unit["growth"]) == LINEAR:
+                length = max_len * (dd / ddg)
+            elif int(unit["growth"]) == LOGISTIC:
+                k = -(INI_LOG - FIL_LOG) / (float(unit["degreeDaysEmergence"]) - ddg)
+                b = -(FIL_LOG + k * ddg)
+                log_max = actual / (1 + math.exp(-b - k * ddg))
+                log_min = actual / (1 + math.exp(-b))
+                deformation = (log_max - log_min) / max_len
+                length = 1.0 / deformation * (actual / (1.0 + math.exp(-b - k * dd)) - log_min)
+            else:
+                length = NODATA
+    return length, dmin + length
+
+
+def lunette(m: int):
+    """lunette[0 .. m-1] of cardioidDistribution (root.cpp:277-284) for m rooted atoms: the C library's atan2"""
+    out = []
+    for i in range(m):
+        sin_alfa = 1.0 - (i + 1.0) / float(m)
+        v = max(0.0, 1.0 - sin_alfa * sin_alfa)
+        cos_alfa = max(math.sqrt(v), 0.0001)
+        alfa = math.atan2(sin_alfa, cos_alfa)
+        out.append(((PI / 2.0) - alfa - sin_alfa * cos_alfa) / PI)
+    return out
+
+
+def _cardioid(shape_factor: float, m: int, top: int, total: int):
+    d = [0.0] * total
+    if m == 0 or top + m > total:
+        return d
+    shape_factor = 1.0 if shape_factor < 1.0 else (2.0 if 2.0 < shape_factor else shape_factor)
+    lun = lunette(m)
+    ld = [0.0] * (2 * m)
+    ld[0] = lun[0]
+    ld[2 * m - 1] = ld[0]
+    for i in range(1, m):
+        ld[i] = lun[i] - lun[i - 1]
+        ld[2 * m - i - 1] = ld[i]
+    li_min = -LOG_02 / m
+    li_max = -LOG_005 / m
+    k = li_min + (li_max - li_min) * (shape_factor - 1)
+    s = 0.0
+    for i in range(2 * m):
+        ld[i] *= math.exp(-k * (i + 0.5))
+        s += ld[i]
+    for i in range(2 * m):
+        ld[i] /= s
+    for i in range(m):
+        d[top + i] = ld[2 * i] + ld[2 * i + 1]
+    return d
+
+
+def _cylinder(deformation: float, m: int, top: int, total: int):
+    c = [1. / (2 * m)] * (2 * m)
+    s = 0.0
+    delta = deformation - 1
+    for i in range(m):
+        c[i] *= deformation
+        deformation -= delta / m
+        s += c[i]
+    for i in range(m, 2 * m):
+        deformation -= delta / m
+        c[i] *= deformation
+        s += c[i]
+    for i in range(m, 2 * m):                       # the reference normalises the lower half only
+        c[i] /= s
+    d = [0.0] * total
+    for i in range(m):
+        d[top + i] = c[2 * i] + c[2 * i + 1]
+    return d
+
+
+def horizon_fraction(soil: dict, depth: float):
+    """getSoilFraction() of the horizon Crit3DSoil::getHorizonIndex (soil.cpp:192-201) finds for `depth`; None when it finds none"""
+    for up, low, frac in zip(soil["upperDepth"], soil["lowerDepth"], soil["soilFraction"]):
+        if depth >= up and depth <= (low + EPSILON):
+            return frac
+    return None
+
+
+def restate_root_density(unit: dict, soil: dict, layer_depth, layer_thickness, length: float):
+    """root::computeRootDensity3D (root.cpp:505-633) on a fresh Crit3DRoot whose currentRootLength is `length`
+    -> (rootDensity[nrLayers], firstRootLayer, lastRootLayer); the early returns leave zeros and NODATA layers"""
+    nl = len(layer_depth)
+    first = last = int(NODATA)
+    dens = [0.0] * nl
+    if nl <= 1 or length <= 0:
+        return dens, first, last
+    shape = CARDIOID if int(unit["rootShape"]) == GAMMA else int(unit["rootShape"])
+    total_depth = float(soil["totalDepth"])
+    nr_atoms = int(total_depth * 100) + 1
+    top = _round_int(float(unit["rootDepthMin"]) / 0.01)
+    rooted = _round_int((length if length < total_depth else total_depth) / 0.01)
+    if rooted == 0:
+        return dens, first, last
+    if top + rooted > nr_atoms:
+        rooted = nr_atoms - top
+    if rooted <= 0:                                 # the reference passes a negative count on as unsigned; here: no roots
+        return dens, first, last
+    thin = _cardioid(float(unit["shapeDeformation"]), rooted, top, nr_atoms) if shape == CARDIOID else \
+        _cylinder(float(unit["shapeDeformation"]), rooted, top, nr_atoms)
+    max_layer_depth = layer_depth[nl - 1] + layer_thickness[nl - 1] * 0.5
+    atom, s = 0, 0.0
+    current = atom * 0.01
+    while current <= max_layer_depth and atom < nr_atoms:
+        for l in range(nl):
+            if current >= layer_depth[l] - layer_thickness[l] * 0.5 and current <= layer_depth[l] + layer_thickness[l] * 0.5:
+                dens[l] += thin[atom]
+                s += thin[atom]
+                break
+        atom += 1
+        current = atom * 0.01
+    if s <= EPSILON:
+        return dens, first, last
+    subset = 0.0
+    for l in range(nl):
+        frac = horizon_fraction(soil, layer_depth[l])
+        if frac is not None:
+            dens[l] *= frac
+            subset += dens[l]
+    if subset > EPSILON and abs(subset - s) > EPSILON:
+        ratio = s / subset
+        for l in range(nl):
+            dens[l] *= ratio
+    for l in range(nl):
+        if dens[l] > EPSILON:
+            if first == int(NODATA):
+                first = l
+            last = l
+    return dens, first, last
+
+
+def restate_root_maps(dem, crop_index, soil_index, units, soils, layer_depth, layer_thickness, degree_days, flag: float = NODATA) -> dict:
+    """both functions on every cell that is a DEM cell (isEqual), has a crop and a soil index and degree days that are neither the flag nor NODATA;
+    the flag in every output elsewhere.  The density vector is kept per (unit, soil, length): the cells of a key share it."""
+    dem = np.asarray(dem, np.float32)
+    dd = np.asarray(degree_days, np.float32)
+    fl = float(np.float32(flag))
+    nl = len(layer_depth)
+    ld, lt = [float(x) for x in layer_depth], [float(x) for x in layer_thickness]
+    out = dict(length=np.full(dem.shape, fl), depth=np.full(dem.shape, fl), first=np.full(dem.shape, int(fl), np.int32),
+               last=np.full(dem.shape, int(fl), np.int32), density=np.full((nl,) + dem.shape, fl))
+    ci, si = np.asarray(crop_index), np.asarray(soil_index)
+    ok = (np.abs(dem.astype(np.float64) - fl) >= EPSILON) & (ci >= 0) & (si >= 0) & (np.abs(dd.astype(np.float64) - fl) >= EPSILON) & (np.abs(dd.astype(np.float64) - NODATA) >= EPSILON)
+    cache = {}
+    for r, c in np.argwhere(ok):
+        u, s = units[int(ci[r, c])], soils[int(si[r, c])]
+        length, depth = restate_root_length(u, float(dd[r, c]), float(s["totalDepth"]))
+        key = (int(ci[r, c]), int(si[r, c]), length)
+        if key not in cache:
+            cache[key] = restate_root_density(u, s, ld, lt, length)
+        dens, first, last = cache[key]
+        out["length"][r, c], out["depth"][r, c], out["first"][r, c], out["last"][r, c] = length, depth, first, last
+        out["density"][:, r, c] = dens
+    return out
