@@ -177,6 +177,15 @@ class SF3DError(RuntimeError):
     pass
 
 
+def bind_signatures(sf, signatures: dict):
+    """attach a name -> (restype, argtypes) table to a loaded library (AttributeError = symbol missing: fail loudly)"""
+    for name, (res, args) in signatures.items():
+        fn = getattr(sf.lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return sf
+
+
 def _arr(a, dtype):
     a = np.ascontiguousarray(a, dtype=dtype)
     return a
@@ -195,10 +204,7 @@ class SF3D:
             raise SF3DError(f"shared library not found: {path}")
         self.path = path
         self.lib = C.CDLL(str(path), mode=C.RTLD_LOCAL)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(self.lib, name)        # AttributeError = symbol missing: fail loudly
-            fn.restype = res
-            fn.argtypes = args
+        bind_signatures(self, SIGNATURES)
         self.backend = self.lib.sf3d_backend_name().decode()
 
     # -- helpers -------------------------------------------------------------------------

@@ -16,11 +16,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 from pathlib import Path
 
 import numpy as np
 
-from . import capi, esri
+from . import capi, raster
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -67,20 +68,13 @@ SIGNATURES = {
 
 def bind(sf: capi.SF3D) -> capi.SF3D:
     """attach the signatures of include/sf3d_crop.h to a loaded product library (AttributeError if a symbol is missing)"""
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(sf.lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return sf
+    return capi.bind_signatures(sf, SIGNATURES)
 
 
 # ------------------------------------------------------------------------------------------------ binding
 
-def _f32(a, shape=None):
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    if shape is not None and a.shape != tuple(shape):
-        raise ValueError(f"map of shape {a.shape}, the crop raster is {tuple(shape)}")
-    return a
+_f32 = partial(raster.f32, what="crop")
+_index = raster.index
 
 
 def unit_array(units):
@@ -105,10 +99,6 @@ def initialize(sf: capi.SF3D, dem, unit_index, units, latitude: float, flag: flo
     sf._crop_shape = dem.shape
     sf.check(sf.lib.sf3d_crop_initialize(dem.shape[0], dem.shape[1], dem.ctypes.data_as(pf32), float(flag), idx.ctypes.data_as(pi32), len(units),
                                          unit_array(units), float(latitude)), "crop_initialize")
-
-
-def _index(which, names) -> int:
-    return names.index(which) if isinstance(which, str) else int(which)
 
 
 def set_state(sf: capi.SF3D, which, values) -> None:
@@ -168,19 +158,12 @@ def clean(sf: capi.SF3D) -> None:
 
 def save_crop_state(sf: capi.SF3D, directory, header: dict) -> Path:
     """<directory>/crop/{degreeDays, LAI, dailyTmin, dailyTmax}.flt/.hdr"""
-    d = Path(directory) / "crop"
-    d.mkdir(parents=True, exist_ok=True)
-    for name, stem in STATE_FILES.items():
-        esri.write_grid(d / stem, get_state(sf, name), header)
-    return d
+    return raster.save_state(directory, "crop", STATE_FILES, partial(get_state, sf), header)
 
 
 def load_crop_state(sf: capi.SF3D, directory) -> None:
     """the four maps of <directory>/crop onto the device (the raster must be initialised with the same DEM)"""
-    d = Path(directory) / "crop"
-    for name, stem in STATE_FILES.items():
-        grid, _ = esri.read_grid(d / stem)
-        set_state(sf, name, grid)
+    raster.load_state(directory, "crop", STATE_FILES, partial(set_state, sf))
 
 
 # ------------------------------------------------------------------------------------------------ restatement (checker)

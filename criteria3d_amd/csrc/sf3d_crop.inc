@@ -177,17 +177,16 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_crop_day(CropView v)
     v.st[2][c] = flag; v.st[3][c] = flag;                                     /* emptyGrid on the daily extremes (from a map: initializeCropMaps) */
 }
 
-/* ---- host side: one device block of CROP_MAPS x nCells 4-byte values and the crop table; calls run on the solver's stream and touch
- * nothing of the solver.  A HIP failure here does not mark the solver unusable. */
+/* ---- host side: one device block of CROP_MAPS x nCells 4-byte values and the crop table; calls go through the shared raster path at the
+ * end of sf3d_maps.inc. */
 sf3d_error_t DeviceSolver::crop_free()
 {
     if (!impl_) return SF3D_OK;
     CropCache& K = impl_->crop;
-    if (K.base || K.units || K.mine) {
+    if (K.base || K.units) {
         if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
         if (K.base) (void)hipFree(K.base);
         if (K.units) (void)hipFree(K.units);
-        if (K.mine) (void)hipFree(K.mine);
     }
     K = CropCache();
     return SF3D_OK;
@@ -199,30 +198,24 @@ sf3d_error_t DeviceSolver::crop_alloc(uint32_t nCells, const CropUnitDev* units,
     if (e != SF3D_OK) return e;
     crop_free();
     CropCache& K = impl_->crop;
-    SNOW_TRY(hipMalloc((void**)&K.base, (size_t)CROP_MAPS * nCells * sizeof(float)));
-    SNOW_TRY(hipMalloc((void**)&K.units, (size_t)CROP_MAX_UNITS * sizeof(CropUnitDev)));
+    RASTER_TRY(hipMalloc((void**)&K.base, (size_t)CROP_MAPS * nCells * sizeof(float)));
+    RASTER_TRY(hipMalloc((void**)&K.units, (size_t)CROP_MAX_UNITS * sizeof(CropUnitDev)));
     K.nCells = nCells; K.nUnits = nUnits;
-    if (nUnits) SNOW_TRY(hipMemcpyAsync(K.units, units, (size_t)nUnits * sizeof(CropUnitDev), hipMemcpyHostToDevice, impl_->stream));
-    SNOW_TRY(hipStreamSynchronize(impl_->stream));
+    if (nUnits) RASTER_TRY(hipMemcpyAsync(K.units, units, (size_t)nUnits * sizeof(CropUnitDev), hipMemcpyHostToDevice, impl_->stream));
+    RASTER_TRY(hipStreamSynchronize(impl_->stream));
     return SF3D_OK;
 }
 
 sf3d_error_t DeviceSolver::crop_upload(int map, const void* src)
 {
-    CropCache& K = impl_->crop;
-    SNOW_TRY(hipSetDevice(impl_->device));
-    SNOW_TRY(hipMemcpyAsync(K.base + (size_t)map * K.nCells, src, (size_t)K.nCells * sizeof(float), hipMemcpyHostToDevice, impl_->stream));
-    SNOW_TRY(hipStreamSynchronize(impl_->stream));         /* the caller's map is free again on return */
-    return SF3D_OK;
+    const CropCache& K = impl_->crop;
+    return raster_upload(K.base + (size_t)map * K.nCells, src, (size_t)K.nCells * sizeof(float));
 }
 
 sf3d_error_t DeviceSolver::crop_download(int map, float* dst)
 {
-    CropCache& K = impl_->crop;
-    SNOW_TRY(hipSetDevice(impl_->device));
-    SNOW_TRY(hipMemcpyAsync(dst, K.base + (size_t)map * K.nCells, (size_t)K.nCells * sizeof(float), hipMemcpyDeviceToHost, impl_->stream));
-    SNOW_TRY(hipStreamSynchronize(impl_->stream));
-    return SF3D_OK;
+    const CropCache& K = impl_->crop;
+    return raster_download(dst, K.base + (size_t)map * K.nCells, (size_t)K.nCells * sizeof(float));
 }
 
 bool DeviceSolver::crop_snow_inputs_ready(uint32_t nCells) const
@@ -230,7 +223,7 @@ bool DeviceSolver::crop_snow_inputs_ready(uint32_t nCells) const
     return impl_ && impl_->snow.base && impl_->snow.hourDone && impl_->snow.nCells == nCells;
 }
 
-static void crop_view(CropView& v, const CropCache& K, float flag, const uint8_t* mineDev)
+static void crop_view(CropView& v, const CropCache& K, float flag)
 {
     const size_t n = K.nCells;
     for (int k = 0; k < 4; ++k) v.st[k] = K.base + (size_t)(CROP_MAP_STATE + k) * n;
@@ -239,67 +232,41 @@ static void crop_view(CropView& v, const CropCache& K, float flag, const uint8_t
     v.dem = K.base + (size_t)CROP_MAP_DEM * n;
     v.index = reinterpret_cast<const int32_t*>(K.base + (size_t)CROP_MAP_INDEX * n);
     v.units = K.units;
-    v.mine = mineDev;
     v.nCells = K.nCells; v.nUnits = K.nUnits; v.flag = flag;
 }
-
-/* which: 0 k_et0_hour, 1 k_crop_day */
-#define CROP_LAUNCH(which, kernel)                                                                                            \
-    do {                                                                                                                      \
-        const dim3 grid((K.nCells + SF3D_BLOCK - 1) / SF3D_BLOCK);                                                            \
-        hipEvent_t ev[2] = {nullptr, nullptr};                                                                                \
-        if (I.timing) { SNOW_TRY(hipEventCreate(&ev[0])); SNOW_TRY(hipEventCreate(&ev[1])); SNOW_TRY(hipEventRecord(ev[0], I.stream)); } \
-        hipLaunchKernelGGL(kernel, grid, dim3(SF3D_BLOCK), 0, I.stream, v);                                                   \
-        SNOW_TRY(hipGetLastError());                                                                                          \
-        if (I.timing) SNOW_TRY(hipEventRecord(ev[1], I.stream));                                                              \
-        SNOW_TRY(hipStreamSynchronize(I.stream));              /* the caller's maps are free again on return */               \
-        K.lastMs[which] = 0.;                                                                                                 \
-        if (I.timing) {                                                                                                       \
-            float ms = 0.f;                                                                                                   \
-            SNOW_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));                                                                 \
-            (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);                                                       \
-            K.lastMs[which] = ms;                                                                                             \
-        }                                                                                                                     \
-    } while (0)
 
 sf3d_error_t DeviceSolver::crop_hour(const float* const in[5], float clearSky, float flag, const uint8_t* mine)
 {
     Impl& I = *impl_;
     CropCache& K = I.crop;
     const size_t n = K.nCells;
-    SNOW_TRY(hipSetDevice(I.device));
+    RASTER_TRY(hipSetDevice(I.device));
     if (in)
-        for (int k = 0; k < 5; ++k) SNOW_TRY(hipMemcpyAsync(K.base + (size_t)(CROP_MAP_IN + k) * n, in[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
-    if (mine) {
-        if (!K.mine) SNOW_TRY(hipMalloc((void**)&K.mine, n));
-        SNOW_TRY(hipMemcpyAsync(K.mine, mine, n, hipMemcpyHostToDevice, I.stream));
-    }
+        for (int k = 0; k < 5; ++k) RASTER_TRY(hipMemcpyAsync(K.base + (size_t)(CROP_MAP_IN + k) * n, in[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
     CropView v{};
-    crop_view(v, K, flag, mine ? K.mine : nullptr);
+    const sf3d_error_t e = raster_mask(mine, n, &v.mine);
+    if (e != SF3D_OK) return e;
+    crop_view(v, K, flag);
     if (!in) {                                  /* the maps sf3d_snow_compute_hour uploaded: air temperature, relative humidity, wind, global radiation, transmissivity */
         static const int snowInput[5] = {0, 2, 3, 4, 6};
         for (int k = 0; k < 5; ++k) v.in[k] = I.snow.base + (size_t)(SNOW_MAP_IN + snowInput[k]) * n;
     }
     v.clearSky = clearSky;
-    CROP_LAUNCH(0, k_et0_hour);
-    return SF3D_OK;
+    return raster_launch(k_et0_hour, n, v, K.lastMs[0]);
 }
 
 sf3d_error_t DeviceSolver::crop_day(int dateDoy, int currentDoy, double latitude, float flag, const uint8_t* mine)
 {
     Impl& I = *impl_;
     CropCache& K = I.crop;
-    const size_t n = K.nCells;
-    SNOW_TRY(hipSetDevice(I.device));
-    if (mine) {
-        if (!K.mine) SNOW_TRY(hipMalloc((void**)&K.mine, n));
-        SNOW_TRY(hipMemcpyAsync(K.mine, mine, n, hipMemcpyHostToDevice, I.stream));
-    }
+    RASTER_TRY(hipSetDevice(I.device));
     CropView v{};
-    crop_view(v, K, flag, mine ? K.mine : nullptr);
+    const sf3d_error_t e = raster_mask(mine, K.nCells, &v.mine);
+    if (e != SF3D_OK) return e;
+    crop_view(v, K, flag);
     v.latitude = latitude; v.dateDoy = dateDoy; v.currentDoy = currentDoy;
-    CROP_LAUNCH(1, k_crop_day);
-    return SF3D_OK;
+    return raster_launch(k_crop_day, K.nCells, v, K.lastMs[1]);
 }
 
+/* which: 0 k_et0_hour, 1 k_crop_day */
 double DeviceSolver::crop_kernel_ms(int which) const { return (impl_ && (which == 0 || which == 1)) ? impl_->crop.lastMs[which] : 0.; }

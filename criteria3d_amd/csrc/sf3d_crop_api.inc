@@ -12,30 +12,9 @@ struct CropHost {
     uint32_t nRows = 0, nCols = 0;
     float flag = -9999.f;
     double latitude = 0.;
-    std::vector<uint8_t> mine;                 /* strips: 1 on the cells this rank computes */
-    uint64_t mineColVer = 0, mineGen = 0;      /* (MP.colVer, LM.gen) it was made from */
 } CR;
 
 void cropClear() { CR = CropHost(); (void)dev().crop_free(); }
-
-sf3d_error_t cropFail(const char* what, sf3d_error_t e) { if (e == SF3D_SOLVER_ERROR) fprintf(stderr, "sf3d: %s: %s\n", what, dev().last_error()); return e; }
-
-/* strips: the cells whose column (first node of the output maps' column table) this rank owns; null when the run is not distributed */
-const uint8_t* cropMine()
-{
-    const size_t n = (size_t)CR.nRows * CR.nCols;
-    if (!(LM.on && MP.set && MP.nCells == n && !LM.gpart.owner.empty())) return nullptr;
-    if (CR.mine.size() != n || CR.mineColVer != MP.colVer || CR.mineGen != LM.gen) {
-        CR.mine.assign(n, 0);
-        for (size_t c = 0; c < n; ++c) {
-            int32_t first = -1;
-            for (uint32_t l = 0; l < MP.nLayers && first < 0; ++l) first = MP.col[l * n + c];
-            if (first >= 0 && (size_t)first < LM.gpart.owner.size() && LM.gpart.owner[first] == distRank) CR.mine[c] = 1;
-        }
-        CR.mineColVer = MP.colVer; CR.mineGen = LM.gen;
-    }
-    return CR.mine.data();
-}
 
 }  // namespace
 
@@ -54,14 +33,14 @@ sf3d_error_t sf3d_crop_initialize(uint32_t nrRows, uint32_t nrCols, const float*
     }
     cropClear();
     sf3d_error_t e = dev().crop_alloc(n, reinterpret_cast<const CropUnitDev*>(units), nUnits);
-    if (e != SF3D_OK) return cropFail("crop initialize", e);
+    if (e != SF3D_OK) return rasterFail("crop initialize", e);
     CR.nRows = nrRows; CR.nCols = nrCols; CR.flag = flag; CR.latitude = latitude;
     const std::vector<float> empty(n, flag);
     e = dev().crop_upload(CROP_MAP_DEM, dem);
     if (e == SF3D_OK) e = dev().crop_upload(CROP_MAP_INDEX, index.data());
     for (int k = 0; k < 5 && e == SF3D_OK; ++k) e = dev().crop_upload(CROP_MAP_STATE + k, empty.data());      /* the four state maps and ET0 */
     for (int k = 0; k < 5 && e == SF3D_OK; ++k) e = dev().crop_upload(CROP_MAP_IN + k, empty.data());
-    if (e != SF3D_OK) { cropFail("crop initialize", e); cropClear(); return e; }
+    if (e != SF3D_OK) { rasterFail("crop initialize", e); cropClear(); return e; }
     CR.on = true;
     return SF3D_OK;
 }
@@ -71,7 +50,7 @@ sf3d_error_t sf3d_crop_set_state(int which, uint32_t nrCells, const float* map)
     if (!CR.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != CR.nRows * CR.nCols) return SF3D_PARAMETER_ERROR;
     if (which < 0 || which >= SF3D_CROP_STATE_COUNT) return SF3D_INDEX_ERROR;
-    return cropFail("crop set state", dev().crop_upload(CROP_MAP_STATE + which, map));
+    return rasterFail("crop set state", dev().crop_upload(CROP_MAP_STATE + which, map));
 }
 
 sf3d_error_t sf3d_crop_get_state(int which, uint32_t nrCells, float* map)
@@ -79,14 +58,14 @@ sf3d_error_t sf3d_crop_get_state(int which, uint32_t nrCells, float* map)
     if (!CR.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != CR.nRows * CR.nCols) return SF3D_PARAMETER_ERROR;
     if (which < 0 || which >= SF3D_CROP_STATE_COUNT) return SF3D_INDEX_ERROR;
-    return cropFail("crop get state", dev().crop_download(CROP_MAP_STATE + which, map));
+    return rasterFail("crop get state", dev().crop_download(CROP_MAP_STATE + which, map));
 }
 
 sf3d_error_t sf3d_crop_get_et0(uint32_t nrCells, float* map)
 {
     if (!CR.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != CR.nRows * CR.nCols) return SF3D_PARAMETER_ERROR;
-    return cropFail("crop get et0", dev().crop_download(CROP_MAP_ET0, map));
+    return rasterFail("crop get et0", dev().crop_download(CROP_MAP_ET0, map));
 }
 
 sf3d_error_t sf3d_crop_set_degree_days(uint32_t nrCells, const float* map, int currentDoy)      /* initializeCropFromDegreeDays, criteria3DProject.cpp:524-573 */
@@ -95,7 +74,7 @@ sf3d_error_t sf3d_crop_set_degree_days(uint32_t nrCells, const float* map, int c
     if (!map || nrCells != CR.nRows * CR.nCols || currentDoy < 1 || currentDoy > 366) return SF3D_PARAMETER_ERROR;
     sf3d_error_t e = dev().crop_upload(CROP_MAP_STATE + SF3D_CROP_DEGREE_DAYS, map);
     if (e == SF3D_OK) e = dev().crop_day(-1, currentDoy, CR.latitude, CR.flag, nullptr);
-    return cropFail("crop set degree days", e);
+    return rasterFail("crop set degree days", e);
 }
 
 sf3d_error_t sf3d_crop_compute_hour(uint32_t nrCells, const float* airTemperature, const float* relativeHumidity, const float* windIntensity,
@@ -108,14 +87,14 @@ sf3d_error_t sf3d_crop_compute_hour(uint32_t nrCells, const float* airTemperatur
     for (int k = 0; k < 5; ++k) given += in[k] ? 1 : 0;
     if (given != 0 && given != 5) return SF3D_PARAMETER_ERROR;
     if (given == 0 && !(SN.on && SN.nRows == CR.nRows && SN.nCols == CR.nCols && dev().crop_snow_inputs_ready(nrCells))) return SF3D_PARAMETER_ERROR;
-    return cropFail("crop compute hour", dev().crop_hour(given ? in : nullptr, clearSkyTransmissivity, CR.flag, cropMine()));
+    return rasterFail("crop compute hour", dev().crop_hour(given ? in : nullptr, clearSkyTransmissivity, CR.flag, mapsOwnedCells(nrCells)));
 }
 
 sf3d_error_t sf3d_crop_daily_update(int dateDoy, int currentDoy)
 {
     if (!CR.on) return SF3D_MEMORY_ERROR;
     if (dateDoy < 1 || dateDoy > 366 || currentDoy < 1 || currentDoy > 366) return SF3D_PARAMETER_ERROR;
-    return cropFail("crop daily update", dev().crop_day(dateDoy, currentDoy, CR.latitude, CR.flag, cropMine()));
+    return rasterFail("crop daily update", dev().crop_day(dateDoy, currentDoy, CR.latitude, CR.flag, mapsOwnedCells((size_t)CR.nRows * CR.nCols)));
 }
 
 double sf3d_crop_kernel_ms(int which) { return dev().crop_kernel_ms(which); }

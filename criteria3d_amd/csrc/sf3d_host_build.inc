@@ -122,27 +122,27 @@ __global__ void k_dist_ping(DistView d, unsigned long long token, long long time
  * the model (release) - a rebuilt model may number its nodes differently */
 struct MapsCache {
     int32_t* col = nullptr; double* thick = nullptr; double* slope = nullptr; MapGeo* geo = nullptr; float* out = nullptr; int* missing = nullptr;
-    size_t colCap = 0, thickCap = 0, slopeCap = 0, geoCap = 0, outCap = 0;
+    uint8_t* mine = nullptr;                    /* strips: the ownership mask of the raster call in flight (raster_mask) */
+    size_t colCap = 0, thickCap = 0, slopeCap = 0, geoCap = 0, outCap = 0, mineCap = 0;
     uint64_t colVer = 0, slopeVer = 0;          /* versions of MapsInput that are on the device (0: none) */
     std::vector<MapGeo> geoHost;
     void free_all()
     {
-        for (void* q : {(void*)col, (void*)thick, (void*)slope, (void*)geo, (void*)out, (void*)missing}) if (q) (void)hipFree(q);
+        for (void* q : {(void*)col, (void*)thick, (void*)slope, (void*)geo, (void*)out, (void*)missing, (void*)mine}) if (q) (void)hipFree(q);
         *this = MapsCache();
     }
 };
 
 /* hourly snow model (sf3d_snow.inc): the maps of include/sf3d_snow.h; they belong to the raster and stay when the model is released */
-struct SnowCache { float* base = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0; double lastMs = 0.; bool hourDone = false; };
+struct SnowCache { float* base = nullptr; uint32_t nCells = 0; double lastMs = 0.; bool hourDone = false; };
 /* hourly ET0 and daily crop maps (sf3d_crop.inc): the maps of include/sf3d_crop.h and the crop table; as the snow maps, they belong to the raster */
-struct CropCache { float* base = nullptr; CropUnitDev* units = nullptr; uint8_t* mine = nullptr; uint32_t nCells = 0, nUnits = 0; double lastMs[2] = {0., 0.}; };
+struct CropCache { float* base = nullptr; CropUnitDev* units = nullptr; uint32_t nCells = 0, nUnits = 0; double lastMs[2] = {0., 0.}; };
 
 /* root maps (sf3d_root.inc): the maps of include/sf3d_root.h, the tables and the density table; they belong to the raster too */
 struct RootCache {
     char* cells = nullptr;              /* ROOT_MAP_WORDS x nCells 4-byte words: the per-cell maps */
     char* tables = nullptr;             /* units, soils, layer grid, lunette, rows, the density table: one block */
     double* out = nullptr;              /* the gathered density maps, allocated by the first getter: nrLayers x nCells */
-    uint8_t* mine = nullptr;
     size_t off[16] = {0};               /* offsets of the tables in `tables` */
     uint32_t nCells = 0, nUnits = 0, nSoils = 0, nRows = 0, nrLayers = 0, lunetteMax = 0;
     bool computed = false;
@@ -281,6 +281,14 @@ struct DeviceSolver::Impl {
              snprintf(err_, sizeof(err_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
              if (impl_ && impl_->stream) (void)hipStreamSynchronize(impl_->stream);           \
              fatal_ = true;                                                                    \
+             return SF3D_SOLVER_ERROR; } } while (0)
+
+/* the raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc) touch nothing of the solver: a HIP failure there does not set fatal_ */
+#define RASTER_TRY(expr)                                                                       \
+    do { hipError_t e_ = (expr);                                                               \
+         if (e_ != hipSuccess) {                                                               \
+             snprintf(err_, sizeof(err_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+             if (impl_ && impl_->stream) (void)hipStreamSynchronize(impl_->stream);           \
              return SF3D_SOLVER_ERROR; } } while (0)
 
 DeviceSolver& DeviceSolver::instance() { static DeviceSolver s; return s; }

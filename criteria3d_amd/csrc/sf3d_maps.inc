@@ -228,3 +228,54 @@ sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const M
     if (missing) *missing = miss;
     return SF3D_OK;
 }
+
+/* ---- shared by the raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc): their calls run on the solver's stream, touch nothing of
+ * the solver and synchronise the stream before they return, so the caller's maps are free again and one device mask serves all three. */
+sf3d_error_t DeviceSolver::raster_upload(void* dev, const void* host, size_t bytes)
+{
+    RASTER_TRY(hipSetDevice(impl_->device));
+    RASTER_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, impl_->stream));
+    RASTER_TRY(hipStreamSynchronize(impl_->stream));
+    return SF3D_OK;
+}
+
+sf3d_error_t DeviceSolver::raster_download(void* host, const void* dev, size_t bytes)
+{
+    RASTER_TRY(hipSetDevice(impl_->device));
+    RASTER_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, impl_->stream));
+    RASTER_TRY(hipStreamSynchronize(impl_->stream));
+    return SF3D_OK;
+}
+
+/* strips: the mask of sf3d_maps_api.inc's mapsOwnedCells, uploaded on every call (it is derived from the column table and the partition,
+ * so the buffer goes with the model: MapsCache); *dev stays null when every cell is computed */
+sf3d_error_t DeviceSolver::raster_mask(const uint8_t* mine, size_t nCells, const uint8_t** dev)
+{
+    *dev = nullptr;
+    if (!mine) return SF3D_OK;
+    MapsCache& C = impl_->maps;
+    RASTER_TRY(maps_reserve(C.mine, C.mineCap, nCells));
+    RASTER_TRY(hipMemcpyAsync(C.mine, mine, nCells, hipMemcpyHostToDevice, impl_->stream));
+    *dev = C.mine;
+    return SF3D_OK;
+}
+
+template <class Arg> sf3d_error_t DeviceSolver::raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms)
+{
+    Impl& I = *impl_;
+    const dim3 grid((uint32_t)((count + SF3D_BLOCK - 1) / SF3D_BLOCK));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (I.timing) { RASTER_TRY(hipEventCreate(&ev[0])); RASTER_TRY(hipEventCreate(&ev[1])); RASTER_TRY(hipEventRecord(ev[0], I.stream)); }
+    hipLaunchKernelGGL(kernel, grid, dim3(SF3D_BLOCK), 0, I.stream, arg);
+    RASTER_TRY(hipGetLastError());
+    if (I.timing) RASTER_TRY(hipEventRecord(ev[1], I.stream));
+    RASTER_TRY(hipStreamSynchronize(I.stream));
+    ms = 0.;
+    if (I.timing) {
+        float t = 0.f;
+        RASTER_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
+        ms = t;
+    }
+    return SF3D_OK;
+}

@@ -16,6 +16,8 @@ struct MapsHost {
     std::vector<int32_t> colDev;               /* strip-local model: col in local numbering */
     uint64_t colDevVer = 0, colDevGen = 0;     /* (colVer, LM.gen) it was made from */
     uint64_t colDevVerDev = 0;                 /* its version for the device */
+    std::vector<uint8_t> mine;                 /* strips: 1 on the cells this rank computes (mapsOwnedCells) */
+    uint64_t mineColVer = 0, mineGen = 0;      /* (colVer, LM.gen) it was made from */
     struct Geo { uint16_t soil, horizon; double cohesion, tanFriction, bulkDensity; };
     std::vector<Geo> geo;
     std::vector<MapGeo> geoClass;
@@ -26,6 +28,32 @@ void mapsClear() { MP = MapsHost(); }
 
 const double kMapEpsilon = 0.00001;            /* commonConstants.h:252 */
 const double kMapDegToRad = 0.01745329252;     /* commonConstants.h:255 */
+
+/* strips, the one ownership rule of every raster call: a rank computes the cells whose column it owns, and a column goes with its first
+ * node in the column table */
+bool mapsOwnsCell(size_t c)
+{
+    int32_t first = -1;
+    for (uint32_t l = 0; l < MP.nLayers && first < 0; ++l) first = MP.col[l * MP.nCells + c];
+    return first >= 0 && (size_t)first < LM.gpart.owner.size() && LM.gpart.owner[first] == distRank;
+}
+
+/* 1 on the cells of an n-cell raster that this rank computes; null (every cell) when the run is not distributed, no column table is set or
+ * the raster is not the column table's */
+const uint8_t* mapsOwnedCells(size_t n)
+{
+    if (!(LM.on && MP.set && MP.nCells == n && !LM.gpart.owner.empty())) return nullptr;
+    if (MP.mineColVer != MP.colVer || MP.mineGen != LM.gen) {      /* (colVer is never 0 once set) */
+        MP.mine.resize(n);
+        for (size_t c = 0; c < n; ++c) MP.mine[c] = mapsOwnsCell(c);
+        MP.mineColVer = MP.colVer; MP.mineGen = LM.gen;
+    }
+    return MP.mine.data();
+}
+
+/* shared by the snow, crop and root entry points */
+sf3d_error_t rasterFail(const char* what, sf3d_error_t e) { if (e == SF3D_SOLVER_ERROR) fprintf(stderr, "sf3d: %s: %s\n", what, dev().last_error()); return e; }
+bool rasterIsFlag(float v, float flag) { return std::fabs(static_cast<double>(v) - static_cast<double>(flag)) < 0.00001; }      /* isEqual(float, float) */
 
 }  // namespace
 
@@ -95,9 +123,7 @@ sf3d_error_t sf3d_compute_output_map(int variable, int layer, float flag, float*
             const size_t nc = MP.nCells;
             MP.colDev.assign(MP.col.size(), -1);
             for (size_t c = 0; c < nc; ++c) {
-                int32_t first = -1;
-                for (uint32_t l = 0; l < MP.nLayers && first < 0; ++l) first = MP.col[l * nc + c];
-                if (first < 0 || (size_t)first >= LM.gpart.owner.size() || LM.gpart.owner[first] != distRank) continue;
+                if (!mapsOwnsCell(c)) continue;
                 for (uint32_t l = 0; l < MP.nLayers; ++l) {
                     const int32_t g = MP.col[l * nc + c];
                     if (g >= 0) MP.colDev[l * nc + c] = LM.g2l[g];

@@ -230,6 +230,13 @@ public:
 
 private:
     DeviceSolver() = default;
+    /* what the three raster blocks share (end of sf3d_maps.inc): a copy on the solver's stream that returns once it is done, the
+     * ownership mask of a strip on the device (null stays null), and kernel<<<ceil(count / SF3D_BLOCK), SF3D_BLOCK>>>(arg) with its
+     * event-timed milliseconds (0 when timing is off) in `ms` */
+    sf3d_error_t raster_upload(void* dev, const void* host, size_t bytes);
+    sf3d_error_t raster_download(void* host, const void* dev, size_t bytes);
+    sf3d_error_t raster_mask(const uint8_t* mine, size_t nCells, const uint8_t** dev);
+    template <class Arg> sf3d_error_t raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms);
     struct Impl;
     Impl* impl_ = nullptr;
     Ctrl mirror_{};

@@ -216,8 +216,8 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_root_gather(RootView v)
         v.out[(size_t)k * v.nCells + c] = has ? v.table[(size_t)(v.layer0 + k) * v.nRows + (uint32_t)key] : flag;
 }
 
-/* ---- host side: the per-cell block, one block of tables and the gathered density maps; calls run on the solver's stream and touch
- * nothing of the solver.  A HIP failure here does not mark the solver unusable. */
+/* ---- host side: the per-cell block, one block of tables and the gathered density maps; calls go through the shared raster path at the end
+ * of sf3d_maps.inc. */
 enum { ROOT_T_UNITS = 0, ROOT_T_SOIL_DEPTH, ROOT_T_LAYER_DEPTH, ROOT_T_LAYER_THICKNESS, ROOT_T_LAYER_FRAC, ROOT_T_LUNETTE, ROOT_T_TABLE, ROOT_T_SOIL_MAXN,
        ROOT_T_PAIR_ROW, ROOT_T_ROW_UNIT, ROOT_T_ROW_SOIL, ROOT_T_ROW_N, ROOT_T_ROW_LAYERS, ROOT_T_END };
 
@@ -225,12 +225,11 @@ sf3d_error_t DeviceSolver::root_free()
 {
     if (!impl_) return SF3D_OK;
     RootCache& K = impl_->root;
-    if (K.cells || K.tables || K.out || K.mine) {
+    if (K.cells || K.tables || K.out) {
         if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
         if (K.cells) (void)hipFree(K.cells);
         if (K.tables) (void)hipFree(K.tables);
         if (K.out) (void)hipFree(K.out);
-        if (K.mine) (void)hipFree(K.mine);
     }
     K = RootCache();
     return SF3D_OK;
@@ -242,7 +241,7 @@ static void* root_cell_map(const RootCache& K, int map)
     return (map < 2) ? K.cells + (size_t)map * n * 8 : K.cells + 16 * n + (size_t)(map - 2) * n * 4;
 }
 
-static void root_view(RootView& v, const RootCache& K, float flag, const uint8_t* mineDev)
+static void root_view(RootView& v, const RootCache& K, float flag)
 {
     v.length = (double*)root_cell_map(K, ROOT_MAP_LENGTH); v.depth = (double*)root_cell_map(K, ROOT_MAP_DEPTH);
     v.dem = (const float*)root_cell_map(K, ROOT_MAP_DEM); v.dd = (const float*)root_cell_map(K, ROOT_MAP_DD);
@@ -255,29 +254,9 @@ static void root_view(RootView& v, const RootCache& K, float flag, const uint8_t
     v.rowLayers = (const int32_t*)(K.tables + K.off[ROOT_T_ROW_LAYERS]);
     v.table = (const double*)(K.tables + K.off[ROOT_T_TABLE]);
     v.out = K.out;
-    v.mine = mineDev;
     v.nCells = K.nCells; v.nUnits = K.nUnits; v.nSoils = K.nSoils; v.nRows = K.nRows; v.nrLayers = K.nrLayers; v.layer0 = 0; v.layerCount = 0;
     v.flag = flag;
 }
-
-/* which: 0 k_root_cell, 1 k_root_table, 2 k_root_gather; count: threads */
-#define ROOT_LAUNCH(which, kernel, count, arg)                                                                                \
-    do {                                                                                                                      \
-        const dim3 grid(((count) + SF3D_BLOCK - 1) / SF3D_BLOCK);                                                             \
-        hipEvent_t ev[2] = {nullptr, nullptr};                                                                                \
-        if (I.timing) { SNOW_TRY(hipEventCreate(&ev[0])); SNOW_TRY(hipEventCreate(&ev[1])); SNOW_TRY(hipEventRecord(ev[0], I.stream)); } \
-        hipLaunchKernelGGL(kernel, grid, dim3(SF3D_BLOCK), 0, I.stream, arg);                                                 \
-        SNOW_TRY(hipGetLastError());                                                                                          \
-        if (I.timing) SNOW_TRY(hipEventRecord(ev[1], I.stream));                                                              \
-        SNOW_TRY(hipStreamSynchronize(I.stream));                                                                             \
-        K.lastMs[which] = 0.;                                                                                                 \
-        if (I.timing) {                                                                                                       \
-            float ms = 0.f;                                                                                                   \
-            SNOW_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));                                                                 \
-            (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);                                                       \
-            K.lastMs[which] = ms;                                                                                             \
-        }                                                                                                                     \
-    } while (0)
 
 sf3d_error_t DeviceSolver::root_alloc(const RootSetup& S)
 {
@@ -299,19 +278,19 @@ sf3d_error_t DeviceSolver::root_alloc(const RootSetup& S)
                                          bytes[9], bytes[10], bytes[11], 0};
     size_t total = 0;
     for (int k = 0; k < ROOT_T_END; ++k) { K.off[k] = total; total += (bytes[k] + 7) & ~(size_t)7; }
-    SNOW_TRY(hipMalloc((void**)&K.cells, (size_t)ROOT_MAP_WORDS * n * 4));
-    SNOW_TRY(hipMalloc((void**)&K.tables, total ? total : 8));
+    RASTER_TRY(hipMalloc((void**)&K.cells, (size_t)ROOT_MAP_WORDS * n * 4));
+    RASTER_TRY(hipMalloc((void**)&K.tables, total ? total : 8));
     K.nCells = S.nCells; K.nUnits = S.nUnits; K.nSoils = S.nSoils; K.nRows = S.nRows; K.nrLayers = S.nrLayers; K.lunetteMax = S.lunetteMax;
     for (int k = 0; k < ROOT_T_END; ++k)
-        if (src[k] && srcBytes[k]) SNOW_TRY(hipMemcpyAsync(K.tables + K.off[k], src[k], srcBytes[k], hipMemcpyHostToDevice, I.stream));
-    SNOW_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
-    SNOW_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
-    SNOW_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+        if (src[k] && srcBytes[k]) RASTER_TRY(hipMemcpyAsync(K.tables + K.off[k], src[k], srcBytes[k], hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
     /* before the first compute every output holds the flag: the degree days are the flag everywhere and k_root_cell runs once below */
     {
         const std::vector<float> empty(n, S.flag);
-        SNOW_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DD), empty.data(), n * 4, hipMemcpyHostToDevice, I.stream));
-        SNOW_TRY(hipStreamSynchronize(I.stream));
+        RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DD), empty.data(), n * 4, hipMemcpyHostToDevice, I.stream));
+        RASTER_TRY(hipStreamSynchronize(I.stream));
     }
     if (rows) {
         RootTableView t{};
@@ -327,13 +306,14 @@ sf3d_error_t DeviceSolver::root_alloc(const RootSetup& S)
         t.table = (double*)(K.tables + K.off[ROOT_T_TABLE]);
         t.rowLayers = (int32_t*)(K.tables + K.off[ROOT_T_ROW_LAYERS]);
         t.nRows = S.nRows; t.nrLayers = S.nrLayers; t.lunetteMax = S.lunetteMax;
-        ROOT_LAUNCH(1, k_root_table, S.nRows, t);
+        e = raster_launch(k_root_table, rows, t, K.lastMs[1]);
+        if (e != SF3D_OK) return e;
     }
     RootView v{};
-    root_view(v, K, S.flag, nullptr);
-    ROOT_LAUNCH(0, k_root_cell, K.nCells, v);
+    root_view(v, K, S.flag);
+    e = raster_launch(k_root_cell, n, v, K.lastMs[0]);
     K.lastMs[0] = 0.;
-    return SF3D_OK;
+    return e;
 }
 
 bool DeviceSolver::root_crop_degree_days_ready(uint32_t nCells) const { return impl_ && impl_->crop.base && impl_->crop.nCells == nCells; }
@@ -343,28 +323,22 @@ sf3d_error_t DeviceSolver::root_compute(const float* dd, float flag, const uint8
     Impl& I = *impl_;
     RootCache& K = I.root;
     const size_t n = K.nCells;
-    SNOW_TRY(hipSetDevice(I.device));
-    if (dd) SNOW_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DD), dd, n * sizeof(float), hipMemcpyHostToDevice, I.stream));
-    if (mine) {
-        if (!K.mine) SNOW_TRY(hipMalloc((void**)&K.mine, n));
-        SNOW_TRY(hipMemcpyAsync(K.mine, mine, n, hipMemcpyHostToDevice, I.stream));
-    }
+    RASTER_TRY(hipSetDevice(I.device));
+    if (dd) RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DD), dd, n * sizeof(float), hipMemcpyHostToDevice, I.stream));
     RootView v{};
-    root_view(v, K, flag, mine ? K.mine : nullptr);
+    sf3d_error_t e = raster_mask(mine, n, &v.mine);
+    if (e != SF3D_OK) return e;
+    root_view(v, K, flag);
     if (!dd) v.dd = I.crop.base + (size_t)(CROP_MAP_STATE + 0) * n;             /* degreeDaysMap of the crop block */
-    ROOT_LAUNCH(0, k_root_cell, K.nCells, v);
-    K.computed = true;
-    return SF3D_OK;
+    e = raster_launch(k_root_cell, n, v, K.lastMs[0]);
+    if (e == SF3D_OK) K.computed = true;
+    return e;
 }
 
 sf3d_error_t DeviceSolver::root_download(int map, void* dst)
 {
-    Impl& I = *impl_;
-    RootCache& K = I.root;
-    SNOW_TRY(hipSetDevice(I.device));
-    SNOW_TRY(hipMemcpyAsync(dst, root_cell_map(K, map), (size_t)K.nCells * (map < 2 ? 8 : 4), hipMemcpyDeviceToHost, I.stream));
-    SNOW_TRY(hipStreamSynchronize(I.stream));
-    return SF3D_OK;
+    const RootCache& K = impl_->root;
+    return raster_download(dst, root_cell_map(K, map), (size_t)K.nCells * (map < 2 ? 8 : 4));
 }
 
 /* layer < 0: every layer, [layer][cell] */
@@ -373,17 +347,16 @@ sf3d_error_t DeviceSolver::root_density(int layer, double* dst, float flag)
     Impl& I = *impl_;
     RootCache& K = I.root;
     const size_t n = K.nCells;
-    SNOW_TRY(hipSetDevice(I.device));
-    if (!K.out) SNOW_TRY(hipMalloc((void**)&K.out, (size_t)K.nrLayers * n * sizeof(double)));
+    RASTER_TRY(hipSetDevice(I.device));
+    if (!K.out) RASTER_TRY(hipMalloc((void**)&K.out, (size_t)K.nrLayers * n * sizeof(double)));
     RootView v{};
-    root_view(v, K, flag, nullptr);
+    root_view(v, K, flag);
     v.layer0 = layer < 0 ? 0 : (uint32_t)layer;
     v.layerCount = layer < 0 ? K.nrLayers : 1;
-    ROOT_LAUNCH(2, k_root_gather, K.nCells, v);
-    SNOW_TRY(hipMemcpyAsync(dst, K.out, (size_t)v.layerCount * n * sizeof(double), hipMemcpyDeviceToHost, I.stream));
-    SNOW_TRY(hipStreamSynchronize(I.stream));
-    return SF3D_OK;
+    const sf3d_error_t e = raster_launch(k_root_gather, n, v, K.lastMs[2]);
+    return e != SF3D_OK ? e : raster_download(dst, K.out, (size_t)v.layerCount * n * sizeof(double));
 }
 
+/* which: 0 k_root_cell, 1 k_root_table, 2 k_root_gather */
 double DeviceSolver::root_kernel_ms(int which) const { return (impl_ && which >= 0 && which < 3) ? impl_->root.lastMs[which] : 0.; }
 uint32_t DeviceSolver::root_table_rows() const { return impl_ ? impl_->root.nRows : 0; }

@@ -17,30 +17,9 @@ struct RootHost {
     bool on = false;
     uint32_t nRows = 0, nCols = 0, nrLayers = 0;
     float flag = -9999.f;
-    std::vector<uint8_t> mine;                 /* strips: 1 on the cells this rank computes */
-    uint64_t mineColVer = 0, mineGen = 0;      /* (MP.colVer, LM.gen) it was made from */
 } RT;
 
 void rootClear() { RT = RootHost(); (void)dev().root_free(); }
-
-sf3d_error_t rootFail(const char* what, sf3d_error_t e) { if (e == SF3D_SOLVER_ERROR) fprintf(stderr, "sf3d: %s: %s\n", what, dev().last_error()); return e; }
-
-/* strips: as cropMine (sf3d_crop_api.inc) on this raster */
-const uint8_t* rootMine()
-{
-    const size_t n = (size_t)RT.nRows * RT.nCols;
-    if (!(LM.on && MP.set && MP.nCells == n && !LM.gpart.owner.empty())) return nullptr;
-    if (RT.mine.size() != n || RT.mineColVer != MP.colVer || RT.mineGen != LM.gen) {
-        RT.mine.assign(n, 0);
-        for (size_t c = 0; c < n; ++c) {
-            int32_t first = -1;
-            for (uint32_t l = 0; l < MP.nLayers && first < 0; ++l) first = MP.col[l * n + c];
-            if (first >= 0 && (size_t)first < LM.gpart.owner.size() && LM.gpart.owner[first] == distRank) RT.mine[c] = 1;
-        }
-        RT.mineColVer = MP.colVer; RT.mineGen = LM.gen;
-    }
-    return RT.mine.data();
-}
 
 /* lunette[0 .. m-1] of cardioidDistribution (root.cpp:277-284) for m = 1 .. maxM, m's values at m (m - 1) / 2: they depend on the two
  * integers only; atan2 and sqrt are the C library's, PI is commonConstants.h:249 */
@@ -82,7 +61,7 @@ sf3d_error_t sf3d_root_initialize(uint32_t nrRows, uint32_t nrCols, const float*
         if ((cropIndex[c] >= 0 && (uint32_t)cropIndex[c] >= nUnits) || (soilIndex[c] >= 0 && (uint32_t)soilIndex[c] >= nSoils)) return SF3D_PARAMETER_ERROR;
         ci[c] = cropIndex[c] < 0 ? -1 : cropIndex[c];
         si[c] = soilIndex[c] < 0 ? -1 : soilIndex[c];
-        if (ci[c] >= 0 && si[c] >= 0 && !(std::fabs((double)dem[c] - (double)flag) < 0.00001)) { pairOn[(size_t)ci[c] * nSoils + si[c]] = 1; soilOn[si[c]] = 1; }
+        if (ci[c] >= 0 && si[c] >= 0 && !rasterIsFlag(dem[c], flag)) { pairOn[(size_t)ci[c] * nSoils + si[c]] = 1; soilOn[si[c]] = 1; }
     }
     /* per soil: the largest number of rooted atoms a cell can ask for, and the atoms; the caps hold for the soils of the raster */
     std::vector<double> soilDepth(nSoils), layerFrac((size_t)nSoils * nrLayers, -1.0);
@@ -128,7 +107,7 @@ sf3d_error_t sf3d_root_initialize(uint32_t nrRows, uint32_t nrCols, const float*
     S.layerDepth = layerDepth; S.layerThickness = layerThickness; S.layerFrac = layerFrac.data(); S.lunette = lunette.data();
     S.rowUnit = rowUnit.data(); S.rowSoil = rowSoil.data(); S.rowN = rowN.data(); S.flag = flag;
     const sf3d_error_t e = dev().root_alloc(S);
-    if (e != SF3D_OK) { rootFail("root initialize", e); rootClear(); return e; }
+    if (e != SF3D_OK) { rasterFail("root initialize", e); rootClear(); return e; }
     RT.nRows = nrRows; RT.nCols = nrCols; RT.nrLayers = nrLayers; RT.flag = flag;
     RT.on = true;
     return SF3D_OK;
@@ -139,21 +118,21 @@ sf3d_error_t sf3d_root_compute(uint32_t nrCells, const float* degreeDays)
     if (!RT.on) return SF3D_MEMORY_ERROR;
     if (nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
     if (!degreeDays && !(CR.on && CR.nRows == RT.nRows && CR.nCols == RT.nCols && dev().root_crop_degree_days_ready(nrCells))) return SF3D_PARAMETER_ERROR;
-    return rootFail("root compute", dev().root_compute(degreeDays, RT.flag, rootMine()));
+    return rasterFail("root compute", dev().root_compute(degreeDays, RT.flag, mapsOwnedCells(nrCells)));
 }
 
 sf3d_error_t sf3d_root_get_length(uint32_t nrCells, double* map)
 {
     if (!RT.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
-    return rootFail("root get length", dev().root_download(ROOT_MAP_LENGTH, map));
+    return rasterFail("root get length", dev().root_download(ROOT_MAP_LENGTH, map));
 }
 
 sf3d_error_t sf3d_root_get_depth(uint32_t nrCells, double* map)
 {
     if (!RT.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
-    return rootFail("root get depth", dev().root_download(ROOT_MAP_DEPTH, map));
+    return rasterFail("root get depth", dev().root_download(ROOT_MAP_DEPTH, map));
 }
 
 sf3d_error_t sf3d_root_get_layers(uint32_t nrCells, int32_t* first, int32_t* last)
@@ -162,7 +141,7 @@ sf3d_error_t sf3d_root_get_layers(uint32_t nrCells, int32_t* first, int32_t* las
     if (!first || !last || nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
     sf3d_error_t e = dev().root_download(ROOT_MAP_FIRST, first);
     if (e == SF3D_OK) e = dev().root_download(ROOT_MAP_LAST, last);
-    return rootFail("root get layers", e);
+    return rasterFail("root get layers", e);
 }
 
 sf3d_error_t sf3d_root_get_density(int layer, uint32_t nrCells, double* map)
@@ -170,14 +149,14 @@ sf3d_error_t sf3d_root_get_density(int layer, uint32_t nrCells, double* map)
     if (!RT.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
     if (layer < -1 || layer >= (int)RT.nrLayers) return SF3D_INDEX_ERROR;
-    return rootFail("root get density", dev().root_density(layer, map, RT.flag));
+    return rasterFail("root get density", dev().root_density(layer, map, RT.flag));
 }
 
 sf3d_error_t sf3d_root_get_keys(uint32_t nrCells, int32_t* map)
 {
     if (!RT.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
-    return rootFail("root get keys", dev().root_download(ROOT_MAP_KEY, map));
+    return rasterFail("root get keys", dev().root_download(ROOT_MAP_KEY, map));
 }
 
 uint32_t sf3d_root_table_rows(void) { return RT.on ? dev().root_table_rows() : 0; }

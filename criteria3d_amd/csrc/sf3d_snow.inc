@@ -256,22 +256,14 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_snow_hour(SnowView v)
 }
 
 /* ---- host side: the maps live in one device block of SNOW_MAPS x nCells floats; a call uploads, launches on the solver's stream, and
- * copies back only what it is asked for.  Nothing of the solver is touched.  A HIP failure here does not mark the solver unusable. */
-#define SNOW_TRY(expr)                                                                         \
-    do { hipError_t e_ = (expr);                                                               \
-         if (e_ != hipSuccess) {                                                               \
-             snprintf(err_, sizeof(err_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-             if (impl_ && impl_->stream) (void)hipStreamSynchronize(impl_->stream);           \
-             return SF3D_SOLVER_ERROR; } } while (0)
-
+ * copies back only what it is asked for (the shared raster path at the end of sf3d_maps.inc). */
 sf3d_error_t DeviceSolver::snow_free()
 {
     if (!impl_) return SF3D_OK;
     SnowCache& S = impl_->snow;
-    if (S.base || S.mine) {
+    if (S.base) {
         if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
-        if (S.base) (void)hipFree(S.base);
-        if (S.mine) (void)hipFree(S.mine);
+        (void)hipFree(S.base);
     }
     S = SnowCache();
     return SF3D_OK;
@@ -283,27 +275,21 @@ sf3d_error_t DeviceSolver::snow_alloc(uint32_t nCells)
     if (e != SF3D_OK) return e;
     snow_free();
     SnowCache& S = impl_->snow;
-    SNOW_TRY(hipMalloc((void**)&S.base, (size_t)SNOW_MAPS * nCells * sizeof(float)));
+    RASTER_TRY(hipMalloc((void**)&S.base, (size_t)SNOW_MAPS * nCells * sizeof(float)));
     S.nCells = nCells;
     return SF3D_OK;
 }
 
 sf3d_error_t DeviceSolver::snow_upload(int map, const float* src)
 {
-    SnowCache& S = impl_->snow;
-    SNOW_TRY(hipSetDevice(impl_->device));
-    SNOW_TRY(hipMemcpyAsync(S.base + (size_t)map * S.nCells, src, (size_t)S.nCells * sizeof(float), hipMemcpyHostToDevice, impl_->stream));
-    SNOW_TRY(hipStreamSynchronize(impl_->stream));         /* the caller's map is free again on return */
-    return SF3D_OK;
+    const SnowCache& S = impl_->snow;
+    return raster_upload(S.base + (size_t)map * S.nCells, src, (size_t)S.nCells * sizeof(float));
 }
 
 sf3d_error_t DeviceSolver::snow_download(int map, float* dst)
 {
-    SnowCache& S = impl_->snow;
-    SNOW_TRY(hipSetDevice(impl_->device));
-    SNOW_TRY(hipMemcpyAsync(dst, S.base + (size_t)map * S.nCells, (size_t)S.nCells * sizeof(float), hipMemcpyDeviceToHost, impl_->stream));
-    SNOW_TRY(hipStreamSynchronize(impl_->stream));
-    return SF3D_OK;
+    const SnowCache& S = impl_->snow;
+    return raster_download(dst, S.base + (size_t)map * S.nCells, (size_t)S.nCells * sizeof(float));
 }
 
 sf3d_error_t DeviceSolver::snow_hour(const float* const in[8], const SnowParamsDev& p, float flag, const uint8_t* mine)
@@ -311,36 +297,20 @@ sf3d_error_t DeviceSolver::snow_hour(const float* const in[8], const SnowParamsD
     Impl& I = *impl_;
     SnowCache& S = I.snow;
     const size_t n = S.nCells;
-    SNOW_TRY(hipSetDevice(I.device));
+    RASTER_TRY(hipSetDevice(I.device));
     for (int k = 0; k < 8; ++k)
-        if (in[k]) SNOW_TRY(hipMemcpyAsync(S.base + (size_t)(SNOW_MAP_IN + k) * n, in[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
-    if (mine) {
-        if (!S.mine) SNOW_TRY(hipMalloc((void**)&S.mine, n));
-        SNOW_TRY(hipMemcpyAsync(S.mine, mine, n, hipMemcpyHostToDevice, I.stream));
-    }
+        if (in[k]) RASTER_TRY(hipMemcpyAsync(S.base + (size_t)(SNOW_MAP_IN + k) * n, in[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
     SnowView v{};
+    const sf3d_error_t e = raster_mask(mine, n, &v.mine);
+    if (e != SF3D_OK) return e;
     for (int k = 0; k < 7; ++k) v.st[k] = S.base + (size_t)(SNOW_MAP_STATE + k) * n;
     for (int k = 0; k < 6; ++k) v.out[k] = S.base + (size_t)(SNOW_MAP_OUT + k) * n;
     for (int k = 0; k < 8; ++k) v.in[k] = in[k] ? S.base + (size_t)(SNOW_MAP_IN + k) * n : nullptr;
     v.dem = S.base + (size_t)SNOW_MAP_DEM * n;
-    v.mine = mine ? S.mine : nullptr;
     v.nCells = S.nCells; v.flag = flag; v.p = p;
-    const dim3 grid((S.nCells + SF3D_BLOCK - 1) / SF3D_BLOCK);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (I.timing) { SNOW_TRY(hipEventCreate(&ev[0])); SNOW_TRY(hipEventCreate(&ev[1])); SNOW_TRY(hipEventRecord(ev[0], I.stream)); }
-    hipLaunchKernelGGL(k_snow_hour, grid, dim3(SF3D_BLOCK), 0, I.stream, v);
-    SNOW_TRY(hipGetLastError());
-    if (I.timing) SNOW_TRY(hipEventRecord(ev[1], I.stream));
-    SNOW_TRY(hipStreamSynchronize(I.stream));              /* the caller's input maps are free again on return */
-    S.hourDone = true;                                     /* the input maps of this hour stay in the block (sf3d_crop_compute_hour may read them) */
-    S.lastMs = 0.;
-    if (I.timing) {
-        float ms = 0.f;
-        SNOW_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-        S.lastMs = ms;
-    }
-    return SF3D_OK;
+    const sf3d_error_t el = raster_launch(k_snow_hour, n, v, S.lastMs);
+    if (el == SF3D_OK) S.hourDone = true;                  /* the input maps of this hour stay in the block (sf3d_crop_compute_hour may read them) */
+    return el;
 }
 
 double DeviceSolver::snow_kernel_ms() const { return impl_ ? impl_->snow.lastMs : 0.; }

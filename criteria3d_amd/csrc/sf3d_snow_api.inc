@@ -11,13 +11,9 @@ struct SnowHost {
     float flag = -9999.f;
     std::vector<float> dem;
     sf3d_snow_parameters_t par;
-    std::vector<uint8_t> mine;                 /* strips: 1 on the cells this rank computes */
-    uint64_t mineColVer = 0, mineGen = 0;      /* (MP.colVer, LM.gen) it was made from */
 } SN;
 
 const sf3d_snow_parameters_t kSnowDefaults = {0.02, 0.2, 1, 0.05, 2, -0.5, 0.05};      /* initializeSnowParameters, snow.cpp:39-50 */
-
-bool snowIsFlag(float v, float flag) { return std::fabs(static_cast<double>(v) - static_cast<double>(flag)) < 0.00001; }      /* isEqual(float, float) */
 
 void snowClear() { SN = SnowHost(); (void)dev().snow_free(); }
 
@@ -31,7 +27,7 @@ sf3d_error_t snowReset(const std::vector<float>& swe)
     std::vector<float> ice(n, SN.flag), lwc(n, SN.flag), ie(n, SN.flag), se(n, SN.flag), ts(n, SN.flag), age(n, SN.flag), zero(n, SN.flag);
     for (size_t c = 0; c < n; ++c) {
         const float initSWE = swe[c];
-        if (snowIsFlag(initSWE, SN.flag)) continue;
+        if (rasterIsFlag(initSWE, SN.flag)) continue;
         ice[c] = initSWE; lwc[c] = 0; age[c] = -9999;
         ts[c] = float(initSnowSurfaceTemp);
         if (initSWE > 0) se[c] = float(initSnowSurfaceTemp * 1000. * 2.1 * skin);                 /* computeSurfaceEnergySnow */
@@ -44,8 +40,6 @@ sf3d_error_t snowReset(const std::vector<float>& swe)
     for (int k = 0; k < 6; ++k) { const sf3d_error_t e = dev().snow_upload(SNOW_MAP_OUT + k, zero.data()); if (e != SF3D_OK) return e; }
     return SF3D_OK;
 }
-
-sf3d_error_t snowFail(const char* what, sf3d_error_t e) { if (e == SF3D_SOLVER_ERROR) fprintf(stderr, "sf3d: %s: %s\n", what, dev().last_error()); return e; }
 
 }  // namespace
 
@@ -64,17 +58,17 @@ sf3d_error_t sf3d_snow_initialize(uint32_t nrRows, uint32_t nrCols, const float*
     const uint32_t n = nrRows * nrCols;
     snowClear();
     sf3d_error_t e = dev().snow_alloc(n);
-    if (e != SF3D_OK) return snowFail("snow initialize", e);
+    if (e != SF3D_OK) return rasterFail("snow initialize", e);
     SN.nRows = nrRows; SN.nCols = nrCols; SN.flag = flag;
     SN.dem.assign(dem, dem + n);
     SN.par = parameters ? *parameters : kSnowDefaults;
     /* setConstantValueWithBase(0, dtm): SWE 0 on the DEM's cells, the flag elsewhere */
     std::vector<float> swe(n);
-    for (uint32_t c = 0; c < n; ++c) swe[c] = snowIsFlag(dem[c], flag) ? flag : 0.f;
+    for (uint32_t c = 0; c < n; ++c) swe[c] = rasterIsFlag(dem[c], flag) ? flag : 0.f;
     e = dev().snow_upload(SNOW_MAP_DEM, SN.dem.data());
     if (e == SF3D_OK) e = dev().snow_upload(SNOW_MAP_STATE, swe.data());
     if (e == SF3D_OK) e = snowReset(swe);
-    if (e != SF3D_OK) { snowFail("snow initialize", e); snowClear(); return e; }
+    if (e != SF3D_OK) { rasterFail("snow initialize", e); snowClear(); return e; }
     SN.on = true;
     return SF3D_OK;
 }
@@ -93,7 +87,7 @@ sf3d_error_t sf3d_snow_reset(void)
     std::vector<float> swe((size_t)SN.nRows * SN.nCols);
     sf3d_error_t e = dev().snow_download(SNOW_MAP_STATE, swe.data());
     if (e == SF3D_OK) e = snowReset(swe);
-    return snowFail("snow reset", e);
+    return rasterFail("snow reset", e);
 }
 
 sf3d_error_t sf3d_snow_set_state(int which, uint32_t nrCells, const float* map)
@@ -101,7 +95,7 @@ sf3d_error_t sf3d_snow_set_state(int which, uint32_t nrCells, const float* map)
     if (!SN.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != SN.nRows * SN.nCols) return SF3D_PARAMETER_ERROR;
     if (which < 0 || which >= SF3D_SNOW_STATE_COUNT) return SF3D_INDEX_ERROR;
-    return snowFail("snow set state", dev().snow_upload(SNOW_MAP_STATE + which, map));
+    return rasterFail("snow set state", dev().snow_upload(SNOW_MAP_STATE + which, map));
 }
 
 sf3d_error_t sf3d_snow_get_state(int which, uint32_t nrCells, float* map)
@@ -109,7 +103,7 @@ sf3d_error_t sf3d_snow_get_state(int which, uint32_t nrCells, float* map)
     if (!SN.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != SN.nRows * SN.nCols) return SF3D_PARAMETER_ERROR;
     if (which < 0 || which >= SF3D_SNOW_STATE_COUNT) return SF3D_INDEX_ERROR;
-    return snowFail("snow get state", dev().snow_download(SNOW_MAP_STATE + which, map));
+    return rasterFail("snow get state", dev().snow_download(SNOW_MAP_STATE + which, map));
 }
 
 sf3d_error_t sf3d_snow_get_output(int which, uint32_t nrCells, float* map)
@@ -117,7 +111,7 @@ sf3d_error_t sf3d_snow_get_output(int which, uint32_t nrCells, float* map)
     if (!SN.on) return SF3D_MEMORY_ERROR;
     if (!map || nrCells != SN.nRows * SN.nCols) return SF3D_PARAMETER_ERROR;
     if (which < 0 || which >= SF3D_SNOW_OUTPUT_COUNT) return SF3D_INDEX_ERROR;
-    return snowFail("snow get output", dev().snow_download(SNOW_MAP_OUT + which, map));
+    return rasterFail("snow get output", dev().snow_download(SNOW_MAP_OUT + which, map));
 }
 
 sf3d_error_t sf3d_snow_compute_hour(uint32_t nrCells, const float* airTemperature, const float* precipitation, const float* relativeHumidity,
@@ -130,22 +124,7 @@ sf3d_error_t sf3d_snow_compute_hour(uint32_t nrCells, const float* airTemperatur
     for (int k = 0; k < 7; ++k) if (!in[k]) return SF3D_PARAMETER_ERROR;
     const SnowParamsDev p = {SN.par.skinThickness, SN.par.soilAlbedo, SN.par.snowVegetationHeight, SN.par.snowWaterHoldingCapacity,
                              SN.par.tempMaxWithSnow, SN.par.tempMinWithRain, SN.par.snowSurfaceDampingDepth, clearSkyTransmissivity};
-    /* strips: the cells whose column (first node of the output maps' column table) this rank owns */
-    const uint8_t* mine = nullptr;
-    const size_t n = (size_t)SN.nRows * SN.nCols;
-    if (LM.on && MP.set && MP.nCells == n && !LM.gpart.owner.empty()) {
-        if (SN.mine.size() != n || SN.mineColVer != MP.colVer || SN.mineGen != LM.gen) {
-            SN.mine.assign(n, 0);
-            for (size_t c = 0; c < n; ++c) {
-                int32_t first = -1;
-                for (uint32_t l = 0; l < MP.nLayers && first < 0; ++l) first = MP.col[l * n + c];
-                if (first >= 0 && (size_t)first < LM.gpart.owner.size() && LM.gpart.owner[first] == distRank) SN.mine[c] = 1;
-            }
-            SN.mineColVer = MP.colVer; SN.mineGen = LM.gen;
-        }
-        mine = SN.mine.data();
-    }
-    return snowFail("snow compute hour", dev().snow_hour(in, p, SN.flag, mine));
+    return rasterFail("snow compute hour", dev().snow_hour(in, p, SN.flag, mapsOwnedCells(nrCells)));
 }
 
 double sf3d_snow_kernel_ms(void) { return dev().snow_kernel_ms(); }

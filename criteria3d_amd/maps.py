@@ -45,11 +45,7 @@ SIGNATURES = {
 
 def bind(sf: capi.SF3D) -> capi.SF3D:
     """attach the signatures of include/sf3d_maps.h to a loaded product library (AttributeError if a symbol is missing)"""
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(sf.lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return sf
+    return capi.bind_signatures(sf, SIGNATURES)
 
 
 # ------------------------------------------------------------------------------------------------ binding

@@ -17,7 +17,7 @@ import math
 
 import numpy as np
 
-from . import capi
+from . import capi, raster
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -69,11 +69,7 @@ SIGNATURES = {
 
 def bind(sf: capi.SF3D) -> capi.SF3D:
     """attach the signatures of include/sf3d_root.h to a loaded product library (AttributeError if a symbol is missing)"""
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(sf.lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return sf
+    return capi.bind_signatures(sf, SIGNATURES)
 
 
 # ------------------------------------------------------------------------------------------------ binding
@@ -127,9 +123,7 @@ def compute(sf: capi.SF3D, degree_days=None) -> None:
     if degree_days is None:
         sf.check(sf.lib.sf3d_root_compute(n, pf32()), "root_compute")
         return
-    v = np.ascontiguousarray(degree_days, np.float32)
-    if v.shape != tuple(sf._root_shape):
-        raise ValueError(f"map of shape {v.shape}, the root raster is {tuple(sf._root_shape)}")
+    v = raster.f32(degree_days, sf._root_shape, "root")
     sf.check(sf.lib.sf3d_root_compute(n, v.ctypes.data_as(pf32)), "root_compute")
 
 

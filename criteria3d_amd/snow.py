@@ -15,11 +15,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 from pathlib import Path
 
 import numpy as np
 
-from . import capi, esri
+from . import capi, raster
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -64,20 +65,13 @@ SIGNATURES = {
 
 def bind(sf: capi.SF3D) -> capi.SF3D:
     """attach the signatures of include/sf3d_snow.h to a loaded product library (AttributeError if a symbol is missing)"""
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(sf.lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return sf
+    return capi.bind_signatures(sf, SIGNATURES)
 
 
 # ------------------------------------------------------------------------------------------------ binding
 
-def _f32(a, shape=None):
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    if shape is not None and a.shape != tuple(shape):
-        raise ValueError(f"map of shape {a.shape}, the snow raster is {tuple(shape)}")
-    return a
+_f32 = partial(raster.f32, what="snow")
+_index = raster.index
 
 
 def _params(parameters) -> Parameters:
@@ -103,10 +97,6 @@ def set_parameters(sf: capi.SF3D, parameters: dict) -> None:
 def reset(sf: capi.SF3D) -> None:
     """resetSnowModel on the SWE map the device holds (after a hand-edited SWE map)"""
     sf.check(sf.lib.sf3d_snow_reset(), "snow_reset")
-
-
-def _index(which, names) -> int:
-    return names.index(which) if isinstance(which, str) else int(which)
 
 
 def set_state(sf: capi.SF3D, which, values) -> None:
@@ -171,19 +161,12 @@ def surface_sources(model, liquid_mm, flag: float = NODATA) -> np.ndarray:
 
 def save_snow_state(sf: capi.SF3D, directory, header: dict) -> Path:
     """saveSnowState: <directory>/snow/{SWE, AgeOfSnow, SnowSurfaceTemp, IceContent, LWContent, InternalEnergy, SurfaceInternalEnergy}.flt/.hdr"""
-    d = Path(directory) / "snow"
-    d.mkdir(parents=True, exist_ok=True)
-    for name, stem in STATE_FILES.items():
-        esri.write_grid(d / stem, get_state(sf, name), header)
-    return d
+    return raster.save_state(directory, "snow", STATE_FILES, partial(get_state, sf), header)
 
 
 def load_snow_state(sf: capi.SF3D, directory) -> None:
     """loadSnowState: the seven maps of <directory>/snow onto the device (the raster must be initialised with the same DEM)"""
-    d = Path(directory) / "snow"
-    for name, stem in STATE_FILES.items():
-        grid, _ = esri.read_grid(d / stem)
-        set_state(sf, name, grid)
+    raster.load_state(directory, "snow", STATE_FILES, partial(set_state, sf))
 
 
 # ------------------------------------------------------------------------------------------------ restatement (checker)

@@ -3,31 +3,14 @@ window of the Ravone project; all ranks may share one GPU.  The control plane is
 rank's maps, the owner of every node and the per-node getter values of the nodes it owns (tests/test_gpu_output_maps.py merges them).
 usage: python scripts/multirank_maps_worker.py <rank> <world> <port> <steps> <outfile>    (SF3D_TEST_SPARSE_BUILD=1: strip-local build)"""
 import os
-import sys
-from pathlib import Path
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import multirank_common as mc
 import numpy as np
-import torch.distributed as dist
-from criteria3d_amd import capi, catchment as cm, maps
+from criteria3d_amd import catchment as cm, maps
+from tests.scenarios import ravone_project_model
 
-rank, world, port, steps, outfile = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
-os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ["MASTER_PORT"] = str(port)
-dist.init_process_group("gloo", rank=rank, world_size=world)
-
-
-def allgather(b):
-    out = [None] * world
-    dist.all_gather_object(out, b)
-    return out
-
-
-from tests.scenarios import ravone_project_model          # noqa: E402
-sf = capi.load_product()
-sf.check(sf.lib.sf3d_set_device(int(os.environ.get("SF3D_TEST_DEVICE", "0"))), "set_device")
+rank, world, steps, outfile = mc.start()
 m = ravone_project_model((980, 1060, 330, 420))
-sparse = os.environ.get("SF3D_TEST_SPARSE_BUILD") == "1"
-sf.check(sf.lib.sf3d_reset_solver_state(), "reset")
-cm.build(sf, m, threads=1, dist=(rank, world, allgather), sparse=sparse)
+sf = mc.build(m, columns=False, sparse=os.environ.get("SF3D_TEST_SPARSE_BUILD") == "1")
 cm.run_hour(sf, m, 25.0, max_steps=steps)
 maps.set_output(sf, m)
 res = {"owner": sf.owner_map(world, m.n)}
@@ -38,7 +21,4 @@ for var, name in maps.GETTERS.items():
     fn = getattr(sf.lib, name)
     res[f"get_{var}"] = np.array([fn(int(i), maps.FIELD_CAPACITY) if var == maps.WATER_DEFICIT else fn(int(i)) for i in mine], np.float64)
 res["mine"] = mine
-np.savez(outfile, **res)
-dist.barrier()
-sf.lib.sf3d_clean()
-dist.destroy_process_group()
+mc.finish(sf, outfile, res)
