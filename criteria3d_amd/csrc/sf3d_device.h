@@ -525,6 +525,41 @@ struct RootSetup {      /* what sf3d_root_initialize hands to DeviceSolver::root
 enum { ROOT_MAP_LENGTH = 0, ROOT_MAP_DEPTH = 1, ROOT_MAP_DEM = 2, ROOT_MAP_DD = 3, ROOT_MAP_CROP = 4, ROOT_MAP_SOIL = 5, ROOT_MAP_FIRST = 6, ROOT_MAP_LAST = 7,
        ROOT_MAP_KEY = 8, ROOT_MAPS = 9, ROOT_MAP_WORDS = 11 };
 
+/* ---- hourly meteo maps from station data (sf3d_meteo.inc, include/sf3d_meteo.h): one thread per raster cell, the station table in LDS ---- */
+#define METEO_MAX_STATIONS 1024         /* SF3D_METEO_MAX_STATIONS: x, y (doubles) and value (float) of every station: 20 KiB of LDS */
+#define METEO_MAX_PROXIES 8             /* SF3D_METEO_MAX_PROXIES */
+enum { METEO_AIR_TEMPERATURE = 0, METEO_PRECIPITATION = 1, METEO_AIR_REL_HUMIDITY = 2, METEO_WIND_SCALAR_INTENSITY = 3, METEO_GLOBAL_IRRADIANCE = 4,
+       METEO_ATM_TRANSMISSIVITY = 5, METEO_AIR_DEW_TEMPERATURE = 6, METEO_VARIABLES = 7 };
+enum { METEO_IDW = 0, METEO_SHEPARD = 1, METEO_SHEPARD_MODIFIED = 2 };
+struct MeteoProxyDev {  /* sf3d_meteo_proxy_t */
+    int32_t active, isHeight, inversion;
+    float slope, lapseRateH0, lapseRateH1, inversionLapseRate;
+    int32_t reserved;
+};
+struct MeteoView {      /* k_meteo_idw */
+    const float* dem;
+    const float* proxyMap[METEO_MAX_PROXIES];   /* null: the proxy's values are the DEM's */
+    const double* sx;                   /* the station table of the call, in device memory: staged into LDS by every block */
+    const double* sy;
+    const float* sv;
+    float* out;
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    double xll, yll, cellSize;
+    uint32_t nCells, nRows, nCols, nStations, nProxies;
+    int32_t var, method, allZero, useDetrending, detrendingVar;
+    float flag, radius0, rainfallThreshold;
+    MeteoProxyDev proxy[METEO_MAX_PROXIES];
+};
+struct MeteoCall {      /* what sf3d_meteo_interpolate hands to DeviceSolver::meteo_interpolate: host pointers */
+    const double* x;
+    const double* y;
+    const float* value;
+    uint32_t nStations, nProxies;
+    int32_t var, method, allZero, useDetrending, detrendingVar;
+    float radius0, rainfallThreshold;
+    MeteoProxyDev proxy[METEO_MAX_PROXIES];
+};
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 

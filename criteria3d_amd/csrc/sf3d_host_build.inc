@@ -149,6 +149,17 @@ struct RootCache {
     double lastMs[3] = {0., 0., 0.};
 };
 
+/* hourly meteo maps (sf3d_meteo.inc): the DEM, the proxy rasters and one map per variable of include/sf3d_meteo.h; they belong to the raster too */
+struct MeteoCache {
+    float* base = nullptr;              /* (1 + nProxies + METEO_VARIABLES) x nCells floats */
+    char* stations = nullptr;           /* METEO_MAX_STATIONS x (x, y: doubles; value: float) */
+    bool hasMap[METEO_MAX_PROXIES] = {false};
+    uint32_t nCells = 0, nRows = 0, nCols = 0, nProxies = 0;
+    double xll = 0., yll = 0., cellSize = 0.;
+    float flag = -9999.f;
+    double lastMs = 0.;
+};
+
 struct DeviceSolver::Impl {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -271,6 +282,7 @@ struct DeviceSolver::Impl {
     SnowCache snow;
     CropCache crop;
     RootCache root;
+    MeteoCache meteo;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the

@@ -227,6 +227,14 @@ public:
     sf3d_error_t root_free();
     double root_kernel_ms(int which) const;
     uint32_t root_table_rows() const;
+    /* hourly meteo maps from station data (sf3d_meteo.inc): the DEM, the proxy rasters and one map per variable, independent of the node
+     * model as the snow, crop and root maps are */
+    sf3d_error_t meteo_alloc(uint32_t nRows, uint32_t nCols, const float* dem, float flag, double xll, double yll, double cellSize, uint32_t nProxies,
+                             const float* const* proxyMaps);
+    sf3d_error_t meteo_interpolate(const MeteoCall& call, const uint8_t* mine, float* out);
+    sf3d_error_t meteo_download(int var, float* dst);
+    sf3d_error_t meteo_free();
+    double meteo_kernel_ms() const;
 
 private:
     DeviceSolver() = default;

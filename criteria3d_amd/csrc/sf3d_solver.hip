@@ -49,3 +49,4 @@
 #include "sf3d_snow.inc"
 #include "sf3d_crop.inc"
 #include "sf3d_root.inc"
+#include "sf3d_meteo.inc"
