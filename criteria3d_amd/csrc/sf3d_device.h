@@ -462,6 +462,7 @@ struct CropView {
 /* ---- root length / depth / density maps (sf3d_root.inc, include/sf3d_root.h): one thread per raster cell, the density vectors in a keyed table ---- */
 #define ROOT_MAX_SOILS 1024             /* SF3D_ROOT_MAX_SOILS */
 #define ROOT_MAX_LAYERS 64              /* SF3D_ROOT_MAX_LAYERS */
+#define ROOT_MAX_HORIZONS 16            /* SF3D_ROOT_MAX_HORIZONS */
 #define ROOT_MAX_ATOMS 1024             /* SF3D_ROOT_MAX_ATOMS: int(totalDepth * 100) + 1 */
 struct RootUnitDev {    /* sf3d_root_unit_t: what computeRootLength3D / computeRootDensity3D read of Crit3DCrop and Crit3DRoot */
     int32_t rootShape, growth, isRootStatic, degreeDaysRootGrowth;
@@ -559,6 +560,63 @@ struct MeteoCall {      /* what sf3d_meteo_interpolate hands to DeviceSolver::me
     float radius0, rainfallThreshold;
     MeteoProxyDev proxy[METEO_MAX_PROXIES];
 };
+
+/* ---- hourly evaporation, transpiration and rain sinks (sf3d_sink.inc, include/sf3d_sink.h): one thread per raster cell walks its column ---- */
+#define SINK_HORIZON_VALUES 5           /* per horizon: waterContentHH, FC, WP, SAT, getSoilFraction() */
+enum { SINK_H_HH = 0, SINK_H_FC = 1, SINK_H_WP = 2, SINK_H_SAT = 3, SINK_H_FRACTION = 4 };
+struct SinkUnitDev {    /* sf3d_sink_unit_t: what assignTranspiration reads of Crit3DCrop besides the roots */
+    double kcMax, fRAW;
+    int32_t waterSurplusResistant, reserved;
+};
+struct SinkView {       /* k_sink_hour; the maps of one block share a base pointer (scalar registers: one pair per pointer) */
+    const int32_t* col;                 /* [nrLayers][nCells] node of the cell in the layer (device numbering), -1 = none: the column table of the output maps */
+    const double *H, *Se, *z;           /* the solver's accepted state, read only */
+    const uint16_t* cls;
+    const SoilDev* soils;
+    char* cells;                        /* this block's per-cell maps (SINK_MAP_*): two double maps, then 4-byte maps */
+    const float* et0;                   /* this block's copies or the crop block's maps */
+    const float* lai;
+    const float* dd;
+    const float* liquid;                /* this block's copy or the snow block's liquid-water output */
+    const char* rootCells;              /* the root block's per-cell maps (ROOT_MAP_*): length, first / last root layer, key */
+    const double* rootTable;            /* the keyed density table [layer * rootRows + key] */
+    const SinkUnitDev* units;
+    const int32_t* horizon;             /* [soil * nrLayers + layer]: getHorizonIndex(layerDepth[layer]), -1: none */
+    const double* horizonValues;        /* [(soil * ROOT_MAX_HORIZONS + horizon) * SINK_HORIZON_VALUES + SINK_H_*] */
+    const double* layerTables;          /* [3][nrLayers]: layerThickness, evapCoeff, layerEvapCoeff (the last two used up to lastEvapLayer) */
+    double* sink;                       /* [nodes of the device model] node sinks [m3 s-1] */
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    double area;                        /* cellSize squared */
+    uint32_t ns, nCells, nrLayers, nUnits, nSoils, rootRows;
+    int32_t lastEvapLayer;
+    float flag;
+};
+struct SinkSetup {      /* what sf3d_sink_initialize keeps for DeviceSolver::sink_alloc: host pointers */
+    uint32_t nCells, nrLayers, nUnits, nSoils;
+    int32_t lastEvapLayer;
+    const float* dem;
+    const int32_t* cropIndex;
+    const int32_t* soilIndex;
+    const SinkUnitDev* units;
+    const int32_t* horizon;
+    const double* horizonValues;
+    const double* layerDepth;
+    const double* thick;
+    const double* evapCoeff;
+    const double* layerEvapCoeff;
+    double area;
+    float flag;
+};
+struct SinkCall {       /* what sf3d_sink_compute_hour hands to DeviceSolver::sink_hour: host pointers, null = the crop / snow block's map */
+    const float* et0;
+    const float* lai;
+    const float* dd;
+    const float* liquid;
+    const uint8_t* mine;
+};
+/* the per-cell block of the sink maps: two double maps, then seven maps of 4-byte values */
+enum { SINK_MAP_EVAPORATION = 0, SINK_MAP_TRANSPIRATION = 1, SINK_MAP_DEM = 2, SINK_MAP_ET0 = 3, SINK_MAP_LAI = 4, SINK_MAP_DD = 5, SINK_MAP_LIQUID = 6,
+       SINK_MAP_CROP = 7, SINK_MAP_SOIL = 8, SINK_MAPS = 9, SINK_MAP_WORDS = 11 };
 
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };

@@ -160,6 +160,21 @@ struct MeteoCache {
     double lastMs = 0.;
 };
 
+/* hourly sinks (sf3d_sink.inc): the per-cell maps and the tables of include/sf3d_sink.h belong to the raster; the node array follows the
+ * model the device works on (its size and numbering) and is freed with it */
+struct SinkCache {
+    char* cells = nullptr;              /* SINK_MAP_WORDS x nCells 4-byte words: the per-cell maps */
+    char* tables = nullptr;             /* units, horizon table, horizon values, layer grid, evaporation coefficients: one block */
+    double* nodes = nullptr;            /* [nodesN] node sinks */
+    size_t off[8] = {0};
+    uint32_t nCells = 0, nrLayers = 0, nUnits = 0, nSoils = 0, nodesN = 0;
+    int32_t lastEvapLayer = 0;
+    double area = 0.;
+    float flag = -9999.f;
+    bool computed = false;
+    double lastMs = 0.;
+};
+
 struct DeviceSolver::Impl {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -283,6 +298,7 @@ struct DeviceSolver::Impl {
     CropCache crop;
     RootCache root;
     MeteoCache meteo;
+    SinkCache sink;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the
@@ -349,6 +365,7 @@ sf3d_error_t DeviceSolver::release()
     I.allocs.clear();
     g_deviceBytes = 0;
     I.maps.free_all();
+    if (I.sink.nodes) { (void)hipFree(I.sink.nodes); I.sink.nodes = nullptr; I.sink.nodesN = 0; I.sink.computed = false; }      /* the node sinks follow the model's numbering */
     if (I.comm && I.pCommDestroy) { I.pCommDestroy(I.comm); I.comm = nullptr; }
     I.rcclMode = false; I.rcclMine = I.rcclGathered = nullptr;
     for (void* p : I.peerMaps) hipIpcCloseMemHandle(p);

@@ -235,6 +235,19 @@ public:
     sf3d_error_t meteo_download(int var, float* dst);
     sf3d_error_t meteo_free();
     double meteo_kernel_ms() const;
+    /* hourly evaporation, transpiration and rain sinks (sf3d_sink.inc): the per-cell maps and the tables belong to the raster as the other
+     * blocks' do, the node array to the model on the device (release() frees it); sink_hour reads the accepted state after sync_to_device as
+     * output_map does and the root block's maps, and, where a map of `call` is null, the crop / snow block's */
+    sf3d_error_t sink_alloc(const SinkSetup& setup);
+    bool sink_allocated() const;
+    bool sink_root_ready(uint32_t nCells, uint32_t nrLayers) const;
+    bool sink_snow_ready(uint32_t nCells) const;
+    sf3d_error_t sink_hour(HostModel& m, const ParamsHost& p, const MapsInput& in, const SinkCall& call);
+    sf3d_error_t sink_download_nodes(double* dst, uint32_t count);     /* the device model's numbering */
+    sf3d_error_t sink_download_cells(int map, double* dst);
+    bool sink_computed() const;
+    sf3d_error_t sink_free();
+    double sink_kernel_ms() const;
 
 private:
     DeviceSolver() = default;

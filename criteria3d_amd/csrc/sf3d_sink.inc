@@ -1,0 +1,319 @@
+/* part of sf3d_solver.hip (included there after the meteo maps) - the hourly water sinks of the application on the device: the cell loop of
+ * Crit3DProject::assignETreal (bin/CRITERIA3D/criteria3DProject.cpp:796-911) around Project3D::assignEvaporation
+ * (src/project3D/project3D.cpp:2377-2451) and Project3D::assignTranspiration (:2461-2610), and the rain term of assignPrecipitation
+ * (criteria3DProject.cpp:954-964).  k_sink_hour: one thread per raster cell walks its column; the column table is [layer][cell], so the lanes
+ * of a wave read one layer of 64 neighbouring cells.  Every input is already on the device: ET0, LAI and degree days (the crop block), the
+ * liquid water (the snow block), root length, first / last root layer and the keyed density table (the root block), and the water content of
+ * every node - what getCriteria3DVar(volumetricWaterContent) returns for the accepted state, through map_node_value of sf3d_maps.inc.
+ *
+ * The bar is the compiled reference's bits (tests/golden/water_sinks.npz): the same double operations in the same order
+ * (-ffp-contract=off, IEEE division), exp through the C library's routine (fexp), layerTranspiration rounded to float where the reference
+ * keeps it in a std::vector<float>.  No per-thread array of layers: the redistribution and the final loop evaluate layerTranspiration again
+ * from the same loads, which gives the same bits.  A node's sink is read, changed and written by its own cell's thread only; every
+ * subtraction is made on its own, in the reference's order (evaporation iteration by iteration, then transpiration, then rain).
+ *
+ * Kept from the reference on purpose:
+ *  - the water content is read again, unchanged, in each of the up to three evaporation iterations;
+ *  - a layer without a node takes part in the evaporation loop with the water content NODATA (nothing evaporates) and is skipped by
+ *    transpiration; a layer without a horizon is skipped by both;
+ *  - waterStress is 1 - 0 / 0 = NaN when every root layer was skipped: both comparisons are false and nothing is redistributed. */
+
+#define SINK_NODATA (-9999)
+#define SINK_EPSILON 0.00001
+#define SINK_DBL_EPSILON 2.220446049250313e-16
+
+/* getCriteria3DVar(volumetricWaterContent, node), project3D.cpp:2756-2810 */
+__device__ __forceinline__ double sink_vwc(const SinkView& v, int32_t n)
+{
+    if (n < 0) return (double)SINK_NODATA;                                 /* getNodeWaterContent: INDEX_ERROR -> NODATA */
+    const double w = ((uint32_t)n < v.ns) ? (v.H[n] - v.z[n]) : map_theta(v.soils[v.cls[n]], v.Se[n]);
+    return map_sentinel(w) ? (double)SINK_NODATA : w;
+}
+
+/* one root layer of assignTranspiration's first loop (:2525-2572): false when the layer is skipped; else the layer's root density, whether it
+ * is stressed, and layerTranspiration as the float the reference stores */
+__device__ __forceinline__ bool sink_root_layer(const SinkView& v, uint32_t c, uint32_t layer, int32_t si, int32_t key, const SinkUnitDev& u,
+                                                double maxTranspiration, double& density, bool& stressed, float& layerTranspiration)
+{
+    const int32_t n = v.col[(size_t)layer * v.nCells + c];
+    if (n < 0) return false;
+    const int32_t h = v.horizon[(size_t)si * v.nrLayers + layer];
+    if (h < 0) return false;
+    const double* hz = v.horizonValues + ((size_t)si * ROOT_MAX_HORIZONS + (uint32_t)h) * SINK_HORIZON_VALUES;
+    const double FC = hz[SINK_H_FC], WP = hz[SINK_H_WP], SAT = hz[SINK_H_SAT];
+    const double waterSurplusStressFraction = u.waterSurplusResistant ? 0. : 0.5;
+    const double volWaterContent = sink_vwc(v, n);
+    const double volWaterSurplusThreshold = SAT - waterSurplusStressFraction * (SAT - FC);
+    const double volWaterScarcityThreshold = FC - u.fRAW * (FC - WP);
+    double ratio;
+    if (volWaterContent <= WP) { ratio = 0; stressed = true; }
+    else if (volWaterContent < volWaterScarcityThreshold) { ratio = (volWaterContent - WP) / (volWaterScarcityThreshold - WP); stressed = true; }
+    else if ((volWaterContent - volWaterSurplusThreshold) > SINK_EPSILON) { ratio = (SAT - volWaterContent) / (SAT - volWaterSurplusThreshold); stressed = true; }
+    else { ratio = 1; stressed = false; }
+    density = v.rootTable[(size_t)layer * v.rootRows + (uint32_t)key];
+    layerTranspiration = (float)(maxTranspiration * density * ratio);
+    return true;
+}
+
+__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v)
+{
+    fm_init();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    const size_t nc = v.nCells;
+    const uint32_t nl = v.nrLayers;
+    const float flag = v.flag;
+    /* the sinks of the column start the hour at 0 (waterSinkSource of runModelHour) */
+    const int32_t s0 = v.col[c];
+    double* const actualMaps = reinterpret_cast<double*>(v.cells);                                       /* evaporation, transpiration */
+    const float* const dem = reinterpret_cast<const float*>(v.cells + 16 * nc);
+    const int32_t* const cropIndex = reinterpret_cast<const int32_t*>(v.cells + 16 * nc + (size_t)(SINK_MAP_CROP - 2) * nc * 4);
+    const int32_t* const soilIndex = reinterpret_cast<const int32_t*>(v.cells + 16 * nc + (size_t)(SINK_MAP_SOIL - 2) * nc * 4);
+    const double* const thick = v.layerTables;
+    const double* const evapCoeff = v.layerTables + nl;
+    const double* const layerEvapCoeff = v.layerTables + 2 * (size_t)nl;
+    for (uint32_t l = 1; l < nl; ++l) {
+        const int32_t n = v.col[(size_t)l * nc + c];
+        if (n >= 0) v.sink[n] = 0.;
+    }
+    const bool cell = !(v.mine && !v.mine[c]) && !snow_eqf(dem[c], flag) && s0 >= 0;
+    if (!cell) {
+        if (s0 >= 0) v.sink[s0] = 0.;
+        actualMaps[c] = (double)flag; actualMaps[nc + c] = (double)flag;
+        return;
+    }
+    double surfaceSink = 0.;
+    const double area = v.area;
+    const int32_t siRaw = soilIndex[c];
+    const int32_t si = (siRaw >= 0 && siRaw < (int32_t)v.nSoils) ? siRaw : -1;
+    const double et0 = (double)v.et0[c];
+    float currentLAI = 0;                                                /* assignETreal :818-824 */
+    { const float laiMapValue = v.lai[c]; if (!snow_eqf(laiMapValue, flag)) currentLAI = laiMapValue; }
+    const double lai = currentLAI;
+    const double covSurfFraction = (lai < SINK_EPSILON) ? 0. : 1 - fexp(-0.6 * lai);       /* getCoveredSurfaceFraction :2295-2301 */
+
+    /* ---- assignEvaporation :2377-2451 ---- */
+    double actualEvaporationSum = 0;
+    const double maxEvaporation = et0 * (1.0 - covSurfFraction);
+    if (!(maxEvaporation < SINK_EPSILON)) {
+        const double surfaceWater = sink_vwc(v, s0) * 1000;
+        double surfaceEvaporation = dmin(maxEvaporation, surfaceWater);
+        const double surfaceFlow = area * (surfaceEvaporation / 1000.) / 3600.;
+        if (surfaceFlow <= SINK_DBL_EPSILON) surfaceEvaporation = 0.;
+        else { surfaceSink -= surfaceFlow; actualEvaporationSum += surfaceEvaporation; }
+        double residualEvaporation = maxEvaporation - surfaceEvaporation;
+        if (!(residualEvaporation < SINK_EPSILON || si < 0)) {
+            int nrIteration = 0;
+            while (residualEvaporation > SINK_EPSILON && nrIteration < 3) {
+                double iterationEvapSum = 0;
+                for (int32_t layer = 1; layer <= v.lastEvapLayer; ++layer) {
+                    const int32_t n = v.col[(size_t)layer * nc + c];
+                    const int32_t h = v.horizon[(size_t)si * nl + layer];
+                    if (h < 0) continue;
+                    const double* hz = v.horizonValues + ((size_t)si * ROOT_MAX_HORIZONS + (uint32_t)h) * SINK_HORIZON_VALUES;
+                    const double evapThreshold = hz[SINK_H_HH] + (1 - evapCoeff[layer]) * (hz[SINK_H_FC] - hz[SINK_H_HH]) * 0.5;
+                    const double layerWaterContent = sink_vwc(v, n) * hz[SINK_H_FRACTION];
+                    const double wcAboveThreshold = dmax(layerWaterContent - evapThreshold, 0.0);
+                    const double evapAvailableWater = wcAboveThreshold * thick[layer] * 1000.;
+                    const double layerEvaporation = dmin(evapAvailableWater, residualEvaporation * layerEvapCoeff[layer]);
+                    if (layerEvaporation > SINK_EPSILON && n >= 0) {      /* (without a node the water content is NODATA: nothing is available) */
+                        const double flow = area * (layerEvaporation / 1000.) / 3600.;
+                        v.sink[n] -= flow;
+                        actualEvaporationSum += layerEvaporation;
+                        iterationEvapSum += layerEvaporation;
+                    }
+                }
+                residualEvaporation -= iterationEvapSum;
+                nrIteration++;
+            }
+        }
+    }
+
+    /* ---- assignTranspiration :2461-2610, behind the conditions of assignETreal :850-864 ---- */
+    double actualTranspiration = 0;
+    const int32_t ci = cropIndex[c];
+    const int32_t key = reinterpret_cast<const int32_t*>(v.rootCells + 16 * nc + (size_t)(ROOT_MAP_KEY - 2) * nc * 4)[c];
+    const double currentDegreeDays = (double)v.dd[c];
+    bool transpire = ci >= 0 && ci < (int32_t)v.nUnits && currentLAI > 0
+                     && !(lai < SINK_EPSILON || snow_eq(currentDegreeDays, (double)SINK_NODATA)) && nl > 1 && si >= 0;
+    double maxTranspiration = 0.;
+    if (transpire) {
+        const double kcFactor = 1 + (v.units[ci].kcMax - 1) * covSurfFraction;             /* getPotentialTranspiration :2323-2328 */
+        maxTranspiration = et0 * covSurfFraction * kcFactor;
+        transpire = !(maxTranspiration < SINK_EPSILON);
+    }
+    /* the root block: length <= 0, an empty density row (no key) and NODATA root layers end the function (:2487-2498) */
+    if (transpire) transpire = key >= 0 && (uint32_t)key < v.rootRows && reinterpret_cast<const double*>(v.rootCells)[c] > 0;
+    int32_t firstRootLayer = SINK_NODATA, lastRootLayer = SINK_NODATA;
+    if (transpire) {
+        firstRootLayer = reinterpret_cast<const int32_t*>(v.rootCells + 16 * nc + (size_t)(ROOT_MAP_FIRST - 2) * nc * 4)[c];
+        lastRootLayer = reinterpret_cast<const int32_t*>(v.rootCells + 16 * nc + (size_t)(ROOT_MAP_LAST - 2) * nc * 4)[c];
+        transpire = firstRootLayer != SINK_NODATA && lastRootLayer != SINK_NODATA && firstRootLayer >= 0 && lastRootLayer < (int32_t)nl;
+    }
+    if (transpire) {
+        const SinkUnitDev u = v.units[ci];
+        double rootDensityWithoutStress = 0.0, transpirationSubsetMax = 0;
+        for (int32_t layer = firstRootLayer; layer <= lastRootLayer; ++layer) {
+            double density; bool stressed; float layerTranspiration;
+            if (!sink_root_layer(v, c, (uint32_t)layer, si, key, u, maxTranspiration, density, stressed, layerTranspiration)) continue;
+            if (!stressed) rootDensityWithoutStress += density;
+            transpirationSubsetMax += maxTranspiration * density;
+            actualTranspiration += layerTranspiration;
+        }
+        const double waterStress = 1 - (actualTranspiration / transpirationSubsetMax);
+        const bool redistribute = waterStress > SINK_EPSILON && rootDensityWithoutStress > SINK_EPSILON;
+        const double redistribution = redistribute ? transpirationSubsetMax * dmin(waterStress, rootDensityWithoutStress) : 0.;
+        actualTranspiration = 0;
+        for (int32_t layer = firstRootLayer; layer <= lastRootLayer; ++layer) {
+            double density; bool stressed; float layerTranspiration;
+            if (!sink_root_layer(v, c, (uint32_t)layer, si, key, u, maxTranspiration, density, stressed, layerTranspiration)) continue;      /* its layerTranspiration stays 0 */
+            if (redistribute && !stressed && layerTranspiration > 0)
+                layerTranspiration = (float)((double)layerTranspiration + redistribution * (density / rootDensityWithoutStress));
+            const double flow = area * (layerTranspiration / 1000.) / 3600.;
+            if (flow > SINK_DBL_EPSILON) {
+                const int32_t n = v.col[(size_t)layer * nc + c];
+                v.sink[n] -= flow;
+                actualTranspiration += layerTranspiration;
+            }
+        }
+    }
+
+    /* ---- the rain term of assignPrecipitation (criteria3DProject.cpp:939-964), precSurfaceWater = liquidWater ---- */
+    const float liquidWater = v.liquid[c];
+    if (!snow_eqf(liquidWater, flag) && liquidWater > 0) {
+        const double surfaceFlow = area * (liquidWater / 1000.);
+        if ((surfaceFlow / 3600.) > 0.) surfaceSink += surfaceFlow / 3600.;
+    }
+    v.sink[s0] = surfaceSink;
+    actualMaps[c] = actualEvaporationSum;
+    actualMaps[nc + c] = actualTranspiration;
+}
+
+/* ---- host side: the per-cell block, one block of tables and the node array; calls go through the shared raster path at the end of
+ * sf3d_maps.inc. */
+enum { SINK_T_UNITS = 0, SINK_T_HORIZON_VALUES, SINK_T_THICK, SINK_T_EVAP_COEFF, SINK_T_LAYER_EVAP_COEFF, SINK_T_HORIZON, SINK_T_END };      /* the three layer tables are adjacent */
+
+sf3d_error_t DeviceSolver::sink_free()
+{
+    if (!impl_) return SF3D_OK;
+    SinkCache& K = impl_->sink;
+    if (K.cells || K.tables || K.nodes) {
+        if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
+        if (K.cells) (void)hipFree(K.cells);
+        if (K.tables) (void)hipFree(K.tables);
+        if (K.nodes) (void)hipFree(K.nodes);
+    }
+    K = SinkCache();
+    return SF3D_OK;
+}
+
+static void* sink_cell_map(const SinkCache& K, int map)
+{
+    const size_t n = K.nCells;
+    return (map < 2) ? K.cells + (size_t)map * n * 8 : K.cells + 16 * n + (size_t)(map - 2) * n * 4;
+}
+
+sf3d_error_t DeviceSolver::sink_alloc(const SinkSetup& S)
+{
+    sf3d_error_t e = ensure_device();
+    if (e != SF3D_OK) return e;
+    sink_free();
+    Impl& I = *impl_;
+    SinkCache& K = I.sink;
+    const size_t n = S.nCells, nl = S.nrLayers;
+    const size_t bytes[SINK_T_END] = {(size_t)CROP_MAX_UNITS * sizeof(SinkUnitDev), (size_t)S.nSoils * ROOT_MAX_HORIZONS * SINK_HORIZON_VALUES * sizeof(double),
+                                      nl * sizeof(double), nl * sizeof(double), nl * sizeof(double), (size_t)S.nSoils * nl * sizeof(int32_t)};
+    const void* src[SINK_T_END] = {S.units, S.horizonValues, S.thick, S.evapCoeff, S.layerEvapCoeff, S.horizon};
+    const size_t srcBytes[SINK_T_END] = {S.nUnits * sizeof(SinkUnitDev), bytes[1], bytes[2], bytes[3], bytes[4], bytes[5]};
+    size_t total = 0;
+    for (int k = 0; k < SINK_T_END; ++k) { K.off[k] = total; total += (bytes[k] + 7) & ~(size_t)7; }
+    RASTER_TRY(hipMalloc((void**)&K.cells, (size_t)SINK_MAP_WORDS * n * 4));
+    RASTER_TRY(hipMalloc((void**)&K.tables, total ? total : 8));
+    K.nCells = S.nCells; K.nrLayers = S.nrLayers; K.nUnits = S.nUnits; K.nSoils = S.nSoils; K.lastEvapLayer = S.lastEvapLayer; K.area = S.area; K.flag = S.flag;
+    for (int k = 0; k < SINK_T_END; ++k)
+        if (src[k] && srcBytes[k]) RASTER_TRY(hipMemcpyAsync(K.tables + K.off[k], src[k], srcBytes[k], hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    {   /* before the first hour both actual maps hold the flag */
+        const std::vector<double> empty(2 * n, (double)S.flag);
+        RASTER_TRY(hipMemcpyAsync(K.cells, empty.data(), 2 * n * 8, hipMemcpyHostToDevice, I.stream));
+        RASTER_TRY(hipStreamSynchronize(I.stream));
+    }
+    return SF3D_OK;
+}
+
+bool DeviceSolver::sink_allocated() const { return impl_ && impl_->sink.cells; }
+bool DeviceSolver::sink_computed() const { return impl_ && impl_->sink.nodes && impl_->sink.computed; }
+bool DeviceSolver::sink_root_ready(uint32_t nCells, uint32_t nrLayers) const
+{
+    return impl_ && impl_->root.cells && impl_->root.computed && impl_->root.nCells == nCells && impl_->root.nrLayers == nrLayers;
+}
+bool DeviceSolver::sink_snow_ready(uint32_t nCells) const { return crop_snow_inputs_ready(nCells); }
+
+sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const MapsInput& in, const SinkCall& call)
+{
+    sf3d_error_t e = sync_to_device(m, p);
+    if (e != SF3D_OK) return e;
+    if (world_ > 1 && !connected_) { snprintf(err_, sizeof(err_), "multi-GPU model used before sf3d_dist_connect / sf3d_dist_finalize"); return SF3D_SOLVER_ERROR; }
+    Impl& I = *impl_;
+    SinkCache& K = I.sink;
+    MapsCache& C = I.maps;
+    const RootCache& R = I.root;
+    const size_t n = K.nCells, colN = (size_t)in.nCells * in.nLayers;
+    if (C.colVer != in.colVer) {                                           /* the column table of the output maps, uploaded as output_map does */
+        RASTER_TRY(maps_reserve(C.col, C.colCap, colN));
+        RASTER_TRY(maps_reserve(C.thick, C.thickCap, in.nLayers));
+        RASTER_TRY(hipMemcpyAsync(C.col, in.col, colN * 4, hipMemcpyHostToDevice, I.stream));
+        RASTER_TRY(hipMemcpyAsync(C.thick, in.thick, (size_t)in.nLayers * 8, hipMemcpyHostToDevice, I.stream));
+        C.colVer = in.colVer;
+    }
+    if (!K.nodes || K.nodesN != I.v.N) {
+        if (K.nodes) { (void)hipFree(K.nodes); K.nodes = nullptr; }
+        K.nodesN = 0; K.computed = false;
+        RASTER_TRY(hipMalloc((void**)&K.nodes, ((size_t)I.v.N ? (size_t)I.v.N : 1) * sizeof(double)));
+        K.nodesN = I.v.N;
+        RASTER_TRY(hipMemsetAsync(K.nodes, 0, (size_t)I.v.N * sizeof(double), I.stream));      /* nodes of no column, and of other ranks' columns, stay 0 */
+    }
+    const float* maps[4] = {call.et0, call.lai, call.dd, call.liquid};
+    for (int k = 0; k < 4; ++k)
+        if (maps[k]) RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_ET0 + k), maps[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
+    SinkView v{};
+    e = raster_mask(call.mine, n, &v.mine);
+    if (e != SF3D_OK) return e;
+    v.col = C.col;
+    v.H = I.v.X[mirror_.cur]; v.Se = I.v.Se; v.z = I.v.z; v.cls = I.v.cls; v.soils = I.v.soils;
+    v.cells = K.cells;
+    v.et0 = call.et0 ? (const float*)sink_cell_map(K, SINK_MAP_ET0) : I.crop.base + (size_t)CROP_MAP_ET0 * n;
+    v.lai = call.lai ? (const float*)sink_cell_map(K, SINK_MAP_LAI) : I.crop.base + (size_t)(CROP_MAP_STATE + 1) * n;
+    v.dd = call.dd ? (const float*)sink_cell_map(K, SINK_MAP_DD) : I.crop.base + (size_t)(CROP_MAP_STATE + 0) * n;
+    v.liquid = call.liquid ? (const float*)sink_cell_map(K, SINK_MAP_LIQUID) : I.snow.base + (size_t)(SNOW_MAP_OUT + 5) * n;
+    v.rootCells = R.cells;
+    v.rootTable = (const double*)(R.tables + R.off[ROOT_T_TABLE]); v.rootRows = R.nRows;
+    v.units = (const SinkUnitDev*)(K.tables + K.off[SINK_T_UNITS]);
+    v.horizon = (const int32_t*)(K.tables + K.off[SINK_T_HORIZON]);
+    v.horizonValues = (const double*)(K.tables + K.off[SINK_T_HORIZON_VALUES]);
+    v.layerTables = (const double*)(K.tables + K.off[SINK_T_THICK]);
+    v.sink = K.nodes;
+    v.area = K.area;
+    v.ns = I.v.ns; v.nCells = K.nCells; v.nrLayers = K.nrLayers; v.nUnits = K.nUnits; v.nSoils = K.nSoils;
+    v.lastEvapLayer = K.lastEvapLayer; v.flag = K.flag;
+    e = raster_launch(k_sink_hour, n, v, K.lastMs);
+    if (e == SF3D_OK) K.computed = true;
+    return e;
+}
+
+sf3d_error_t DeviceSolver::sink_download_nodes(double* dst, uint32_t count)
+{
+    const SinkCache& K = impl_->sink;
+    if (count != K.nodesN) { snprintf(err_, sizeof(err_), "node sinks: %u nodes asked, the device holds %u", count, K.nodesN); return SF3D_SOLVER_ERROR; }
+    return raster_download(dst, K.nodes, (size_t)count * sizeof(double));
+}
+
+sf3d_error_t DeviceSolver::sink_download_cells(int map, double* dst)
+{
+    const SinkCache& K = impl_->sink;
+    return raster_download(dst, sink_cell_map(K, map), (size_t)K.nCells * sizeof(double));
+}
+
+double DeviceSolver::sink_kernel_ms() const { return impl_ ? impl_->sink.lastMs : 0.; }

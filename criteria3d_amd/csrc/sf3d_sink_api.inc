@@ -1,0 +1,215 @@
+/* part of sf3d_api.cpp (included at its end, after the meteo entry points) - the C entry points of include/sf3d_sink.h.  The host keeps the
+ * raster and the tables until the first hour uploads them (no device is needed before), evaluates what needs the C library's exp
+ * (initializeEvaporationCoefficient) and getHorizonIndex of every (soil, layer), hands the column table of sf3d_maps.h to the device in the
+ * numbering of the model it works on, and moves the node sinks between that numbering and the caller's. */
+#include <cmath>
+
+#include "sf3d_sink.h"
+
+static_assert(sizeof(sf3d_sink_unit_t) == sizeof(SinkUnitDev) && sizeof(SinkUnitDev) == 24, "the sink unit table is copied as it is");
+static_assert(sizeof(sf3d_sink_soil_t) == 8 + 7 * 8 * SF3D_ROOT_MAX_HORIZONS, "sf3d_sink_soil_t has no padding");
+static_assert(SF3D_ROOT_MAX_HORIZONS == ROOT_MAX_HORIZONS, "sf3d_root.h and sf3d_device.h disagree");
+
+namespace {
+
+struct SinkHost {
+    bool on = false, uploaded = false;
+    uint32_t nRows = 0, nCols = 0, nrLayers = 0, nUnits = 0, nSoils = 0;
+    int32_t lastEvapLayer = 0;
+    float flag = -9999.f;
+    double area = 0.;
+    std::vector<float> dem;
+    std::vector<int32_t> cropIndex, soilIndex, horizon;
+    std::vector<SinkUnitDev> units;
+    std::vector<double> horizonValues, layerDepth, thick, evapCoeff, layerEvapCoeff;
+    std::vector<double> nodes;                 /* the last download, in the device model's numbering */
+} SK;
+
+void sinkClear() { SK = SinkHost(); (void)dev().sink_free(); }
+
+const double kMaxEvaporationDepth = 0.25;      /* MAX_EVAPORATION_DEPTH, commonConstants.h:116 */
+
+/* Project3D::getSoilLayerIndex, project3D.cpp:1764-1776 */
+int sinkLayerIndex(uint32_t nrLayers, const double* layerDepth, const double* layerThickness, double depth)
+{
+    if (nrLayers == 0 || depth < 0) return -9999;
+    for (uint32_t layer = 0; layer < nrLayers; ++layer)
+        if (depth <= layerDepth[layer] + layerThickness[layer] * 0.5) return (int)layer;
+    return -9999;
+}
+
+/* the column table for the device, as sf3d_compute_output_map builds it */
+void sinkColumns(MapsInput& in)
+{
+    in.nCells = MP.nCells; in.nLayers = MP.nLayers; in.thick = MP.thick.data();
+    if (!LM.on) { in.col = MP.col.data(); in.colVer = MP.colVer; return; }
+    if (MP.colDevVer != MP.colVer || MP.colDevGen != LM.gen) {
+        const size_t nc = MP.nCells;
+        MP.colDev.assign(MP.col.size(), -1);
+        for (size_t c = 0; c < nc; ++c) {
+            if (!mapsOwnsCell(c)) continue;
+            for (uint32_t l = 0; l < MP.nLayers; ++l) {
+                const int32_t g = MP.col[l * nc + c];
+                if (g >= 0) MP.colDev[l * nc + c] = LM.g2l[g];
+            }
+        }
+        MP.colDevVer = MP.colVer; MP.colDevGen = LM.gen;
+        MP.colDevVerDev = ++mapsVersion;
+    }
+    in.col = MP.colDev.data(); in.colVer = MP.colDevVerDev;
+}
+
+/* the node sinks of the last hour from the device into SK.nodes */
+sf3d_error_t sinkFetch()
+{
+    if (!SK.on || !dev().sink_computed()) return SF3D_MEMORY_ERROR;
+    const uint32_t count = LM.on ? (uint32_t)LM.l2g.size() : M.N;
+    SK.nodes.resize(count);
+    return rasterFail("sink nodes", dev().sink_download_nodes(SK.nodes.data(), count));
+}
+
+}  // namespace
+
+extern "C" {
+
+sf3d_error_t sf3d_sink_initialize(uint32_t nrRows, uint32_t nrCols, const float* dem, float flag, double cellSize, uint32_t nrLayers,
+                                  const double* layerDepth, const double* layerThickness, double computationSoilDepth, const int32_t* cropIndex,
+                                  const int32_t* soilIndex, uint32_t nUnits, const sf3d_sink_unit_t* units, uint32_t nSoils, const sf3d_sink_soil_t* soils)
+{
+    if (nrRows == 0 || nrCols == 0 || !dem || !cropIndex || !soilIndex || (uint64_t)nrRows * nrCols > 0x7fffffffull) return SF3D_PARAMETER_ERROR;
+    if (nrLayers == 0 || nrLayers > SF3D_ROOT_MAX_LAYERS || !layerDepth || !layerThickness || !(cellSize > 0)) return SF3D_PARAMETER_ERROR;
+    if (nUnits > SF3D_CROP_MAX_UNITS || (nUnits > 0 && !units) || nSoils > SF3D_ROOT_MAX_SOILS || (nSoils > 0 && !soils)) return SF3D_PARAMETER_ERROR;
+    for (uint32_t s = 0; s < nSoils; ++s)
+        if (soils[s].nrHorizons < 0 || soils[s].nrHorizons > SF3D_ROOT_MAX_HORIZONS) return SF3D_PARAMETER_ERROR;
+    const uint32_t n = nrRows * nrCols;
+    for (uint32_t c = 0; c < n; ++c)
+        if ((cropIndex[c] >= 0 && (uint32_t)cropIndex[c] >= nUnits) || (soilIndex[c] >= 0 && (uint32_t)soilIndex[c] >= nSoils)) return SF3D_PARAMETER_ERROR;
+    /* initializeEvaporationCoefficient, project3D.cpp:2331-2368 */
+    int lastEvapLayer = sinkLayerIndex(nrLayers, layerDepth, layerThickness, kMaxEvaporationDepth);
+    if (computationSoilDepth < kMaxEvaporationDepth) lastEvapLayer = sinkLayerIndex(nrLayers, layerDepth, layerThickness, computationSoilDepth);
+    if (lastEvapLayer == -9999) return SF3D_PARAMETER_ERROR;
+    std::vector<double> evapCoeff(nrLayers, 0.), layerEvapCoeff(nrLayers, 0.);
+    double coeffSum = 0;
+    for (int layer = 1; layer <= lastEvapLayer; layer++) {
+        const double depthCoeff = std::max((layerDepth[layer] - layerDepth[1]) / (kMaxEvaporationDepth - layerDepth[1]), 0.0);
+        evapCoeff[layer] = exp(-2 * depthCoeff);
+        layerEvapCoeff[layer] = evapCoeff[layer] * (layerThickness[layer] / 0.04);
+        coeffSum += layerEvapCoeff[layer];
+    }
+    const double invCoeffSum = 1.0 / coeffSum;
+    for (int layer = 1; layer <= lastEvapLayer; layer++) layerEvapCoeff[layer] *= invCoeffSum;
+
+    sinkClear();
+    SK.nRows = nrRows; SK.nCols = nrCols; SK.nrLayers = nrLayers; SK.nUnits = nUnits; SK.nSoils = nSoils; SK.lastEvapLayer = lastEvapLayer;
+    SK.flag = flag; SK.area = cellSize * cellSize;
+    SK.dem.assign(dem, dem + n);
+    SK.cropIndex.resize(n); SK.soilIndex.resize(n);
+    for (uint32_t c = 0; c < n; ++c) { SK.cropIndex[c] = cropIndex[c] < 0 ? -1 : cropIndex[c]; SK.soilIndex[c] = soilIndex[c] < 0 ? -1 : soilIndex[c]; }
+    SK.units.resize(nUnits);
+    for (uint32_t u = 0; u < nUnits; ++u) SK.units[u] = SinkUnitDev{units[u].kcMax, units[u].fRAW, units[u].isWaterSurplusResistant ? 1 : 0, 0};
+    SK.horizon.assign((size_t)nSoils * nrLayers, -1);
+    SK.horizonValues.assign((size_t)nSoils * SF3D_ROOT_MAX_HORIZONS * SINK_HORIZON_VALUES, 0.);
+    for (uint32_t s = 0; s < nSoils; ++s) {
+        const sf3d_sink_soil_t& so = soils[s];
+        for (int32_t h = 0; h < so.nrHorizons; ++h) {
+            double* hz = SK.horizonValues.data() + ((size_t)s * SF3D_ROOT_MAX_HORIZONS + h) * SINK_HORIZON_VALUES;
+            hz[SINK_H_HH] = so.waterContentHH[h]; hz[SINK_H_FC] = so.waterContentFC[h]; hz[SINK_H_WP] = so.waterContentWP[h];
+            hz[SINK_H_SAT] = so.waterContentSAT[h]; hz[SINK_H_FRACTION] = so.soilFraction[h];
+        }
+        for (uint32_t l = 0; l < nrLayers; ++l)                           /* Crit3DSoil::getHorizonIndex(layerDepth[l]), soil.cpp:192-201 */
+            for (int32_t h = 0; h < so.nrHorizons; ++h)
+                if (layerDepth[l] >= so.upperDepth[h] && layerDepth[l] <= (so.lowerDepth[h] + 0.00001)) { SK.horizon[(size_t)s * nrLayers + l] = h; break; }
+    }
+    SK.layerDepth.assign(layerDepth, layerDepth + nrLayers); SK.thick.assign(layerThickness, layerThickness + nrLayers);
+    SK.evapCoeff = evapCoeff; SK.layerEvapCoeff = layerEvapCoeff;
+    SK.on = true;
+    return SF3D_OK;
+}
+
+sf3d_error_t sf3d_sink_get_tables(double* evapCoeff, double* layerEvapCoeff, int32_t* lastEvapLayer, int32_t* horizonOfSoilLayer)
+{
+    if (!SK.on) return SF3D_MEMORY_ERROR;
+    if (evapCoeff) std::copy(SK.evapCoeff.begin(), SK.evapCoeff.end(), evapCoeff);
+    if (layerEvapCoeff) std::copy(SK.layerEvapCoeff.begin(), SK.layerEvapCoeff.end(), layerEvapCoeff);
+    if (lastEvapLayer) *lastEvapLayer = SK.lastEvapLayer;
+    if (horizonOfSoilLayer) for (size_t k = 0; k < SK.horizon.size(); ++k) horizonOfSoilLayer[k] = SK.horizon[k] < 0 ? -9999 : SK.horizon[k];
+    return SF3D_OK;
+}
+
+sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const float* lai, const float* degreeDays, const float* liquidWater)
+{
+    if (!SK.on) return SF3D_MEMORY_ERROR;
+    if (nrCells != SK.nRows * SK.nCols) return SF3D_PARAMETER_ERROR;
+    NEED_INIT_E;
+    if (!MP.set || MP.nCells != nrCells || MP.nLayers != SK.nrLayers) return SF3D_TOPOGRAPHY_ERROR;
+    if (MP.maxNode >= 0 && (uint32_t)MP.maxNode >= M.N) return SF3D_TOPOGRAPHY_ERROR;
+    if ((!et0 || !lai || !degreeDays) && !(CR.on && CR.nRows == SK.nRows && CR.nCols == SK.nCols && dev().root_crop_degree_days_ready(nrCells))) return SF3D_PARAMETER_ERROR;
+    if (!liquidWater && !(SN.on && SN.nRows == SK.nRows && SN.nCols == SK.nCols && dev().sink_snow_ready(nrCells))) return SF3D_PARAMETER_ERROR;
+    if (!(RT.on && RT.nRows == SK.nRows && RT.nCols == SK.nCols && dev().sink_root_ready(nrCells, SK.nrLayers))) return SF3D_PARAMETER_ERROR;
+    if (!SK.uploaded || !dev().sink_allocated()) {
+        SinkSetup S{};
+        S.nCells = nrCells; S.nrLayers = SK.nrLayers; S.nUnits = SK.nUnits; S.nSoils = SK.nSoils; S.lastEvapLayer = SK.lastEvapLayer;
+        S.dem = SK.dem.data(); S.cropIndex = SK.cropIndex.data(); S.soilIndex = SK.soilIndex.data(); S.units = SK.units.data();
+        S.horizon = SK.horizon.data(); S.horizonValues = SK.horizonValues.data(); S.layerDepth = SK.layerDepth.data(); S.thick = SK.thick.data();
+        S.evapCoeff = SK.evapCoeff.data(); S.layerEvapCoeff = SK.layerEvapCoeff.data(); S.area = SK.area; S.flag = SK.flag;
+        const sf3d_error_t e = dev().sink_alloc(S);
+        if (e != SF3D_OK) return rasterFail("sink upload", e);
+        SK.uploaded = true;
+    }
+    HostModel& D = deviceModel();
+    MapsInput in;
+    sinkColumns(in);
+    SinkCall call{et0, lai, degreeDays, liquidWater, mapsOwnedCells(nrCells)};
+    return rasterFail("sink compute hour", dev().sink_hour(D, P, in, call));
+}
+
+sf3d_error_t sf3d_sink_get_node_sinks(uint32_t nrNodes, double* sinks)
+{
+    if (!SK.on) return SF3D_MEMORY_ERROR;
+    NEED_INIT_E;
+    if (!sinks || nrNodes != M.N) return SF3D_PARAMETER_ERROR;
+    const sf3d_error_t e = sinkFetch();
+    if (e != SF3D_OK) return e;
+    if (!LM.on) { std::copy(SK.nodes.begin(), SK.nodes.end(), sinks); return SF3D_OK; }
+    std::fill(sinks, sinks + nrNodes, 0.);
+    for (size_t k = 0; k < LM.l2g.size(); ++k) sinks[LM.l2g[k]] = SK.nodes[k];
+    return SF3D_OK;
+}
+
+sf3d_error_t sf3d_sink_get_actual(uint32_t nrCells, double* evaporation, double* transpiration)
+{
+    if (!SK.on || !dev().sink_allocated()) return SF3D_MEMORY_ERROR;
+    if (nrCells != SK.nRows * SK.nCols) return SF3D_PARAMETER_ERROR;
+    sf3d_error_t e = SF3D_OK;
+    if (evaporation) e = dev().sink_download_cells(SINK_MAP_EVAPORATION, evaporation);
+    if (e == SF3D_OK && transpiration) e = dev().sink_download_cells(SINK_MAP_TRANSPIRATION, transpiration);
+    return rasterFail("sink get actual", e);
+}
+
+sf3d_error_t sf3d_sink_apply(void)
+{
+    if (!SK.on) return SF3D_MEMORY_ERROR;
+    NEED_INIT_E;
+    const sf3d_error_t e = sinkFetch();
+    if (e != SF3D_OK) return e;
+    if (M.sink.size() < M.N) return SF3D_MEMORY_ERROR;
+    if (!LM.on) std::copy(SK.nodes.begin(), SK.nodes.end(), M.sink.begin());
+    else {
+        /* a rank's staging copy is read at its own nodes only (and may hold no pages elsewhere): the other ranks' nodes, 0 in this rank's array, are left alone */
+        if (!LM.trimmed) std::fill(M.sink.begin(), M.sink.begin() + M.N, 0.);
+        for (size_t k = 0; k < LM.l2g.size(); ++k) M.sink[LM.l2g[k]] = SK.nodes[k];
+    }
+    if (!M.sinkDirty) { M.sinkLo = 0; M.sinkHi = M.N; M.sinkDirty = true; }      /* what N single setters leave */
+    else { M.sinkLo = 0; if (M.N > M.sinkHi) M.sinkHi = M.N; }
+    return SF3D_OK;
+}
+
+double sf3d_sink_kernel_ms(void) { return dev().sink_kernel_ms(); }
+
+sf3d_error_t sf3d_sink_clean(void)
+{
+    sinkClear();
+    return SF3D_OK;
+}
+
+} /* extern "C" */

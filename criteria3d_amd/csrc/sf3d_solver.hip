@@ -50,3 +50,4 @@
 #include "sf3d_crop.inc"
 #include "sf3d_root.inc"
 #include "sf3d_meteo.inc"
+#include "sf3d_sink.inc"

@@ -650,6 +650,52 @@ def soil_root_table(soils) -> list:
                  soilFraction=[1.0 - float(h["coarse"]) for h in s["horizons"]]) for s in soils]
 
 
+def sink_unit_table(crop_rows, land_units) -> list:
+    """the land units as the sink module takes them (beside crop_table / root_table): kcMax and fRAW as loadCropParameters reads them
+    (cropDbTools.cpp:86, 97-100: a missing raw_fraction is 0.6) and isWaterSurplusResistant() (crop.cpp:353-356: id_crop == "RICE").  A
+    unit that is no crop gets a zero entry."""
+    by_id = {}
+    for r in crop_rows:
+        by_id.setdefault(str(r["id_crop"]), r)
+    out = []
+    for u in land_units:
+        cid = u.get("id_crop")
+        entry = dict(id_crop="" if cid is None else str(cid), isCrop=int(is_crop(cid)), kcMax=0.0, fRAW=0.0, isWaterSurplusResistant=0)
+        if entry["isCrop"]:
+            r = by_id.get(entry["id_crop"])
+            if r is None:
+                raise ValueError(f"Missing crop: {entry['id_crop']}")
+            fraw = db_double(r.get("raw_fraction"))
+            entry.update(kcMax=_db_float(r["kc_max"]), fRAW=0.6 if fraw == NODATA else fraw, isWaterSurplusResistant=int(entry["id_crop"] == "RICE"))
+        out.append(entry)
+    return out
+
+
+def theta_from_sign_psi(h: dict, sign_psi: float) -> float:
+    """soil::thetaFromSignPsi (soil.cpp:652-679) of a horizon of load_all_soils: potential [kPa] -> volumetric water content [m3 m-3]"""
+    if sign_psi >= 0.0 or abs(sign_psi) <= h["he"]:
+        se = 1.0
+    else:
+        se = math.pow(1.0 + math.pow(h["alpha"] * abs(sign_psi), h["n"]), -h["m"]) / h["sc"]
+    return se * (h["theta_s"] - h["theta_r"]) + h["theta_r"]
+
+
+def soil_sink_table(soils) -> list:
+    """the soils of load_all_soils as the sink module takes them, same index as soil_root_table: per horizon upperDepth, lowerDepth,
+    getSoilFraction() and the water contents setHorizon derives (soil.cpp:1009-1016): SAT = thetaS, FC at the clay-dependent field
+    capacity, WP at -1600 kPa, HH at -3000 kPa, each times the soil fraction"""
+    out = []
+    for s in soils:
+        hz = s["horizons"]
+        frac = [1.0 - float(h["coarse"]) for h in hz]
+        out.append(dict(upperDepth=[float(h["upper"]) for h in hz], lowerDepth=[float(h["lower"]) for h in hz], soilFraction=frac,
+                        waterContentSAT=[h["theta_s"] * f for h, f in zip(hz, frac)],
+                        waterContentFC=[theta_from_sign_psi(h, h["field_capacity"]) * f for h, f in zip(hz, frac)],
+                        waterContentWP=[theta_from_sign_psi(h, -1600.0) * f for h, f in zip(hz, frac)],
+                        waterContentHH=[theta_from_sign_psi(h, -3000.0) * f for h, f in zip(hz, frac)]))
+    return out
+
+
 def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> Model:
     """The solver model `Project3D::initialize3DModel` builds (project3D.cpp:456-616), as arrays for the bulk ABI:
     setSoilIndexMap :708-755, computation depth :494-515, setSoilLayers / setLayersDepth :1568-1661, setIndexMaps :758-818,

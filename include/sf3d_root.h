@@ -5,7 +5,7 @@
  * (agrolib/crop/crop.cpp:651-691, over root::getRootLengthDD, agrolib/crop/root.cpp:139-170) and root::computeRootDensity3D
  * (root.cpp:505-633, over cardioidDistribution / cylindricalDistribution, root.cpp:255-364) - each on a fresh copy of cropList[unit].
  * The values are the reference's to the bit (tests/golden/root_density.npz: a pin of the compiled reference).  The transpiration sink
- * itself (the stress logic of assignTranspiration, the sink arrays), evaporation and precipitation stay with the caller.
+ * itself (the stress logic of assignTranspiration, the sink arrays), evaporation and the rain term read these maps on the device: sf3d_sink.h.
  *
  * The density vector of a cell depends on its land unit, its soil and numberOfRootedLayers = round(min(currentRootLength, totalDepth) /
  * 0.01) only.  sf3d_root_initialize builds the vectors of every (unit, soil) pair of the raster for every number of rooted atoms once

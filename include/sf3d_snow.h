@@ -2,7 +2,8 @@
  * sf3d_snow.h - the hourly snow model of the application on the MI355X: what Crit3DProject::computeSnowModel
  * (bin/CRITERIA3D/criteria3DProject.cpp:1815-1878) runs before the hour's water is handed to the solver -
  * Crit3DSnow::computeSnowBrooksModel (src/snow/snow.cpp:142-525, the Brooks energy balance) on the seven float state maps of
- * Crit3DSnowMaps - and the liquid water assignPrecipitation (:914-968) then feeds the solver (prec - snowFall + snowMelt).
+ * Crit3DSnowMaps - and the liquid water assignPrecipitation (:914-968) then feeds the solver (prec - snowFall + snowMelt; sf3d_sink.h
+ * reads it on the device and adds the rain term to the node sinks).
  * One kernel launch per hour (k_snow_hour, one thread per raster cell); the maps stay on the device, and the values are the
  * reference's to the bit (tests/golden/snow_brooks.npz: a pin of the compiled reference).
  *

@@ -1,0 +1,197 @@
+"""The hourly water sinks on the device (include/sf3d_sink.h, k_sink_hour) against the compiled-reference pin
+tests/golden/water_sinks.npz: node sinks and both actual maps of every hour bit for bit, zero cells excluded, with every map passed in and
+with NULL maps read from the crop and snow blocks; the nrLayers = 1 case; sf3d_sink_apply against the node-by-node setter and the compute
+call without apply against the run without it (C2's F20 hour); the crop, snow and root blocks undisturbed; two ranks sharing the GPU."""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import capi, catchment as cm, crop, root, sinks, snow
+from tests import crop_cases as cc
+from tests import root_cases as rc
+from tests import sink_cases as sc
+from tests.snow_cases import melt_forcing
+
+pytestmark = pytest.mark.gpu
+ROOT = Path(__file__).resolve().parent.parent
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return sc.load_pin()
+
+
+def _need_glibc_set(product):
+    if product.lib.sf3d_libm_set() != 1:
+        pytest.skip("this build evaluates the 0.50-ulp routines, not the C library's bits (-DSF3D_LIBM_GLIBC=0): bit identity with the compiled reference is not its contract")
+
+
+def _model(product, pin):
+    m = sc.node_model(pin)
+    product.check(product.lib.sf3d_reset_solver_state(), "reset")
+    cm.build(product, m, threads=1)
+    sc.set_state(product, pin, m)
+    return m
+
+
+def _same(got, want, what):
+    for name in want:
+        bad = sc.bits(got[name]) != sc.bits(want[name])
+        print(f"{what} {name}: {int(bad.sum())} values differ")
+        assert not bad.any(), (what, name, int(bad.sum()), np.asarray(got[name])[bad][:4], np.asarray(want[name])[bad][:4])
+
+
+def _outputs(product, n):
+    e, t = sinks.get_actual(product)
+    return dict(sinks=sinks.get_node_sinks(product, n), evaporation=e, transpiration=t)
+
+
+def test_every_hour_equals_the_pin(product, pin):
+    _need_glibc_set(product)
+    m = _model(product, pin)
+    assert np.array_equal(sc.bits(product.water_content(0, m.n)), sc.bits(pin["vwc"]))             # the state the fixture's water contents were read from
+    rc.initialize(product, pin)
+    sc.initialize(product, pin)
+    for k in range(len(pin["et0"])):
+        sc.hour(product, pin, k)
+        _same(_outputs(product, m.n), {name: pin[name][k] for name in ("sinks", "evaporation", "transpiration")}, f"hour {k}")
+    sc.hour(product, pin, 0)                                                                        # an earlier hour again: nothing is left over
+    _same(_outputs(product, m.n), {name: pin[name][0] for name in ("sinks", "evaporation", "transpiration")}, "hour 0 again")
+    product.lib.sf3d_clean()
+
+
+def test_one_layer(product, pin):
+    _need_glibc_set(product)
+    m = _model(product, pin)
+    sinks.set_columns(product, pin["columns"][:1], pin["layer_thickness"][:1])
+    root.initialize(product, pin["dem"], pin["crop_index"], pin["soil_index"], pin["unit_list"], pin["soil_list"], pin["layer_depth"][:1], pin["layer_thickness"][:1],
+                    float(pin["flag"]))
+    sc.initialize(product, pin, one_layer=True)
+    for j, k in enumerate(int(v) for v in pin["one_layer_hours"]):
+        sc.hour(product, pin, k)
+        got = _outputs(product, m.n)
+        _same(got, dict(sinks=pin["one_layer_sinks"][j], evaporation=pin["one_layer_evaporation"][j], transpiration=pin["one_layer_transpiration"][j]), f"one layer, hour {k}")
+        assert not got["sinks"][m.ns:].any() and np.all(got["transpiration"][got["transpiration"] != float(pin["flag"])] == 0)
+    product.lib.sf3d_clean()
+
+
+def test_null_maps_read_the_blocks_and_leave_them_undisturbed(product, pin):
+    _need_glibc_set(product)
+    m = _model(product, pin)
+    dem, flag = pin["dem"], float(pin["flag"])
+    k = 3
+    rc.initialize(product, pin)
+    sc.initialize(product, pin)
+    units = cc.load_pin()["unit_list"]
+    unit_index = np.where(pin["crop_index"] < 0, 0, pin["crop_index"]) % len(units)
+    snow.initialize(product, dem, flag)
+    crop.initialize(product, dem, unit_index, units, 44.5, flag)
+    for met in melt_forcing(dem.shape, dem, flag)[11:13]:
+        snow.compute_hour(product, met)
+        crop.compute_hour(product, None)
+    crop.set_state(product, "degreeDays", pin["sink_degree_days"][k])
+    crop.set_state(product, "lai", pin["lai"][k])
+    root.compute(product, None)
+    before = dict(snow.all_maps(product)); before.update(crop.all_maps(product)); before.update({"root_" + n: v for n, v in root.all_maps(product).items()})
+    et0, liquid = crop.get_et0(product), snow.get_output(product, "liquid")
+    assert np.count_nonzero((et0 != flag) & (et0 > 0)) > 300 and np.count_nonzero((liquid != flag) & (liquid > 0)) > 300
+    sinks.compute_hour(product, None, None, None, None)
+    null_form = _outputs(product, m.n)
+    sinks.compute_hour(product, et0, pin["lai"][k], pin["sink_degree_days"][k], liquid)
+    _same(null_form, _outputs(product, m.n), "NULL form against the same maps passed in")
+    want = sinks.restate_sink_hour(dem, flag, float(pin["cell_size"]), pin["columns"], pin["vwc"], pin["crop_index"], pin["soil_index"], pin["sink_units"], pin["sink_soils"],
+                                   pin["layer_depth"], pin["layer_thickness"], float(pin["computation_depth"]), et0, pin["lai"][k], pin["sink_degree_days"][k], liquid,
+                                   sc.roots_of(pin, k), m.n)
+    _same(null_form, {name: want[name] for name in ("sinks", "evaporation", "transpiration")}, "NULL form against the restatement")
+    assert np.count_nonzero(null_form["sinks"][m.ns:] < 0) > 1000 and np.count_nonzero(null_form["sinks"][:m.ns] > 0) > 100
+    after = dict(snow.all_maps(product)); after.update(crop.all_maps(product)); after.update({"root_" + n: v for n, v in root.all_maps(product).items()})
+    for name, v in before.items():
+        assert np.array_equal(v, after[name], equal_nan=True), name
+    snow.clean(product); crop.clean(product)
+    assert product.lib.sf3d_sink_compute_hour(dem.size, None, None, None, None) == capi.PARAMETER_ERROR
+    product.lib.sf3d_clean()
+
+
+def _c2_run(product, pin, mode):
+    """C2 in its F20 hour with the column table of its own grid; mode: "none", "apply" (compute + apply before every step), "setter" (the
+    downloaded array through sf3d_set_node_water_sink_source node by node), "compute" (compute without apply between every two steps)"""
+    m = cm.catchment_model(32, 24, 14)
+    product.check(product.lib.sf3d_reset_solver_state(), "reset")
+    cm.build(product, m, threads=1)
+    if mode != "none":
+        cols = np.asarray(m.meta["index"]).astype(np.int32)
+        sinks.set_columns(product, cols, pin["layer_thickness"])
+        rc.initialize(product, pin)
+        sc.initialize(product, pin)
+    rain = np.zeros(m.n)
+    rain[:m.ns] = cm.rain_rate(20.0, m.cell_area)
+    product.set_sink_source_bulk(0, rain)
+    t, k = 0.0, 0
+    while t < 3600.0 and k < 40:
+        if mode in ("apply", "setter"):
+            sc.hour(product, pin, k % len(pin["et0"]))
+            if mode == "apply":
+                sinks.apply(product)
+            else:
+                q = sinks.get_node_sinks(product, m.n)
+                for i in range(m.n):
+                    product.lib.sf3d_set_node_water_sink_source(i, float(q[i]))
+        dt = product.lib.sf3d_compute_step(3600.0 - t)
+        assert dt > 0.0
+        t += dt
+        if mode == "compute":
+            sc.hour(product, pin, k % len(pin["et0"]))
+            sinks.get_node_sinks(product, m.n)
+        k += 1
+    s, c = cm.snapshot(product, m), product.counters()
+    product.lib.sf3d_clean()
+    return s, c
+
+
+def test_apply_is_the_setter_and_compute_leaves_the_solver_untouched(product, pin):
+    (s0, c0), (s1, c1) = _c2_run(product, pin, "apply"), _c2_run(product, pin, "setter")
+    assert np.array_equal(s0["H"], s1["H"]) and np.array_equal(s0["Se"], s1["Se"]) and c0 == c1
+    (s2, c2), (s3, c3) = _c2_run(product, pin, "none"), _c2_run(product, pin, "compute")
+    assert np.array_equal(s2["H"], s3["H"]) and np.array_equal(s2["Se"], s3["Se"]) and c2 == c3
+    assert not np.array_equal(s0["H"], s2["H"])                   # the sinks did reach the solver
+
+
+def test_two_ranks_merge_to_the_single_rank_sinks(product, pin, tmp_path):
+    _need_glibc_set(product)
+    world, port, which = 2, 29791, 4
+    outs = [tmp_path / f"sink_r{r}.npz" for r in range(world)]
+    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60"), "SF3D_BENCH_SHARE_GPU": "1"}
+    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_sink_worker.py"), str(r), str(world), str(port), str(which), str(outs[r])],
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
+    logs = []
+    for pr in procs:
+        try:
+            o, _ = pr.communicate(timeout=300)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        logs.append(o)
+    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
+    ranks = [np.load(o) for o in outs]
+    flag = float(pin["flag"])
+    n = len(pin["vwc"])
+    owner = np.full(n, 255, np.int64)
+    for r, res in enumerate(ranks):
+        owner[res["owner"] == r] = r
+    assert set(np.unique(owner)) == {0, 1}
+    cell_owner = owner[:pin["dem"].size].reshape(pin["dem"].shape)      # a column goes with its surface node
+    merged = dict(sinks=np.zeros(n), evaporation=np.full(pin["dem"].shape, flag), transpiration=np.full(pin["dem"].shape, flag))
+    for r, res in enumerate(ranks):
+        mine = cell_owner == r
+        computed = mine & (pin["columns"][0] >= 0)
+        assert np.all(res["evaporation"][~computed] == flag) and np.all(res["transpiration"][~computed] == flag), r      # another rank's cells: the flag
+        assert not res["sinks"][owner != r].any(), r                                                                      # and their nodes 0
+        merged["sinks"][owner == r] = res["sinks"][owner == r]
+        merged["evaporation"][mine] = res["evaporation"][mine]
+        merged["transpiration"][mine] = res["transpiration"][mine]
+    _same(merged, {name: pin[name][which] for name in ("sinks", "evaporation", "transpiration")}, "merged ranks")

@@ -1,0 +1,134 @@
+"""The hourly water sinks without a GPU: the restatement of assignEvaporation / assignTranspiration (criteria3d_amd/sinks.py) against the
+compiled-reference pin tests/golden/water_sinks.npz, bit for bit in every node and cell of every hour, zero excluded; the fixture's arm
+table; the host-evaluated tables of sf3d_sink_initialize against the recorded ones; the error codes that need no device."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import capi, catchment as cm, sinks
+from tests import sink_cases as sc
+from tests.golden import make_water_sinks as gen
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return sc.load_pin()
+
+
+@pytest.fixture(scope="module")
+def restated(pin):
+    arms = {}
+    return [sc.restated(pin, k, arms) for k in range(len(pin["et0"]))], arms
+
+
+def test_restatement_equals_the_pin(pin, restated):
+    for k, got in enumerate(restated[0]):
+        for name in sc.OUTPUTS:
+            want = pin[name][k]
+            bad = sc.bits(got[name]) != sc.bits(want)
+            assert not bad.any(), (k, name, int(bad.sum()))
+        assert np.count_nonzero(pin["sinks_et"][k]) > 1000 and np.isfinite(pin["sinks"][k]).all()
+    flag = float(pin["flag"])
+    assert np.count_nonzero(pin["evaporation"] > 0) > 2000 and np.count_nonzero((pin["transpiration"] > 0)) > 1000
+    assert np.all(pin["evaporation"][:, pin["columns"][0] < 0] == flag)
+
+
+def test_one_layer_case(pin):
+    for j, k in enumerate(pin["one_layer_hours"]):
+        got = sc.restated(pin, int(k), one_layer=True)
+        assert np.array_equal(sc.bits(got["sinks_et"]), sc.bits(pin["one_layer_sinks_et"][j])) and np.array_equal(sc.bits(got["sinks"]), sc.bits(pin["one_layer_sinks"][j]))
+        assert np.array_equal(sc.bits(got["evaporation"]), sc.bits(pin["one_layer_evaporation"][j]))
+        t = pin["one_layer_transpiration"][j]
+        assert np.array_equal(sc.bits(got["transpiration"]), sc.bits(t)) and np.all(t[t != float(pin["flag"])] == 0)
+        ns = pin["dem"].size
+        assert not pin["one_layer_sinks"][j][ns:].any() and np.count_nonzero(pin["one_layer_sinks"][j][:ns] < 0) > 0 and np.count_nonzero(pin["one_layer_sinks"][j][:ns] > 0) > 0
+
+
+def test_no_arm_is_empty(pin, restated):
+    recorded = dict(zip((str(n) for n in pin["arm_names"]), (int(v) for v in pin["arm_counts"])))
+    for arm in gen.REQUIRED_ARMS:
+        assert recorded.get(arm, 0) > 0, arm
+    assert recorded == restated[1]                                # the restatement walks the same arms as often
+
+
+def test_host_tables_equal_the_recorded_ones(pin):
+    ec, lec, last = sinks.evaporation_coefficients(pin["layer_depth"], pin["layer_thickness"], float(pin["computation_depth"]))
+    assert last == int(pin["last_evap_layer"]) and np.array_equal(sc.bits(ec), sc.bits(pin["evap_coeff"])) and np.array_equal(sc.bits(lec), sc.bits(pin["layer_evap_coeff"]))
+    assert np.array_equal(sinks.horizon_table(pin["sink_soils"], pin["layer_depth"]), pin["horizon"]) and (pin["horizon"] == -9999).any()
+    sf = capi.load_product()
+    sc.initialize(sf, pin)                                        # no device needed
+    t = sinks.get_tables(sf)
+    assert t["last_evap_layer"] == int(pin["last_evap_layer"]) and np.array_equal(t["horizon"], pin["horizon"])
+    assert np.array_equal(sc.bits(t["evap_coeff"]), sc.bits(pin["evap_coeff"])) and np.array_equal(sc.bits(t["layer_evap_coeff"]), sc.bits(pin["layer_evap_coeff"]))
+    sc.initialize(sf, pin, one_layer=True)
+    assert sinks.get_tables(sf)["last_evap_layer"] == int(pin["one_layer_last_evap_layer"]) == 0
+    sinks.clean(sf)
+
+
+def test_error_codes_without_a_device(pin):
+    sf = capi.load_product()
+    sinks.bind(sf)
+    lib = sf.lib
+    lib.sf3d_clean()
+    dem, flag = pin["dem"], float(pin["flag"])
+    n = dem.size
+    f = np.zeros(n, np.float32)
+    pf = f.ctypes.data_as(sinks.pf32)
+    d = np.zeros(n, np.float64)
+    assert lib.sf3d_sink_compute_hour(n, pf, pf, pf, pf) == capi.MEMORY_ERROR and lib.sf3d_sink_apply() == capi.MEMORY_ERROR
+    assert lib.sf3d_sink_get_actual(n, d.ctypes.data_as(sinks.pf64), None) == capi.MEMORY_ERROR
+    ld, lt = np.ascontiguousarray(pin["layer_depth"]), np.ascontiguousarray(pin["layer_thickness"])
+    ci, si = np.ascontiguousarray(pin["crop_index"], np.int32), np.ascontiguousarray(pin["soil_index"], np.int32)
+    ua, sa = sinks.unit_array(pin["sink_units"]), sinks.soil_array(pin["sink_soils"])
+
+    def init(dem_=dem, layers=len(ld), cell=4.0, nu=len(pin["sink_units"]), ns=len(pin["sink_soils"]), units=ua, soils=sa, ldp=ld, depth=0.95):
+        return lib.sf3d_sink_initialize(dem.shape[0], dem.shape[1], None if dem_ is None else dem_.ctypes.data_as(sinks.pf32), flag, cell, layers,
+                                        None if ldp is None else ldp.ctypes.data_as(sinks.pf64), lt.ctypes.data_as(sinks.pf64), depth, ci.ctypes.data_as(sinks.pi32),
+                                        si.ctypes.data_as(sinks.pi32), nu, units, ns, soils)
+    assert init(dem_=None) == capi.PARAMETER_ERROR and init(ldp=None) == capi.PARAMETER_ERROR and init(units=None) == capi.PARAMETER_ERROR      # null pointers
+    assert init(layers=0) == capi.PARAMETER_ERROR and init(layers=sinks.MAX_LAYERS + 1) == capi.PARAMETER_ERROR                                   # caps
+    assert init(nu=sinks.MAX_UNITS + 1) == capi.PARAMETER_ERROR and init(ns=sinks.MAX_SOILS + 1) == capi.PARAMETER_ERROR
+    assert init(nu=3) == capi.PARAMETER_ERROR and init(ns=2) == capi.PARAMETER_ERROR                                                              # an index beyond the table
+    assert init(cell=0.0) == capi.PARAMETER_ERROR and init(depth=-1.0) == capi.PARAMETER_ERROR                                                   # initializeEvaporationCoefficient fails
+    assert lib.sf3d_sink_get_tables(None, None, None, None) == capi.MEMORY_ERROR                   # a refused initialise leaves no raster
+    assert init() == capi.OK
+    assert lib.sf3d_sink_compute_hour(n - 1, pf, pf, pf, pf) == capi.PARAMETER_ERROR               # wrong nrCells
+    assert lib.sf3d_sink_compute_hour(n, pf, pf, pf, pf) == capi.MEMORY_ERROR                      # no model
+    m = cm.catchment_model(dem.shape[1], dem.shape[0], len(ld))
+    cm.build(sf, m, finalize=False)                                                                 # host-side staging only
+    assert lib.sf3d_sink_compute_hour(n, pf, pf, pf, pf) == capi.TOPOGRAPHY_ERROR                  # no column table
+    sinks.set_columns(sf, pin["columns"][:4], lt[:4])
+    assert lib.sf3d_sink_compute_hour(n, pf, pf, pf, pf) == capi.TOPOGRAPHY_ERROR                  # one of another layer grid
+    sinks.set_columns(sf, pin["columns"], lt)
+    assert lib.sf3d_sink_compute_hour(n, None, pf, pf, pf) == capi.PARAMETER_ERROR                 # NULL ET0 without a crop block
+    assert lib.sf3d_sink_compute_hour(n, pf, None, pf, pf) == capi.PARAMETER_ERROR and lib.sf3d_sink_compute_hour(n, pf, pf, None, pf) == capi.PARAMETER_ERROR
+    assert lib.sf3d_sink_compute_hour(n, pf, pf, pf, None) == capi.PARAMETER_ERROR                 # NULL liquid water without a snow block
+    assert lib.sf3d_sink_compute_hour(n, pf, pf, pf, pf) == capi.PARAMETER_ERROR                   # no root block
+    nodes = np.zeros(m.n)
+    assert lib.sf3d_sink_get_node_sinks(m.n - 1, nodes.ctypes.data_as(sinks.pf64)) == capi.PARAMETER_ERROR and lib.sf3d_sink_get_node_sinks(m.n, None) == capi.PARAMETER_ERROR
+    assert lib.sf3d_sink_get_node_sinks(m.n, nodes.ctypes.data_as(sinks.pf64)) == capi.MEMORY_ERROR and lib.sf3d_sink_apply() == capi.MEMORY_ERROR      # before the first hour
+    assert lib.sf3d_sink_clean() == capi.OK and lib.sf3d_sink_get_tables(None, None, None, None) == capi.MEMORY_ERROR
+    lib.sf3d_clean()
+
+
+def test_sink_unit_and_soil_table_readers():
+    import json
+    from pathlib import Path
+    from criteria3d_amd import project3d as p3
+    golden = Path(__file__).resolve().parent / "golden"
+    rows = json.loads((golden / "ravone_crops.json").read_text())
+    inp = p3.load_project_fixture(golden / "ravone_project.npz")
+    table = p3.sink_unit_table(rows["crop"], inp.land_units)
+    assert [t["id_crop"] for t in table] == ["SHRUB", "BROADLEAF", "BARE"] and table[2]["kcMax"] == 0.0
+    assert all(0.5 < t["kcMax"] < 2.0 and 0.0 < t["fRAW"] < 1.0 and t["isWaterSurplusResistant"] == 0 for t in table[:2])
+    rice = dict(rows["crop"][1], id_crop="RICE", raw_fraction="")
+    t = p3.sink_unit_table([rice], [dict(id=1, id_crop="RICE")])[0]
+    assert t["isWaterSurplusResistant"] == 1 and t["fRAW"] == 0.6                  # a missing raw_fraction
+    sinks.unit_array(table)
+    soils = p3.soil_sink_table(inp.soils)
+    assert len(soils) == len(inp.soils) <= sinks.MAX_SOILS
+    for s in soils:
+        for h in range(len(s["upperDepth"])):                                      # HH < WP < FC < SAT, as the potentials -3000 < -1600 < field capacity < 0 kPa
+            assert 0.0 <= s["waterContentHH"][h] < s["waterContentWP"][h] < s["waterContentFC"][h] < s["waterContentSAT"][h] < 1.0
+    sinks.soil_array(soils)
