@@ -168,6 +168,7 @@ struct SinkCache {
     double* nodes = nullptr;            /* [nodesN] node sinks */
     size_t off[8] = {0};
     uint32_t nCells = 0, nrLayers = 0, nUnits = 0, nSoils = 0, nodesN = 0;
+    uint64_t nodesColVer = 0;           /* the version of the column table `nodes` was last written under (MapsCache::colVer is shared with the output maps) */
     int32_t lastEvapLayer = 0;
     double area = 0.;
     float flag = -9999.f;

@@ -273,7 +273,13 @@ sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const Ma
         K.nodesN = 0; K.computed = false;
         RASTER_TRY(hipMalloc((void**)&K.nodes, ((size_t)I.v.N ? (size_t)I.v.N : 1) * sizeof(double)));
         K.nodesN = I.v.N;
-        RASTER_TRY(hipMemsetAsync(K.nodes, 0, (size_t)I.v.N * sizeof(double), I.stream));      /* nodes of no column, and of other ranks' columns, stay 0 */
+        K.nodesColVer = 0;
+    }
+    if (K.nodesColVer != in.colVer) {
+        /* nodes of no column, and of other ranks' columns, hold 0: the kernel zeroes a node through this hour's table only, so under another table
+         * (sf3d_set_output_columns, or another partition) a node that has left its column would keep the sink of the last hour */
+        RASTER_TRY(hipMemsetAsync(K.nodes, 0, (size_t)I.v.N * sizeof(double), I.stream));
+        K.nodesColVer = in.colVer;
     }
     const float* maps[4] = {call.et0, call.lai, call.dd, call.liquid};
     for (int k = 0; k < 4; ++k)

@@ -1,5 +1,7 @@
-"""Forcing shared by tests/test_gpu_snow.py and scripts/multirank_snow_worker.py (no tests here)."""
+"""Forcing shared by tests/test_gpu_snow.py, tests/test_snow_host.py and scripts/multirank_snow_worker.py (no tests here)."""
 import numpy as np
+
+from criteria3d_amd import snow
 
 
 def melt_forcing(shape, dem, flag):
@@ -10,3 +12,61 @@ def melt_forcing(shape, dem, flag):
         return dict(airT=f(t), prec=f(prec), relHum=f(80.0), windInt=f(2.0), globalRad=f(rad), beamRad=f(rad * 0.7), transmissivity=f(0.6),
                     clearSkyTransmissivity=0.75)
     return [maps_(-3.0, 2.0, 0.0)] * 12 + [maps_(9.0, 1.0, 500.0)] * 4
+
+
+SHAPES = ((7, 37), (3, 11), (1, 300))          # 259 cells: one block and three lanes; 33: less than a wave; 300: a partial second block
+FLAG = -9999.0
+# every one of snow.PARAMETER_NAMES away from snow.DEFAULT_PARAMETERS, inside physical ranges
+OTHER_PARAMETERS = dict(skinThickness=0.03, soilAlbedo=0.3, snowVegetationHeight=0.5, snowWaterHoldingCapacity=0.08, tempMaxWithSnow=1.5,
+                        tempMinWithRain=-1.0, snowSurfaceDampingDepth=0.08)
+
+
+def small_forcing(shape, seed):
+    """(dem, flag, six hours of meteo maps) on a raster of any shape, every cell with values of its own: two cold hours with precipitation
+    (snow builds), one hour inside the mixed-precipitation band of the default and of OTHER_PARAMETERS, two warm sunny hours (melt), and one
+    hour with the flag (and 0) in relHum, the flag in transmissivity and more than 100 mm of surface water on some cells.  The DEM holds
+    the flag in the first and the middle cell and in a few more; the last cell is valid, takes no flag and no free water."""
+    rng = np.random.default_rng(seed)
+    flag = np.float32(FLAG)
+    n = shape[0] * shape[1]
+    dem = rng.uniform(50.0, 900.0, shape).astype(np.float32)
+    dem[rng.random(shape) < 0.04] = flag
+    dem.flat[0] = flag
+    dem.flat[n // 2] = flag
+    dem.flat[-1] = np.float32(333.0)
+
+    def u(lo, hi, last):
+        v = rng.uniform(lo, hi, shape).astype(np.float32)
+        v.flat[-1] = np.float32(last)
+        return v
+
+    def hour(t, prec, rad, last):
+        glob = u(*rad, last[2])
+        return dict(airT=u(*t, last[0]), prec=u(*prec, last[1]), relHum=u(45.0, 98.0, 80.0), windInt=u(0.0, 7.0, 2.0), globalRad=glob,
+                    beamRad=(glob * np.float32(0.7)).astype(np.float32), transmissivity=u(0.2, 0.74, 0.6), clearSkyTransmissivity=0.75)
+    hours = [hour((-9.0, -1.5), (1.0, 5.0), (20.0, 90.0), (-4.0, 3.0, 50.0)), hour((-9.0, -1.5), (1.0, 5.0), (0.0, 0.0), (-4.0, 3.0, 0.0)),
+             hour((-0.4, 1.4), (0.5, 4.0), (0.0, 60.0), (0.5, 2.0, 30.0)),
+             hour((5.0, 14.0), (0.0, 0.6), (300.0, 800.0), (10.0, 0.2, 600.0)), hour((5.0, 14.0), (0.0, 0.0), (300.0, 800.0), (10.0, 0.0, 600.0)),
+             hour((2.5, 9.0), (0.0, 2.0), (50.0, 400.0), (6.0, 1.0, 200.0))]
+    h = hours[5]
+    pick = rng.random((4,) + shape)
+    pick[:, -1, -1] = 1.0
+    h["relHum"][pick[0] < 0.15] = flag                       # dew point: no humidity
+    h["relHum"][(pick[0] >= 0.15) & (pick[0] < 0.25)] = 0
+    h["transmissivity"][pick[1] < 0.2] = flag                # cloud cover default
+    water = np.where(pick[2] < 0.15, 150.0, np.where(pick[2] < 0.5, 0.0, rng.uniform(-5.0, 60.0, shape))).astype(np.float32)      # free water above 100 mm
+    water.flat[-1] = 0
+    h["surfaceWater"] = water
+    return dem, float(flag), hours
+
+
+def restated_run(dem, flag, hours, parameters=None):
+    """snow.restate_snow_hour carried along hour by hour from initializeSnowMaps / resetSnowModel under `parameters`: the thirteen maps
+    after every hour"""
+    fl = np.float32(flag)
+    state = snow.restate_reset(np.where(dem == fl, fl, np.float32(0)), flag, parameters)
+    out = []
+    for met in hours:
+        state = snow.restate_snow_hour(state, met, dem, flag, parameters)
+        out.append(state)
+    return out

@@ -1,7 +1,8 @@
 """The hourly water sinks on the device (include/sf3d_sink.h, k_sink_hour) against the compiled-reference pin
 tests/golden/water_sinks.npz: node sinks and both actual maps of every hour bit for bit, zero cells excluded, with every map passed in and
 with NULL maps read from the crop and snow blocks; the nrLayers = 1 case; sf3d_sink_apply against the node-by-node setter and the compute
-call without apply against the run without it (C2's F20 hour); the crop, snow and root blocks undisturbed; two ranks sharing the GPU."""
+call without apply against the run without it (C2's F20 hour); the crop, snow and root blocks undisturbed; two ranks sharing the GPU;
+rasters with a partial block, less than a wave and a single row against the restatement, and a column table changed between two hours."""
 import os
 import subprocess
 import sys
@@ -113,6 +114,100 @@ def test_null_maps_read_the_blocks_and_leave_them_undisturbed(product, pin):
         assert np.array_equal(v, after[name], equal_nan=True), name
     snow.clean(product); crop.clean(product)
     assert product.lib.sf3d_sink_compute_hour(dem.size, None, None, None, None) == capi.PARAMETER_ERROR
+    product.lib.sf3d_clean()
+
+
+def _small(product, pin, shape):
+    """a small case on the device: its node model, potentials and column table, the root and sink blocks on its raster; the water contents the device holds"""
+    case = sc.small_case(pin, shape, seed=shape[1])
+    m = _model(product, case)
+    vwc = product.water_content(0, m.n)
+    rc.initialize(product, case, case["dem"], case["crop_index"], case["soil_index"])
+    sc.initialize(product, case)
+    return case, m, vwc
+
+
+def _wanted(case, k, vwc, columns=None):
+    want = sc.restated_case(case, k, vwc, columns)
+    return {name: want[name] for name in ("sinks", "evaporation", "transpiration")}
+
+
+@pytest.mark.parametrize("shape", sc.SHAPES)
+def test_other_raster_shapes_against_the_restatement(product, pin, shape):
+    """259 cells: one block plus three lanes; 33 cells: less than a wave; one row of 300: a partial second block.  Two hours with maps of
+    their own against restate_sink_hour on the water contents the device holds: nothing of the first hour is left in the second."""
+    _need_glibc_set(product)
+    case, m, vwc = _small(product, pin, shape)
+    flag, n, nl = float(case["flag"]), case["dem"].size, len(case["layer_depth"])
+    soil_nodes = sc.soil_nodes_of_computing_cells(case)
+    for k in range(len(case["et0"])):
+        sc.hour(product, case, k)
+        got = _outputs(product, m.n)
+        _same(got, _wanted(case, k, vwc), f"raster {shape}, hour {k}")
+        e, t = got["evaporation"], got["transpiration"]
+        assert e.flat[-1] > 0 and t.flat[-1] > 0                                                    # the last lane computes
+        assert e.flat[0] == flag and t.flat[0] == flag and e.flat[n // 2] == flag and t.flat[n // 2] == flag      # flag cells
+        assert e.flat[2] == flag and not got["sinks"][np.arange(nl) * n + 2].any()                  # the column left out under a valid cell
+        assert not got["sinks"][np.arange(nl) * n].any()                                            # the column under a flag cell
+        # (the restatement reaches 0.142 to 0.232 on the host's water contents: sc.SINK_SHARE, tests/test_sink_host.py)
+        assert np.count_nonzero(got["sinks"][m.ns:] < 0) >= sc.SINK_SHARE * soil_nodes
+    product.lib.sf3d_clean()
+
+
+def _one_step(product, case, feed):
+    """the first computeStep of the case's model after `feed` has handed the sinks over: what the step took, H and Se"""
+    m = _model(product, case)
+    feed(m)
+    dt = product.lib.sf3d_compute_step(3600.0)
+    s = cm.snapshot(product, m)
+    return dt, s["H"], s["Se"]
+
+
+def test_a_changed_column_table_leaves_no_sinks_behind(product, pin):
+    """Hour A on the full column table, then the same maps on a table of the same layer grid in which some computing cells have lost
+    their whole column and others their nodes from layer 3 down: a node outside this hour's table holds 0, as the reference starts
+    every hour with waterSinkSource = 0 in every node (runModelHour); and what sf3d_sink_apply hands to the solver is that array."""
+    _need_glibc_set(product)
+    shape = (7, 37)
+    case, m, vwc = _small(product, pin, shape)
+    n, nl = case["dem"].size, len(case["layer_depth"])
+    sc.hour(product, case, 0)
+    hour_a = _outputs(product, m.n)
+    _same(hour_a, _wanted(case, 0, vwc), "hour A")
+    columns = case["columns"].copy().reshape(nl, n)
+    computing = np.flatnonzero(sc.computing_cells(case).ravel())
+    columns[:, computing[1::5]] = -1                                      # the whole column gone
+    columns[3:, computing[3::5]] = -1                                     # the nodes from layer 3 down gone
+    columns[3:, 7:9] = -1                                                 # (the trees whose deep layers transpire)
+    columns = columns.reshape(case["columns"].shape)
+    outside = np.ones(m.n, bool)
+    outside[case["columns"][case["columns"] >= 0]] = False
+    was_outside = outside.copy()
+    outside[:] = True
+    outside[columns[columns >= 0]] = False
+    left = outside & ~was_outside & (hour_a["sinks"] != 0)
+    assert np.count_nonzero(left) > 100 and np.count_nonzero(left[:m.ns]) > 10      # the nodes that leave the table held sinks in hour A
+    sinks.set_columns(product, columns, case["layer_thickness"])
+    sc.hour(product, case, 0)
+    hour_b = _outputs(product, m.n)
+    stale = outside & (hour_b["sinks"] != 0)
+    print(f"{int(stale.sum())} of {int(outside.sum())} nodes outside the new table hold a sink", hour_b["sinks"][stale][:3], np.flatnonzero(stale)[:3])
+    _same(hour_b, _wanted(case, 0, vwc, columns), "hour B")
+    assert not stale.any() and np.count_nonzero(hour_b["sinks"]) > 300
+    # the hand-over: apply leaves the array as it is, and the solver steps as after the node-by-node setter
+    sinks.apply(product)
+    assert np.array_equal(sc.bits(sinks.get_node_sinks(product, m.n)), sc.bits(hour_b["sinks"]))
+    dt0 = product.lib.sf3d_compute_step(3600.0)
+    s0 = cm.snapshot(product, m)
+    q = hour_b["sinks"]
+
+    def setter(m):
+        for i in range(m.n):
+            product.lib.sf3d_set_node_water_sink_source(i, float(q[i]))
+    dt1, h1, se1 = _one_step(product, case, setter)
+    dt2, h2, se2 = _one_step(product, case, lambda m: None)
+    assert dt0 == dt1 > 0.0 and np.array_equal(s0["H"], h1) and np.array_equal(s0["Se"], se1)
+    assert dt2 > 0.0 and not np.array_equal(h1, h2)                      # the sinks did reach the solver
     product.lib.sf3d_clean()
 
 

@@ -1,7 +1,8 @@
 """The hourly snow model on the device (include/sf3d_snow.h, k_snow_hour) against the compiled-reference pin tests/golden/snow_brooks.npz:
 all thirteen maps after every checkpoint hour bit for bit, zero cells excluded; the same run interrupted at hour 48 through get_state /
 set_state and through the application's snow/ state folder; the solver does not notice the calls; a melt hour's liquid water drives the
-product and the oracle to the same state; two ranks sharing the GPU merge to the single-rank maps; the error codes."""
+product and the oracle to the same state; two ranks sharing the GPU merge to the single-rank maps; the error codes; rasters with a
+partial block, less than a wave and a single row, and a parameter set away from the defaults, against the restatement."""
 import os
 import subprocess
 import sys
@@ -13,6 +14,7 @@ import pytest
 from criteria3d_amd import capi, catchment as cm, maps, snow
 from tests import tolerances
 from tests.scenarios import ravone_project_model
+from tests import snow_cases
 from tests.snow_cases import melt_forcing
 
 pytestmark = pytest.mark.gpu
@@ -217,6 +219,62 @@ def test_two_ranks_merge_to_the_single_rank_maps(product, tmp_path):
             mine = cell_owner == r
             assert np.array_equal(_bits(res[n][mine]), _bits(single[n][mine])), (n, r)
             assert np.array_equal(_bits(res[n][~mine]), _bits(ranks[r]["initial_" + n][~mine])), (n, r)      # untouched elsewhere
+
+
+def _same_maps(got, want, what):
+    for n in snow.STATE + snow.OUTPUT:
+        bad = _bits(got[n]) != _bits(want[n])
+        print(f"{what} {n}: {int(bad.sum())} cells differ")
+        assert not bad.any(), (what, n, int(bad.sum()), got[n][bad][:4], want[n][bad][:4])
+
+
+@pytest.mark.parametrize("shape", snow_cases.SHAPES)
+def test_other_raster_shapes_against_the_restatement(product, shape):
+    """259 cells: one block plus three lanes; 33 cells: less than a wave; one row of 300: a partial second block.  Six hours (snow builds,
+    falls mixed, melts; flags in relHum and transmissivity, free water) with snow.restate_snow_hour carried along: all thirteen maps after
+    every hour.  tests/test_snow_host.py checks that the forcing does what it says."""
+    _need_glibc_set(product)
+    dem, flag, hours = snow_cases.small_forcing(shape, seed=shape[1])
+    want = snow_cases.restated_run(dem, flag, hours)
+    snow.initialize(product, dem, flag)
+    for h, met in enumerate(hours):
+        snow.compute_hour(product, met)
+        got = snow.all_maps(product)
+        _same_maps(got, want[h], f"raster {shape}, hour {h}")
+        assert np.all(got["swe"][dem == np.float32(flag)] == np.float32(flag))
+    assert want[1]["swe"].flat[-1] > 0 and max(want[3]["snowMelt"].flat[-1], want[4]["snowMelt"].flat[-1]) > 0      # the last lane built snow and melted it
+    assert any(np.count_nonzero(w["liquid"] > 0) > 0 for w in want)
+    snow.clean(product)
+
+
+def test_non_default_parameters_against_the_restatement(product):
+    """Every one of the seven parameters away from its default (snow_cases.OTHER_PARAMETERS), once passed to sf3d_snow_initialize and once
+    set by sf3d_snow_set_parameters (and sf3d_snow_reset, whose surface energy reads skinThickness) on a raster initialised with the defaults.
+    No run of the compiled reference pins these values: snow.restate_snow_hour, which equals it on the defaults, is the only authority
+    here.  tests/test_snow_host.py checks that each parameter alone changes the result of this forcing."""
+    _need_glibc_set(product)
+    shape = (7, 37)
+    p = snow_cases.OTHER_PARAMETERS
+    dem, flag, hours = snow_cases.small_forcing(shape, seed=shape[1])
+    want = snow_cases.restated_run(dem, flag, hours, p)
+    default = snow_cases.restated_run(dem, flag, hours[:1])
+    runs = []
+    for how in ("initialize", "set_parameters"):
+        if how == "initialize":
+            snow.initialize(product, dem, flag, p)
+        else:
+            snow.initialize(product, dem, flag)
+            snow.set_parameters(product, p)
+            snow.reset(product)
+        runs.append([])
+        for h, met in enumerate(hours):
+            snow.compute_hour(product, met)
+            runs[-1].append(snow.all_maps(product))
+            _same_maps(runs[-1][h], want[h], f"{how}, hour {h}")
+        snow.clean(product)
+    for h in range(len(hours)):
+        _same_maps(runs[0][h], runs[1][h], f"both ways, hour {h}")
+    assert not np.array_equal(_bits(want[0]["surfaceTemp"]), _bits(default[0]["surfaceTemp"]))      # (not the default run)
 
 
 def test_error_paths(product, pin):

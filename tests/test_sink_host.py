@@ -1,6 +1,6 @@
 """The hourly water sinks without a GPU: the restatement of assignEvaporation / assignTranspiration (criteria3d_amd/sinks.py) against the
 compiled-reference pin tests/golden/water_sinks.npz, bit for bit in every node and cell of every hour, zero excluded; the fixture's arm
-table; the host-evaluated tables of sf3d_sink_initialize against the recorded ones; the error codes that need no device."""
+table; the small rasters of tests/sink_cases.py reach every arm too; the host-evaluated tables of sf3d_sink_initialize against the recorded ones; the error codes that need no device."""
 import ctypes as C
 
 import numpy as np
@@ -50,6 +50,29 @@ def test_no_arm_is_empty(pin, restated):
     for arm in gen.REQUIRED_ARMS:
         assert recorded.get(arm, 0) > 0, arm
     assert recorded == restated[1]                                # the restatement walks the same arms as often
+
+
+def test_small_cases_reach_every_arm(pin, oracle):
+    """the rasters tests/test_gpu_sink.py runs off the fixture: 259, 33 and 300 cells.  The water contents come from the CPU oracle's
+    van Genuchten curve on the cases' potentials; here they only steer the arms."""
+    union = {}
+    for shape in sc.SHAPES:
+        case = sc.small_case(pin, shape, seed=shape[1])
+        vwc = sc.host_water_content(oracle, case)
+        flag = float(case["flag"])
+        assert case["dem"].flat[0] == flag and case["dem"].flat[case["dem"].size // 2] == flag and case["dem"].flat[2] != flag
+        assert np.all(case["columns"].reshape(len(case["columns"]), -1)[:, 2] == -1) and np.all(case["columns"][:, -1, -1] >= 0)
+        soil_nodes = sc.soil_nodes_of_computing_cells(case)
+        for k in range(len(case["et0"])):
+            got = sc.restated_case(case, k, vwc, arms=union)
+            e, t = got["evaporation"], got["transpiration"]
+            assert np.count_nonzero((e != flag) & (e > 0)) > 0 and np.count_nonzero((t != flag) & (t > 0)) > 0, (shape, k)
+            assert e.flat[-1] > 0 and t.flat[-1] > 0 and e.flat[0] == flag and t.flat[2] == flag, (shape, k)      # the last lane computes
+            share = np.count_nonzero(got["sinks"][case["dem"].size:] < 0) / soil_nodes
+            print(f"{shape} hour {k}: {share:.3f} of the soil nodes under computing cells hold a sink")
+            assert share >= sc.SINK_SHARE, (shape, k, share)
+    missing = [arm for arm in gen.REQUIRED_ARMS if union.get(arm, 0) == 0]
+    assert not missing, missing
 
 
 def test_host_tables_equal_the_recorded_ones(pin):

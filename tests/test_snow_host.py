@@ -1,6 +1,7 @@
 """The hourly snow model, the parts that need no GPU: the C entry points of include/sf3d_snow.h and the binding table, the error codes a
 call gives before a raster exists, the fixture (a pin of the compiled reference) is not vacuous, the python restatement of the point
-model equals it bit for bit over all 96 hours, the per-node sources of assignPrecipitation, the snow/ state folder."""
+model equals it bit for bit over all 96 hours, the small rasters' forcing of tests/snow_cases.py is not vacuous and reads every parameter,
+the per-node sources of assignPrecipitation, the snow/ state folder."""
 import re
 import subprocess
 from pathlib import Path
@@ -9,6 +10,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from criteria3d_amd import build, capi, esri, snow
+from tests import snow_cases
 
 ROOT = Path(__file__).resolve().parent.parent
 PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
@@ -102,6 +104,44 @@ def test_restatement_equals_the_compiled_reference_for_all_96_hours():
             for k, n in enumerate(names):
                 bad = _bits(state[n]) != _bits(want[k])
                 assert not bad.any(), (h + 1, n, int(bad.sum()))
+
+
+def test_small_forcing_is_not_vacuous():
+    """the six hours tests/test_gpu_snow.py runs off the pin, on 259, 33 and 300 cells: snow builds, falls mixed, melts; the last hour walks
+    the pin's arms "dew point: no humidity", "cloud cover default (flag)" and "free water" """
+    for shape in snow_cases.SHAPES:
+        dem, flag, hours = snow_cases.small_forcing(shape, seed=shape[1])
+        fl = np.float32(flag)
+        valid = dem != fl
+        assert dem.flat[0] == fl and dem.flat[dem.size // 2] == fl and dem.flat[-1] != fl and valid.sum() > dem.size // 2
+        run = snow_cases.restated_run(dem, flag, hours)
+        assert all(np.isfinite(m).all() for maps in run for m in maps.values())
+        assert run[1]["swe"].flat[-1] > 0 and max(run[3]["snowMelt"].flat[-1], run[4]["snowMelt"].flat[-1]) > 0      # the last lane builds snow and melts it
+        assert np.all(run[1]["swe"][valid] > 0) and np.count_nonzero(run[3]["snowMelt"][valid] > 0) > valid.sum() // 2
+        fall, prec = run[2]["snowFall"][valid], hours[2]["prec"][valid]
+        assert np.count_nonzero((fall > 0) & (fall < prec)) > valid.sum() // 2                      # mixed precipitation
+        assert any(np.count_nonzero((maps["liquid"] != fl) & (maps["liquid"] > 0)) > 0 for maps in run)
+        assert np.count_nonzero(run[4]["lwc"][valid] > 0) > 0                                       # liquid water held in the pack
+        last = hours[5]
+        free = valid & (last["surfaceWater"] > 100)
+        assert free.sum() > 0 and np.all(run[5]["swe"][free] == fl) and np.all(run[5]["snowMelt"][free] == 0)
+        computed = valid & ~free
+        assert np.count_nonzero(computed & (last["relHum"] == fl)) > 0 and np.count_nonzero(computed & (last["relHum"] == 0)) > 0
+        assert np.count_nonzero(computed & (last["transmissivity"] == fl)) > 0 and np.all(run[5]["swe"][computed] != fl)
+
+
+def test_every_parameter_matters_to_the_small_forcing():
+    """each of the seven parameters alone moved to its value in snow_cases.OTHER_PARAMETERS changes at least one map of the six hours: a
+    kernel that ignored one of them would not equal the restatement in test_non_default_parameters_against_the_restatement"""
+    assert set(snow_cases.OTHER_PARAMETERS) == set(snow.PARAMETER_NAMES)
+    dem, flag, hours = snow_cases.small_forcing((7, 37), seed=37)
+    default = snow_cases.restated_run(dem, flag, hours)
+    for name in snow.PARAMETER_NAMES:
+        assert snow_cases.OTHER_PARAMETERS[name] != snow.DEFAULT_PARAMETERS[name], name
+        run = snow_cases.restated_run(dem, flag, hours, {name: snow_cases.OTHER_PARAMETERS[name]})
+        differing = sum(int((_bits(a[n]) != _bits(b[n])).sum()) for a, b in zip(run, default) for n in snow.STATE + snow.OUTPUT)
+        print(f"{name}: {differing} map values differ from the default run")
+        assert differing > 0, name
 
 
 def test_point_model_by_hand():
