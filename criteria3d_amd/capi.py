@@ -31,6 +31,7 @@ ERROR_NAMES = ["ok", "index error", "memory error", "topography error", "boundar
 u8, u16, u32, u64 = C.c_uint8, C.c_uint16, C.c_uint32, C.c_uint64
 f64, f32, i32 = C.c_double, C.c_float, C.c_int
 pd = C.POINTER(C.c_double)
+pf32, pf64, pi32 = C.POINTER(C.c_float), pd, C.POINTER(C.c_int32)     # the raster bindings' names (maps.py, snow.py, crop.py, root.py, meteo.py, sinks.py)
 p8, p16, p32, p64 = C.POINTER(u8), C.POINTER(u16), C.POINTER(u32), C.POINTER(u64)
 cstr, vp = C.c_char_p, C.c_void_p
 

@@ -22,6 +22,7 @@ from pathlib import Path
 import numpy as np
 
 from . import capi, raster
+from .capi import pf32, pi32
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -49,8 +50,6 @@ class Unit(C.Structure):
     _fields_ = [(n, C.c_int32) for n in UNIT_INT_FIELDS] + [(n, C.c_double) for n in UNIT_DOUBLE_FIELDS]
 
 
-pf32 = C.POINTER(C.c_float)
-pi32 = C.POINTER(C.c_int32)
 punit = C.POINTER(Unit)
 # name -> (restype, argtypes): every symbol include/sf3d_crop.h declares
 SIGNATURES = {
@@ -93,9 +92,7 @@ def initialize(sf: capi.SF3D, dem, unit_index, units, latitude: float, flag: flo
     index per cell, negative where there is none; units: list of dicts with UNIT_FIELDS, one per land unit."""
     bind(sf)
     dem = _f32(dem)
-    idx = np.ascontiguousarray(unit_index, dtype=np.int32)
-    if idx.shape != dem.shape:
-        raise ValueError(f"unit index of shape {idx.shape}, the DEM is {dem.shape}")
+    idx = raster.i32(unit_index, dem.shape, "crop")
     sf._crop_shape = dem.shape
     sf.check(sf.lib.sf3d_crop_initialize(dem.shape[0], dem.shape[1], dem.ctypes.data_as(pf32), float(flag), idx.ctypes.data_as(pi32), len(units),
                                          unit_array(units), float(latitude)), "crop_initialize")

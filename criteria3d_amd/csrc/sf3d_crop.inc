@@ -182,13 +182,8 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_crop_day(CropView v)
 sf3d_error_t DeviceSolver::crop_free()
 {
     if (!impl_) return SF3D_OK;
-    CropCache& K = impl_->crop;
-    if (K.base || K.units) {
-        if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
-        if (K.base) (void)hipFree(K.base);
-        if (K.units) (void)hipFree(K.units);
-    }
-    K = CropCache();
+    raster_release({impl_->crop.base, impl_->crop.units});
+    impl_->crop = CropCache();
     return SF3D_OK;
 }
 
@@ -218,10 +213,11 @@ sf3d_error_t DeviceSolver::crop_download(int map, float* dst)
     return raster_download(dst, K.base + (size_t)map * K.nCells, (size_t)K.nCells * sizeof(float));
 }
 
-bool DeviceSolver::crop_snow_inputs_ready(uint32_t nCells) const
-{
-    return impl_ && impl_->snow.base && impl_->snow.hourDone && impl_->snow.nCells == nCells;
-}
+/* ---- what the other blocks read from this one, once it is allocated on their raster */
+bool DeviceSolver::crop_allocated(uint32_t nCells) const { return impl_ && impl_->crop.base && impl_->crop.nCells == nCells; }
+static const float* crop_et0(const CropCache& K) { return K.base + (size_t)CROP_MAP_ET0 * K.nCells; }
+static const float* crop_degree_days(const CropCache& K) { return K.base + (size_t)(CROP_MAP_STATE + 0) * K.nCells; }      /* SF3D_CROP_DEGREE_DAYS */
+static const float* crop_lai(const CropCache& K) { return K.base + (size_t)(CROP_MAP_STATE + 1) * K.nCells; }              /* SF3D_CROP_LAI */
 
 static void crop_view(CropView& v, const CropCache& K, float flag)
 {
@@ -247,10 +243,8 @@ sf3d_error_t DeviceSolver::crop_hour(const float* const in[5], float clearSky, f
     const sf3d_error_t e = raster_mask(mine, n, &v.mine);
     if (e != SF3D_OK) return e;
     crop_view(v, K, flag);
-    if (!in) {                                  /* the maps sf3d_snow_compute_hour uploaded: air temperature, relative humidity, wind, global radiation, transmissivity */
-        static const int snowInput[5] = {0, 2, 3, 4, 6};
-        for (int k = 0; k < 5; ++k) v.in[k] = I.snow.base + (size_t)(SNOW_MAP_IN + snowInput[k]) * n;
-    }
+    if (!in)                                    /* the maps sf3d_snow_compute_hour uploaded */
+        for (int k = 0; k < 5; ++k) v.in[k] = snow_hour_input(I.snow, k);
     v.clearSky = clearSky;
     return raster_launch(k_et0_hour, n, v, K.lastMs[0]);
 }

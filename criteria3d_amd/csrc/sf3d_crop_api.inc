@@ -23,7 +23,7 @@ extern "C" {
 sf3d_error_t sf3d_crop_initialize(uint32_t nrRows, uint32_t nrCols, const float* dem, float flag, const int32_t* cropIndex, uint32_t nUnits,
                                   const sf3d_crop_unit_t* units, double latitude)       /* initializeCropMaps, criteria3DProject.cpp:415-433 */
 {
-    if (nrRows == 0 || nrCols == 0 || !dem || !cropIndex || (uint64_t)nrRows * nrCols > 0x7fffffffull) return SF3D_PARAMETER_ERROR;
+    if (!rasterShapeOk(nrRows, nrCols, dem) || !cropIndex) return SF3D_PARAMETER_ERROR;
     if (nUnits > SF3D_CROP_MAX_UNITS || (nUnits > 0 && !units)) return SF3D_PARAMETER_ERROR;
     const uint32_t n = nrRows * nrCols;
     std::vector<int32_t> index(n);
@@ -86,7 +86,7 @@ sf3d_error_t sf3d_crop_compute_hour(uint32_t nrCells, const float* airTemperatur
     int given = 0;
     for (int k = 0; k < 5; ++k) given += in[k] ? 1 : 0;
     if (given != 0 && given != 5) return SF3D_PARAMETER_ERROR;
-    if (given == 0 && !(SN.on && SN.nRows == CR.nRows && SN.nCols == CR.nCols && dev().crop_snow_inputs_ready(nrCells))) return SF3D_PARAMETER_ERROR;
+    if (given == 0 && !(rasterFeeds(SN, CR.nRows, CR.nCols) && dev().snow_hour_done(nrCells))) return SF3D_PARAMETER_ERROR;
     return rasterFail("crop compute hour", dev().crop_hour(given ? in : nullptr, clearSkyTransmissivity, CR.flag, mapsOwnedCells(nrCells)));
 }
 

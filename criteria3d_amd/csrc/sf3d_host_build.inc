@@ -312,7 +312,7 @@ struct DeviceSolver::Impl {
              fatal_ = true;                                                                    \
              return SF3D_SOLVER_ERROR; } } while (0)
 
-/* the raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc) touch nothing of the solver: a HIP failure there does not set fatal_ */
+/* the raster blocks and the shared raster path (end of sf3d_maps.inc) touch nothing of the solver: a HIP failure there does not set fatal_ */
 #define RASTER_TRY(expr)                                                                       \
     do { hipError_t e_ = (expr);                                                               \
          if (e_ != hipSuccess) {                                                               \

@@ -169,21 +169,32 @@ template <class T> static hipError_t maps_reserve(T*& p, size_t& cap, size_t cou
     return e;
 }
 
-sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const MapsInput& in, int var, int layer, float flag, float* out, int* missing)
+/* the column table of the model the device works on, for output_map and sink_hour: brings the model up to date, refuses a multi-GPU model
+ * that is not connected, and uploads `col` and `thick` when their version is not the one on the device (MapsCache::colVer) */
+sf3d_error_t DeviceSolver::raster_columns(HostModel& m, const ParamsHost& p, const MapsInput& in)
 {
     sf3d_error_t e = sync_to_device(m, p);
     if (e != SF3D_OK) return e;
     if (world_ > 1 && !connected_) { snprintf(err_, sizeof(err_), "multi-GPU model used before sf3d_dist_connect / sf3d_dist_finalize"); return SF3D_SOLVER_ERROR; }
     Impl& I = *impl_;
     MapsCache& C = I.maps;
-    const size_t cells = in.nCells, colN = (size_t)in.nCells * in.nLayers;
-    if (C.colVer != in.colVer) {
-        HIP_TRY(maps_reserve(C.col, C.colCap, colN));
-        HIP_TRY(maps_reserve(C.thick, C.thickCap, in.nLayers));
-        HIP_TRY(hipMemcpyAsync(C.col, in.col, colN * 4, hipMemcpyHostToDevice, I.stream));
-        HIP_TRY(hipMemcpyAsync(C.thick, in.thick, (size_t)in.nLayers * 8, hipMemcpyHostToDevice, I.stream));
-        C.colVer = in.colVer;
-    }
+    if (C.colVer == in.colVer) return SF3D_OK;
+    const size_t colN = (size_t)in.nCells * in.nLayers;
+    RASTER_TRY(maps_reserve(C.col, C.colCap, colN));
+    RASTER_TRY(maps_reserve(C.thick, C.thickCap, in.nLayers));
+    RASTER_TRY(hipMemcpyAsync(C.col, in.col, colN * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(C.thick, in.thick, (size_t)in.nLayers * 8, hipMemcpyHostToDevice, I.stream));
+    C.colVer = in.colVer;
+    return SF3D_OK;
+}
+
+sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const MapsInput& in, int var, int layer, float flag, float* out, int* missing)
+{
+    const sf3d_error_t e = raster_columns(m, p, in);
+    if (e != SF3D_OK) return e;
+    Impl& I = *impl_;
+    MapsCache& C = I.maps;
+    const size_t cells = in.nCells;
     if (in.slope && C.slopeVer != in.slopeVer) {
         HIP_TRY(maps_reserve(C.slope, C.slopeCap, 2 * cells));
         HIP_TRY(hipMemcpyAsync(C.slope, in.slope, 2 * cells * 8, hipMemcpyHostToDevice, I.stream));
@@ -229,8 +240,41 @@ sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const M
     return SF3D_OK;
 }
 
-/* ---- shared by the raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc): their calls run on the solver's stream, touch nothing of
- * the solver and synchronise the stream before they return, so the caller's maps are free again and one device mask serves all three. */
+/* ---- shared by the five raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc, sf3d_meteo.inc, sf3d_sink.inc) and the output maps
+ * above.  A block's calls run on the solver's stream, touch nothing of the solver and synchronise the stream before they return, so the
+ * caller's maps are free again and one device mask serves all of them.  The column table reaches the device through raster_columns alone
+ * (the output maps and the sinks).  What one block reads from another it asks of that block's accessors, which stand in the owning
+ * block's file beside the predicate that makes the read safe: snow_hour_done / snow_hour_input, snow_liquid_water (sf3d_snow.inc),
+ * crop_allocated / crop_et0, crop_lai, crop_degree_days (sf3d_crop.inc), root_computed (sf3d_root.inc; its maps go to the sink kernel
+ * as one block). */
+
+/* a block of per-cell maps whose first two are 8-byte maps and the others 4-byte ones (RootCache::cells, SinkCache::cells) */
+static void* raster_cell_map(char* cells, size_t nCells, int map)
+{
+    return (map < 2) ? cells + (size_t)map * nCells * 8 : cells + 16 * nCells + (size_t)(map - 2) * nCells * 4;
+}
+
+/* one block for `count` tables of bytes[k] bytes, each at a multiple of 8 (off[k]); the tables with a source are filled from it */
+sf3d_error_t DeviceSolver::raster_tables(char*& tables, size_t* off, int count, const size_t* bytes, const void* const* src, const size_t* srcBytes)
+{
+    size_t total = 0;
+    for (int k = 0; k < count; ++k) { off[k] = total; total += (bytes[k] + 7) & ~(size_t)7; }
+    RASTER_TRY(hipMalloc((void**)&tables, total ? total : 8));
+    for (int k = 0; k < count; ++k)
+        if (src[k] && srcBytes[k]) RASTER_TRY(hipMemcpyAsync(tables + off[k], src[k], srcBytes[k], hipMemcpyHostToDevice, impl_->stream));
+    return SF3D_OK;
+}
+
+/* frees a block's device memory once the stream is idle; the caller resets its cache struct */
+void DeviceSolver::raster_release(std::initializer_list<void*> blocks)
+{
+    bool any = false;
+    for (void* q : blocks) any = any || q;
+    if (!any) return;
+    if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
+    for (void* q : blocks) if (q) (void)hipFree(q);
+}
+
 sf3d_error_t DeviceSolver::raster_upload(void* dev, const void* host, size_t bytes)
 {
     RASTER_TRY(hipSetDevice(impl_->device));

@@ -51,9 +51,34 @@ const uint8_t* mapsOwnedCells(size_t n)
     return MP.mine.data();
 }
 
-/* shared by the snow, crop and root entry points */
+/* the column table, the layer thickness and their version for the device, in the numbering of the model the device works on: a rank of a
+ * strip-local model fills the cells whose column it owns (local indices there, -1 in every other column) */
+void mapsDeviceInput(MapsInput& in)
+{
+    in.nCells = MP.nCells; in.nLayers = MP.nLayers; in.thick = MP.thick.data();
+    if (!LM.on) { in.col = MP.col.data(); in.colVer = MP.colVer; return; }
+    if (MP.colDevVer != MP.colVer || MP.colDevGen != LM.gen) {
+        const size_t nc = MP.nCells;
+        MP.colDev.assign(MP.col.size(), -1);
+        for (size_t c = 0; c < nc; ++c) {
+            if (!mapsOwnsCell(c)) continue;
+            for (uint32_t l = 0; l < MP.nLayers; ++l) {
+                const int32_t g = MP.col[l * nc + c];
+                if (g >= 0) MP.colDev[l * nc + c] = LM.g2l[g];
+            }
+        }
+        MP.colDevVer = MP.colVer; MP.colDevGen = LM.gen;
+        MP.colDevVerDev = ++mapsVersion;
+    }
+    in.col = MP.colDev.data(); in.colVer = MP.colDevVerDev;
+}
+
+/* shared by the entry points of the five raster blocks */
 sf3d_error_t rasterFail(const char* what, sf3d_error_t e) { if (e == SF3D_SOLVER_ERROR) fprintf(stderr, "sf3d: %s: %s\n", what, dev().last_error()); return e; }
 bool rasterIsFlag(float v, float flag) { return std::fabs(static_cast<double>(v) - static_cast<double>(flag)) < 0.00001; }      /* isEqual(float, float) */
+bool rasterShapeOk(uint32_t nrRows, uint32_t nrCols, const float* dem) { return nrRows != 0 && nrCols != 0 && dem && (uint64_t)nrRows * nrCols <= 0x7fffffffull; }
+/* block `b` (SN, CR, RT) is initialised on the raster of nrRows x nrCols cells, so a block on that raster may read its maps on the device */
+template <class Block> bool rasterFeeds(const Block& b, uint32_t nrRows, uint32_t nrCols) { return b.on && b.nRows == nrRows && b.nCols == nrCols; }
 
 }  // namespace
 
@@ -115,25 +140,7 @@ sf3d_error_t sf3d_compute_output_map(int variable, int layer, float flag, float*
 
     HostModel& D = deviceModel();
     MapsInput in;
-    in.nCells = MP.nCells; in.nLayers = MP.nLayers; in.thick = MP.thick.data();
-    if (!LM.on) { in.col = MP.col.data(); in.colVer = MP.colVer; }
-    else {
-        /* a rank fills the cells whose column it owns: local indices there, -1 in every other column */
-        if (MP.colDevVer != MP.colVer || MP.colDevGen != LM.gen) {
-            const size_t nc = MP.nCells;
-            MP.colDev.assign(MP.col.size(), -1);
-            for (size_t c = 0; c < nc; ++c) {
-                if (!mapsOwnsCell(c)) continue;
-                for (uint32_t l = 0; l < MP.nLayers; ++l) {
-                    const int32_t g = MP.col[l * nc + c];
-                    if (g >= 0) MP.colDev[l * nc + c] = LM.g2l[g];
-                }
-            }
-            MP.colDevVer = MP.colVer; MP.colDevGen = LM.gen;
-            MP.colDevVerDev = ++mapsVersion;
-        }
-        in.col = MP.colDev.data(); in.colVer = MP.colDevVerDev;
-    }
+    mapsDeviceInput(in);
     if (MP.slope.size() == (size_t)2 * MP.nCells) { in.slope = MP.slope.data(); in.slopeVer = MP.slopeVer; }
     /* geotechnics per soil class (the classes of sf3d_set_soil_properties, through the index table of sf3d_set_node_soil) */
     MP.geoClass.assign(M.soils.size(), MapGeo{0., 0., 0., 0.});

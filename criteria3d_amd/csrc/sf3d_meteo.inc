@@ -229,13 +229,8 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_meteo_idw(MeteoView v)
 sf3d_error_t DeviceSolver::meteo_free()
 {
     if (!impl_) return SF3D_OK;
-    MeteoCache& K = impl_->meteo;
-    if (K.base || K.stations) {
-        if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
-        if (K.base) (void)hipFree(K.base);
-        if (K.stations) (void)hipFree(K.stations);
-    }
-    K = MeteoCache();
+    raster_release({impl_->meteo.base, impl_->meteo.stations});
+    impl_->meteo = MeteoCache();
     return SF3D_OK;
 }
 

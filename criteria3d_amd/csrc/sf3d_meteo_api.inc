@@ -33,7 +33,7 @@ extern "C" {
 sf3d_error_t sf3d_meteo_initialize(uint32_t nrRows, uint32_t nrCols, const float* dem, float flag, double xllCorner, double yllCorner, double cellSize,
                                    uint32_t nProxies, const float* const* proxyMaps)
 {
-    if (nrRows == 0 || nrCols == 0 || !dem || (uint64_t)nrRows * nrCols > 0x7fffffffull || !(cellSize > 0)) return SF3D_PARAMETER_ERROR;
+    if (!rasterShapeOk(nrRows, nrCols, dem) || !(cellSize > 0)) return SF3D_PARAMETER_ERROR;
     if (nProxies > SF3D_METEO_MAX_PROXIES || (nProxies > 0 && !proxyMaps)) return SF3D_PARAMETER_ERROR;
     meteoClear();
     const sf3d_error_t e = dev().meteo_alloc(nrRows, nrCols, dem, flag, xllCorner, yllCorner, cellSize, nProxies, proxyMaps);

@@ -9,6 +9,7 @@
 #define SF3D_MODEL_H
 
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 #include "sf3d.h"
@@ -199,29 +200,33 @@ public:
      * *missing = 1 when a factor of safety needed a soil class without geotechnics */
     sf3d_error_t output_map(HostModel& m, const ParamsHost& p, const MapsInput& in, int var, int layer, float flag, float* out, int* missing);
     /* hourly snow model (sf3d_snow.inc): SNOW_MAPS float maps of nCells on the device, independent of the node model (release() keeps
-     * them); map = index into the block (SNOW_MAP_*) */
+     * them); map = index into the block (SNOW_MAP_*).  snow_hour_done: an hour has run on nCells cells, so its inputs and outputs are in the
+     * block for the crop and sink blocks to read */
     sf3d_error_t ensure_device();                /* device choice and the solver's stream, without a model */
     sf3d_error_t snow_alloc(uint32_t nCells);
     sf3d_error_t snow_upload(int map, const float* src);
     sf3d_error_t snow_download(int map, float* dst);
     sf3d_error_t snow_hour(const float* const in[8], const SnowParamsDev& p, float flag, const uint8_t* mine);
+    bool snow_hour_done(uint32_t nCells) const;
     sf3d_error_t snow_free();
     double snow_kernel_ms() const;
     /* hourly ET0 / daily crop maps (sf3d_crop.inc): CROP_MAPS maps of nCells on the device and the crop table, independent of the node
-     * model as the snow maps are; in == nullptr: k_et0_hour reads the five maps the last snow_hour left in the snow block */
+     * model as the snow maps are; in == nullptr: k_et0_hour reads the five maps the last snow_hour left in the snow block.  crop_allocated:
+     * the block holds nCells cells, so its ET0, LAI and degree-day maps are there for the root and sink blocks to read */
     sf3d_error_t crop_alloc(uint32_t nCells, const CropUnitDev* units, uint32_t nUnits);
     sf3d_error_t crop_upload(int map, const void* src);
     sf3d_error_t crop_download(int map, float* dst);
-    bool crop_snow_inputs_ready(uint32_t nCells) const;
+    bool crop_allocated(uint32_t nCells) const;
     sf3d_error_t crop_hour(const float* const in[5], float clearSky, float flag, const uint8_t* mine);
     sf3d_error_t crop_day(int dateDoy, int currentDoy, double latitude, float flag, const uint8_t* mine);
     sf3d_error_t crop_free();
     double crop_kernel_ms(int which) const;
     /* root length / depth / density maps (sf3d_root.inc): the per-cell maps, the tables and the keyed density table, independent of the
-     * node model as the snow and crop maps are; dd == nullptr: k_root_cell reads the degree-day map of the crop block */
+     * node model as the snow and crop maps are; dd == nullptr: k_root_cell reads the degree-day map of the crop block.  root_computed:
+     * root_compute has run on nCells cells and nrLayers layers, so the sink block may read its maps and its density table */
     sf3d_error_t root_alloc(const RootSetup& setup);
     sf3d_error_t root_compute(const float* dd, float flag, const uint8_t* mine);
-    bool root_crop_degree_days_ready(uint32_t nCells) const;
+    bool root_computed(uint32_t nCells, uint32_t nrLayers) const;
     sf3d_error_t root_download(int map, void* dst);
     sf3d_error_t root_density(int layer, double* dst, float flag);
     sf3d_error_t root_free();
@@ -240,8 +245,6 @@ public:
      * output_map does and the root block's maps, and, where a map of `call` is null, the crop / snow block's */
     sf3d_error_t sink_alloc(const SinkSetup& setup);
     bool sink_allocated() const;
-    bool sink_root_ready(uint32_t nCells, uint32_t nrLayers) const;
-    bool sink_snow_ready(uint32_t nCells) const;
     sf3d_error_t sink_hour(HostModel& m, const ParamsHost& p, const MapsInput& in, const SinkCall& call);
     sf3d_error_t sink_download_nodes(double* dst, uint32_t count);     /* the device model's numbering */
     sf3d_error_t sink_download_cells(int map, double* dst);
@@ -251,13 +254,17 @@ public:
 
 private:
     DeviceSolver() = default;
-    /* what the three raster blocks share (end of sf3d_maps.inc): a copy on the solver's stream that returns once it is done, the
-     * ownership mask of a strip on the device (null stays null), and kernel<<<ceil(count / SF3D_BLOCK), SF3D_BLOCK>>>(arg) with its
-     * event-timed milliseconds (0 when timing is off) in `ms` */
+    /* what the five raster blocks and the output maps share (sf3d_maps.inc): the column table of the device's model (output_map and
+     * sink_hour), a copy on the solver's stream that returns once it is done, the ownership mask of a strip on the device (null stays
+     * null), kernel<<<ceil(count / SF3D_BLOCK), SF3D_BLOCK>>>(arg) with its event-timed milliseconds (0 when timing is off) in `ms`, one
+     * device block for a list of tables, and the release of a block's device memory */
+    sf3d_error_t raster_columns(HostModel& m, const ParamsHost& p, const MapsInput& in);
     sf3d_error_t raster_upload(void* dev, const void* host, size_t bytes);
     sf3d_error_t raster_download(void* host, const void* dev, size_t bytes);
     sf3d_error_t raster_mask(const uint8_t* mine, size_t nCells, const uint8_t** dev);
     template <class Arg> sf3d_error_t raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms);
+    sf3d_error_t raster_tables(char*& tables, size_t* off, int count, const size_t* bytes, const void* const* src, const size_t* srcBytes);
+    void raster_release(std::initializer_list<void*> blocks);
     struct Impl;
     Impl* impl_ = nullptr;
     Ctrl mirror_{};

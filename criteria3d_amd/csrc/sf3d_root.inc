@@ -224,29 +224,18 @@ enum { ROOT_T_UNITS = 0, ROOT_T_SOIL_DEPTH, ROOT_T_LAYER_DEPTH, ROOT_T_LAYER_THI
 sf3d_error_t DeviceSolver::root_free()
 {
     if (!impl_) return SF3D_OK;
-    RootCache& K = impl_->root;
-    if (K.cells || K.tables || K.out) {
-        if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
-        if (K.cells) (void)hipFree(K.cells);
-        if (K.tables) (void)hipFree(K.tables);
-        if (K.out) (void)hipFree(K.out);
-    }
-    K = RootCache();
+    raster_release({impl_->root.cells, impl_->root.tables, impl_->root.out});
+    impl_->root = RootCache();
     return SF3D_OK;
-}
-
-static void* root_cell_map(const RootCache& K, int map)
-{
-    const size_t n = K.nCells;
-    return (map < 2) ? K.cells + (size_t)map * n * 8 : K.cells + 16 * n + (size_t)(map - 2) * n * 4;
 }
 
 static void root_view(RootView& v, const RootCache& K, float flag)
 {
-    v.length = (double*)root_cell_map(K, ROOT_MAP_LENGTH); v.depth = (double*)root_cell_map(K, ROOT_MAP_DEPTH);
-    v.dem = (const float*)root_cell_map(K, ROOT_MAP_DEM); v.dd = (const float*)root_cell_map(K, ROOT_MAP_DD);
-    v.cropIndex = (const int32_t*)root_cell_map(K, ROOT_MAP_CROP); v.soilIndex = (const int32_t*)root_cell_map(K, ROOT_MAP_SOIL);
-    v.first = (int32_t*)root_cell_map(K, ROOT_MAP_FIRST); v.last = (int32_t*)root_cell_map(K, ROOT_MAP_LAST); v.key = (int32_t*)root_cell_map(K, ROOT_MAP_KEY);
+    const auto map = [&K](int k) { return raster_cell_map(K.cells, K.nCells, k); };
+    v.length = (double*)map(ROOT_MAP_LENGTH); v.depth = (double*)map(ROOT_MAP_DEPTH);
+    v.dem = (const float*)map(ROOT_MAP_DEM); v.dd = (const float*)map(ROOT_MAP_DD);
+    v.cropIndex = (const int32_t*)map(ROOT_MAP_CROP); v.soilIndex = (const int32_t*)map(ROOT_MAP_SOIL);
+    v.first = (int32_t*)map(ROOT_MAP_FIRST); v.last = (int32_t*)map(ROOT_MAP_LAST); v.key = (int32_t*)map(ROOT_MAP_KEY);
     v.units = (const RootUnitDev*)(K.tables + K.off[ROOT_T_UNITS]);
     v.soilDepth = (const double*)(K.tables + K.off[ROOT_T_SOIL_DEPTH]);
     v.soilMaxN = (const int32_t*)(K.tables + K.off[ROOT_T_SOIL_MAXN]);
@@ -276,20 +265,17 @@ sf3d_error_t DeviceSolver::root_alloc(const RootSetup& S)
                                    S.rowN, nullptr};
     const size_t srcBytes[ROOT_T_END] = {S.nUnits * sizeof(RootUnitDev), bytes[1], bytes[2], bytes[3], bytes[4], lunetteCount * sizeof(double), 0, bytes[7], bytes[8],
                                          bytes[9], bytes[10], bytes[11], 0};
-    size_t total = 0;
-    for (int k = 0; k < ROOT_T_END; ++k) { K.off[k] = total; total += (bytes[k] + 7) & ~(size_t)7; }
     RASTER_TRY(hipMalloc((void**)&K.cells, (size_t)ROOT_MAP_WORDS * n * 4));
-    RASTER_TRY(hipMalloc((void**)&K.tables, total ? total : 8));
     K.nCells = S.nCells; K.nUnits = S.nUnits; K.nSoils = S.nSoils; K.nRows = S.nRows; K.nrLayers = S.nrLayers; K.lunetteMax = S.lunetteMax;
-    for (int k = 0; k < ROOT_T_END; ++k)
-        if (src[k] && srcBytes[k]) RASTER_TRY(hipMemcpyAsync(K.tables + K.off[k], src[k], srcBytes[k], hipMemcpyHostToDevice, I.stream));
-    RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
-    RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
-    RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    e = raster_tables(K.tables, K.off, ROOT_T_END, bytes, src, srcBytes);
+    if (e != SF3D_OK) return e;
+    RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, ROOT_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, ROOT_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, ROOT_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
     /* before the first compute every output holds the flag: the degree days are the flag everywhere and k_root_cell runs once below */
     {
         const std::vector<float> empty(n, S.flag);
-        RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DD), empty.data(), n * 4, hipMemcpyHostToDevice, I.stream));
+        RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, ROOT_MAP_DD), empty.data(), n * 4, hipMemcpyHostToDevice, I.stream));
         RASTER_TRY(hipStreamSynchronize(I.stream));
     }
     if (rows) {
@@ -316,20 +302,18 @@ sf3d_error_t DeviceSolver::root_alloc(const RootSetup& S)
     return e;
 }
 
-bool DeviceSolver::root_crop_degree_days_ready(uint32_t nCells) const { return impl_ && impl_->crop.base && impl_->crop.nCells == nCells; }
-
 sf3d_error_t DeviceSolver::root_compute(const float* dd, float flag, const uint8_t* mine)
 {
     Impl& I = *impl_;
     RootCache& K = I.root;
     const size_t n = K.nCells;
     RASTER_TRY(hipSetDevice(I.device));
-    if (dd) RASTER_TRY(hipMemcpyAsync(root_cell_map(K, ROOT_MAP_DD), dd, n * sizeof(float), hipMemcpyHostToDevice, I.stream));
+    if (dd) RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, ROOT_MAP_DD), dd, n * sizeof(float), hipMemcpyHostToDevice, I.stream));
     RootView v{};
     sf3d_error_t e = raster_mask(mine, n, &v.mine);
     if (e != SF3D_OK) return e;
     root_view(v, K, flag);
-    if (!dd) v.dd = I.crop.base + (size_t)(CROP_MAP_STATE + 0) * n;             /* degreeDaysMap of the crop block */
+    if (!dd) v.dd = crop_degree_days(I.crop);                                   /* degreeDaysMap of the crop block */
     e = raster_launch(k_root_cell, n, v, K.lastMs[0]);
     if (e == SF3D_OK) K.computed = true;
     return e;
@@ -338,7 +322,7 @@ sf3d_error_t DeviceSolver::root_compute(const float* dd, float flag, const uint8
 sf3d_error_t DeviceSolver::root_download(int map, void* dst)
 {
     const RootCache& K = impl_->root;
-    return raster_download(dst, root_cell_map(K, map), (size_t)K.nCells * (map < 2 ? 8 : 4));
+    return raster_download(dst, raster_cell_map(K.cells, K.nCells, map), (size_t)K.nCells * (map < 2 ? 8 : 4));
 }
 
 /* layer < 0: every layer, [layer][cell] */
@@ -355,6 +339,12 @@ sf3d_error_t DeviceSolver::root_density(int layer, double* dst, float flag)
     v.layerCount = layer < 0 ? K.nrLayers : 1;
     const sf3d_error_t e = raster_launch(k_root_gather, n, v, K.lastMs[2]);
     return e != SF3D_OK ? e : raster_download(dst, K.out, (size_t)v.layerCount * n * sizeof(double));
+}
+
+/* what the sink block asks before it reads this block's maps and its density table */
+bool DeviceSolver::root_computed(uint32_t nCells, uint32_t nrLayers) const
+{
+    return impl_ && impl_->root.cells && impl_->root.computed && impl_->root.nCells == nCells && impl_->root.nrLayers == nrLayers;
 }
 
 /* which: 0 k_root_cell, 1 k_root_table, 2 k_root_gather */

@@ -49,7 +49,7 @@ sf3d_error_t sf3d_root_initialize(uint32_t nrRows, uint32_t nrCols, const float*
                                   const double* layerThickness, const int32_t* cropIndex, const int32_t* soilIndex, uint32_t nUnits,
                                   const sf3d_root_unit_t* units, uint32_t nSoils, const sf3d_root_soil_t* soils)
 {
-    if (nrRows == 0 || nrCols == 0 || !dem || !cropIndex || !soilIndex || (uint64_t)nrRows * nrCols > 0x7fffffffull) return SF3D_PARAMETER_ERROR;
+    if (!rasterShapeOk(nrRows, nrCols, dem) || !cropIndex || !soilIndex) return SF3D_PARAMETER_ERROR;
     if (nrLayers == 0 || nrLayers > SF3D_ROOT_MAX_LAYERS || !layerDepth || !layerThickness) return SF3D_PARAMETER_ERROR;
     if (nUnits > SF3D_CROP_MAX_UNITS || (nUnits > 0 && !units) || nSoils > SF3D_ROOT_MAX_SOILS || (nSoils > 0 && !soils)) return SF3D_PARAMETER_ERROR;
     for (uint32_t s = 0; s < nSoils; ++s)
@@ -117,7 +117,7 @@ sf3d_error_t sf3d_root_compute(uint32_t nrCells, const float* degreeDays)
 {
     if (!RT.on) return SF3D_MEMORY_ERROR;
     if (nrCells != RT.nRows * RT.nCols) return SF3D_PARAMETER_ERROR;
-    if (!degreeDays && !(CR.on && CR.nRows == RT.nRows && CR.nCols == RT.nCols && dev().root_crop_degree_days_ready(nrCells))) return SF3D_PARAMETER_ERROR;
+    if (!degreeDays && !(rasterFeeds(CR, RT.nRows, RT.nCols) && dev().crop_allocated(nrCells))) return SF3D_PARAMETER_ERROR;
     return rasterFail("root compute", dev().root_compute(degreeDays, RT.flag, mapsOwnedCells(nrCells)));
 }
 

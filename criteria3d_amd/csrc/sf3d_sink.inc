@@ -196,21 +196,9 @@ enum { SINK_T_UNITS = 0, SINK_T_HORIZON_VALUES, SINK_T_THICK, SINK_T_EVAP_COEFF,
 sf3d_error_t DeviceSolver::sink_free()
 {
     if (!impl_) return SF3D_OK;
-    SinkCache& K = impl_->sink;
-    if (K.cells || K.tables || K.nodes) {
-        if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
-        if (K.cells) (void)hipFree(K.cells);
-        if (K.tables) (void)hipFree(K.tables);
-        if (K.nodes) (void)hipFree(K.nodes);
-    }
-    K = SinkCache();
+    raster_release({impl_->sink.cells, impl_->sink.tables, impl_->sink.nodes});
+    impl_->sink = SinkCache();
     return SF3D_OK;
-}
-
-static void* sink_cell_map(const SinkCache& K, int map)
-{
-    const size_t n = K.nCells;
-    return (map < 2) ? K.cells + (size_t)map * n * 8 : K.cells + 16 * n + (size_t)(map - 2) * n * 4;
 }
 
 sf3d_error_t DeviceSolver::sink_alloc(const SinkSetup& S)
@@ -225,16 +213,13 @@ sf3d_error_t DeviceSolver::sink_alloc(const SinkSetup& S)
                                       nl * sizeof(double), nl * sizeof(double), nl * sizeof(double), (size_t)S.nSoils * nl * sizeof(int32_t)};
     const void* src[SINK_T_END] = {S.units, S.horizonValues, S.thick, S.evapCoeff, S.layerEvapCoeff, S.horizon};
     const size_t srcBytes[SINK_T_END] = {S.nUnits * sizeof(SinkUnitDev), bytes[1], bytes[2], bytes[3], bytes[4], bytes[5]};
-    size_t total = 0;
-    for (int k = 0; k < SINK_T_END; ++k) { K.off[k] = total; total += (bytes[k] + 7) & ~(size_t)7; }
     RASTER_TRY(hipMalloc((void**)&K.cells, (size_t)SINK_MAP_WORDS * n * 4));
-    RASTER_TRY(hipMalloc((void**)&K.tables, total ? total : 8));
     K.nCells = S.nCells; K.nrLayers = S.nrLayers; K.nUnits = S.nUnits; K.nSoils = S.nSoils; K.lastEvapLayer = S.lastEvapLayer; K.area = S.area; K.flag = S.flag;
-    for (int k = 0; k < SINK_T_END; ++k)
-        if (src[k] && srcBytes[k]) RASTER_TRY(hipMemcpyAsync(K.tables + K.off[k], src[k], srcBytes[k], hipMemcpyHostToDevice, I.stream));
-    RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
-    RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
-    RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    e = raster_tables(K.tables, K.off, SINK_T_END, bytes, src, srcBytes);
+    if (e != SF3D_OK) return e;
+    RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, SINK_MAP_DEM), S.dem, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, SINK_MAP_CROP), S.cropIndex, n * 4, hipMemcpyHostToDevice, I.stream));
+    RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, SINK_MAP_SOIL), S.soilIndex, n * 4, hipMemcpyHostToDevice, I.stream));
     {   /* before the first hour both actual maps hold the flag */
         const std::vector<double> empty(2 * n, (double)S.flag);
         RASTER_TRY(hipMemcpyAsync(K.cells, empty.data(), 2 * n * 8, hipMemcpyHostToDevice, I.stream));
@@ -245,29 +230,15 @@ sf3d_error_t DeviceSolver::sink_alloc(const SinkSetup& S)
 
 bool DeviceSolver::sink_allocated() const { return impl_ && impl_->sink.cells; }
 bool DeviceSolver::sink_computed() const { return impl_ && impl_->sink.nodes && impl_->sink.computed; }
-bool DeviceSolver::sink_root_ready(uint32_t nCells, uint32_t nrLayers) const
-{
-    return impl_ && impl_->root.cells && impl_->root.computed && impl_->root.nCells == nCells && impl_->root.nrLayers == nrLayers;
-}
-bool DeviceSolver::sink_snow_ready(uint32_t nCells) const { return crop_snow_inputs_ready(nCells); }
 
 sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const MapsInput& in, const SinkCall& call)
 {
-    sf3d_error_t e = sync_to_device(m, p);
+    sf3d_error_t e = raster_columns(m, p, in);
     if (e != SF3D_OK) return e;
-    if (world_ > 1 && !connected_) { snprintf(err_, sizeof(err_), "multi-GPU model used before sf3d_dist_connect / sf3d_dist_finalize"); return SF3D_SOLVER_ERROR; }
     Impl& I = *impl_;
     SinkCache& K = I.sink;
-    MapsCache& C = I.maps;
     const RootCache& R = I.root;
-    const size_t n = K.nCells, colN = (size_t)in.nCells * in.nLayers;
-    if (C.colVer != in.colVer) {                                           /* the column table of the output maps, uploaded as output_map does */
-        RASTER_TRY(maps_reserve(C.col, C.colCap, colN));
-        RASTER_TRY(maps_reserve(C.thick, C.thickCap, in.nLayers));
-        RASTER_TRY(hipMemcpyAsync(C.col, in.col, colN * 4, hipMemcpyHostToDevice, I.stream));
-        RASTER_TRY(hipMemcpyAsync(C.thick, in.thick, (size_t)in.nLayers * 8, hipMemcpyHostToDevice, I.stream));
-        C.colVer = in.colVer;
-    }
+    const size_t n = K.nCells;
     if (!K.nodes || K.nodesN != I.v.N) {
         if (K.nodes) { (void)hipFree(K.nodes); K.nodes = nullptr; }
         K.nodesN = 0; K.computed = false;
@@ -283,17 +254,17 @@ sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const Ma
     }
     const float* maps[4] = {call.et0, call.lai, call.dd, call.liquid};
     for (int k = 0; k < 4; ++k)
-        if (maps[k]) RASTER_TRY(hipMemcpyAsync(sink_cell_map(K, SINK_MAP_ET0 + k), maps[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
+        if (maps[k]) RASTER_TRY(hipMemcpyAsync(raster_cell_map(K.cells, n, SINK_MAP_ET0 + k), maps[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
     SinkView v{};
     e = raster_mask(call.mine, n, &v.mine);
     if (e != SF3D_OK) return e;
-    v.col = C.col;
+    v.col = I.maps.col;
     v.H = I.v.X[mirror_.cur]; v.Se = I.v.Se; v.z = I.v.z; v.cls = I.v.cls; v.soils = I.v.soils;
     v.cells = K.cells;
-    v.et0 = call.et0 ? (const float*)sink_cell_map(K, SINK_MAP_ET0) : I.crop.base + (size_t)CROP_MAP_ET0 * n;
-    v.lai = call.lai ? (const float*)sink_cell_map(K, SINK_MAP_LAI) : I.crop.base + (size_t)(CROP_MAP_STATE + 1) * n;
-    v.dd = call.dd ? (const float*)sink_cell_map(K, SINK_MAP_DD) : I.crop.base + (size_t)(CROP_MAP_STATE + 0) * n;
-    v.liquid = call.liquid ? (const float*)sink_cell_map(K, SINK_MAP_LIQUID) : I.snow.base + (size_t)(SNOW_MAP_OUT + 5) * n;
+    v.et0 = call.et0 ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_ET0) : crop_et0(I.crop);
+    v.lai = call.lai ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_LAI) : crop_lai(I.crop);
+    v.dd = call.dd ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_DD) : crop_degree_days(I.crop);
+    v.liquid = call.liquid ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_LIQUID) : snow_liquid_water(I.snow);
     v.rootCells = R.cells;
     v.rootTable = (const double*)(R.tables + R.off[ROOT_T_TABLE]); v.rootRows = R.nRows;
     v.units = (const SinkUnitDev*)(K.tables + K.off[SINK_T_UNITS]);
@@ -319,7 +290,7 @@ sf3d_error_t DeviceSolver::sink_download_nodes(double* dst, uint32_t count)
 sf3d_error_t DeviceSolver::sink_download_cells(int map, double* dst)
 {
     const SinkCache& K = impl_->sink;
-    return raster_download(dst, sink_cell_map(K, map), (size_t)K.nCells * sizeof(double));
+    return raster_download(dst, raster_cell_map(K.cells, K.nCells, map), (size_t)K.nCells * sizeof(double));
 }
 
 double DeviceSolver::sink_kernel_ms() const { return impl_ ? impl_->sink.lastMs : 0.; }

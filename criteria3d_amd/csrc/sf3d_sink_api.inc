@@ -38,27 +38,6 @@ int sinkLayerIndex(uint32_t nrLayers, const double* layerDepth, const double* la
     return -9999;
 }
 
-/* the column table for the device, as sf3d_compute_output_map builds it */
-void sinkColumns(MapsInput& in)
-{
-    in.nCells = MP.nCells; in.nLayers = MP.nLayers; in.thick = MP.thick.data();
-    if (!LM.on) { in.col = MP.col.data(); in.colVer = MP.colVer; return; }
-    if (MP.colDevVer != MP.colVer || MP.colDevGen != LM.gen) {
-        const size_t nc = MP.nCells;
-        MP.colDev.assign(MP.col.size(), -1);
-        for (size_t c = 0; c < nc; ++c) {
-            if (!mapsOwnsCell(c)) continue;
-            for (uint32_t l = 0; l < MP.nLayers; ++l) {
-                const int32_t g = MP.col[l * nc + c];
-                if (g >= 0) MP.colDev[l * nc + c] = LM.g2l[g];
-            }
-        }
-        MP.colDevVer = MP.colVer; MP.colDevGen = LM.gen;
-        MP.colDevVerDev = ++mapsVersion;
-    }
-    in.col = MP.colDev.data(); in.colVer = MP.colDevVerDev;
-}
-
 /* the node sinks of the last hour from the device into SK.nodes */
 sf3d_error_t sinkFetch()
 {
@@ -76,7 +55,7 @@ sf3d_error_t sf3d_sink_initialize(uint32_t nrRows, uint32_t nrCols, const float*
                                   const double* layerDepth, const double* layerThickness, double computationSoilDepth, const int32_t* cropIndex,
                                   const int32_t* soilIndex, uint32_t nUnits, const sf3d_sink_unit_t* units, uint32_t nSoils, const sf3d_sink_soil_t* soils)
 {
-    if (nrRows == 0 || nrCols == 0 || !dem || !cropIndex || !soilIndex || (uint64_t)nrRows * nrCols > 0x7fffffffull) return SF3D_PARAMETER_ERROR;
+    if (!rasterShapeOk(nrRows, nrCols, dem) || !cropIndex || !soilIndex) return SF3D_PARAMETER_ERROR;
     if (nrLayers == 0 || nrLayers > SF3D_ROOT_MAX_LAYERS || !layerDepth || !layerThickness || !(cellSize > 0)) return SF3D_PARAMETER_ERROR;
     if (nUnits > SF3D_CROP_MAX_UNITS || (nUnits > 0 && !units) || nSoils > SF3D_ROOT_MAX_SOILS || (nSoils > 0 && !soils)) return SF3D_PARAMETER_ERROR;
     for (uint32_t s = 0; s < nSoils; ++s)
@@ -143,9 +122,9 @@ sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const fl
     NEED_INIT_E;
     if (!MP.set || MP.nCells != nrCells || MP.nLayers != SK.nrLayers) return SF3D_TOPOGRAPHY_ERROR;
     if (MP.maxNode >= 0 && (uint32_t)MP.maxNode >= M.N) return SF3D_TOPOGRAPHY_ERROR;
-    if ((!et0 || !lai || !degreeDays) && !(CR.on && CR.nRows == SK.nRows && CR.nCols == SK.nCols && dev().root_crop_degree_days_ready(nrCells))) return SF3D_PARAMETER_ERROR;
-    if (!liquidWater && !(SN.on && SN.nRows == SK.nRows && SN.nCols == SK.nCols && dev().sink_snow_ready(nrCells))) return SF3D_PARAMETER_ERROR;
-    if (!(RT.on && RT.nRows == SK.nRows && RT.nCols == SK.nCols && dev().sink_root_ready(nrCells, SK.nrLayers))) return SF3D_PARAMETER_ERROR;
+    if ((!et0 || !lai || !degreeDays) && !(rasterFeeds(CR, SK.nRows, SK.nCols) && dev().crop_allocated(nrCells))) return SF3D_PARAMETER_ERROR;
+    if (!liquidWater && !(rasterFeeds(SN, SK.nRows, SK.nCols) && dev().snow_hour_done(nrCells))) return SF3D_PARAMETER_ERROR;
+    if (!(rasterFeeds(RT, SK.nRows, SK.nCols) && dev().root_computed(nrCells, SK.nrLayers))) return SF3D_PARAMETER_ERROR;
     if (!SK.uploaded || !dev().sink_allocated()) {
         SinkSetup S{};
         S.nCells = nrCells; S.nrLayers = SK.nrLayers; S.nUnits = SK.nUnits; S.nSoils = SK.nSoils; S.lastEvapLayer = SK.lastEvapLayer;
@@ -158,7 +137,7 @@ sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const fl
     }
     HostModel& D = deviceModel();
     MapsInput in;
-    sinkColumns(in);
+    mapsDeviceInput(in);
     SinkCall call{et0, lai, degreeDays, liquidWater, mapsOwnedCells(nrCells)};
     return rasterFail("sink compute hour", dev().sink_hour(D, P, in, call));
 }

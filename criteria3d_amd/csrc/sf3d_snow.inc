@@ -260,12 +260,8 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_snow_hour(SnowView v)
 sf3d_error_t DeviceSolver::snow_free()
 {
     if (!impl_) return SF3D_OK;
-    SnowCache& S = impl_->snow;
-    if (S.base) {
-        if (impl_->stream) (void)hipStreamSynchronize(impl_->stream);
-        (void)hipFree(S.base);
-    }
-    S = SnowCache();
+    raster_release({impl_->snow.base});
+    impl_->snow = SnowCache();
     return SF3D_OK;
 }
 
@@ -312,5 +308,19 @@ sf3d_error_t DeviceSolver::snow_hour(const float* const in[8], const SnowParamsD
     if (el == SF3D_OK) S.hourDone = true;                  /* the input maps of this hour stay in the block (sf3d_crop_compute_hour may read them) */
     return el;
 }
+
+/* ---- what the other blocks read from this one, once an hour has run on their raster */
+enum { SNOW_OUT_LIQUID_WATER = 5 };                        /* SF3D_SNOW_OUT_LIQUID_WATER of include/sf3d_snow.h */
+
+bool DeviceSolver::snow_hour_done(uint32_t nCells) const { return impl_ && impl_->snow.base && impl_->snow.hourDone && impl_->snow.nCells == nCells; }
+
+/* input k of k_et0_hour among the maps the last hour uploaded: air temperature, relative humidity, wind, global radiation, transmissivity */
+static const float* snow_hour_input(const SnowCache& S, int k)
+{
+    static const int snowInput[5] = {0, 2, 3, 4, 6};
+    return S.base + (size_t)(SNOW_MAP_IN + snowInput[k]) * S.nCells;
+}
+
+static const float* snow_liquid_water(const SnowCache& S) { return S.base + (size_t)(SNOW_MAP_OUT + SNOW_OUT_LIQUID_WATER) * S.nCells; }
 
 double DeviceSolver::snow_kernel_ms() const { return impl_ ? impl_->snow.lastMs : 0.; }

@@ -54,7 +54,7 @@ sf3d_error_t sf3d_snow_default_parameters(sf3d_snow_parameters_t* parameters)
 
 sf3d_error_t sf3d_snow_initialize(uint32_t nrRows, uint32_t nrCols, const float* dem, float flag, const sf3d_snow_parameters_t* parameters)
 {
-    if (nrRows == 0 || nrCols == 0 || !dem || (uint64_t)nrRows * nrCols > 0x7fffffffull) return SF3D_PARAMETER_ERROR;
+    if (!rasterShapeOk(nrRows, nrCols, dem)) return SF3D_PARAMETER_ERROR;
     const uint32_t n = nrRows * nrCols;
     snowClear();
     sf3d_error_t e = dev().snow_alloc(n);

@@ -14,12 +14,12 @@ Two halves:
 The reference loops restated here are Qt application code (not buildable here) and are not pinned against compiled reference code."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import capi
+from .capi import pf32, pi32          # noqa: F401 (tests take maps.pi32)
 from .project3d import DEG_TO_RAD, EPSILON, GRAVITY, NODATA, soil_layer_index
 
 # criteria3DVariable (agrolib/meteo/meteo.h:110-114)
@@ -32,8 +32,6 @@ LAYER_VARIABLES = (VOLUMETRIC_WATER_CONTENT, WATER_TOTAL_POTENTIAL, WATER_MATRIC
 COLUMN_VARIABLES = (MINIMUM_FACTOR_OF_SAFETY, AVG_DEGREE_OF_SATURATION)
 FIELD_CAPACITY = 3.0                     # project3D.cpp:2793 (TODO of the reference: not read from the horizon)
 
-pf32 = C.POINTER(C.c_float)
-pi32 = C.POINTER(C.c_int32)
 # name -> (restype, argtypes): every symbol include/sf3d_maps.h declares
 SIGNATURES = {
     "sf3d_set_output_columns": (capi.u8, [capi.u32, capi.u32, pi32, capi.pd]),
@@ -58,13 +56,17 @@ def columns(model) -> tuple[np.ndarray, np.ndarray]:
     return np.ascontiguousarray(idx.reshape(nz, -1), dtype=np.int32), np.array([0.0] + list(model.meta["layers"]), dtype=np.float64)
 
 
+def set_columns(sf: capi.SF3D, col, thick) -> None:
+    """sf3d_set_output_columns: col[layer] = the node of every cell of the raster (any shape per layer), -1 where there is none"""
+    bind(sf)
+    col, thick = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(thick, np.float64)
+    sf.check(sf.lib.sf3d_set_output_columns(col[0].size, col.shape[0], col.ctypes.data_as(pi32), thick.ctypes.data_as(capi.pd)), "set_output_columns")
+
+
 def set_output(sf: capi.SF3D, model, increase_slope: bool = False) -> None:
     """the three setters for a model of project3d.project_model: column table, geotechnics of every (soil, horizon) of the soil list,
     cell slopes"""
-    bind(sf)
-    col, thick = columns(model)
-    nz, nc = col.shape
-    sf.check(sf.lib.sf3d_set_output_columns(nc, nz, col.ctypes.data_as(pi32), thick.ctypes.data_as(capi.pd)), "set_output_columns")
+    set_columns(sf, *columns(model))
     for si, hi, coh, fri, bd in model.meta["geotechnics"]:
         sf.check(sf.lib.sf3d_set_horizon_geotechnics(si, hi, coh, fri, bd), f"set_horizon_geotechnics({si}, {hi})")
     set_slopes(sf, model, increase_slope)

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi, raster
+from .capi import pf32, pf64
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -49,8 +50,6 @@ class Settings(C.Structure):
                [("nProxies", C.c_int32), ("reserved", C.c_int32), ("proxy", Proxy * MAX_PROXIES)]
 
 
-pf32 = C.POINTER(C.c_float)
-pf64 = C.POINTER(C.c_double)
 ppf32 = C.POINTER(pf32)
 psettings = C.POINTER(Settings)
 # name -> (restype, argtypes): every symbol include/sf3d_meteo.h declares

@@ -1,7 +1,8 @@
-"""What the Python bindings of the raster blocks (snow.py, crop.py, root.py) share: float maps checked against the raster's shape, names
-of state maps, and the folder of ESRI float grids a block's state is saved to."""
+"""What the Python bindings of the raster blocks (snow.py, crop.py, root.py, meteo.py, sinks.py) share: maps checked against the raster's
+shape, names of state maps, and the folder of ESRI float grids a block's state is saved to."""
 from __future__ import annotations
 
+from functools import partial
 from pathlib import Path
 
 import numpy as np
@@ -9,12 +10,16 @@ import numpy as np
 from . import esri
 
 
-def f32(a, shape=None, what: str = ""):
-    """`a` as a contiguous float32 array; ValueError when it is not of the `what` raster's shape"""
-    a = np.ascontiguousarray(a, dtype=np.float32)
+def _map(a, shape=None, what: str = "", dtype=np.float32):
+    """`a` as a contiguous array of `dtype`; ValueError when it is not of the `what` raster's shape"""
+    a = np.ascontiguousarray(a, dtype=dtype)
     if shape is not None and a.shape != tuple(shape):
         raise ValueError(f"map of shape {a.shape}, the {what} raster is {tuple(shape)}")
     return a
+
+
+f32 = partial(_map, dtype=np.float32)          # a float map
+i32 = partial(_map, dtype=np.int32)            # an index map
 
 
 def index(which, names) -> int:

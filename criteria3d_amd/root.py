@@ -18,6 +18,7 @@ import math
 import numpy as np
 
 from . import capi, raster
+from .capi import pf32, pf64, pi32
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -47,9 +48,6 @@ class Soil(C.Structure):
                 ("lowerDepth", C.c_double * MAX_HORIZONS), ("soilFraction", C.c_double * MAX_HORIZONS)]
 
 
-pf32 = C.POINTER(C.c_float)
-pf64 = C.POINTER(C.c_double)
-pi32 = C.POINTER(C.c_int32)
 punit = C.POINTER(Unit)
 psoil = C.POINTER(Soil)
 # name -> (restype, argtypes): every symbol include/sf3d_root.h declares
@@ -102,10 +100,7 @@ def initialize(sf: capi.SF3D, dem, crop_index, soil_index, units, soils, layer_d
     UNIT_FIELDS), the soils (project3d.soil_root_table) and the layer grid (layer 0: the surface); builds the density table"""
     bind(sf)
     dem = np.ascontiguousarray(dem, np.float32)
-    ci = np.ascontiguousarray(crop_index, np.int32)
-    si = np.ascontiguousarray(soil_index, np.int32)
-    if ci.shape != dem.shape or si.shape != dem.shape:
-        raise ValueError(f"index maps of shape {ci.shape} / {si.shape}, the DEM is {dem.shape}")
+    ci, si = raster.i32(crop_index, dem.shape, "root"), raster.i32(soil_index, dem.shape, "root")
     ld = np.ascontiguousarray(layer_depth, np.float64)
     lt = np.ascontiguousarray(layer_thickness, np.float64)
     if ld.shape != lt.shape or ld.ndim != 1:

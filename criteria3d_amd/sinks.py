@@ -18,7 +18,8 @@ import math
 
 import numpy as np
 
-from . import capi, root
+from . import capi, maps, raster, root
+from .capi import pf32, pf64, pi32
 
 NODATA = -9999
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -41,9 +42,6 @@ class Soil(C.Structure):
     _fields_ = [("nrHorizons", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_double * MAX_HORIZONS) for n in HORIZON_FIELDS]
 
 
-pf32 = C.POINTER(C.c_float)
-pf64 = C.POINTER(C.c_double)
-pi32 = C.POINTER(C.c_int32)
 punit = C.POINTER(Unit)
 psoil = C.POINTER(Soil)
 # name -> (restype, argtypes): every symbol include/sf3d_sink.h declares
@@ -57,13 +55,10 @@ SIGNATURES = {
     "sf3d_sink_kernel_ms": (capi.f64, []),
     "sf3d_sink_clean": (capi.u8, []),
 }
-# sf3d_set_output_columns of include/sf3d_maps.h: the column table the sink call reads
-COLUMN_SIGNATURE = {"sf3d_set_output_columns": (capi.u8, [capi.u32, capi.u32, pi32, pf64])}
 
 
 def bind(sf: capi.SF3D) -> capi.SF3D:
     """attach the signatures of include/sf3d_sink.h to a loaded product library (AttributeError if a symbol is missing)"""
-    capi.bind_signatures(sf, COLUMN_SIGNATURE)
     return capi.bind_signatures(sf, SIGNATURES)
 
 
@@ -91,18 +86,11 @@ def soil_array(soils):
     return arr
 
 
-def _map(a, shape, dtype, what):
-    a = np.ascontiguousarray(a, dtype=dtype)
-    if a.shape != tuple(shape):
-        raise ValueError(f"{what} of shape {a.shape}, the raster is {tuple(shape)}")
-    return a
-
-
 def initialize(sf: capi.SF3D, dem, cell_size, crop_index, soil_index, units, soils, layer_depth, layer_thickness, computation_depth, flag: float = -9999.0):
     """sf3d_sink_initialize: needs no device (the first hour uploads the tables); keeps the raster's shape on `sf`"""
     bind(sf)
     dem = np.ascontiguousarray(dem, np.float32)
-    ci, si = _map(crop_index, dem.shape, np.int32, "crop index"), _map(soil_index, dem.shape, np.int32, "soil index")
+    ci, si = raster.i32(crop_index, dem.shape, "sink"), raster.i32(soil_index, dem.shape, "sink")
     ld, lt = np.ascontiguousarray(layer_depth, np.float64), np.ascontiguousarray(layer_thickness, np.float64)
     ua, sa = unit_array(units), soil_array(soils)
     sf.check(sf.lib.sf3d_sink_initialize(dem.shape[0], dem.shape[1], dem.ctypes.data_as(pf32), float(flag), float(cell_size), len(ld), ld.ctypes.data_as(pf64),
@@ -112,11 +100,8 @@ def initialize(sf: capi.SF3D, dem, cell_size, crop_index, soil_index, units, soi
 
 
 def set_columns(sf: capi.SF3D, columns, layer_thickness):
-    """sf3d_set_output_columns: columns[layer][row][col] = node, -1 where there is none"""
-    bind(sf)
-    col = np.ascontiguousarray(columns, np.int32)
-    lt = np.ascontiguousarray(layer_thickness, np.float64)
-    sf.check(sf.lib.sf3d_set_output_columns(col[0].size, col.shape[0], col.ctypes.data_as(pi32), lt.ctypes.data_as(pf64)), "set_output_columns")
+    """sf3d_set_output_columns (the column table the sink call reads): columns[layer][row][col] = node, -1 where there is none"""
+    maps.set_columns(sf, columns, layer_thickness)
 
 
 def get_tables(sf: capi.SF3D):
@@ -131,9 +116,8 @@ def get_tables(sf: capi.SF3D):
 def compute_hour(sf: capi.SF3D, et0=None, lai=None, degree_days=None, liquid_water=None):
     """sf3d_sink_compute_hour: a map left None is read from the crop block (ET0, LAI, degree days) / the snow block (liquid water)"""
     shape = sf._sink_shape
-    maps = [None if m is None else _map(m, shape, np.float32, what) for m, what in
-            ((et0, "ET0"), (lai, "LAI"), (degree_days, "degree days"), (liquid_water, "liquid water"))]
-    sf.check(sf.lib.sf3d_sink_compute_hour(shape[0] * shape[1], *[None if m is None else m.ctypes.data_as(pf32) for m in maps]), "sink_compute_hour")
+    given = [None if m is None else raster.f32(m, shape, "sink") for m in (et0, lai, degree_days, liquid_water)]
+    sf.check(sf.lib.sf3d_sink_compute_hour(shape[0] * shape[1], *[None if m is None else m.ctypes.data_as(pf32) for m in given]), "sink_compute_hour")
 
 
 def get_node_sinks(sf: capi.SF3D, n_nodes: int) -> np.ndarray:

@@ -21,6 +21,7 @@ from pathlib import Path
 import numpy as np
 
 from . import capi, raster
+from .capi import pf32
 
 NODATA = -9999.0
 EPSILON = 0.00001                               # commonConstants.h:252
@@ -46,7 +47,6 @@ class Parameters(C.Structure):
     _fields_ = [(n, C.c_double) for n in PARAMETER_NAMES]
 
 
-pf32 = C.POINTER(C.c_float)
 pparams = C.POINTER(Parameters)
 # name -> (restype, argtypes): every symbol include/sf3d_snow.h declares
 SIGNATURES = {

@@ -33,8 +33,7 @@ def build(m, columns=True, **kw):
     cm.build(sf, m, threads=1, dist=(dist.get_rank(), dist.get_world_size(), allgather), **kw)
     maps.bind(sf)
     if columns:
-        col, thick = maps.columns(m)
-        sf.check(sf.lib.sf3d_set_output_columns(col.shape[1], col.shape[0], col.ctypes.data_as(maps.pi32), thick.ctypes.data_as(capi.pd)), "set_output_columns")
+        maps.set_columns(sf, *maps.columns(m))
     return sf
 
 

@@ -13,12 +13,9 @@ import pytest
 from criteria3d_amd import build, capi, crop, esri, project3d as p3
 from tests import crop_cases as cc
 from tests import tolerances
+from tests.raster_helpers import bits as _bits
 
 ROOT = Path(__file__).resolve().parent.parent
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

@@ -14,23 +14,15 @@ import pytest
 from criteria3d_amd import capi, catchment as cm, crop, snow
 from tests import crop_cases as cc
 from tests.scenarios import ravone_project_model
+from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
 def pin():
     return cc.load_pin()
-
-
-def _need_glibc_set(product):
-    if product.lib.sf3d_libm_set() != 1:
-        pytest.skip("this build evaluates the 0.50-ulp routines, not the C library's bits (-DSF3D_LIBM_GLIBC=0): bit identity with the compiled reference is not its contract")
 
 
 def _checker(pin, what):

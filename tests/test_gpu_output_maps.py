@@ -11,6 +11,7 @@ import pytest
 
 from criteria3d_amd import capi, catchment as cm, maps
 from tests.scenarios import ravone_project_model
+from tests.raster_helpers import bits as _bits
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -41,10 +42,6 @@ def _device(sf, model, increase_slope=False):
     out = {var: maps.output_maps(sf, model, var, flag=FLAG) for var in maps.LAYER_VARIABLES + maps.COLUMN_VARIABLES}
     out[maps.FACTOR_OF_SAFETY] = maps.output_maps(sf, model, maps.FACTOR_OF_SAFETY, flag=FLAG)
     return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

@@ -12,14 +12,10 @@ import pytest
 from criteria3d_amd import crop, root, snow
 from tests import raster_chain
 from tests import root_cases as rc
+from tests.raster_helpers import bits as _bits
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
 
 
 def test_two_ranks_chain_the_three_blocks_and_merge_to_the_single_rank_maps(product, tmp_path):

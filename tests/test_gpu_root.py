@@ -13,6 +13,7 @@ import pytest
 
 from criteria3d_amd import capi, catchment as cm, crop, root
 from tests import root_cases as rc
+from tests.raster_helpers import need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -21,11 +22,6 @@ ROOT = Path(__file__).resolve().parent.parent
 @pytest.fixture(scope="module")
 def pin():
     return rc.load_pin()
-
-
-def _need_glibc_set(product):
-    if product.lib.sf3d_libm_set() != 1:
-        pytest.skip("this build evaluates the 0.50-ulp routines, not the C library's bits (-DSF3D_LIBM_GLIBC=0): bit identity with the compiled reference is not its contract")
 
 
 def _same(got, want, what):

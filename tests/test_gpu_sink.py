@@ -2,7 +2,8 @@
 tests/golden/water_sinks.npz: node sinks and both actual maps of every hour bit for bit, zero cells excluded, with every map passed in and
 with NULL maps read from the crop and snow blocks; the nrLayers = 1 case; sf3d_sink_apply against the node-by-node setter and the compute
 call without apply against the run without it (C2's F20 hour); the crop, snow and root blocks undisturbed; two ranks sharing the GPU;
-rasters with a partial block, less than a wave and a single row against the restatement, and a column table changed between two hours."""
+rasters with a partial block, less than a wave and a single row against the restatement, a column table changed between two hours, and the
+output maps driven alternately with the sink hour under a table that changes."""
 import os
 import subprocess
 import sys
@@ -11,11 +12,12 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from criteria3d_amd import capi, catchment as cm, crop, root, sinks, snow
+from criteria3d_amd import capi, catchment as cm, crop, maps, root, sinks, snow
 from tests import crop_cases as cc
 from tests import root_cases as rc
 from tests import sink_cases as sc
 from tests.snow_cases import melt_forcing
+from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -24,11 +26,6 @@ ROOT = Path(__file__).resolve().parent.parent
 @pytest.fixture(scope="module")
 def pin():
     return sc.load_pin()
-
-
-def _need_glibc_set(product):
-    if product.lib.sf3d_libm_set() != 1:
-        pytest.skip("this build evaluates the 0.50-ulp routines, not the C library's bits (-DSF3D_LIBM_GLIBC=0): bit identity with the compiled reference is not its contract")
 
 
 def _model(product, pin):
@@ -163,6 +160,18 @@ def _one_step(product, case, feed):
     return dt, s["H"], s["Se"]
 
 
+def _changed_columns(case):
+    """the case's column table on the same layer grid, in which some computing cells have lost their whole column and others their
+    nodes from layer 3 down"""
+    n, nl = case["dem"].size, len(case["layer_depth"])
+    columns = case["columns"].copy().reshape(nl, n)
+    computing = np.flatnonzero(sc.computing_cells(case).ravel())
+    columns[:, computing[1::5]] = -1                                      # the whole column gone
+    columns[3:, computing[3::5]] = -1                                     # the nodes from layer 3 down gone
+    columns[3:, 7:9] = -1                                                 # (the trees whose deep layers transpire)
+    return columns.reshape(case["columns"].shape)
+
+
 def test_a_changed_column_table_leaves_no_sinks_behind(product, pin):
     """Hour A on the full column table, then the same maps on a table of the same layer grid in which some computing cells have lost
     their whole column and others their nodes from layer 3 down: a node outside this hour's table holds 0, as the reference starts
@@ -170,16 +179,10 @@ def test_a_changed_column_table_leaves_no_sinks_behind(product, pin):
     _need_glibc_set(product)
     shape = (7, 37)
     case, m, vwc = _small(product, pin, shape)
-    n, nl = case["dem"].size, len(case["layer_depth"])
     sc.hour(product, case, 0)
     hour_a = _outputs(product, m.n)
     _same(hour_a, _wanted(case, 0, vwc), "hour A")
-    columns = case["columns"].copy().reshape(nl, n)
-    computing = np.flatnonzero(sc.computing_cells(case).ravel())
-    columns[:, computing[1::5]] = -1                                      # the whole column gone
-    columns[3:, computing[3::5]] = -1                                     # the nodes from layer 3 down gone
-    columns[3:, 7:9] = -1                                                 # (the trees whose deep layers transpire)
-    columns = columns.reshape(case["columns"].shape)
+    columns = _changed_columns(case)
     outside = np.ones(m.n, bool)
     outside[case["columns"][case["columns"] >= 0]] = False
     was_outside = outside.copy()
@@ -208,6 +211,36 @@ def test_a_changed_column_table_leaves_no_sinks_behind(product, pin):
     dt2, h2, se2 = _one_step(product, case, lambda m: None)
     assert dt0 == dt1 > 0.0 and np.array_equal(s0["H"], h1) and np.array_equal(s0["Se"], se1)
     assert dt2 > 0.0 and not np.array_equal(h1, h2)                      # the sinks did reach the solver
+    product.lib.sf3d_clean()
+
+
+@pytest.mark.parametrize("shape", ((3, 11), (7, 37)))
+def test_output_maps_and_sinks_share_one_column_table_on_the_device(product, pin, shape):
+    """The output maps and the sink hour upload the column table through one function and keep one version of it on the device.  Driven
+    alternately - map, sink hour, map, another table, sink hour, map - each call works on the table in force: the sinks equal the
+    restatement on it, a map is not disturbed by the sink hour between two of them, and the map after the change holds the flag exactly
+    where the new table has no node and the earlier bits wherever both tables name the same node."""
+    _need_glibc_set(product)
+    case, m, vwc = _small(product, pin, shape)
+    flag = np.float32(maps.NODATA)
+    water_content = lambda: maps.output_maps(product, m, maps.VOLUMETRIC_WATER_CONTENT)
+    first = water_content()
+    sc.hour(product, case, 0)
+    _same(_outputs(product, m.n), _wanted(case, 0, vwc), f"raster {shape}, the case's table")
+    second = water_content()
+    assert np.array_equal(_bits(first), _bits(second))
+    assert np.array_equal(first == flag, case["columns"] < 0)
+    columns = _changed_columns(case)
+    gone = (columns < 0) & (case["columns"] >= 0)
+    assert np.count_nonzero(gone) > 100                                  # the change takes nodes away
+    sinks.set_columns(product, columns, case["layer_thickness"])
+    sc.hour(product, case, 1)
+    _same(_outputs(product, m.n), _wanted(case, 1, vwc, columns), f"raster {shape}, the changed table")
+    third = water_content()
+    print(f"raster {shape}: {int(np.count_nonzero(gone))} nodes left the table, {int(np.count_nonzero(third == flag))} flag values in the third map")
+    assert np.array_equal(third == flag, columns < 0)
+    same_node = (columns >= 0) & (columns == case["columns"])
+    assert np.array_equal(_bits(third)[same_node], _bits(first)[same_node]) and np.count_nonzero(same_node) > columns.size // 3
     product.lib.sf3d_clean()
 
 

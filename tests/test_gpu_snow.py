@@ -16,6 +16,7 @@ from tests import tolerances
 from tests.scenarios import ravone_project_model
 from tests import snow_cases
 from tests.snow_cases import melt_forcing
+from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -23,19 +24,10 @@ PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
 WINDOW = (980, 1108, 300, 428)          # the 128 x 128 project window of the output-map tests
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
 def pin():
     z = np.load(PIN)
     return {k: z[k] for k in z.files}
-
-
-def _need_glibc_set(product):
-    if product.lib.sf3d_libm_set() != 1:
-        pytest.skip("this build evaluates the 0.50-ulp routines, not the C library's bits (-DSF3D_LIBM_GLIBC=0): bit identity with the compiled reference is not its contract")
 
 
 def _meteo(pin, h):

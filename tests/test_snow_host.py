@@ -11,13 +11,10 @@ import numpy as np
 
 from criteria3d_amd import build, capi, esri, snow
 from tests import snow_cases
+from tests.raster_helpers import bits as _bits
 
 ROOT = Path(__file__).resolve().parent.parent
 PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_snow_header_and_binding_table_agree():
