@@ -1,5 +1,6 @@
 """What tests/test_crop_host.py, tests/test_gpu_crop.py and scripts/multirank_crop_worker.py share (no tests here): the pin
-tests/golden/crop_et0.npz decoded, its calendar replayed on a backend (the numpy restatement or the device), a small forcing."""
+tests/golden/crop_et0.npz decoded, its calendar replayed on a backend (the numpy restatement or the device), a small forcing, and a
+raster of any shape with its three stages (degree-day map, one hour, one daily update) restated."""
 from pathlib import Path
 
 import numpy as np
@@ -121,3 +122,44 @@ def small_forcing(shape, dem, flag, hours=5):
             m["windInt"][tuple(v[2])] = np.float32(flag)
         out.append(m)
     return out
+
+
+# ---- a raster of any shape on the pin's units
+
+SHAPES = ((7, 37), (3, 11), (1, 300))          # 259 cells: one block and three lanes; 33: less than a wave; 300: a partial second block
+DOY = 310
+# the least shares of the DEM cells (isEqual: -9999.5 counts) that hold ET0 > 0 after the hour and LAI > 0 after the day: 200 and 50 of the
+# 255 DEM cells of 7 x 37.  The restatement reaches them on every shape (tests/test_crop_host.py).
+ET0_SHARE, LAI_SHARE = 200 / 255, 50 / 255
+
+
+def small_raster(pin, shape, seed=7):
+    """DEM, unit index and degree-day map of a raster of any shape (>= 8 cells, >= 7 columns): the first three cells and the last one hold
+    the flag, the three lanes before the last hold a tree, one inner cell lies at -9999.5 (a DEM cell by isEqual, none by int())"""
+    rng = np.random.default_rng(seed)
+    flag = -9999.0
+    rows, cols = shape
+    dem = rng.uniform(50.0, 400.0, shape).astype(np.float32)
+    dem.flat[:3] = flag
+    dem.flat[-1] = flag
+    dem[rows // 2, 3] = -9999.5
+    idx = rng.integers(-1, len(pin["unit_list"]), shape).astype(np.int32)
+    idx.flat[-4:-1] = 3                                    # the last lanes that compute hold a tree
+    dd0 = np.where(rng.random(shape) < 0.9, rng.uniform(0.0, 3000.0, shape), flag).astype(np.float32)
+    dem_cells = int(np.count_nonzero(np.abs(dem.astype(np.float64) - flag) >= 1e-5))
+    return dict(dem=dem, idx=idx, dd0=dd0, flag=flag, units=pin["unit_list"], latitude=44.5, inner=(rows // 2, 3), dem_cells=dem_cells,
+                met=small_forcing(shape, dem, flag)[3])
+
+
+def small_raster_stages(r):
+    """the five maps after each of the three stages, restated: [after set_degree_days, after the hour, after the daily update]"""
+    dem, idx, units, lat, flag = r["dem"], r["idx"], r["units"], r["latitude"], r["flag"]
+    want = crop.restate_degree_days(dem, idx, units, lat, r["dd0"], DOY, flag)
+    want["et0"] = np.full(dem.shape, np.float32(flag))
+    stages = [dict(want)]
+    want["et0"] = crop.restate_et0_hour(dem, r["met"], flag)
+    want["dailyTmin"], want["dailyTmax"] = crop.restate_daily_temperatures(want["dailyTmin"], want["dailyTmax"], r["met"]["airT"], flag)
+    stages.append(dict(want))
+    want.update(crop.restate_crop_day(want, dem, idx, units, lat, DOY, DOY, flag))
+    stages.append(dict(want))
+    return stages

@@ -148,7 +148,6 @@ def small_case(pin, shape, seed, hours=2):
     columns[:, dem == flag] = -1
     columns[:, 0, 0] = np.arange(nl) * n                                       # a flag cell that keeps its column: its nodes hold 0
     columns.reshape(nl, n)[:, 2] = -1                                          # a valid cell without any node
-    hz_of = sinks.horizon_table(pin["sink_soils"], pin["layer_depth"])
     psi = np.array(PSI)[rng.integers(0, len(PSI), nl * n)]
     psi[:n] = np.array(SURFACE_WATER)[rng.integers(0, len(SURFACE_WATER), n)]
     case.update(dem=dem, crop_index=ci, soil_index=si, et0=et0, lai=lai, sink_degree_days=dd, liquid_water=liquid, columns=columns, psi=psi)
@@ -172,11 +171,19 @@ def small_case(pin, shape, seed, hours=2):
     # the last lane computes: the tree again, unstressed, under a partly open canopy, less water on the surface than the demand, rain
     _column(case, n - 1, potentials=unstressed, surface_water=0.0001, crop_index=TREE, soil_index=0, et0=np.float32(0.45), lai=np.float32(1.0),
             sink_degree_days=np.float32(700.0), liquid_water=np.float32(1.2))
-    # per node: soil and horizon of its cell and layer; cells without a soil take soil 0, layers below the soil horizon 0 (the fixture's rule)
-    node_soil = np.broadcast_to(np.where(si < 0, 0, si)[None], (nl,) + shape).ravel().astype(np.int32)
+    set_node_classes(case)
+    return case
+
+
+def set_node_classes(case):
+    """per node: soil and horizon of its cell and layer; cells without a soil take soil 0, layers below the soil horizon 0 (the fixture's
+    rule).  Called again by whoever places further cells by hand (tests/map_cases.py)."""
+    si = case["soil_index"]
+    nl, n = len(case["layer_depth"]), si.size
+    hz_of = sinks.horizon_table(case["sink_soils"], case["layer_depth"])
+    node_soil = np.broadcast_to(np.where(si < 0, 0, si)[None], (nl,) + si.shape).ravel().astype(np.int32)
     layer = np.repeat(np.arange(nl), n)
     case["node_soil"], case["node_horizon"] = node_soil, np.where(hz_of[node_soil, layer] < 0, 0, hz_of[node_soil, layer]).astype(np.int32)
-    return case
 
 
 def roots_restated(case, k):

@@ -1,5 +1,6 @@
 """Hourly ET0, daily extremes and the daily crop maps, the parts that need no GPU: the numpy restatements equal the compiled-reference
-pin tests/golden/crop_et0.npz bit for bit at every checkpoint, the pin reaches every arm, the crop-table reader and isCrop on the
+pin tests/golden/crop_et0.npz bit for bit at every checkpoint, the pin reaches every arm, the small rasters of the GPU test hold ET0 and
+LAI on the shares of cells it asks for, the crop-table reader and isCrop on the
 Ravone project's crop rows, the C entry points of include/sf3d_crop.h and the binding table, the crop/ state folder."""
 import json
 import re
@@ -117,6 +118,25 @@ def test_restatements_equal_the_compiled_reference_at_every_checkpoint(pin):
     names = list(crop.MAPS)
     assert (pin["maps"][:, names.index("et0")] > 0).any() and (pin["maps"][:, names.index("lai")] > 0).any()
     assert (pin["maps"][:, names.index("dailyTmax")] > -100).any()
+
+
+@pytest.mark.parametrize("shape", cc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_small_rasters_hold_et0_and_lai_on_the_shares_the_gpu_test_asks_for(pin, shape):
+    """the bounds of tests/test_gpu_crop.py's small-raster test are the restatement's: 200 and 50 cells of the 255 DEM cells of 7 x 37"""
+    r = cc.small_raster(pin, shape)
+    dem, flag = r["dem"], np.float32(r["flag"])
+    assert dem.shape == shape and np.all(dem.flat[:3] == flag) and dem.flat[-1] == flag and dem[r["inner"]] == np.float32(-9999.5)
+    assert np.all(r["idx"].flat[-4:-1] == 3) and int(pin["unit_list"][3]["type"]) == crop.TREE
+    assert r["dem_cells"] == dem.size - 4
+    if shape == (7, 37):
+        assert cc.ET0_SHARE * r["dem_cells"] == 200 and cc.LAI_SHARE * r["dem_cells"] == 50
+    after_degree_days, after_hour, after_day = cc.small_raster_stages(r)
+    assert np.all(after_degree_days["et0"] == flag) and np.count_nonzero(after_degree_days["degreeDays"] != flag) > 0
+    et0 = after_hour["et0"]
+    assert np.count_nonzero(et0 > 0) > cc.ET0_SHARE * r["dem_cells"] and et0.flat[-2] > 0 and et0[r["inner"]] == flag and et0.flat[-1] == flag
+    assert np.count_nonzero(after_day["lai"] > 0) > cc.LAI_SHARE * r["dem_cells"]
+    for stage in (after_degree_days, after_hour, after_day):
+        assert sorted(stage) == sorted(crop.MAPS) and all(np.isfinite(v).all() for v in stage.values())
 
 
 def test_point_models_by_hand():

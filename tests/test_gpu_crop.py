@@ -1,6 +1,6 @@
 """Hourly ET0, daily extremes and daily crop maps on the device (include/sf3d_crop.h, k_et0_hour / k_crop_day) against the
 compiled-reference pin tests/golden/crop_et0.npz: all five maps at every checkpoint of the calendar bit for bit, zero cells excluded; a
-raster with a partial wave and a partial block against the restatement; the run interrupted through get_state / set_state and through
+raster with a partial wave and a partial block, one of less than a wave and a single row of 300 cells against the restatement; the run interrupted through get_state / set_state and through
 the crop/ state folder; NULL inputs read what the snow hour uploaded; the solver does not notice the calls; two ranks sharing the GPU
 merge to the single-rank maps; the error codes."""
 import os
@@ -42,40 +42,31 @@ def test_all_five_maps_equal_the_pin_at_every_checkpoint(product, pin):
     crop.clean(product)
 
 
-def test_partial_wave_and_partial_block_against_the_restatement(product, pin):
-    """7 x 37 = 259 cells: one full block plus three lanes"""
+@pytest.mark.parametrize("shape", cc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_partial_wave_and_partial_block_against_the_restatement(product, pin, shape):
+    """7 x 37 = 259 cells: one full block plus three lanes; 3 x 11: less than a wave; one row of 300: a partial second block.  The degree-day
+    map, one hour and one daily update against the restatement (cc.small_raster_stages); the shares of cells that must hold ET0 and LAI
+    are asserted on the restatement in tests/test_crop_host.py"""
     _need_glibc_set(product)
-    rng = np.random.default_rng(7)
-    flag = -9999.0
-    dem = rng.uniform(50.0, 400.0, (7, 37)).astype(np.float32)
-    dem[0, :3] = flag
-    dem[6, 36] = flag
-    dem[3, 3] = -9999.5
-    idx = rng.integers(-1, len(pin["unit_list"]), dem.shape).astype(np.int32)
-    idx[6, 33:36] = 3                                      # the last lanes of the second block hold a tree
-    units, lat = pin["unit_list"], 44.5
+    r = cc.small_raster(pin, shape)
+    dem, idx, units, lat, flag = r["dem"], r["idx"], r["units"], r["latitude"], r["flag"]
+    after_degree_days, after_hour, after_day = cc.small_raster_stages(r)
     crop.initialize(product, dem, idx, units, lat, flag)
-    dd0 = np.where(rng.random(dem.shape) < 0.9, rng.uniform(0.0, 3000.0, dem.shape), flag).astype(np.float32)
-    crop.set_degree_days(product, dd0, 310)
-    want = crop.restate_degree_days(dem, idx, units, lat, dd0, 310, flag)
-    want["et0"] = np.full(dem.shape, np.float32(flag))
+    crop.set_degree_days(product, r["dd0"], cc.DOY)
     got = crop.all_maps(product)
     for n in crop.MAPS:
-        assert np.array_equal(_bits(got[n]), _bits(want[n])), ("degree-day map", n)
-    met = cc.small_forcing(dem.shape, dem, flag)[3]
-    crop.compute_hour(product, met)
-    want["et0"] = crop.restate_et0_hour(dem, met, flag)
-    want["dailyTmin"], want["dailyTmax"] = crop.restate_daily_temperatures(want["dailyTmin"], want["dailyTmax"], met["airT"], flag)
+        assert np.array_equal(_bits(got[n]), _bits(after_degree_days[n])), ("degree-day map", n)
+    crop.compute_hour(product, r["met"])
     got = crop.all_maps(product)
-    assert np.count_nonzero(got["et0"] > 0) > 200 and got["et0"][6, 35] > 0 and got["et0"][3, 3] == np.float32(flag)
+    assert np.count_nonzero(got["et0"] > 0) > cc.ET0_SHARE * r["dem_cells"] and got["et0"].flat[-2] > 0 and got["et0"][r["inner"]] == np.float32(flag)
+    assert got["et0"].flat[-1] == np.float32(flag)
     for n in crop.MAPS:
-        assert np.array_equal(_bits(got[n]), _bits(want[n])), ("hour", n)
-    crop.daily_update(product, 310)
-    want.update(crop.restate_crop_day(want, dem, idx, units, lat, 310, 310, flag))
+        assert np.array_equal(_bits(got[n]), _bits(after_hour[n])), ("hour", n)
+    crop.daily_update(product, cc.DOY)
     got = crop.all_maps(product)
-    assert np.count_nonzero(got["lai"] > 0) > 50
+    assert np.count_nonzero(got["lai"] > 0) > cc.LAI_SHARE * r["dem_cells"]
     for n in crop.MAPS:
-        assert np.array_equal(_bits(got[n]), _bits(want[n])), ("day", n)
+        assert np.array_equal(_bits(got[n]), _bits(after_day[n])), ("day", n)
     crop.clean(product)
 
 

@@ -2,7 +2,8 @@
 tests/golden/meteo_idw.npz: every cell of every case and method bit for bit; the getter against the map returned directly; a second
 variable leaves the first one's map alone; a meteo call between the snow hour and the crop hour that reads its maps changes neither
 (the shared mask buffer and stream); two ranks sharing the GPU merge to the single-rank map; 257 x 3 cells with 1 024 stations against
-the restatement (the LDS staging loop and the tail block at the cap)."""
+the restatement, every method (the LDS staging loop and the tail block at the cap); 3 x 11 and 1 x 300 cells with 300 stations against the
+restatement, every method (less than a wave, a partial second block, a staging pass that ends inside the block)."""
 import os
 import subprocess
 import sys
@@ -119,7 +120,7 @@ def test_two_ranks_merge_to_the_single_rank_map(product, pin, tmp_path):
     assert np.count_nonzero(merged != flag) > 600
 
 
-@pytest.mark.parametrize("method", ["idw", "shepard_modified"])
+@pytest.mark.parametrize("method", ["idw", "shepard", "shepard_modified"])
 def test_1024_stations_on_257_x_3_cells_against_the_restatement(product, pin, method):
     r = mc.cap_raster(pin)
     assert len(r["x"]) == meteo.MAX_STATIONS and r["dem"].size % 256 == 3
@@ -131,4 +132,21 @@ def test_1024_stations_on_257_x_3_cells_against_the_restatement(product, pin, me
     assert got.flat[0] == r["flag"] and got.flat[-1] != r["flag"] and np.count_nonzero(got != r["flag"]) == r["dem"].size - 2
     with pytest.raises(capi.SF3DError):                                   # one station beyond the cap
         meteo.interpolate(product, "airT", method, np.append(r["x"], 0.0), np.append(r["y"], 0.0), np.append(r["value"], 0.0), r["area"], r["settings"])
+    meteo.clean(product)
+
+
+@pytest.mark.parametrize("method", meteo.METHODS)
+@pytest.mark.parametrize("shape", mc.SMALL_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_300_stations_on_small_rasters_against_the_restatement(product, pin, shape, method):
+    """33 cells: less than a wave; one row of 300: a partial second block.  300 stations: the second pass of the LDS staging loop ends at
+    lane 44.  The single row holds every neighbourhood size of shepardSearchNeighbour (tests/test_meteo_host.py)."""
+    r = mc.small_raster(pin, shape)
+    flag = r["flag"]
+    meteo.initialize(product, r["dem"], r["xll"], r["yll"], r["cell_size"], r["proxy_maps"], float(flag))
+    got = meteo.interpolate(product, "airT", method, r["x"], r["y"], r["value"], r["area"], r["settings"])
+    want = meteo.restate_interpolate(r["dem"], r["xll"], r["yll"], r["cell_size"], r["proxy_maps"], "airT", method, r["x"], r["y"], r["value"], r["area"],
+                                     r["settings"], float(flag))
+    print(f"{shape} {method}: {int((mc.bits(got) != mc.bits(want)).sum())} values differ")
+    _same(got, want, f"300 stations on {shape}, {method}")
+    assert got.flat[0] == flag and got.flat[-1] != flag and np.count_nonzero(got != flag) == r["dem"].size - 2
     meteo.clean(product)

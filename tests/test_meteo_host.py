@@ -1,6 +1,6 @@
 """The hourly meteo maps from station data, the parts that need no GPU: the ABI of include/sf3d_meteo.h against the binding, the Python
 restatement of interpolate() equal to the compiled-reference pin tests/golden/meteo_idw.npz bit for bit in every cell of every case, the
-pin's arms and cases, the caps and the options that stay with the caller refused through the C ABI without a device, and the entry
+pin's arms and cases, the neighbourhood sizes and the distinct distances of the small rasters of the GPU test, the caps and the options that stay with the caller refused through the C ABI without a device, and the entry
 points absent from sf3d.h and the drop-in shim."""
 import ctypes
 import re
@@ -90,6 +90,33 @@ def test_no_cell_has_two_stations_at_equal_float_distances(pin):
         dx, dy = x.astype(np.float32)[None, :] - xf[:, None], y.astype(np.float32)[None, :] - yf[:, None]
         d = np.sort(np.sqrt(dx * dx + dy * dy), axis=1)
         assert not (d[:, 1:] == d[:, :-1]).any(), len(x)
+
+
+def test_small_rasters_hold_every_neighbourhood_size_and_no_equal_distances(pin):
+    """3 x 11 and 1 x 300 cells under 300 stations (tests/test_gpu_meteo.py): counted with float distances as meteo._neighbours counts
+    them, the single row holds cells with fewer than 5 stations inside the initial radius (the 5 nearest of all, sorted), with 5 to 10
+    (input order) and with more than 10 (the 10 nearest, sorted); no cell of either raster has two stations at equal float distance"""
+    for shape in mc.SMALL_SHAPES:
+        r = mc.small_raster(pin, shape)
+        assert r["dem"].shape == shape and len(r["x"]) == len(r["y"]) == len(r["value"]) == mc.SMALL_STATIONS == 256 + 44
+        assert np.array_equal(r["x"], mc.cap_raster(pin)["x"][:300]) and r["dem"].flat[0] == r["flag"] and r["dem"].flat[-1] != r["flag"]
+        d = mc.float_distances(r)
+        assert d.dtype == np.float32 and d.shape == (r["dem"].size, 300)
+        radius = meteo.shepard_initial_radius(r["area"], 300)
+        inside = np.count_nonzero((d <= radius) & (d > 0), axis=1)
+        few, some, many = (int(np.count_nonzero(k)) for k in (inside < meteo.SHEPARD_MIN, (inside >= meteo.SHEPARD_MIN) & (inside <= meteo.SHEPARD_MAX),
+                                                             inside > meteo.SHEPARD_MAX))
+        print(f"{shape}: radius {radius}, cells with < 5 stations inside {few}, with 5 to 10 {some}, with more {many}")
+        for cell in (1, r["dem"].size - 1):                                  # the counts are _neighbours' own
+            idx, rad = meteo._neighbours(d[cell], radius)
+            assert len(idx) == (meteo.SHEPARD_MIN if inside[cell] < meteo.SHEPARD_MIN else min(inside[cell], meteo.SHEPARD_MAX))
+            assert (rad == radius) == (meteo.SHEPARD_MIN <= inside[cell] <= meteo.SHEPARD_MAX)
+        if shape == (1, 300):
+            assert few > 0 and some > 0 and many > 0, (few, some, many)
+        else:
+            assert some > 0 and many > 0, (few, some, many)
+        ds = np.sort(d, axis=1)
+        assert not (ds[:, 1:] == ds[:, :-1]).any() and ds.min() > meteo.EPSILON, shape
 
 
 def test_restatement_equals_the_compiled_reference_in_every_cell_of_every_case(pin):

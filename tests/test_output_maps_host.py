@@ -1,6 +1,8 @@
 """Output maps, the parts that need no GPU: the C entry points of include/sf3d_maps.h are exported by the product library and match the
 binding table, the geotechnics of the soil database (getUSCSClass, the fall-back of setHorizon), the layer stack the output depth lists
-map through, the restated factor of safety against closed-form values, and the resources of the new kernel (no scratch, full occupancy)."""
+map through, the restated factor of safety against closed-form values, the resources of the new kernel (no scratch, full occupancy),
+and the small ragged rasters of tests/map_cases.py on the CPU oracle: every arm of the output maps is reached on each of the three shapes
+and both retention curves, and the factor of safety of a hand-placed column with a hole and of one without a surface node, step by step."""
 import json
 import math
 import re
@@ -12,6 +14,8 @@ import pytest
 
 from criteria3d_amd import build, capi, maps
 from criteria3d_amd import project3d as p3
+from tests import map_cases as mpc
+from tests import sink_cases as sc
 from tests.kernel_notes import kernel_resources
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -198,6 +202,142 @@ def test_factor_of_safety_restatement_on_one_column_against_closed_form():
     avg = maps.restate_avg_degree_of_saturation(index, thick, wc, wmin, wmax)
     sw = sum(wc[l] * 0.1 for l in (1, 2, 3)); sr = sum(0.05 * 0.1 for _ in range(3)); ss = sum(0.45 * 0.1 for _ in range(3))
     assert avg[0, 0] == np.float32((sw - sr) / (ss - sr))
+
+
+# ------------------------------------------------------------------------------------------------ the small ragged rasters are not vacuous
+
+_ORACLE_RUNS = {}
+
+
+def _oracle_run(oracle, shape, curve):
+    """(case, per-node getter values of the oracle after mpc.prepare), once per shape and curve"""
+    if (shape, curve) not in _ORACLE_RUNS:
+        case = mpc.small_map_case(sc.load_pin(), shape, seed=shape[1])
+        mpc.prepare(oracle, case, mpc.CURVES[curve])
+        g = maps.node_getter_values(oracle, case["model"].n)
+        oracle.lib.sf3d_clean()
+        _ORACLE_RUNS[shape, curve] = case, g
+    return _ORACLE_RUNS[shape, curve]
+
+
+@pytest.mark.parametrize("curve", list(mpc.CURVES))
+@pytest.mark.parametrize("shape", mpc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_small_map_cases_reach_every_arm_on_the_oracle(oracle, shape, curve):
+    case, g = _oracle_run(oracle, shape, curve)
+    m = case["model"]
+    n, nl = m.ns, len(case["layer_depth"])
+    index = np.asarray(m.meta["index"])
+    col = index.reshape(nl, n)
+    surf, soil = col[0][col[0] >= 0], col[1:][col[1:] >= 0]
+    assert len(m.meta["geotechnics"]) == len(m.soil_table) == 9
+    for k in (2, 3, 4):                                                  # cohesion, friction angle, bulk density: distinct per row
+        assert len({row[k] for row in m.meta["geotechnics"]}) == 9
+    slope = m.meta["slope"]
+    assert slope.dtype == np.float32 and slope.flat[mpc.FLAT] == 0 and slope.flat[mpc.STEEP] == 75 and 0 <= slope.min() and np.sort(slope.ravel())[-2] <= 60
+    # surface water: ponded, a film of at most 1 mm, none
+    water = g[maps.VOLUMETRIC_WATER_CONTENT]
+    assert np.count_nonzero(water[surf] > 0.001) > 0 and np.count_nonzero((water[surf] > 0) & (water[surf] <= 0.001)) > 0
+    assert np.count_nonzero(water[surf] <= 0) > 0
+    assert water[mpc.DRY_SURFACE] < 0 and 0 < water[mpc.THIN_SURFACE] <= 0.001 and water[mpc.PONDED_SURFACE] > 0.001 and water[n - 1] > 0.002
+    dos = g[maps.DEGREE_OF_SATURATION]
+    assert dos[mpc.DRY_SURFACE] == 0 and 0 < dos[mpc.THIN_SURFACE] < 1 and dos[mpc.PONDED_SURFACE] == 1
+    psi = g[maps.WATER_MATRIC_POTENTIAL]
+    assert np.count_nonzero(psi[soil] >= 0) > 0 and np.count_nonzero(psi[soil] < 0) > 0
+    # available water exactly 0 (the dmax(0, ..) arm) on every soil class, and > 0 elsewhere
+    available = g[maps.AVAILABLE_WATER_CONTENT]
+    cls = m.soil_index.astype(int) * 8 + m.horizon_index.astype(int)
+    assert set(cls[soil[available[soil] == 0] - n]) == set(cls) and len(set(cls)) == 9
+    assert np.count_nonzero(available[soil] > 0) > 0
+    deficit = g[maps.WATER_DEFICIT]
+    assert np.count_nonzero(deficit[soil] < 0) > 0 and np.count_nonzero(deficit[soil] > 0) > 0
+    inflow, outflow = g[maps.WATER_INFLOW], g[maps.WATER_OUTFLOW]
+    for nodes in (surf, soil):
+        assert np.count_nonzero(inflow[nodes] > 0) > 0 and np.count_nonzero(outflow[nodes] < 0) > 0
+    # the restated maps
+    plain, steeper = mpc.restated(m, g), mpc.restated(m, g, increase_slope=True)
+    for var, v in plain.items():
+        assert np.isfinite(v).all() and np.isfinite(steeper[var]).all(), var
+    flag = np.float32(mpc.FLAG)
+    fos = plain[maps.FACTOR_OF_SAFETY].reshape(nl, n)
+    minimum = plain[maps.MINIMUM_FACTOR_OF_SAFETY].ravel()
+    candidates = np.where(fos == flag, np.inf, fos.astype(np.float64))
+    has = np.isfinite(candidates.min(axis=0))
+    layer_of_minimum = np.argmin(candidates, axis=0)
+    assert np.array_equal(minimum[has], candidates.min(axis=0)[has].astype(np.float32)) and np.all(minimum[~has] == flag)
+    taken = set(layer_of_minimum[has])
+    assert len(taken) >= 4 and {1, nl - 1} <= taken, taken
+    assert layer_of_minimum[mpc.SHALLOW] == 1 and layer_of_minimum[mpc.DEEP] == nl - 1
+    surface_only, soil_only, holed = (k.ravel() for k in mpc.column_kinds(index))
+    assert surface_only.sum() >= 1 and soil_only.sum() >= 1 and holed.sum() >= 1
+    assert surface_only[mpc.SURFACE_ONLY] and soil_only[mpc.SOIL_ONLY] and holed[mpc.HOLES]
+    assert all(col[l, mpc.HOLES] < 0 and col[l + 1, mpc.HOLES] >= 0 and l + 1 in mpc.LAYER_CALLS for l in mpc.HOLE_LAYERS)
+    average = plain[maps.AVG_DEGREE_OF_SATURATION].ravel()
+    assert average[mpc.SURFACE_ONLY] == flag and np.all(fos[:, mpc.SURFACE_ONLY] == flag) and minimum[mpc.SURFACE_ONLY] == flag
+    assert average[mpc.SOIL_ONLY] == flag and np.all(fos[1:, mpc.SOIL_ONLY] != flag) and minimum[mpc.SOIL_ONLY] != flag
+    assert all(v.ravel()[2] == flag for v in plain.values() for v in v.reshape(-1, n))            # the valid cell without any node
+    assert average[n - 1] != flag and minimum[n - 1] != flag and np.all(fos[1:, n - 1] != flag)      # the last cell computes
+    for var in (maps.FACTOR_OF_SAFETY, maps.MINIMUM_FACTOR_OF_SAFETY):
+        assert not np.array_equal(plain[var], steeper[var]), var
+    tan_steeper = maps.slope_terms(slope, True)[0]
+    assert tan_steeper.flat[mpc.STEEP] == math.tan(89 * p3.DEG_TO_RAD) and maps.slope_terms(slope, False)[0].flat[mpc.FLAT] == max(p3.EPSILON, math.tan(p3.EPSILON))      # the cap, the floor
+    assert steeper[maps.FACTOR_OF_SAFETY].reshape(nl, n)[1, mpc.STEEP] != plain[maps.FACTOR_OF_SAFETY].reshape(nl, n)[1, mpc.STEEP]
+    assert plain[maps.FACTOR_OF_SAFETY].reshape(nl, n)[1, mpc.FLAT] > 1000
+
+
+@pytest.mark.parametrize("shape", mpc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_plain_curve_gives_other_available_water_and_deficit_on_every_soil_class(oracle, shape):
+    (case, modified), (_, plain) = _oracle_run(oracle, shape, "modified"), _oracle_run(oracle, shape, "plain")
+    m = case["model"]
+    cls = m.soil_index.astype(int) * 8 + m.horizon_index.astype(int)
+    soil = np.unique(np.asarray(m.meta["index"])[1:]); soil = soil[soil >= 0]
+    for var in (maps.AVAILABLE_WATER_CONTENT, maps.WATER_DEFICIT):
+        differs = modified[var][soil] != plain[var][soil]
+        assert set(cls[soil[differs] - m.ns]) == set(cls), var
+
+
+def test_factor_of_safety_of_the_hand_placed_columns_step_by_step(oracle):
+    """computeFactorOfSafety (project3D.cpp:2618-2721) in plain Python floats, not through maps.restate_*: the column with a hole directly
+    above layers 7 and 13 (layers 5 to 7, where the weight skips layer 6), the column without a surface node (layers 1 to 3, no surface-water
+    term) and the shallow-minimum column (layers 1 to 3 and the column minimum)"""
+    shape = (3, 11)
+    case, g = _oracle_run(oracle, shape, "plain")
+    m = case["model"]
+    n, nl = m.ns, len(case["layer_depth"])
+    col = np.asarray(m.meta["index"]).reshape(nl, n)
+    thick = [0.0] + list(m.meta["layers"])
+    geo = {(s, h): (c, f, b) for s, h, c, f, b in m.meta["geotechnics"]}
+    water, dos, psi = g[maps.VOLUMETRIC_WATER_CONTENT], g[maps.DEGREE_OF_SATURATION], g[maps.WATER_MATRIC_POTENTIAL]
+    restated = mpc.restated(m, g)
+    fos_maps, minimum = restated[maps.FACTOR_OF_SAFETY].reshape(nl, n), restated[maps.MINIMUM_FACTOR_OF_SAFETY].ravel()
+
+    def by_hand(cell, layer):
+        slope_angle = max(float(m.meta["slope"].flat[cell]) * 0.01745329252, 0.00001)
+        tan_angle = max(0.00001, math.tan(slope_angle))
+        node = int(col[layer, cell])
+        assert node >= 0
+        cohesion, friction, _ = geo[int(m.soil_index[node - n]), int(m.horizon_index[node - n])]
+        tan_friction = math.tan(friction * 0.01745329252)
+        friction_effect = tan_friction / tan_angle
+        suction_stress = min(0.0, float(psi[node]) * 9.80665) * float(dos[node])
+        weight_sum = 0.0
+        if col[0, cell] >= 0 and water[col[0, cell]] > 0:
+            weight_sum += float(water[col[0, cell]]) * 9.80665
+        for l in range(1, layer + 1):
+            k = int(col[l, cell])
+            if k >= 0:
+                bulk = geo[int(m.soil_index[k - n]), int(m.horizon_index[k - n])][2]
+                weight_sum += (bulk + float(water[k])) * 9.80665 * thick[l]
+        cohesion_effect = 2 * cohesion / (weight_sum * math.sin(2 * slope_angle))
+        suction_effect = (suction_stress * (tan_angle + 1 / tan_angle) * tan_friction) / weight_sum
+        return np.float32(friction_effect + cohesion_effect - suction_effect)
+
+    assert col[0, mpc.HOLES] >= 0 and water[col[0, mpc.HOLES]] > 0 and col[6, mpc.HOLES] < 0 and col[0, mpc.SOIL_ONLY] < 0
+    for cell, layers in ((mpc.HOLES, (5, 7, 13)), (mpc.SOIL_ONLY, (1, 2, 3)), (mpc.SHALLOW, (1, 2, 3))):
+        for layer in layers:
+            want = by_hand(cell, layer)
+            assert np.isfinite(want) and fos_maps[layer, cell] == want, (cell, layer, fos_maps[layer, cell], want)
+    assert fos_maps[6, mpc.HOLES] == np.float32(mpc.FLAG)
+    assert minimum[mpc.SHALLOW] == by_hand(mpc.SHALLOW, 1) == min(by_hand(mpc.SHALLOW, l) for l in range(1, nl))
 
 
 # ------------------------------------------------------------------------------------------------ kernel resources
