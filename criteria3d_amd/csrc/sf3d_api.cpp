@@ -370,6 +370,7 @@ template <class T> void reset(std::vector<T>& v, size_t n) { v.assign(n, T()); }
 #define NEED_NODE_D(i) if ((i) >= M.N) return errValue(SF3D_INDEX_ERROR); else if (skippedByTrim(i)) return (double)SF3D_NODATA; else (void)0
 
 void mapsClear();                               /* sf3d_maps_api.inc: what include/sf3d_maps.h set belongs to one model */
+void radClear();                                /* sf3d_rad_api.inc: the radiation maps, as the meteo maps */
 void sinkClear();                               /* sf3d_sink_api.inc: the sink maps and tables, as the root maps */
 void meteoClear();                              /* sf3d_meteo_api.inc: the meteo maps, as the root maps */
 void rootClear();                               /* sf3d_root_api.inc: the root maps and the density table, as the crop maps */
@@ -400,6 +401,7 @@ sf3d_error_t sf3d_clean(void)                                       /* soilFluxe
     rootClear();
     meteoClear();
     sinkClear();
+    radClear();
     return cleanModel();
 }
 
@@ -1188,3 +1190,4 @@ sf3d_error_t sf3d_device_pow(uint32_t count, const double* x, const double* y, d
 #include "sf3d_root_api.inc"
 #include "sf3d_meteo_api.inc"
 #include "sf3d_sink_api.inc"
+#include "sf3d_rad_api.inc"

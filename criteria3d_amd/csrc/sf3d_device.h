@@ -618,6 +618,53 @@ struct SinkCall {       /* what sf3d_sink_compute_hour hands to DeviceSolver::si
 enum { SINK_MAP_EVAPORATION = 0, SINK_MAP_TRANSPIRATION = 1, SINK_MAP_DEM = 2, SINK_MAP_ET0 = 3, SINK_MAP_LAI = 4, SINK_MAP_DD = 5, SINK_MAP_LIQUID = 6,
        SINK_MAP_CROP = 7, SINK_MAP_SOIL = 8, SINK_MAPS = 9, SINK_MAP_WORDS = 11 };
 
+/* ---- hourly r.sun radiation maps with DEM shadows (sf3d_rad.inc, include/sf3d_rad.h): one thread per raster cell ---- */
+struct RadHourDev {     /* what depends on the date and time only: evaluated once per call on the host (sf3d_rad_setup.inc), stored as the floats S_solpos stores */
+    float declin, rascen, gmst, erv;    /* geometry(), solPos.cpp:426-555 */
+    float cd, sd;                       /* localtrig(): cos / sin of the declination */
+    float etrn;                         /* solcon * erv */
+    float timezone;
+    float localTime;                    /* float(localTime.time) [s] of isIlluminated */
+    int32_t hour, minute, second;       /* local time, after the shift of solarRadiation.cpp:714-726 */
+    float linke, albedo, clearSky;      /* linke: the fixed or the month's value; NODATA in map mode (sf3d_rad.h) */
+    int32_t realSky, realSkyAlgorithm, shadowing;
+};
+struct RadCellDev {     /* what depends on the cell only: evaluated once per raster on the host, uploaded as static maps */
+    float height, lat, lon, cl, sl, press, slope, aspect;    /* cl, sl: float(cos / sin(raddeg * latitude)); press: float(pressureFromAltitude(height) * 0.01) */
+    double cp, sp, ct, st;              /* cos / sin of aspect and tilt as tilt() uses them (solPos.cpp:912-917) */
+    double sinSlope, cosSlope, Fg;      /* the slope-only terms of getDiffuseInclined_Muneer (solarRadiation.cpp:479-496) */
+    double reflGeom;                    /* 1 - cos(float(slope) * DEG_TO_RAD) of getReflectedIrradiance (:534) */
+    int32_t ok;                         /* the range checks of S_solpos on longitude, latitude, pressure, tilt and aspect (solPos.cpp:327-344) */
+};
+struct RadGridDev {     /* the DEM the shadow rays cross */
+    const float* dem;
+    double xll, yll, cellSize, invCellSize;
+    int32_t nRows, nCols;
+    float flag, demMax;                 /* demMax: Crit3DRasterGrid::maximum, evaluated on the host */
+};
+/* the device block: RAD_FLOAT_MAPS float maps of nCells, then RAD_DOUBLE_MAPS double maps, then the int32 map `ok` */
+enum { RAD_MAP_OUT = 0, RAD_MAP_DEM = 5, RAD_MAP_LAT = 6, RAD_MAP_LON = 7, RAD_MAP_CL = 8, RAD_MAP_SL = 9, RAD_MAP_PRESS = 10, RAD_MAP_SLOPE = 11,
+       RAD_MAP_ASPECT = 12, RAD_MAP_TRANSMISSIVITY = 13, RAD_FLOAT_MAPS = 14, RAD_DOUBLE_MAPS = 8, RAD_OUTPUTS = 5 };
+struct RadView {        /* k_rad_hour */
+    float* out[RAD_OUTPUTS];            /* sun elevation (refracted), global, beam, diffuse, reflected */
+    const float* fl;                    /* RAD_MAP_DEM .. RAD_MAP_ASPECT at fl + (map - RAD_MAP_DEM) * nCells */
+    const double* db;                   /* cp, sp, ct, st, sinSlope, cosSlope, Fg, reflGeom at db + k * nCells */
+    const int32_t* ok;
+    const float* transmissivity;        /* this block's copy or the meteo block's map */
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    RadGridDev grid;
+    RadHourDev hour;
+    uint32_t nCells;
+};
+struct RadSetup {       /* what sf3d_rad_initialize hands to DeviceSolver::rad_alloc: host pointers */
+    uint32_t nRows, nCols;
+    const float* fl[RAD_MAP_TRANSMISSIVITY - RAD_MAP_DEM];      /* dem, lat, lon, cl, sl, press, slope, aspect */
+    const double* db[RAD_DOUBLE_MAPS];
+    const int32_t* ok;
+    double xll, yll, cellSize;
+    float flag, demMax;
+};
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 

@@ -157,6 +157,17 @@ struct MeteoCache {
     uint32_t nCells = 0, nRows = 0, nCols = 0, nProxies = 0;
     double xll = 0., yll = 0., cellSize = 0.;
     float flag = -9999.f;
+    bool produced[METEO_VARIABLES] = {false};      /* the variable's map holds an interpolation (meteo_produced) */
+    double lastMs = 0.;
+};
+
+/* hourly radiation maps (sf3d_rad.inc): the five outputs, the static maps of include/sf3d_rad.h and the hour's transmissivity; they belong to
+ * the raster too */
+struct RadCache {
+    char* base = nullptr;               /* RAD_DOUBLE_MAPS double maps, RAD_FLOAT_MAPS float maps, one int32 map, each of nCells */
+    uint32_t nCells = 0, nRows = 0, nCols = 0;
+    double xll = 0., yll = 0., cellSize = 0.;
+    float flag = -9999.f, demMax = -9999.f;
     double lastMs = 0.;
 };
 
@@ -300,6 +311,7 @@ struct DeviceSolver::Impl {
     RootCache root;
     MeteoCache meteo;
     SinkCache sink;
+    RadCache rad;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the

@@ -240,13 +240,13 @@ sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const M
     return SF3D_OK;
 }
 
-/* ---- shared by the five raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc, sf3d_meteo.inc, sf3d_sink.inc) and the output maps
+/* ---- shared by the six raster blocks (sf3d_snow.inc, sf3d_crop.inc, sf3d_root.inc, sf3d_meteo.inc, sf3d_sink.inc, sf3d_rad.inc) and the output maps
  * above.  A block's calls run on the solver's stream, touch nothing of the solver and synchronise the stream before they return, so the
  * caller's maps are free again and one device mask serves all of them.  The column table reaches the device through raster_columns alone
  * (the output maps and the sinks).  What one block reads from another it asks of that block's accessors, which stand in the owning
  * block's file beside the predicate that makes the read safe: snow_hour_done / snow_hour_input, snow_liquid_water (sf3d_snow.inc),
  * crop_allocated / crop_et0, crop_lai, crop_degree_days (sf3d_crop.inc), root_computed (sf3d_root.inc; its maps go to the sink kernel
- * as one block). */
+ * as one block), meteo_produced / meteo_map (sf3d_meteo.inc: the transmissivity map the radiation block reads). */
 
 /* a block of per-cell maps whose first two are 8-byte maps and the others 4-byte ones (RootCache::cells, SinkCache::cells) */
 static void* raster_cell_map(char* cells, size_t nCells, int map)

@@ -286,6 +286,7 @@ sf3d_error_t DeviceSolver::meteo_interpolate(const MeteoCall& call, const uint8_
     v.var = call.var; v.method = call.method; v.allZero = call.allZero; v.useDetrending = call.useDetrending; v.detrendingVar = call.detrendingVar;
     v.flag = K.flag; v.radius0 = call.radius0; v.rainfallThreshold = call.rainfallThreshold;
     e = raster_launch(k_meteo_idw, n, v, K.lastMs);
+    if (e == SF3D_OK) K.produced[call.var] = true;
     if (e != SF3D_OK || !out) return e;
     return raster_download(out, v.out, n * sizeof(float));
 }
@@ -295,5 +296,13 @@ sf3d_error_t DeviceSolver::meteo_download(int var, float* dst)
     const MeteoCache& K = impl_->meteo;
     return raster_download(dst, K.base + (1 + (size_t)K.nProxies + (size_t)var) * K.nCells, (size_t)K.nCells * sizeof(float));
 }
+
+/* what the radiation block reads of this one: the map of a variable, safe once meteo_produced says the block is on the caller's raster
+ * and an interpolation of the variable has run (until then the map holds the flag) */
+bool DeviceSolver::meteo_produced(int var, uint32_t nRows, uint32_t nCols) const
+{
+    return impl_ && impl_->meteo.base && var >= 0 && var < METEO_VARIABLES && impl_->meteo.nRows == nRows && impl_->meteo.nCols == nCols && impl_->meteo.produced[var];
+}
+static const float* meteo_map(const MeteoCache& K, int var) { return K.base + (1 + (size_t)K.nProxies + (size_t)var) * K.nCells; }
 
 double DeviceSolver::meteo_kernel_ms() const { return impl_ ? impl_->meteo.lastMs : 0.; }

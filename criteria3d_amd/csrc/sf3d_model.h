@@ -240,6 +240,15 @@ public:
     sf3d_error_t meteo_download(int var, float* dst);
     sf3d_error_t meteo_free();
     double meteo_kernel_ms() const;
+    bool meteo_produced(int var, uint32_t nRows, uint32_t nCols) const;   /* the block is on this raster and holds an interpolation of `var` */
+    /* hourly r.sun radiation maps (sf3d_rad.inc): the five outputs and the static maps, independent of the node model as the other raster
+     * blocks; transmissivity == nullptr: k_rad_hour reads the map the meteo block holds (the caller asks meteo_produced first) */
+    sf3d_error_t rad_alloc(const RadSetup& setup);
+    sf3d_error_t rad_hour(const RadHourDev& hour, const float* transmissivity, const uint8_t* mine);
+    sf3d_error_t rad_download(int which, float* dst);
+    sf3d_error_t rad_free();
+    double rad_kernel_ms() const;
+    sf3d_error_t rad_trig(int which, uint32_t n, const double* x, const double* y, double* out);     /* test hook: the device build of sf3d_trig.inc */
     /* hourly evaporation, transpiration and rain sinks (sf3d_sink.inc): the per-cell maps and the tables belong to the raster as the other
      * blocks' do, the node array to the model on the device (release() frees it); sink_hour reads the accepted state after sync_to_device as
      * output_map does and the root block's maps, and, where a map of `call` is null, the crop / snow block's */

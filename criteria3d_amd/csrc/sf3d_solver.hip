@@ -51,3 +51,4 @@
 #include "sf3d_root.inc"
 #include "sf3d_meteo.inc"
 #include "sf3d_sink.inc"
+#include "sf3d_rad.inc"

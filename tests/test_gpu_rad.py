@@ -1,0 +1,219 @@
+"""The hourly r.sun radiation maps on the device (include/sf3d_rad.h, k_rad_hour) against the compiled-reference pin
+tests/golden/rad_rsun.npz: every cell of every map and case bit for bit, both hours of the two-hour cases included; the same property
+off the pin against the restatement on 7 x 37, 3 x 11 and 1 x 300 rasters (a partial second block, less than a wave, a partial second
+block in one row) that together reach the arms of the pin; the device build of sf3d_trig.inc against its host build bit for bit;
+transmissivity taken from the meteo block on the device against the same map passed from the host; no side effect on the solver; two
+ranks sharing the GPU merge to the single-rank maps; the maps survive sf3d_initialize and go with sf3d_clean."""
+import ctypes
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import capi, catchment as cm, meteo, radiation as rad
+from tests import rad_cases
+from tests.test_trig_host import acos_ranges, build_trig_host, ptr, trig_ranges
+
+pytestmark = pytest.mark.gpu
+ROOT = Path(__file__).resolve().parent.parent
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return rad_cases.load_pin()
+
+
+def _same(got, want, what):
+    same = rad_cases.same_bits(got, want)
+    assert same.all(), (what, int((~same).sum()), np.argwhere(~same)[:4].tolist(), np.asarray(got)[~same][:4], np.asarray(want)[~same][:4])
+
+
+def _maps(product):
+    return np.stack([rad.get_map(product, n) for n in rad.MAPS])
+
+
+def _start_pin(product, pin, raster, settings):
+    geo = pin["geo"]
+    dummy = pin["dem"][raster]                   # map mode needs a map; the reference never reads it inside the grid
+    s = rad.settings_dict(settings)
+    rad.initialize(product, pin["dem"][raster], geo[0], geo[1], geo[2], pin["lat"][raster], pin["lon"][raster], pin["slope"][raster], pin["aspect"][raster],
+                   linke_map=dummy if s["linkeMode"] == rad.MODE_MAP else None, albedo_map=dummy if s["albedoMode"] == rad.MODE_MAP else None,
+                   settings=settings, flag=float(pin["flag"]))
+
+
+def test_every_cell_of_every_map_and_case_equals_the_pin(product, pin):
+    checked = 0
+    for raster, chain in rad_cases.pin_chains(pin):
+        _start_pin(product, pin, raster, chain[0]["settings"])
+        for case in chain:
+            t = np.ascontiguousarray(pin["transmissivity"][case["transmissivity"]])
+            if "refuses" in case["name"]:
+                assert product.lib.sf3d_rad_compute_hour(*case["when"], t.size, t.ctypes.data_as(capi.pf32)) == capi.PARAMETER_ERROR
+            else:
+                rad.compute_hour(product, case["when"], t)
+            _same(_maps(product), rad_cases.pin_maps(pin, case), case["name"])
+            checked += 1
+    rad.clean(product)
+    assert checked == len(pin["cases"])
+
+
+@pytest.mark.parametrize("shape", rad_cases.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_small_rasters_equal_the_restatement(product, shape):
+    ref = rad_cases.small_reference()
+    g = rad_cases.small_raster(shape)
+    reached = 0
+    for name, settings, hours in rad_cases.small_chains():
+        s = rad.settings_dict(settings)
+        rad.initialize(product, g["dem"], *rad_cases.GEO, g["lat"], g["lon"], g["slope"], g["aspect"],
+                       linke_map=g["dem"] if s["linkeMode"] == rad.MODE_MAP else None, albedo_map=g["dem"] if s["albedoMode"] == rad.MODE_MAP else None,
+                       settings=settings, flag=float(rad_cases.FLAG))
+        for k, (when, tk) in enumerate(hours):
+            rad.compute_hour(product, when, g["transmissivity"][tk])
+            want, arms = ref[(shape, name)][k]
+            _same(_maps(product), want, (shape, name, k))
+            reached |= int(np.bitwise_or.reduce(arms, axis=None))
+    rad.clean(product)
+    assert reached != 0
+    every = 0
+    for (_, _), hours in ref.items():
+        for _, arms in hours:
+            every |= int(np.bitwise_or.reduce(arms, axis=None))
+    assert every == (1 << len(rad.ARMS)) - 1                              # together the three rasters reach the arms of the pin
+
+
+def test_device_trig_equals_the_host_build_bit_for_bit(product, tmp_path):
+    lib = build_trig_host(tmp_path)
+    n = 1_000_000
+    for which, name in enumerate(("sin", "cos", "tan", "acos")):
+        ranges = acos_ranges(60 + which) if which == 3 else trig_ranges(60 + which)
+        x = np.concatenate([np.asarray(v)[:n // len(ranges)] for v in ranges.values()])
+        x = np.concatenate([x, [0.0, -0.0, np.inf, -np.inf, np.nan, 1.0, -1.0, 200.0, -200.0, 5e-324]])
+        host = np.empty_like(x)
+        lib.tr_eval(which, ptr(x), ptr(host), ctypes.c_size_t(x.size))
+        dev = rad.device_trig(product, which, x)
+        nan = np.isnan(host) & np.isnan(dev)
+        assert x.size >= n and np.array_equal(dev.view(np.int64)[~nan], host.view(np.int64)[~nan]), name
+    rng = np.random.default_rng(66)
+    x = np.concatenate([rng.uniform(-1, 1, n), [1.0, -1.0, 0.5, -0.5, 0.0, 2.0 ** -26, 2.0 ** -27]]).astype(np.float32)
+    host = np.empty_like(x)
+    lib.tr_eval_acosf(ptr(x), ptr(host), ctypes.c_size_t(x.size))
+    assert np.array_equal(rad.device_trig(product, 4, x.astype(np.float64)).astype(np.float32).view(np.int32), host.view(np.int32))
+    x = rng.uniform(3.0, 97.0, n).astype(np.float32)
+    e = np.where(rng.uniform(size=n) < 0.5, np.float32(-1.6364), rng.uniform(-4, 4, n)).astype(np.float32)
+    host = np.empty_like(x)
+    lib.tr_eval_powf(ptr(x), ptr(e), ptr(host), ctypes.c_size_t(x.size))
+    dev = rad.device_trig(product, 5, x.astype(np.float64), e.astype(np.float64)).astype(np.float32)
+    nan = np.isnan(host) & np.isnan(dev)
+    assert np.array_equal(dev.view(np.int32)[~nan], host.view(np.int32)[~nan])
+
+
+def test_transmissivity_from_the_meteo_block_equals_the_map_passed_from_the_host(product, pin):
+    raster, when = 1, (2021, 3, 20, 7, 30, 0)
+    dem, geo, flag = pin["dem"][raster], pin["geo"], float(pin["flag"])
+    _start_pin(product, pin, raster, None)
+    n = dem.size
+    null = lambda: product.lib.sf3d_rad_compute_hour(*when, n, None)
+    meteo.clean(product)
+    assert null() == capi.PARAMETER_ERROR                                 # no meteo block
+    meteo.initialize(product, dem[:, :16], geo[0], geo[1], geo[2], flag=flag)
+    rng = np.random.default_rng(5)
+    sx, sy = geo[0] + rng.uniform(-200, 400, 12), geo[1] + rng.uniform(-200, 300, 12)
+    sv = rng.uniform(0.1, 0.8, 12).astype(np.float32)
+    meteo.interpolate(product, "transmissivity", "idw", sx, sy, sv, 600.0 * 500.0, download=False)
+    assert null() == capi.PARAMETER_ERROR                                 # the meteo block is on another raster
+    meteo.initialize(product, dem, geo[0], geo[1], geo[2], flag=flag)
+    meteo.interpolate(product, "airT", "idw", sx, sy, sv, 600.0 * 500.0, download=False)
+    assert null() == capi.PARAMETER_ERROR                                 # on this raster, but no transmissivity yet
+    t = meteo.interpolate(product, "transmissivity", "idw", sx, sy, sv, 600.0 * 500.0)
+    assert ((t > 0.1) & (t < 0.8))[dem != pin["flag"]].all()
+    assert null() == capi.OK
+    from_device = _maps(product)
+    _start_pin(product, pin, raster, None)
+    rad.compute_hour(product, when, t)
+    _same(from_device, _maps(product), "meteo hand-over")
+    assert np.count_nonzero(from_device[1] > 0) > 600                      # not vacuous: global irradiance on the lit cells of the window
+    meteo.clean(product)
+    rad.clean(product)
+
+
+def test_rad_calls_leave_the_solver_untouched(product, pin):
+    """C2 in its F20 hour, a radiation hour between every two computeSteps: H, Se and the work counters of the run without"""
+    def run(with_rad):
+        m = cm.catchment_model(64, 64, 10)
+        product.check(product.lib.sf3d_reset_solver_state(), "reset")
+        cm.build(product, m, threads=1)
+        if with_rad:
+            _start_pin(product, pin, 1, None)
+        product.set_sink_source_bulk(0, np.full(m.ns, cm.rain_rate(20.0, m.cell_area)))
+        t, k = 0.0, 0
+        while t < 3600.0:
+            dt = product.lib.sf3d_compute_step(3600.0 - t)
+            assert dt > 0.0
+            t += dt
+            if with_rad:
+                rad.compute_hour(product, (2021, 3, 20, 6 + k % 10, 30, 0), pin["transmissivity"][k % 2])
+                if k % 5 == 0:
+                    rad.get_map(product, "global")
+            k += 1
+        s, c = cm.snapshot(product, m), product.counters()
+        if with_rad:
+            assert np.count_nonzero(rad.get_map(product, "global") > 0) > 0
+        product.lib.sf3d_clean()
+        return s, c
+    (s0, c0), (s1, c1) = run(False), run(True)
+    assert np.array_equal(s0["H"], s1["H"]) and np.array_equal(s0["Se"], s1["Se"])
+    assert c0 == c1
+
+
+def test_maps_survive_sf3d_initialize_and_go_with_sf3d_clean(product, pin):
+    _start_pin(product, pin, 0, None)
+    rad.compute_hour(product, (2021, 3, 20, 11, 30, 0), pin["transmissivity"][0])
+    before = _maps(product)
+    m = cm.catchment_model(16, 16, 4)
+    product.check(product.lib.sf3d_reset_solver_state(), "reset")
+    cm.build(product, m, threads=1)                                   # sf3d_initialize inside
+    _same(_maps(product), before, "after sf3d_initialize")
+    out = np.empty(before[0].size, np.float32)
+    assert product.lib.sf3d_rad_get_map(5, out.size, out.ctypes.data_as(capi.pf32)) == capi.INDEX_ERROR
+    assert product.lib.sf3d_rad_get_map(0, out.size + 1, out.ctypes.data_as(capi.pf32)) == capi.PARAMETER_ERROR
+    assert product.lib.sf3d_rad_compute_hour(2021, 3, 20, 11, 30, 0, out.size + 1, out.ctypes.data_as(capi.pf32)) == capi.PARAMETER_ERROR
+    product.lib.sf3d_clean()
+    assert product.lib.sf3d_rad_get_map(0, out.size, out.ctypes.data_as(capi.pf32)) == capi.MEMORY_ERROR
+
+
+def test_two_ranks_merge_to_the_single_rank_maps(product, pin, tmp_path):
+    world, port = 2, 29791
+    which = next(k for k, c in enumerate(pin["cases"]) if c["raster"] == 1 and c["name"].endswith("equinox morning"))
+    first, second = pin["cases"][which], pin["cases"][which + 1]
+    outs = [tmp_path / f"rad_r{r}.npz" for r in range(world)]
+    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
+    # each rank under its own time limit; the ranks meet in the process group, so they start together
+    procs = [subprocess.Popen(["timeout", "-k", "10", "240", sys.executable, str(ROOT / "scripts" / "multirank_rad_worker.py"), str(r), str(world), str(port),
+                               str(which), str(outs[r])], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
+    for r, pr in enumerate(procs):
+        o, _ = pr.communicate()
+        if pr.returncode != 0:                                            # stop at the first failure: nothing more runs on the GPU
+            for q in procs:
+                if q.poll() is None:
+                    q.kill()
+            pytest.fail(f"rank {r} ended with {pr.returncode}\n{o}")
+    ranks = [np.load(o) for o in outs]
+    rows, cols = pin["dem"][1].shape
+    idx = np.arange(rows * cols).reshape(rows, cols)                      # the surface node of every cell of catchment_model(cols, rows, 4)
+    owner = np.full(rows * cols * 4, 255, np.int64)
+    for r, res in enumerate(ranks):
+        owner[res["owner"] == r] = r
+    cell_owner = owner[idx]
+    assert set(np.unique(cell_owner)) == {0, 1}
+    flag = np.float32(pin["flag"])
+    for k, case in enumerate((first, second)):
+        merged = np.full((5, rows, cols), flag, np.float32)
+        for r, res in enumerate(ranks):
+            mine = cell_owner == r
+            assert np.all(res[f"hour{k}"][:, ~mine] == flag), r           # another rank's cells: the flag
+            merged[:, mine] = res[f"hour{k}"][:, mine]
+        _same(merged, rad_cases.pin_maps(pin, case), f"merged ranks, hour {k}")      # what the single rank gives (the first test): the pin
+    assert np.count_nonzero(merged[1] > 0) > 500

@@ -1,0 +1,176 @@
+"""The radiation block without a device: the header against the binding, the Python restatement of criteria3d_amd/radiation.py (point
+model through `math`, which is the C library, and the library's acosf / powf) against the compiled-reference pin
+(tests/golden/rad_rsun.npz) bit for bit in every cell, map and case, latlon_maps against the lat / lon maps the reference computed, the
+small rasters of tests/rad_cases.py against the arms of the pin, and what the entry points refuse before they need a device."""
+import ctypes
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import build, capi, radiation as rad
+from tests import rad_cases
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return rad_cases.load_pin()
+
+
+def test_rad_header_and_binding_agree():
+    text = (ROOT / "include" / "sf3d_rad.h").read_text()
+    declared = set(re.findall(r"\b(sf3d_rad_\w+)\s*\(", text))
+    assert declared == set(rad.SIGNATURES)
+    for name, value in dict(REALSKY_TOTALTRANSMISSIVITY=0, REALSKY_LINKE=1, MODE_FIXED=0, MODE_MAP=1, MODE_MONTHLY=2, TILT_FIXED=1, TILT_DEM=2).items():
+        assert re.search(rf"SF3D_RAD_{name} = {value}\b", text) and getattr(rad, name) == value
+    for k, name in enumerate(("SUN_ELEVATION", "GLOBAL", "BEAM", "DIFFUSE", "REFLECTED")):
+        assert re.search(rf"SF3D_RAD_{name} = {k}\b", text) and getattr(rad, name) == k
+    fields = re.search(r"typedef struct \{(.*?)\} sf3d_rad_settings_t;", text, re.S).group(1)
+    names = [n for line in re.findall(r"^\s*(?:int32_t|float)\s+([^;]+);", fields, re.M) for n in re.split(r",\s*", line)]
+    assert [n.split("[")[0] for n in names] == [f[0] for f in rad.Settings._fields_]
+    assert ctypes.sizeof(rad.Settings) == 8 * 4 + 17 * 4
+    assert all(re.search(r"\.(cpp|h):\d+", c) for c in re.findall(r"/\*(.*?)\*/\s*sf3d_error_t sf3d_rad_\w+\(", text, re.S))      # every entry point cites file:line
+
+
+def test_product_library_exports_the_rad_entry_points_outside_the_drop_in_abi():
+    lib = build.build_product()
+    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
+    for name in rad.SIGNATURES:
+        assert re.search(rf" T {name}$", out, re.M), name
+    assert not any("rad" in n.lower().split("_") for n in capi.SIGNATURES)
+
+
+def test_the_pin_reaches_every_arm_and_holds_the_cases_the_issue_lists(pin):
+    assert list(pin["arm_names"]) == list(rad.ARMS) and (pin["arm_counts"] > 0).all()
+    assert (GOLDEN_SIZE := (rad_cases.GOLDEN / "rad_rsun.npz").stat().st_size) <= (rad_cases.GOLDEN / "ravone_window.npz").stat().st_size, GOLDEN_SIZE
+    names = " | ".join(c["name"] for c in pin["cases"])
+    for piece in ("night", "hour of sunrise", "hour of sunset", "noon", "just above zero", "June solstice", "December solstice", "equinox",
+                  "total transmissivity, real sky", "clear sky", "no shadowing", "fixed tilt", "monthly Linke", "Linke map", "albedo map",
+                  "isUTC off", "day before", "day after", "second hour on the same maps"):
+        assert piece in names, piece
+    assert pin["dem"].shape == (2, 24, 32) and (pin["dem"] == pin["flag"]).any()
+    for r in (0, 1):
+        assert (pin["slope_reference"][r] == 0).sum() >= 9                       # the flat patch
+    low = [rad_cases.pin_maps(pin, c)[0] for c in pin["cases"] if "just above zero" in c["name"]]
+    assert all(((m > 0) & (m <= 1e-3)).any() for m in low)
+    rise = [rad_cases.pin_maps(pin, c) for c in pin["cases"] if "hour of sunrise" in c["name"]]
+    assert all(((m[0] > 0) & (m[0] < 3) & (m[1] > 0)).any() for m in rise)       # a lit cell below 3 degrees
+
+
+def test_latlon_maps_equal_the_reference_bit_for_bit(pin):
+    rows, cols = pin["dem"].shape[1:]
+    header = dict(nrows=rows, ncols=cols, xllcorner=pin["geo"][0], yllcorner=pin["geo"][1], cellsize=pin["geo"][2])
+    for r in (0, 1):
+        lat, lon = rad.latlon_maps(header, dem=pin["dem"][r], flag=pin["flag"])
+        assert rad_cases.same_bits(lat, pin["lat"][r]).all() and rad_cases.same_bits(lon, pin["lon"][r]).all()
+    assert 44.4 < float(pin["lat"][0].max()) < 44.6 and 11.2 < float(pin["lon"][0].max()) < 11.4
+
+
+def test_restatement_equals_the_compiled_reference_in_every_cell_map_and_case(pin):
+    geo, flag = pin["geo"], pin["flag"]
+    for raster, chain in rad_cases.pin_chains(pin):
+        prev = None
+        for case in chain:
+            got, _ = rad.restate_radiation_hour(pin["dem"][raster], flag, geo[0], geo[1], geo[2], pin["lat"][raster], pin["lon"][raster], pin["slope"][raster],
+                                                pin["aspect"][raster], case["when"], pin["transmissivity"][case["transmissivity"]], case["settings"], previous=prev)
+            want = rad_cases.pin_maps(pin, case)
+            if got is None:                                                      # a date S_solpos refuses: nothing is written
+                got = np.full_like(want, flag)
+            same = rad_cases.same_bits(got, want)
+            assert same.all(), (case["name"], int((~same).sum()))
+            prev = got
+
+
+def test_the_maps_are_state_across_hours(pin):
+    """a cell whose transmissivity is NODATA in the second hour keeps the first hour's value in the reference's maps"""
+    seen = 0
+    for raster, chain in rad_cases.pin_chains(pin):
+        for first, second in zip(chain, chain[1:]):
+            a, b = rad_cases.pin_maps(pin, first), rad_cases.pin_maps(pin, second)
+            t = pin["transmissivity"][second["transmissivity"]]
+            kept = (t == -9999.0) & (pin["dem"][raster] != pin["flag"]) & (b[0] > 0) & (a[1] != pin["flag"])
+            if kept.any() and (b[1][kept] == a[1][kept]).all() and (b[0][kept] == a[0][kept]).all():
+                seen += int(kept.sum())
+    assert seen > 0
+
+
+def test_small_rasters_reach_the_arms_of_the_pin_and_every_edge():
+    ref = rad_cases.small_reference()
+    reached = 0
+    for (shape, name), hours in ref.items():
+        for maps, arms in hours:
+            reached |= int(np.bitwise_or.reduce(arms, axis=None))
+    missing = [n for k, n in enumerate(rad.ARMS) if not reached >> k & 1]
+    assert not missing, missing
+    # the sun stands in all four quadrants while rays leave the grid: north / east, south / east, south / west, north / west edges
+    quadrants = set()
+    g = rad_cases.small_raster((7, 37))
+    cell = rad.cell_setup(float(g["dem"][1, 1]), float(g["lat"][1, 1]), float(g["lon"][1, 1]), 10.0, 180.0)
+    for name, settings, hours in rad_cases.small_chains():
+        s = rad.settings_dict(settings)
+        for k, (when, _) in enumerate(hours):
+            arms = ref[((7, 37), name)][k][1]
+            if (arms & rad._ARM["shadow: ray left the grid"]).any():
+                sun = rad.sun_position(rad.hour_setup(when, s["timeZone"], bool(s["isUTC"])), cell)
+                quadrants.add(int(sun["azimuth"] // 90))
+    assert quadrants == {0, 1, 2, 3}, quadrants
+    for n, k in (("night, then the sun low in the east, then mid-morning", 1), ("noon, the sun low in the west, after sunset", 1)):
+        maps, arms = ref[((7, 37), n)][k]
+        lit = (arms & rad._ARM["illuminated"]) != 0
+        written = lit & (maps[1] != rad_cases.FLAG) & (maps[0] > 0)          # (a lit cell without transmissivity keeps the hour before)
+        assert written.sum() > 180 and (maps[0][written] < 8).mean() > 0.8, n          # the sun low in the east / in the west
+
+
+def test_refusals_without_a_device(pin):
+    sf = rad.bind(capi.load_product())
+    lib = sf.lib
+    n = 12
+    buf = np.zeros(n, np.float32)
+    pf = buf.ctypes.data_as(capi.pf32)
+    assert lib.sf3d_rad_clean() == capi.OK
+    assert lib.sf3d_rad_get_map(0, n, pf) == capi.MEMORY_ERROR              # before initialise
+    assert lib.sf3d_rad_kernel_ms() == 0.0
+    assert lib.sf3d_rad_default_parameters(None) == capi.PARAMETER_ERROR
+    st = rad.Settings()
+    assert lib.sf3d_rad_default_parameters(ctypes.byref(st)) == capi.OK
+    d = rad.DEFAULT_SETTINGS
+    assert [getattr(st, k) for k in ("realSky", "realSkyAlgorithm", "shadowing", "linkeMode", "albedoMode", "tiltMode", "timeZone", "isUTC")] == \
+        [d[k] for k in ("realSky", "realSkyAlgorithm", "shadowing", "linkeMode", "albedoMode", "tiltMode", "timeZone", "isUTC")]
+    assert (st.linke, st.albedo, st.tilt, st.aspect, st.clearSky) == (4.0, np.float32(0.2), 0.0, 0.0, 0.75) and list(st.linkeMonthly) == [-9999.0] * 12
+
+    def init(rows=3, cols=4, dem=pf, cell=4.0, lat=pf, lon=pf, slope=pf, aspect=pf, linke=None, albedo=None, settings=None):
+        s = ctypes.byref(rad.settings_struct(settings)) if settings is not None else None
+        return lib.sf3d_rad_initialize(rows, cols, dem, -9999.0, 0.0, 0.0, cell, lat, lon, slope, aspect, linke, albedo, s)
+    # shape mismatches and NULL static maps
+    assert init(rows=0) == capi.PARAMETER_ERROR and init(cols=0) == capi.PARAMETER_ERROR and init(dem=None) == capi.PARAMETER_ERROR
+    assert init(cell=0.0) == capi.PARAMETER_ERROR and init(cell=-4.0) == capi.PARAMETER_ERROR
+    assert init(lat=None) == capi.PARAMETER_ERROR and init(lon=None) == capi.PARAMETER_ERROR
+    assert init(slope=None) == capi.PARAMETER_ERROR and init(aspect=None) == capi.PARAMETER_ERROR          # DEM tilt needs both
+    # map mode without a map, modes out of range, a time zone S_solpos refuses
+    assert init(settings=dict(linkeMode=rad.MODE_MAP)) == capi.PARAMETER_ERROR
+    assert init(settings=dict(albedoMode=rad.MODE_MAP)) == capi.PARAMETER_ERROR
+    assert init(settings=dict(albedoMode=rad.MODE_MONTHLY)) == capi.PARAMETER_ERROR
+    assert init(settings=dict(linkeMode=3)) == capi.PARAMETER_ERROR and init(settings=dict(tiltMode=0)) == capi.PARAMETER_ERROR
+    assert init(settings=dict(realSkyAlgorithm=2)) == capi.PARAMETER_ERROR
+    assert init(settings=dict(timeZone=13)) == capi.PARAMETER_ERROR and init(settings=dict(timeZone=-13)) == capi.PARAMETER_ERROR
+    # whatever is acceptable needs a device from here on (SF3D_SOLVER_ERROR without one)
+    assert init(slope=None, aspect=None, settings=dict(tiltMode=rad.TILT_FIXED)) in (capi.OK, capi.SOLVER_ERROR)
+    assert lib.sf3d_rad_clean() == capi.OK
+
+    hour = lambda y=2021, mo=3, d=20, h=11, mi=30, s=0, cells=n, t=pf: lib.sf3d_rad_compute_hour(y, mo, d, h, mi, s, cells, t)
+    assert hour() == capi.MEMORY_ERROR                                      # a valid call, no raster yet
+    # a date outside 1950-2050 that S_solpos refuses (its bound is 2100, solPos.cpp:301), dates and times that are none
+    assert hour(y=1949) == capi.PARAMETER_ERROR and hour(y=2101) == capi.PARAMETER_ERROR and hour(y=1900) == capi.PARAMETER_ERROR
+    assert hour(y=1950, mo=1, d=1, h=0, mi=0) == capi.MEMORY_ERROR and hour(y=2100, mo=12, d=31, h=12) == capi.MEMORY_ERROR
+    assert hour(y=1950, mo=1, d=1, h=0, mi=30, t=pf) == capi.MEMORY_ERROR
+    assert hour(y=2100, mo=12, d=31, h=23, mi=30) == capi.PARAMETER_ERROR   # UTC + 1: the local date is in 2101
+    assert hour(mo=0) == capi.PARAMETER_ERROR and hour(mo=13) == capi.PARAMETER_ERROR and hour(d=0) == capi.PARAMETER_ERROR
+    assert hour(mo=2, d=29) == capi.PARAMETER_ERROR and hour(y=2020, mo=2, d=29) == capi.MEMORY_ERROR
+    assert hour(h=24) == capi.PARAMETER_ERROR and hour(h=-1) == capi.PARAMETER_ERROR and hour(mi=60) == capi.PARAMETER_ERROR and hour(s=60) == capi.PARAMETER_ERROR
+    # NULL transmissivity without a meteo hour
+    assert hour(t=None) == capi.PARAMETER_ERROR
+    assert lib.sf3d_rad_clean() == capi.OK
