@@ -3,21 +3,16 @@ compiled-reference pin tests/golden/crop_et0.npz: all five maps at every checkpo
 raster with a partial wave and a partial block, one of less than a wave and a single row of 300 cells against the restatement; the run interrupted through get_state / set_state and through
 the crop/ state folder; NULL inputs read what the snow hour uploaded; the solver does not notice the calls; two ranks sharing the GPU
 merge to the single-rank maps; the error codes."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, crop, snow
+from tests import ranks as mr
 from tests import crop_cases as cc
 from tests.scenarios import ravone_project_model
 from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
@@ -212,22 +207,8 @@ def test_crop_state_survives_sf3d_initialize_and_goes_with_sf3d_clean(product, p
 
 
 def test_two_ranks_merge_to_the_single_rank_maps(product, pin, tmp_path):
-    world, port, hours = 2, 29771, 4
-    outs = [tmp_path / f"crop_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_crop_worker.py"), str(r), str(world), str(port), str(hours), str(outs[r])],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
-    ranks = [np.load(o) for o in outs]
+    hours = 4
+    ranks = mr.run("scripts/multirank_crop_worker.py", 2, mr.PORTS["crop"], [hours], tmp_path)
     m = ravone_project_model((980, 1060, 330, 420))
     idx = np.asarray(m.meta["index"])[0]
     flag = -9999.0
@@ -242,16 +223,9 @@ def test_two_ranks_merge_to_the_single_rank_maps(product, pin, tmp_path):
     crop.daily_update(product, 200)
     single = crop.all_maps(product)
     crop.clean(product)
-    owner = np.full(m.n, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    cell_owner = np.where(idx >= 0, owner[np.maximum(idx, 0)], 255)
-    assert set(np.unique(cell_owner[idx >= 0])) == {0, 1}
-    merged = np.full(dem.shape, np.float32(flag), np.float32)
-    for r, res in enumerate(ranks):
-        assert np.all(res["et0"][cell_owner != r] == np.float32(flag)), r                   # another rank's cells: the flag
-        merged[cell_owner == r] = res["et0"][cell_owner == r]
-    assert np.array_equal(_bits(merged), _bits(single["et0"])) and np.count_nonzero(merged > 0) > 1000
+    cell_owner = mr.cell_owner(ranks, idx, m.n)
+    merged = mr.merge([res["et0"] for res in ranks], cell_owner, np.float32(flag), others=np.float32(flag), what="et0")      # another rank's cells: the flag
+    assert merged.shape == dem.shape and merged.dtype == np.float32 and np.array_equal(_bits(merged), _bits(single["et0"])) and np.count_nonzero(merged > 0) > 1000
     for n in crop.STATE:
         for r, res in enumerate(ranks):
             mine = cell_owner == r

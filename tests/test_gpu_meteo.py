@@ -4,21 +4,16 @@ variable leaves the first one's map alone; a meteo call between the snow hour an
 (the shared mask buffer and stream); two ranks sharing the GPU merge to the single-rank map; 257 x 3 cells with 1 024 stations against
 the restatement, every method (the LDS staging loop and the tail block at the cap); 3 x 11 and 1 x 300 cells with 300 stations against the
 restatement, every method (less than a wave, a partial second block, a staging pass that ends inside the block)."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, crop, meteo, snow
+from tests import ranks as mr
 from tests import crop_cases as cc
 from tests import meteo_cases as mc
 from tests.snow_cases import melt_forcing
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
@@ -88,34 +83,15 @@ def test_a_meteo_call_between_the_snow_and_the_crop_hour_changes_neither(product
 
 
 def test_two_ranks_merge_to_the_single_rank_map(product, pin, tmp_path):
-    world, port, which = 2, 29777, 16                                     # shepard, 40 stations, air temperature with both proxies
-    outs = [tmp_path / f"meteo_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
-    # each rank under its own time limit; the ranks meet in the process group, so they start together
-    procs = [subprocess.Popen(["timeout", "-k", "10", "240", sys.executable, str(ROOT / "scripts" / "multirank_meteo_worker.py"), str(r), str(world), str(port),
-                               str(which), str(outs[r])], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    for r, pr in enumerate(procs):
-        o, _ = pr.communicate()
-        if pr.returncode != 0:                                            # stop at the first failure: nothing more runs on the GPU
-            for q in procs:
-                if q.poll() is None:
-                    q.kill()
-            pytest.fail(f"rank {r} ended with {pr.returncode}\n{o}")
-    ranks = [np.load(o) for o in outs]
+    which = 16                                                            # shepard, 40 stations, air temperature with both proxies
+    ranks = mr.run("scripts/multirank_meteo_worker.py", 2, mr.PORTS["meteo"], [which], tmp_path)
     rows, cols = pin["dem"].shape
     idx = np.arange(rows * cols).reshape(rows, cols)                      # the surface node of every cell of catchment_model(cols, rows, 4)
-    owner = np.full(rows * cols * 4, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    cell_owner = owner[idx]
-    assert set(np.unique(cell_owner)) == {0, 1}
+    cell_owner = mr.cell_owner(ranks, idx, rows * cols * 4)
     flag = np.float32(pin["flag"])
-    merged = np.full((rows, cols), flag, np.float32)
     for r, res in enumerate(ranks):
-        mine = cell_owner == r
-        assert np.all(res["map"][~mine] == flag), r                       # another rank's cells: the flag
         _same(res["got"], res["map"], f"rank {r} getter")
-        merged[mine] = res["map"][mine]
+    merged = mr.merge([res["map"] for res in ranks], cell_owner, flag, others=flag, what="map")      # another rank's cells: the flag
     _same(merged, pin["cases"][which]["want"], "merged ranks")            # what the single rank gives (the first test): the pin
     assert np.count_nonzero(merged != flag) > 600
 

@@ -2,41 +2,20 @@
 the test box - the exchange (HIP-IPC windows, device-side flags, halo puts, all-gather of partial
 sums) is the same code that runs one rank per GPU.  Each rank owns a row strip; the union of the
 owned nodes must match the oracle like the single-rank run does."""
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm
+from tests import ranks as mr
 from tests.tolerances import HEAT_RTOL, WATER_RTOL, assert_water_nodes
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 RTOL = WATER_RTOL          # 1e-9 (tests/tolerances.py); north_star: 1e-6
 
 
 def _run_ranks_once(world, case, tmp_path, port, env):
-    import os
-    procs, outs = [], []
-    for r in range(world):
-        out = tmp_path / f"rank{r}_{port}.npz"
-        outs.append(out)
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_worker.py"), str(r), str(world),
-                                       str(port), case, str(out)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                                      env={**os.environ, "SF3D_DIST_VERBOSE": "1", "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60"),      # (ranks taking turns on one GPU: the exchange's 10 s bound is for ranks with a GPU each)
-                                           **(env or {})}))
-    logs = []
-    for p in procs:
-        try:
-            o, _ = p.communicate(timeout=600)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    return all(p.returncode == 0 for p in procs), logs, outs
+    returncodes, logs, outs = mr.launch("scripts/multirank_worker.py", world, port, [case], tmp_path, limit_s=600, env={"SF3D_DIST_VERBOSE": "1", **(env or {})})
+    return not any(returncodes), logs, outs
 
 
 SETUP_FAILURES = ("did not answer within the bounded wait", "no answer from rank", "no answer through the window", "self-check kernel failed")
@@ -258,18 +237,8 @@ def test_forced_rccl_on_a_shared_gpu_fails_loudly(tmp_path, monkeypatch):
     """SF3D_EXCHANGE=rccl asks for the ncclSend/ncclRecv exchange; with two ranks on ONE GPU there is no communicator to be had
     (RCCL refuses two ranks on a device): every rank reports it at connect time - nothing hangs, nothing falls back silently"""
     monkeypatch.setenv("SF3D_EXCHANGE", "rccl")
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_worker.py"), str(r), "2", "29631", "c2f20", str(tmp_path / f"r{r}.npz")],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    logs = []
-    for p in procs:
-        try:
-            o, _ = p.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(p.returncode != 0 for p in procs), logs
+    returncodes, logs, _ = mr.launch("scripts/multirank_worker.py", 2, mr.PORTS["rccl_refused"], ["c2f20"], tmp_path, wait_all=True, limit_s=300)
+    assert all(rc != 0 for rc in returncodes), logs
     assert all("RCCL" in o and "one GPU per rank" in o for o in logs), logs
 
 
@@ -277,18 +246,8 @@ def test_connect_without_finalize_is_refused(tmp_path):
     """sf3d_dist_connect alone does not connect a multi-rank model: the ranks' common decision comes with sf3d_dist_finalize (a rank
     whose windows failed while the others' passed would otherwise leave the others spinning in the in-kernel exchange): the first
     call that needs the exchange fails with a message on every rank"""
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_worker.py"), str(r), "2", "29632", "c2f20_nofinalize", str(tmp_path / f"r{r}.npz")],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
-    logs = []
-    for p in procs:
-        try:
-            o, _ = p.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(p.returncode != 0 for p in procs), logs
+    returncodes, logs, _ = mr.launch("scripts/multirank_worker.py", 2, mr.PORTS["no_finalize"], ["c2f20_nofinalize"], tmp_path, wait_all=True, limit_s=300)
+    assert all(rc != 0 for rc in returncodes), logs
     assert all("sf3d_dist_finalize" in o for o in logs), logs
 
 

@@ -7,14 +7,12 @@ Genuchten curve; hand-placed columns for the arms a run does not reach): every m
 loops over the product's getters bit for bit; another flag, one-layer calls against slices of the all-layer call, a call repeated after
 another variable; a column table of another size taken up and given back inside one model; geotechnics missing for one deep horizon."""
 import copy
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, maps
+from tests import ranks as mr
 from tests import map_cases as mpc
 from tests import sink_cases as sc
 from tests.map_cases import restated as _restated
@@ -22,7 +20,6 @@ from tests.scenarios import ravone_project_model
 from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 WINDOW = (980, 1108, 300, 428)          # the catchment's edge, four soils, short BSC columns
 STEPS = 300                             # of the 25 mm hour: ponding and runoff cells appear
 FLAG = -9999.0
@@ -304,29 +301,10 @@ def test_geotechnics_missing_for_one_deep_horizon(product, sink_pin):
     product.lib.sf3d_clean()
 
 
-def _ranks(world, port, tmp_path, steps, sparse):
-    import os
-    outs = [tmp_path / f"maps_r{r}_{port}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60"), "SF3D_TEST_SPARSE_BUILD": "1" if sparse else "0"}
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_maps_worker.py"), str(r), str(world), str(port), str(steps),
-                               str(outs[r])], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
-    return [np.load(o) for o in outs]
-
-
-@pytest.mark.parametrize("sparse,port", [(False, 29751), (True, 29753)])
+@pytest.mark.parametrize("sparse,port", [(False, mr.PORTS["output_maps"][0]), (True, mr.PORTS["output_maps"][1])])
 def test_two_ranks_merge_to_the_single_gpu_maps(product, tmp_path, sparse, port):
     steps = 150
-    ranks = _ranks(2, port, tmp_path, steps, sparse)
+    ranks = mr.run("scripts/multirank_maps_worker.py", 2, port, [steps], tmp_path, env={"SF3D_TEST_SPARSE_BUILD": "1" if sparse else "0"})
     m = ravone_project_model((980, 1060, 330, 420))
     product.check(product.lib.sf3d_reset_solver_state(), "reset")
     cm.build(product, m, threads=1)
@@ -335,24 +313,18 @@ def test_two_ranks_merge_to_the_single_gpu_maps(product, tmp_path, sparse, port)
     single = {var: maps.output_maps(product, m, var, flag=FLAG) for var in maps.LAYER_VARIABLES + (maps.FACTOR_OF_SAFETY,) + maps.COLUMN_VARIABLES}
     g_single = maps.node_getter_values(product, m.n)
     product.lib.sf3d_clean()
-    owner = np.full(m.n, 255, np.int64)                   # (a strip-local build knows the owner of the nodes it staged only)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    assert np.all(owner < 2)
+    mr.cell_owner(ranks, np.arange(m.n), m.n)               # every node has an owner (a strip-local build knows the owner of the nodes it staged only)
     index = np.asarray(m.meta["index"])
     first = np.where(index[0] >= 0, index[0], index.max(axis=0))               # a column's owner is its surface node's
-    cell_owner = np.where(first >= 0, owner[np.maximum(first, 0)], 255)
+    cell_owner = mr.cell_owner(ranks, first, m.n)
     g = {var: np.full(m.n, np.nan) for var in maps.GETTERS}
     for r, res in enumerate(ranks):
         for var in maps.GETTERS:
             g[var][res["mine"]] = res[f"get_{var}"]
     want = _restated(m, g)
     for var, s in single.items():
-        merged = np.full(s.shape, np.float32(FLAG), np.float32)
-        for r, res in enumerate(ranks):
-            mp = res[f"map_{var}"]
-            assert np.all(mp[:, cell_owner != r] == np.float32(FLAG)), (var, r)          # another rank's cells: the flag
-            merged[:, cell_owner == r] = mp[:, cell_owner == r]
+        merged = mr.merge([res[f"map_{var}"] for res in ranks], cell_owner, np.float32(FLAG), others=np.float32(FLAG), what=f"map_{var}")      # another rank's cells: the flag
+        assert merged.shape == s.shape and merged.dtype == np.float32
         assert np.array_equal(_bits(merged), _bits(want[var])), var                       # each rank's maps: its own state, restated
         assert np.array_equal(merged == np.float32(FLAG), s == np.float32(FLAG)), var
         if all(np.array_equal(g[v], g_single[v]) for v in maps.GETTERS):                  # the same state: the single-GPU maps' bits

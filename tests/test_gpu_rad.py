@@ -5,20 +5,16 @@ block in one row) that together reach the arms of the pin; the device build of s
 transmissivity taken from the meteo block on the device against the same map passed from the host; no side effect on the solver; two
 ranks sharing the GPU merge to the single-rank maps; the maps survive sf3d_initialize and go with sf3d_clean."""
 import ctypes
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, meteo, radiation as rad
+from tests import ranks as mr
 from tests import rad_cases
 from tests.test_trig_host import acos_ranges, build_trig_host, ptr, trig_ranges
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
@@ -185,35 +181,15 @@ def test_maps_survive_sf3d_initialize_and_go_with_sf3d_clean(product, pin):
 
 
 def test_two_ranks_merge_to_the_single_rank_maps(product, pin, tmp_path):
-    world, port = 2, 29791
     which = next(k for k, c in enumerate(pin["cases"]) if c["raster"] == 1 and c["name"].endswith("equinox morning"))
     first, second = pin["cases"][which], pin["cases"][which + 1]
-    outs = [tmp_path / f"rad_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
-    # each rank under its own time limit; the ranks meet in the process group, so they start together
-    procs = [subprocess.Popen(["timeout", "-k", "10", "240", sys.executable, str(ROOT / "scripts" / "multirank_rad_worker.py"), str(r), str(world), str(port),
-                               str(which), str(outs[r])], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    for r, pr in enumerate(procs):
-        o, _ = pr.communicate()
-        if pr.returncode != 0:                                            # stop at the first failure: nothing more runs on the GPU
-            for q in procs:
-                if q.poll() is None:
-                    q.kill()
-            pytest.fail(f"rank {r} ended with {pr.returncode}\n{o}")
-    ranks = [np.load(o) for o in outs]
+    ranks = mr.run("scripts/multirank_rad_worker.py", 2, mr.PORTS["rad"], [which], tmp_path)
     rows, cols = pin["dem"][1].shape
     idx = np.arange(rows * cols).reshape(rows, cols)                      # the surface node of every cell of catchment_model(cols, rows, 4)
-    owner = np.full(rows * cols * 4, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    cell_owner = owner[idx]
-    assert set(np.unique(cell_owner)) == {0, 1}
+    cell_owner = mr.cell_owner(ranks, idx, rows * cols * 4)
     flag = np.float32(pin["flag"])
     for k, case in enumerate((first, second)):
-        merged = np.full((5, rows, cols), flag, np.float32)
-        for r, res in enumerate(ranks):
-            mine = cell_owner == r
-            assert np.all(res[f"hour{k}"][:, ~mine] == flag), r           # another rank's cells: the flag
-            merged[:, mine] = res[f"hour{k}"][:, mine]
+        merged = mr.merge([res[f"hour{k}"] for res in ranks], cell_owner, flag, others=flag, what=f"hour{k}")      # another rank's cells: the flag
+        assert merged.shape == (5, rows, cols) and merged.dtype == np.float32
         _same(merged, rad_cases.pin_maps(pin, case), f"merged ranks, hour {k}")      # what the single rank gives (the first test): the pin
     assert np.count_nonzero(merged[1] > 0) > 500

@@ -1,52 +1,27 @@
 """The snow, crop and root blocks share one ownership mask on the host and one mask buffer on the device: two ranks sharing the GPU drive all
 three blocks in one process (scripts/multirank_chain_worker.py) and merge, bit for bit, to what the single rank gives for the same
 calls; a raster that is not the column table's is computed on every cell by every rank."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import crop, root, snow
+from tests import ranks as mr
 from tests import raster_chain
 from tests import root_cases as rc
 from tests.raster_helpers import bits as _bits
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def test_two_ranks_chain_the_three_blocks_and_merge_to_the_single_rank_maps(product, tmp_path):
-    world, port = 2, 29775
-    outs = [tmp_path / f"chain_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_chain_worker.py"), str(r), str(world), str(port), "0", str(outs[r])],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
-    ranks = [np.load(o) for o in outs]
+    ranks = mr.run("scripts/multirank_chain_worker.py", 2, mr.PORTS["chain"], [0], tmp_path)
     pin = rc.load_pin()
     single = raster_chain.run(product, pin)
     single.update(raster_chain.run_small(product))
     snow.clean(product); crop.clean(product); root.clean(product)
     rows, cols = pin["dem"].shape
     idx = np.arange(rows * cols).reshape(rows, cols)                      # the surface node of every cell of catchment_model(cols, rows, 4)
-    owner = np.full(rows * cols * 4, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    cell_owner = owner[idx]
-    assert set(np.unique(cell_owner)) == {0, 1}                           # both ranks own cells
-    assert all(np.count_nonzero(cell_owner == r) > 0 for r in range(world))
+    cell_owner = mr.cell_owner(ranks, idx, rows * cols * 4)                # both ranks own cells
     flag = float(pin["flag"])
     # what another rank's cells hold: the flag in the snow outputs, ET0 and the root maps (-1 in the keys), the state as it was elsewhere
     for r, res in enumerate(ranks):
@@ -59,10 +34,8 @@ def test_two_ranks_chain_the_three_blocks_and_merge_to_the_single_rank_maps(prod
             assert np.array_equal(_bits(res[n][~mine]), _bits(res["initial_" + n][~mine])), (n, r)          # untouched
     # merged by cell owner: the single rank's maps, bit for bit
     for n in raster_chain.SNOW_MAPS + raster_chain.CROP_MAPS + raster_chain.ROOT_MAPS:
-        merged = np.array(single[n])
-        merged[...] = 0
-        for r, res in enumerate(ranks):
-            merged[..., cell_owner == r] = res[n][..., cell_owner == r]
+        merged = mr.merge([res[n] for res in ranks], cell_owner, 0)
+        assert merged.shape == single[n].shape and merged.dtype == single[n].dtype, n
         bad = _bits(merged) != _bits(single[n])
         print(f"{n}: {int(bad.sum())} values differ")
         assert not bad.any(), (n, int(bad.sum()))

@@ -3,20 +3,15 @@ k_root_gather) against the compiled-reference pin tests/golden/root_density.npz:
 cells excluded; degreeDays == NULL reads the crop block's map; rasters with a partial block, less than a wave and a single row against
 the restatement; sf3d_clean and re-initialise; the solver does not notice the calls; two ranks sharing the GPU merge to the single-rank
 maps; the error codes."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, crop, root
+from tests import ranks as mr
 from tests import root_cases as rc
 from tests.raster_helpers import need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
@@ -152,38 +147,17 @@ def test_root_calls_leave_the_solver_untouched(product, pin):
 
 def test_two_ranks_merge_to_the_single_rank_maps(product, pin, tmp_path):
     _need_glibc_set(product)
-    world, port, which = 2, 29773, 2
-    outs = [tmp_path / f"root_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_root_worker.py"), str(r), str(world), str(port), str(which), str(outs[r])],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
-    ranks = [np.load(o) for o in outs]
+    which = 2
+    ranks = mr.run("scripts/multirank_root_worker.py", 2, mr.PORTS["root"], [which], tmp_path)
     rows, cols = pin["dem"].shape
     idx = np.arange(rows * cols).reshape(rows, cols)                      # the surface node of every cell of catchment_model(cols, rows, 4)
-    owner = np.full(rows * cols * 4, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    cell_owner = owner[idx]
-    assert set(np.unique(cell_owner)) == {0, 1}
+    cell_owner = mr.cell_owner(ranks, idx, rows * cols * 4)
     flag = float(pin["flag"])
     single = {n: pin[n][which] for n in rc.OUTPUTS}                       # what the single rank gives (the first test): the pin
-    merged = {n: np.full(single[n].shape, flag, single[n].dtype) for n in rc.OUTPUTS}
-    for r, res in enumerate(ranks):
-        mine = cell_owner == r
-        assert np.all(res["length"][~mine] == flag) and np.all(res["density"][:, ~mine] == flag) and np.all(res["keys"][~mine] == -1), r      # another rank's cells: the flag
-        assert np.all(res["first"][~mine] == int(flag)) and np.all(res["last"][~mine] == int(flag)), r
-        for n in rc.OUTPUTS:
-            merged[n][..., mine] = res[n][..., mine]
+    others = dict(length=flag, density=flag, first=int(flag), last=int(flag))      # another rank's cells: the flag
+    merged = {n: mr.merge([res[n] for res in ranks], cell_owner, flag, others=others.get(n), what=n) for n in rc.OUTPUTS}
+    mr.merge([res["keys"] for res in ranks], cell_owner, -1, others=-1, what="keys")
+    assert all(merged[n].shape == single[n].shape and merged[n].dtype == single[n].dtype for n in rc.OUTPUTS)
     _same(merged, single, "merged ranks")
     assert np.count_nonzero(merged["length"] > 0) > 300
 

@@ -4,15 +4,11 @@ with NULL maps read from the crop and snow blocks; the nrLayers = 1 case; sf3d_s
 call without apply against the run without it (C2's F20 hour); the crop, snow and root blocks undisturbed; two ranks sharing the GPU;
 rasters with a partial block, less than a wave and a single row against the restatement, a column table changed between two hours, and the
 output maps driven alternately with the sink hour under a table that changes."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, crop, maps, root, sinks, snow
+from tests import ranks as mr
 from tests import crop_cases as cc
 from tests import root_cases as rc
 from tests import sink_cases as sc
@@ -20,7 +16,6 @@ from tests.snow_cases import melt_forcing
 from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
@@ -290,36 +285,17 @@ def test_apply_is_the_setter_and_compute_leaves_the_solver_untouched(product, pi
 
 def test_two_ranks_merge_to_the_single_rank_sinks(product, pin, tmp_path):
     _need_glibc_set(product)
-    world, port, which = 2, 29791, 4
-    outs = [tmp_path / f"sink_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60"), "SF3D_BENCH_SHARE_GPU": "1"}
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_sink_worker.py"), str(r), str(world), str(port), str(which), str(outs[r])],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
-    ranks = [np.load(o) for o in outs]
+    which = 4
+    ranks = mr.run("scripts/multirank_sink_worker.py", 2, mr.PORTS["sink"], [which], tmp_path, env={"SF3D_BENCH_SHARE_GPU": "1"})
     flag = float(pin["flag"])
     n = len(pin["vwc"])
-    owner = np.full(n, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    assert set(np.unique(owner)) == {0, 1}
-    cell_owner = owner[:pin["dem"].size].reshape(pin["dem"].shape)      # a column goes with its surface node
-    merged = dict(sinks=np.zeros(n), evaporation=np.full(pin["dem"].shape, flag), transpiration=np.full(pin["dem"].shape, flag))
-    for r, res in enumerate(ranks):
-        mine = cell_owner == r
-        computed = mine & (pin["columns"][0] >= 0)
-        assert np.all(res["evaporation"][~computed] == flag) and np.all(res["transpiration"][~computed] == flag), r      # another rank's cells: the flag
-        assert not res["sinks"][owner != r].any(), r                                                                      # and their nodes 0
-        merged["sinks"][owner == r] = res["sinks"][owner == r]
-        merged["evaporation"][mine] = res["evaporation"][mine]
-        merged["transpiration"][mine] = res["transpiration"][mine]
+    owner = mr.cell_owner(ranks, np.arange(n), n)
+    cell_owner = mr.cell_owner(ranks, np.arange(pin["dem"].size).reshape(pin["dem"].shape), n)      # a column goes with its surface node
+    merged = dict(sinks=mr.merge([res["sinks"] for res in ranks], owner, 0.0, others=0.0, what="sinks"))      # another rank's nodes: 0
+    for name in ("evaporation", "transpiration"):
+        merged[name] = mr.merge([res[name] for res in ranks], cell_owner, flag)
+        for r, res in enumerate(ranks):
+            computed = (cell_owner == r) & (pin["columns"][0] >= 0)
+            assert np.all(res[name][~computed] == flag), (name, r)      # another rank's cells: the flag
+    assert [a.shape for a in merged.values()] == [(n,), pin["dem"].shape, pin["dem"].shape] and all(a.dtype == np.float64 for a in merged.values())
     _same(merged, {name: pin[name][which] for name in ("sinks", "evaporation", "transpiration")}, "merged ranks")

@@ -3,15 +3,13 @@ all thirteen maps after every checkpoint hour bit for bit, zero cells excluded; 
 set_state and through the application's snow/ state folder; the solver does not notice the calls; a melt hour's liquid water drives the
 product and the oracle to the same state; two ranks sharing the GPU merge to the single-rank maps; the error codes; rasters with a
 partial block, less than a wave and a single row, and a parameter set away from the defaults, against the restatement."""
-import os
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, maps, snow
+from tests import ranks as mr
 from tests import tolerances
 from tests.scenarios import ravone_project_model
 from tests import snow_cases
@@ -170,22 +168,8 @@ def test_melt_hour_drives_product_and_oracle_to_the_same_state(product, oracle):
 
 
 def test_two_ranks_merge_to_the_single_rank_maps(product, tmp_path):
-    world, port, hours = 2, 29761, 16
-    outs = [tmp_path / f"snow_r{r}.npz" for r in range(world)]
-    env = {**os.environ, "SF3D_DIST_TIMEOUT_S": os.environ.get("SF3D_DIST_TIMEOUT_S", "60")}
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "scripts" / "multirank_snow_worker.py"), str(r), str(world), str(port), str(hours), str(outs[r])],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(world)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    assert all(pr.returncode == 0 for pr in procs), "\n".join(logs)
-    ranks = [np.load(o) for o in outs]
+    hours = 16
+    ranks = mr.run("scripts/multirank_snow_worker.py", 2, mr.PORTS["snow"], [hours], tmp_path)
     m = ravone_project_model((980, 1060, 330, 420))
     idx = np.asarray(m.meta["index"])[0]
     flag = -9999.0
@@ -195,17 +179,10 @@ def test_two_ranks_merge_to_the_single_rank_maps(product, tmp_path):
         snow.compute_hour(product, met)
     single = snow.all_maps(product)
     snow.clean(product)
-    owner = np.full(m.n, 255, np.int64)
-    for r, res in enumerate(ranks):
-        owner[res["owner"] == r] = r
-    cell_owner = np.where(idx >= 0, owner[np.maximum(idx, 0)], 255)
-    assert set(np.unique(cell_owner[idx >= 0])) == {0, 1}
+    cell_owner = mr.cell_owner(ranks, idx, m.n)
     for n in snow.OUTPUT:
-        merged = np.full(dem.shape, np.float32(flag), np.float32)
-        for r, res in enumerate(ranks):
-            assert np.all(res[n][cell_owner != r] == np.float32(flag)), (n, r)       # another rank's cells: the flag
-            merged[cell_owner == r] = res[n][cell_owner == r]
-        assert np.array_equal(_bits(merged), _bits(single[n])), n
+        merged = mr.merge([res[n] for res in ranks], cell_owner, np.float32(flag), others=np.float32(flag), what=n)      # another rank's cells: the flag
+        assert merged.shape == dem.shape and merged.dtype == np.float32 and np.array_equal(_bits(merged), _bits(single[n])), n
     for n in snow.STATE:
         for r, res in enumerate(ranks):
             mine = cell_owner == r

@@ -1,29 +1,14 @@
 """N>1 path on CPU: world_size 2 and 3 over gloo (tests/partition_worker.py)."""
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm
+from tests import ranks as mr
 
-ROOT = Path(__file__).resolve().parent.parent
 
-
-@pytest.mark.parametrize("world,case,port", [(2, "grid", 29731), (3, "grid", 29732), (2, "ragged", 29733)])
-def test_sharded_jacobi_over_gloo(product, world, case, port):
-    procs = [subprocess.Popen([sys.executable, str(ROOT / "tests" / "partition_worker.py"), str(r), str(world), str(port), case],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=240)[0])
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+@pytest.mark.parametrize("world,case,port", [(2, "grid", mr.PORTS["partition_gloo"][0]), (3, "grid", mr.PORTS["partition_gloo"][1]), (2, "ragged", mr.PORTS["partition_gloo"][2])])
+def test_sharded_jacobi_over_gloo(product, tmp_path, world, case, port):
+    mr.run("tests/partition_worker.py", world, port, [case], tmp_path, outfile=False)
 
 
 def test_strips_are_row_blocks_cut_at_chunk_boundaries(product):
