@@ -10,8 +10,9 @@ Three parts:
     slope and aspect;
   * `restate_radiation_hour`: the point model cell by cell through python's `math` (the C library's sin / cos / tan / exp / pow) and
     the C library's acosf / powf (the float overloads the compiled reference calls) with the reference's types and operation order -
-    the checker of the CPU tests against the compiled-reference pin (tests/golden/rad_rsun.npz), of the GPU tests off the pin, and
-    the source of the arm table.  A checker, never a fallback."""
+    the checker of the CPU tests against the compiled-reference pins (tests/golden/rad_rsun.npz, rad_rsun_places.npz), of the GPU tests
+    off the pins, and the source of their arm tables (ARMS: the radiation model; SUN_ARMS: the sun position and its date).  A checker,
+    never a fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -263,9 +264,40 @@ def _month_days(y: int, m: int) -> int:
     return 29 if (m == 2 and _leap(y)) else (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)[m - 1]
 
 
+# arms of the sun position (S_solpos) and of its date and time, as bits: what a place other than 44 N 11 E and a year other than 2021
+# reach (the table of tests/golden/rad_rsun_places.npz).  hour_setup reports its bits as h["sunArms"] (hour_sun_arms: also for a date
+# S_solpos refuses), cell_setup as c["sunArms"], sun_position as sun["sunArms"]; restate_radiation_hour gives their union per cell.
+SUN_ARMS = ("lmst < 0", "hrang < -180", "hrang > 180", "hrang > 0", "|cz| > 1", "zenetr > 99",
+            "ssha: pole (|cd cl| < 0.001), the hemisphere of the declination", "ssha: pole (|cd cl| < 0.001), the other hemisphere",
+            "ssha: cssha < -1 (polar day)", "ssha: cssha > 1 (polar night)", "srss: ssha <= 1", "srss: ssha >= 179",
+            "tstfix > 720", "tstfix < -720", "sazm: default 180 at a pole (|cl| < 0.001)", "sazm: default 180 off the poles (|ce cl| < 0.001)",
+            "sazm: ca > 1", "sazm: ca < -1", "refrac: elevetr > 85", "refrac: elevetr >= 5", "refrac: -0.575 <= elevetr < 5", "refrac: elevetr < -0.575",
+            "elevref < -9", "zenref > 93", "coszen <= 0",
+            "validate: |latitude| > 90", "validate: |longitude| > 180", "validate: |aspect| > 360", "validate: |slope| > 180",
+            "leap year", "leap year: daynum += 1", "29 February", "day 366", "400-year rule", "100-year rule", "validate: year < 1950",
+            "local date steps back over 1 January", "local date steps back over 1 March", "ectime < 0", "mnlong < 0", "mnanom < 0")
+_SUN = {n: 1 << k for k, n in enumerate(SUN_ARMS)}
+# the arms that only some place or second reaches by the rounding of floats: a pin may miss them, with the failed search written down
+SUN_ARMS_BY_ROUNDING = ("|cz| > 1", "sazm: ca > 1", "sazm: ca < -1", "sazm: default 180 off the poles (|ce cl| < 0.001)")
+# no cell that validate() accepts reaches this one: zenetr <= 99 bounds elevetr at -9, and below -0.575 degrees the correction is
+# -20.774 / tan(elevetr) times a pressure term that validate() keeps in [0, 2000] hPa - never negative, so elevref >= elevetr >= -9
+SUN_ARMS_UNREACHABLE = ("elevref < -9",)
+
+
 def hour_setup(when, time_zone: int, is_utc: bool):
     """the date-and-time part of computeRadiationRsun and S_solpos (solarRadiation.cpp:714-726; solPos.cpp:293-331, 373-382, 426-555):
     None when S_solpos refuses the date"""
+    return _hour(when, time_zone, is_utc)[0]
+
+
+def hour_sun_arms(when, time_zone: int, is_utc: bool) -> int:
+    """the SUN_ARMS bits of the date and time, also of a date S_solpos refuses"""
+    return _hour(when, time_zone, is_utc)[1]
+
+
+def _hour(when, time_zone: int, is_utc: bool):
+    """hour_setup -> (h or None, SUN_ARMS bits)"""
+    bits = 0
     year, month, day, hour, minute, second = map(int, when)
     t = hour * 3600 + minute * 60 + second
     if is_utc:
@@ -286,17 +318,33 @@ def hour_setup(when, time_zone: int, is_utc: bool):
                 month -= 1
                 if month < 1:
                     month, year = 12, year - 1
+                    bits |= _SUN["local date steps back over 1 January"]
+                elif month == 2:
+                    bits |= _SUN["local date steps back over 1 March"]
                 day = _month_days(year, month)
     h = dict(hour=t // 3600)
     h["minute"] = (t - h["hour"] * 3600) // 60
     h["second"] = t - h["hour"] * 3600 - h["minute"] * 60
     h["localTime"] = f32(float(t))
     h["timezone"] = f32(float(time_zone))
+    if year < 1950:
+        bits |= _SUN["validate: year < 1950"]
     if year < 1950 or year > 2100 or abs(time_zone) > 12:
-        return None
+        return None, bits
     daynum = day + (0, 0, 31, 59, 90, 120, 151, 181, 212, 243, 273, 304, 334)[month]
+    if year % 400 == 0:
+        bits |= _SUN["400-year rule"]
+    elif year % 100 == 0:
+        bits |= _SUN["100-year rule"]
+    if _leap(year):
+        bits |= _SUN["leap year"]
+        if month == 2 and day == 29:
+            bits |= _SUN["29 February"]
     if _leap(year) and month > 2:
         daynum += 1
+        bits |= _SUN["leap year: daynum += 1"]
+    if daynum == 366:
+        bits |= _SUN["day 366"]
     dayang = f32(360.0 * (daynum - 1) / 365.0)
     sd = math.sin(RADDEG * dayang)
     cd = math.cos(RADDEG * dayang)
@@ -311,12 +359,17 @@ def hour_setup(when, time_zone: int, is_utc: bool):
     leap = _int(delta / 4.0)
     julday = f32(32916.5 + delta * 365.0 + leap + daynum + utime / 24.0)
     ectime = f32(julday - 51545.0)
+    if ectime < 0.0:
+        bits |= _SUN["ectime < 0"]
 
-    def wrap(v, period):
+    def wrap(v, period, arm=None):
+        nonlocal bits
         v = f32(v - f32(period * _int(v / period)))
+        if v < 0.0 and arm:
+            bits |= _SUN[arm]
         return f32(v + period) if v < 0.0 else v
-    mnlong = wrap(f32(280.460 + 0.9856474 * ectime), 360.0)
-    mnanom = wrap(f32(357.528 + 0.9856003 * ectime), 360.0)
+    mnlong = wrap(f32(280.460 + 0.9856474 * ectime), 360.0, "mnlong < 0")
+    mnanom = wrap(f32(357.528 + 0.9856003 * ectime), 360.0, "mnanom < 0")
     eclong = wrap(f32(mnlong + 1.915 * math.sin(mnanom * RADDEG) + 0.020 * math.sin(2.0 * mnanom * RADDEG)), 360.0)
     ecobli = f32(23.439 - 4.0e-07 * ectime)
     h["declin"] = f32(DEGRAD * math.asin(math.sin(ecobli * RADDEG) * math.sin(eclong * RADDEG)))
@@ -332,7 +385,8 @@ def hour_setup(when, time_zone: int, is_utc: bool):
     h["cd"] = f32(math.cos(RADDEG * h["declin"]))
     h["sd"] = f32(math.sin(RADDEG * h["declin"]))
     h["etrn"] = f32(1367.0 * erv)
-    return h
+    h["sunArms"] = bits
+    return h, bits
 
 
 def cell_setup(height: float, lat: float, lon: float, slope: float, aspect: float) -> dict:
@@ -349,6 +403,8 @@ def cell_setup(height: float, lat: float, lon: float, slope: float, aspect: floa
     c["Fg"] = c["sinSlope"] - slope_rad * c["cosSlope"] - PI * (half * half)
     c["reflGeom"] = 1. - math.cos(slope * DEG_TO_RAD)
     c["ok"] = not (abs(lon) > 180. or abs(lat) > 90. or c["press"] < 0.0 or c["press"] > 2000.0 or abs(slope) > 180.0 or abs(aspect) > 360.0)
+    c["sunArms"] = (_SUN["validate: |latitude| > 90"] if abs(lat) > 90. else 0) | (_SUN["validate: |longitude| > 180"] if abs(lon) > 180. else 0) \
+        | (_SUN["validate: |aspect| > 360"] if abs(aspect) > 360.0 else 0) | (_SUN["validate: |slope| > 180"] if abs(slope) > 180.0 else 0)
     return c
 
 
@@ -357,46 +413,60 @@ def sun_position(h: dict, c: dict):
     if not c["ok"]:
         return None
     sin, cos, tan = math.sin, math.cos, math.tan
+    bits = 0
     lmst = f32(f32(h["gmst"] * 15.) + c["lon"])
     lmst = f32(lmst - f32(360.0 * _int(lmst / 360.0)))
     if lmst < 0.:
         lmst = f32(lmst + 360.0)
+        bits |= _SUN["lmst < 0"]
     hrang = f32(lmst - h["rascen"])
     if hrang < -180.0:
         hrang = f32(hrang + 360.0)
+        bits |= _SUN["hrang < -180"]
     elif hrang > 180.0:
         hrang = f32(hrang - 360.0)
+        bits |= _SUN["hrang > 180"]
     ch = f32(cos(RADDEG * hrang))
     cz = f32(f32(h["sd"] * c["sl"]) + f32(f32(h["cd"] * c["cl"]) * ch))
     if abs(cz) > 1.0:
         cz = 1.0 if cz >= 0.0 else -1.0
+        bits |= _SUN["|cz| > 1"]
     zenetr = f32(_acosf(cz) * DEGRAD)
     if zenetr > 99.0:
         zenetr = 99.0
+        bits |= _SUN["zenetr > 99"]
     elevetr = f32(90. - zenetr)
     cdcl = f32(h["cd"] * c["cl"])
     if abs(cdcl) >= 0.001:
         cssha = f32(f32(-c["sl"] * h["sd"]) / cdcl)
         if cssha < -1.0:
             ssha = 180.0
+            bits |= _SUN["ssha: cssha < -1 (polar day)"]
         elif cssha > 1.0:
             ssha = 0.0
+            bits |= _SUN["ssha: cssha > 1 (polar night)"]
         else:
             ssha = f32(DEGRAD * _acosf(cssha))
     elif (h["declin"] >= 0.0 and c["lat"] > 0.0) or (h["declin"] < 0.0 and c["lat"] < 0.0):
         ssha = 180.0
+        bits |= _SUN["ssha: pole (|cd cl| < 0.001), the hemisphere of the declination"]
     else:
         ssha = 0.0
+        bits |= _SUN["ssha: pole (|cd cl| < 0.001), the other hemisphere"]
     tst = f32(f32(180. + hrang) * 4.)
     tstfix = f32(f32(f32(f32(tst - f32(h["hour"] * 60.)) - float(h["minute"])) - f32(h["second"] / 60.)) + 0.0)
     while tstfix > 720.0:
         tstfix = f32(tstfix - 1440.0)
+        bits |= _SUN["tstfix > 720"]
     while tstfix < -720.0:
         tstfix = f32(tstfix + 1440.0)
+        bits |= _SUN["tstfix < -720"]
     if ssha <= 1.0:
         sretr, ssetr = 2999.0, -2999.0
+        bits |= _SUN["srss: ssha <= 1"]
     elif ssha >= 179.0:
         sretr, ssetr = -2999.0, 2999.0
+        bits |= _SUN["srss: ssha >= 179"]
     else:
         sretr = f32(720.0 - 4.0 * ssha - tstfix)
         ssetr = f32(720.0 + 4.0 * ssha - tstfix)
@@ -408,31 +478,42 @@ def sun_position(h: dict, c: dict):
         ca = f32(f32(f32(se * c["sl"]) - h["sd"]) / cecl)
         if ca > 1.0:
             ca = 1.0
+            bits |= _SUN["sazm: ca > 1"]
         elif ca < -1.0:
             ca = -1.0
+            bits |= _SUN["sazm: ca < -1"]
         azim = f32(180. - f32(_acosf(ca) * DEGRAD))
         if hrang > 0:
             azim = f32(360. - azim)
+            bits |= _SUN["hrang > 0"]
+    else:
+        bits |= _SUN["sazm: default 180 at a pole (|cl| < 0.001)" if abs(c["cl"]) < 0.001 else "sazm: default 180 off the poles (|ce cl| < 0.001)"]
     if elevetr > 85.0:
         refcor = 0.0
+        bits |= _SUN["refrac: elevetr > 85"]
     else:
         tanelev = tan(RADDEG * elevetr)
         if elevetr >= 5.0:
             refcor = _div(58.1, tanelev) - _div(0.07, _pow(tanelev, 3)) + _div(0.000086, _pow(tanelev, 5))
+            bits |= _SUN["refrac: elevetr >= 5"]
         elif elevetr >= -0.575:
             refcor = 1735.0 + elevetr * (-518.2 + elevetr * (103.4 + elevetr * (-12.79 + elevetr * 0.711)))
+            bits |= _SUN["refrac: -0.575 <= elevetr < 5"]
         else:
             refcor = _div(-20.774, tanelev)
+            bits |= _SUN["refrac: elevetr < -0.575"]
         prestemp = (c["press"] * 283.0) / (1013.0 * (273.0 + TEMPERATURE_DEFAULT))
         refcor *= f32(prestemp / 3600.0)
     elevref = f32(elevetr + refcor)
     if elevref < -9.0:
         elevref = -9.0
+        bits |= _SUN["elevref < -9"]
     zenref = f32(90.0 - elevref)
     cos_zenref = cos(RADDEG * zenref)
     coszen = f32(cos_zenref)
     if zenref > 93.0:
         ampress = -1.0
+        bits |= _SUN["zenref > 93"]
     else:
         amass = f32(_div(1.0, f32(cos_zenref + f32(f32(0.50572) * _powf(f32(f32(96.07995) - zenref), f32(-1.6364))))))
         ampress = f32(f32(amass * c["press"]) / 1013.0)
@@ -441,12 +522,13 @@ def sun_position(h: dict, c: dict):
         etr = f32(etrn * coszen)
     else:
         etrn = etr = 0.0
+        bits |= _SUN["coszen <= 0"]
     ca_ = cos(RADDEG * azim)
     sa_ = sin(RADDEG * azim)
     sz = sin(RADDEG * zenref)
     cosinc = f32(coszen * c["ct"] + sz * c["st"] * (ca_ * c["cp"] + sa_ * c["sp"]))
     return dict(relOptAirMassCorr=ampress, azimuth=azim, elevationRefr=elevref, extraIrradianceHorizontal=etr, extraIrradianceNormal=etrn,
-                incidence=f32(_max(0., RAD_TO_DEG * ((PI / 2.0) - _acosf(cosinc)))), rise=f32(sretr * 60.), set=f32(ssetr * 60.))
+                incidence=f32(_max(0., RAD_TO_DEG * ((PI / 2.0) - _acosf(cosinc)))), rise=f32(sretr * 60.), set=f32(ssetr * 60.), sunArms=bits)
 
 
 # arms of the point model, as bits (the arm table of tests/golden/rad_rsun.npz)
@@ -512,11 +594,14 @@ def _separate(clear_sky, transmissivity, elev_deg, sin_elev_deg):
     return tt * kd_r, tt, arm
 
 
-def rad_point(grid: dict, h: dict, c: dict, row: int, col: int, transmissivity: float):
-    """computeRadiationDemPoint + computeRadiationRsun -> (the five values or None when nothing is written, arm bits)"""
+def rad_point(grid: dict, h: dict, c: dict, row: int, col: int, transmissivity: float, sun_arms: list | None = None):
+    """computeRadiationDemPoint + computeRadiationRsun -> (the five values or None when nothing is written, arm bits); sun_arms: a list that
+    receives the SUN_ARMS bits of the cell's sun position"""
     sun = sun_position(h, c)
     if sun is None:
         return None, _ARM["false: S_solpos range check"]
+    if sun_arms is not None:
+        sun_arms.append(sun["sunArms"])
     lit = False
     if sun["rise"] != NODATA and sun["set"] != NODATA and sun["elevationRefr"] != NODATA:
         lit = h["localTime"] >= sun["rise"] and h["localTime"] <= sun["set"] and sun["elevationRefr"] > 0
@@ -621,13 +706,16 @@ def rad_point(grid: dict, h: dict, c: dict, row: int, col: int, transmissivity: 
 
 
 def restate_radiation_hour(dem, flag, xll, yll, cell_size, lat, lon, slope, aspect, when, transmissivity, settings: dict | None = None, previous=None,
-                           mine=None):
+                           mine=None, sun_arms=None):
     """computeRadiationDEM on the host -> (the five maps [5, rows, cols] float32, arm bits [rows, cols] int64), or (None, None) when S_solpos
-    refuses the date.  previous: the maps of the hour before (the flag everywhere without); mine: bool mask of the cells to compute"""
+    refuses the date.  previous: the maps of the hour before (the flag everywhere without); mine: bool mask of the cells to compute;
+    sun_arms: an int64 array [rows, cols] that receives the SUN_ARMS bits of every computed cell (also when the date is refused)"""
     s = settings_dict(settings)
     dem = np.ascontiguousarray(dem, np.float32)
-    h = hour_setup(when, int(s["timeZone"]), bool(s["isUTC"]))
+    h, hour_bits = _hour(when, int(s["timeZone"]), bool(s["isUTC"]))
     if h is None:
+        if sun_arms is not None:
+            sun_arms[...] = np.where((np.abs(dem.astype(np.float64) - float(flag)) >= EPSILON) & (True if mine is None else mine), hour_bits, 0)
         return None, None
     month = int(when[1])
     if s["linkeMode"] == MODE_MONTHLY:
@@ -651,8 +739,11 @@ def restate_radiation_hour(dem, flag, xll, yll, cell_size, lat, lon, slope, aspe
                 continue
             c = cell_setup(float(dem[row, col]), float(lat[row, col]), float(lon[row, col]),
                            f32(s["tilt"]) if fixed else float(slope[row, col]), f32(s["aspect"]) if fixed else float(aspect[row, col]))
-            v, a = rad_point(grid, h, c, row, col, float(trans[row, col]))
+            position = []
+            v, a = rad_point(grid, h, c, row, col, float(trans[row, col]), position)
             arms[row, col] = a
+            if sun_arms is not None:
+                sun_arms[row, col] = hour_bits | c["sunArms"] | sum(position)
             if v is not None:
                 out[:, row, col] = v
     return out, arms

@@ -21,7 +21,7 @@ PORTS = {
     "rccl_refused": 29631, "no_finalize": 29632,        # test_gpu_multirank.py's two negative tests: no second run, no retry
     "partition_gloo": (29731, 29732, 29733),
     "output_maps": (29751, 29753),
-    "snow": 29761, "crop": 29771, "root": 29773, "chain": 29775, "meteo": 29777, "sink": 29791, "rad": 29793,
+    "snow": 29761, "crop": 29771, "root": 29773, "chain": 29775, "meteo": 29777, "sink": 29791, "rad": 29793, "rad_places": 29795,
 }
 
 

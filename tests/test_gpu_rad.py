@@ -3,7 +3,13 @@ tests/golden/rad_rsun.npz: every cell of every map and case bit for bit, both ho
 off the pin against the restatement on 7 x 37, 3 x 11 and 1 x 300 rasters (a partial second block, less than a wave, a partial second
 block in one row) that together reach the arms of the pin; the device build of sf3d_trig.inc against its host build bit for bit;
 transmissivity taken from the meteo block on the device against the same map passed from the host; no side effect on the solver; two
-ranks sharing the GPU merge to the single-rank maps; the maps survive sf3d_initialize and go with sf3d_clean."""
+ranks sharing the GPU merge to the single-rank maps; the maps survive sf3d_initialize and go with sf3d_clean.
+
+Away from 44 N 11 E and from 2021 (tests/golden/rad_rsun_places.npz, the second pin of the compiled reference): every cell of its 39
+cases at 69.67 N, 0.23 N, 33.93 S, 122.4 W and 178.9 W with 4, 10 and 2.5 m cells, cells edited to the poles, the date line and out of
+validate()'s range, leap years, the century rules, dates before 2000 and a refused local year, with the latitude and longitude maps of
+the pin; 7 x 37 and 3 x 11 rasters at 80 N, 80 S, the equator and a pole row against the restatement, whose chains reach every
+sun-position arm (rad.SUN_ARMS) the pin reaches; two ranks on the southern raster merge to the pin."""
 import ctypes
 
 import numpy as np
@@ -31,8 +37,13 @@ def _maps(product):
     return np.stack([rad.get_map(product, n) for n in rad.MAPS])
 
 
+@pytest.fixture(scope="module")
+def places():
+    return rad_cases.load_places_pin()
+
+
 def _start_pin(product, pin, raster, settings):
-    geo = pin["geo"]
+    geo = rad_cases.pin_geo(pin, raster)
     dummy = pin["dem"][raster]                   # map mode needs a map; the reference never reads it inside the grid
     s = rad.settings_dict(settings)
     rad.initialize(product, pin["dem"][raster], geo[0], geo[1], geo[2], pin["lat"][raster], pin["lon"][raster], pin["slope"][raster], pin["aspect"][raster],
@@ -40,7 +51,7 @@ def _start_pin(product, pin, raster, settings):
                    settings=settings, flag=float(pin["flag"]))
 
 
-def test_every_cell_of_every_map_and_case_equals_the_pin(product, pin):
+def _every_cell(product, pin):
     checked = 0
     for raster, chain in rad_cases.pin_chains(pin):
         _start_pin(product, pin, raster, chain[0]["settings"])
@@ -53,7 +64,19 @@ def test_every_cell_of_every_map_and_case_equals_the_pin(product, pin):
             _same(_maps(product), rad_cases.pin_maps(pin, case), case["name"])
             checked += 1
     rad.clean(product)
-    assert checked == len(pin["cases"])
+    return checked
+
+
+def test_every_cell_of_every_map_and_case_equals_the_pin(product, pin):
+    assert _every_cell(product, pin) == len(pin["cases"])
+
+
+def test_every_cell_of_the_places_pin(product, places):
+    """five other places (polar, equator, southern, two western), cells edited to the poles, the date line and out of validate()'s range,
+    leap years and centuries: the latitude and longitude maps are the pin's; the refused hour is SF3D_PARAMETER_ERROR and leaves the maps"""
+    refused = [c for c in places["cases"] if "refuses" in c["name"]]
+    assert len(refused) == 1 and refused[0]["keep"] == 1
+    assert _every_cell(product, places) == len(places["cases"]) >= 36
 
 
 @pytest.mark.parametrize("shape", rad_cases.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
@@ -78,6 +101,29 @@ def test_small_rasters_equal_the_restatement(product, shape):
         for _, arms in hours:
             every |= int(np.bitwise_or.reduce(arms, axis=None))
     assert every == (1 << len(rad.ARMS)) - 1                              # together the three rasters reach the arms of the pin
+
+
+@pytest.mark.parametrize("shape", rad_cases.SHAPES_PLACES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_small_rasters_at_other_places_equal_the_restatement(product, shape):
+    ref, reached = rad_cases.small_reference_places()
+    refused = 0
+    for name, place, settings, hours in rad_cases.small_chains_places():
+        g = rad_cases.small_raster(shape, place)
+        s = rad.settings_dict(settings)
+        rad.initialize(product, g["dem"], *g["geo"], g["lat"], g["lon"], g["slope"], g["aspect"], settings=settings, flag=float(rad_cases.FLAG))
+        for k, (when, tk) in enumerate(hours):
+            t = g["transmissivity"][tk]
+            if rad.hour_setup(when, s["timeZone"], bool(s["isUTC"])) is None:             # S_solpos refuses the date: the maps stay
+                assert product.lib.sf3d_rad_compute_hour(*when, t.size, t.ctypes.data_as(capi.pf32)) == capi.PARAMETER_ERROR
+                refused += 1
+            else:
+                rad.compute_hour(product, when, t)
+            _same(_maps(product), ref[(shape, name)][k][0], (shape, name, k))
+    rad.clean(product)
+    assert refused == 1
+    # what the kernel ran here is what tests/test_rad_host.py counts on the CPU: every sun-position arm the places pin reaches
+    pin = rad_cases.load_places_pin()
+    assert {n for k, n in enumerate(rad.SUN_ARMS) if reached >> k & 1} == {n for n, k in zip(pin["sun_arm_names"], pin["sun_arm_counts"]) if k > 0}
 
 
 def test_device_trig_equals_the_host_build_bit_for_bit(product, tmp_path):
@@ -193,3 +239,20 @@ def test_two_ranks_merge_to_the_single_rank_maps(product, pin, tmp_path):
         assert merged.shape == (5, rows, cols) and merged.dtype == np.float32
         _same(merged, rad_cases.pin_maps(pin, case), f"merged ranks, hour {k}")      # what the single rank gives (the first test): the pin
     assert np.count_nonzero(merged[1] > 0) > 500
+
+
+def test_two_ranks_merge_to_the_places_pin_on_the_southern_raster(product, places, tmp_path):
+    pin = places
+    which = next(k for k, c in enumerate(pin["cases"]) if c["name"].startswith("south: 21 June 2021, morning"))
+    first, second = pin["cases"][which], pin["cases"][which + 1]
+    assert second["keep"] and pin["places"][first["raster"]]["startLatitude"] < 0
+    ranks = mr.run("scripts/multirank_rad_worker.py", 2, mr.PORTS["rad_places"], [which, "places"], tmp_path)
+    rows, cols = pin["dem"][first["raster"]].shape
+    idx = np.arange(rows * cols).reshape(rows, cols)
+    cell_owner = mr.cell_owner(ranks, idx, rows * cols * 4)
+    flag = np.float32(pin["flag"])
+    for k, case in enumerate((first, second)):
+        merged = mr.merge([res[f"hour{k}"] for res in ranks], cell_owner, flag, others=flag, what=f"hour{k}")
+        assert merged.shape == (5, rows, cols) and merged.dtype == np.float32
+        _same(merged, rad_cases.pin_maps(pin, case), f"merged ranks, hour {k}")
+    assert np.count_nonzero(merged[1] > 0) > 200
