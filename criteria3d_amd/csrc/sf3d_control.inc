@@ -322,7 +322,11 @@ __global__ void k_step_begin(Ctrl* c, double maxTimeStep)
 {
     c->maxTimeStep = maxTimeStep;
     c->seqCount = 0;
-    c->aBuf ^= 1u;              /* the matrix of the step accepted before stays intact for its link flow sums (k_accept_links) */
+    {   /* the next slot of the ring: the matrices of the steps accepted before stay intact until their link flow sums are added (k_links_flush) */
+        const uint32_t ring = c->aRing < 2u ? 2u : (c->aRing > (uint32_t)SF3D_LINKS_RING ? (uint32_t)SF3D_LINKS_RING : c->aRing);
+        const uint32_t nx = c->aBuf + 1u;
+        c->aBuf = nx < ring ? nx : 0u;
+    }
     begin_attempt(c);
 }
 

@@ -27,6 +27,10 @@
 #include <stdint.h>
 
 #define SF3D_SLOTS 10
+#ifndef SF3D_LINKS_RING
+#define SF3D_LINKS_RING 8        /* accepted steps whose link flow sums one pass of k_links_flush adds (DevView::A2x, DevView::Hring) */
+#endif
+static_assert(SF3D_LINKS_RING >= 2 && SF3D_LINKS_RING <= 16, "the ring holds the matrix of the step in progress and at least one accepted step's");
 #define SF3D_POOL 5              /* H, Hold, Hbest + two free buffers: the paired sweep writes x' and x'' in one pass */
 #define SF3D_BLOCK 256
 #define SF3D_CHUNK 64            /* one wave64 = 64 consecutive nodes */
@@ -120,9 +124,10 @@ struct Ctrl {
     uint32_t distSilent;    /* ... bit p: rank p was the one that did not answer */
     uint32_t pairRecTimeout; /* 1: a block of a paired pass waited longer than the bound for a neighbouring strip's record (PairGrid::records) */
     uint32_t kfEpoch, haloEpoch, haloPar; int32_t haloBuf;   /* multi GPU: which exchange the many-block halo copies (k_halo_copy) belong to */
-    int32_t acceptBuf;      /* pool index of the accepted H: the link flow sums of the step are added from it ... */
-    uint32_t aBuf, acceptABuf;   /* which A2x the step in progress uses / the accepted step used */
-    double acceptDt;        /* ... with this dt, possibly while the next step's first kernels already run */
+    int32_t acceptBuf;      /* pool index of the accepted H (k_accept_boundary keeps a copy of it in DevView::Hring[acceptABuf]) ... */
+    uint32_t aBuf, acceptABuf;   /* which A2x the step in progress uses / the accepted step used: slots of the ring, < aRing */
+    uint32_t aRing;         /* slots of that ring: SF3D_LINKS_RING where the link flow sums are added in batches, 2 elsewhere (set at build) */
+    double acceptDt;        /* ... with this dt: the host keeps (acceptABuf, acceptDt) of every accepted step until k_links_flush has added its sums */
     /* ---- balances (balanceData_t x4, soilFluxes3D.cpp:37) ---- */
     BalanceDev curStep, prevStep, curPeriod, wholePeriod;
     /* ---- heat part of the step ---- */
@@ -331,6 +336,9 @@ struct ResGrid {
                                          * edge_rows_direct): the records are stored without a walk through the chunk's send list */
 };
 
+/* the accepted steps one launch of k_links_flush adds, in acceptance order */
+struct LinksBatch { uint32_t n, slot[SF3D_LINKS_RING]; double dt[SF3D_LINKS_RING]; };
+
 struct DevView {
     uint32_t N, ns, nb;                 /* nodes, surface nodes, blocks of SF3D_BLOCK threads */
     uint32_t Nnorm;                     /* node count the mean norm of a sweep divides by: N, or the global count for a strip-local model */
@@ -370,10 +378,14 @@ struct DevView {
                                          * neighbour index evaluates it, or the only one where the link has no reverse) */
     const double *larea, *ldist;        /* [10][N] interface area (read only where a chunk's areas differ) and link distance */
     double* lflowSum;                   /* [10][N] */
-    sf3d_d2* A2x[2];                    /* two copies of [5][N] row-normalised off-diagonals, slots paired (2p, 2p+1): 16-byte accesses.  The
-                                         * computeStep in progress assembles and sweeps A2x[Ctrl::aBuf]; k_step_begin flips aBuf, so the matrix of
-                                         * the step accepted before stays intact while its link flow sums are still being added (k_accept_links on the
-                                         * second stream, next to the whole next step instead of next to its k_props only) */
+    sf3d_d2* A2x[SF3D_LINKS_RING];      /* a ring of [5][N] row-normalised off-diagonals, slots paired (2p, 2p+1): 16-byte accesses.  The
+                                         * computeStep in progress assembles and sweeps A2x[Ctrl::aBuf]; k_step_begin moves aBuf one slot on
+                                         * (mod Ctrl::aRing), so the matrices of the accepted steps before it stay intact until one pass of
+                                         * k_links_flush has added their link flow sums.  Ctrl::aRing of them are allocated: SF3D_LINKS_RING
+                                         * on the plain single-GPU path, 2 elsewhere (the sums are added inside the step there) */
+    double* Hring[SF3D_LINKS_RING];     /* [N] each: the accepted head of the step that used the same slot of A2x (k_accept_boundary copies
+                                         * it: the pool buffer is recycled two steps later, and a state setter may overwrite it); null
+                                         * where the sums are added inside the step */
     double *b, *C;
     double* X[SF3D_POOL];
     double *Se, *SeHold, *K, *flow, *bflowRate, *bflowSum;   /* SeHold = Se(Hold), written at approximation 0 */

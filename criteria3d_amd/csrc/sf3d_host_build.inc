@@ -190,10 +190,11 @@ struct SinkCache {
 struct DeviceSolver::Impl {
     int device = -1;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;         /* link flow sums of the accepted step, next to the next step's k_props */
-    hipEvent_t evLinks[2] = {nullptr, nullptr};   /* one per copy of the matrix: recorded after the link sums that read it */
-    bool linksPending[2] = {false, false};
     int overlapAccept = -1;                /* SF3D_OVERLAP_ACCEPT=0 keeps k_accept inside the step */
+    /* link flow sums in batches (plain single-GPU path): the slots of the two rings (DevView::A2x, DevView::Hring) and the time steps of the
+     * accepted steps whose sums are not added yet, in acceptance order.  ring: the model has the rings (0: two matrices, sums inside the step) */
+    uint32_t ring = 0;
+    LinksBatch pend{};
     DevView v{};
     Ctrl* hostCtrl = nullptr;              /* pinned */
     std::vector<void*> allocs;
@@ -276,6 +277,33 @@ struct DeviceSolver::Impl {
         pGroupEnd();
     }
     void rccl_gather(hipStream_t st) { pAllGather(rcclMine, rcclGathered, 4, ncclDouble, comm, st); }
+    /* blocks of kernel `fn` resident at once (occupancy x CUs), remembered per kernel; SF3D_RESIDENT_GRIDS=0: the common grid */
+    uint32_t resident_blocks(const void* fn)
+    {
+        for (auto& r : residentBlocks) if (r.first == fn) return r.second;
+        int perCu = 0, dev = 0; hipDeviceProp_t prop;
+        uint32_t nbk = SF3D_MAX_BLOCKS;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, fn, SF3D_BLOCK, 0) == hipSuccess && perCu > 0
+            && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+            nbk = (uint32_t)perCu * (uint32_t)prop.multiProcessorCount;
+        if (residentGrids == 0) nbk = SF3D_MAX_BLOCKS;
+        residentBlocks.push_back({fn, nbk});
+        return nbk;
+    }
+    /* add the link flow sums of every pending accepted step, in their order, in one pass (k_links_flush) on the solver's stream: whatever
+     * is queued on that stream afterwards - a step, a copy of the sums, an output map - finds them added */
+    hipError_t flush_links()
+    {
+        if (pend.n == 0) return hipSuccess;
+        const void* fn = v.ntStream ? (const void*)k_links_flush<true> : (const void*)k_links_flush<false>;
+        const uint32_t nbk = resident_blocks(fn);
+        const dim3 fgrid(v.nb < nbk ? v.nb : nbk);
+        if (v.ntStream) hipLaunchKernelGGL(k_links_flush<true>, fgrid, dim3(SF3D_BLOCK), 0, stream, v, pend);
+        else hipLaunchKernelGGL(k_links_flush<false>, fgrid, dim3(SF3D_BLOCK), 0, stream, v, pend);
+        pend.n = 0;
+        return hipGetLastError();
+    }
+    bool links_pending(uint32_t slot) const { for (uint32_t k = 0; k < pend.n; ++k) if (pend.slot[k] == slot) return true; return false; }
     /* device slot of every (host slot, node): empty = identity.  Laterals of nodes with fewer links than their chunk's fullest node are
      * moved to the slots where that node keeps the same neighbour offset (sync_to_device), so that a slot means one direction for the
      * whole chunk; host arrays (HostModel, what the API reads and writes) stay in insertion order, the permutation is applied where
@@ -352,7 +380,6 @@ sf3d_error_t DeviceSolver::release()
     if (!impl_) return SF3D_OK;
     Impl& I = *impl_;
     if (I.stream) hipStreamSynchronize(I.stream);
-    if (I.stream2) hipStreamSynchronize(I.stream2);
     if (I.stream3) hipStreamSynchronize(I.stream3);
 #if SF3D_RES_PROFILE
     if (built_ && I.v.res.on && I.v.res.pub) {      /* tuning builds: where block 0 of the resident sweep loop spent its time */
@@ -364,7 +391,7 @@ sf3d_error_t DeviceSolver::release()
         }
     }
 #endif
-    I.linksPending[0] = I.linksPending[1] = false;
+    I.pend.n = 0; I.ring = 0;      /* pending link flow sums go with the arrays they would read (a caller that wants them has fetched them: sync_to_device) */
     if (I.stream3) {      /* the slab experiment's stream and events go with the model (created again on demand) */
         (void)hipStreamDestroy(I.stream3); I.stream3 = nullptr;
         for (auto& ev : I.evSlab) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
@@ -397,8 +424,8 @@ sf3d_error_t DeviceSolver::release()
 sf3d_error_t DeviceSolver::synchronize()
 {
     if (!impl_ || !impl_->stream) return SF3D_OK;
+    if (built_) HIP_TRY(impl_->flush_links());      /* where a caller asks for finished results: the link flow sums of the accepted steps still pending */
     HIP_TRY(hipStreamSynchronize(impl_->stream));
-    if (impl_->stream2) { HIP_TRY(hipStreamSynchronize(impl_->stream2)); impl_->linksPending[0] = impl_->linksPending[1] = false; }
     return SF3D_OK;
 }
 
@@ -452,7 +479,8 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
 {
     { const sf3d_error_t e = ensure_device(); if (e != SF3D_OK) return e; }
     Impl& I = *impl_;
-    if ((I.linksPending[0] || I.linksPending[1]) && (m.graphDirty || m.stateDirty || m.flowSumsDirty || !built_)) { HIP_TRY(hipStreamSynchronize(I.stream2)); I.linksPending[0] = I.linksPending[1] = false; }
+    /* pending link flow sums are added before anything below re-creates the arrays they read (release) or uploads sums or state */
+    if (I.pend.n && built_ && (m.graphDirty || m.stateDirty || m.flowSumsDirty)) HIP_TRY(I.flush_links());
     if (!I.hostCtrl) HIP_TRY(hipHostMalloc((void**)&I.hostCtrl, sizeof(Ctrl), hipHostMallocDefault));
 
     const uint32_t N = m.N, ns = m.ns;
@@ -891,6 +919,27 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         HIP_TRY(dev_alloc(I.allocs, lto, NS)); HIP_TRY(dev_alloc(I.allocs, lkind, NS));
         HIP_TRY(dev_alloc(I.allocs, larea, NS)); HIP_TRY(dev_alloc(I.allocs, ldist, NS));
         HIP_TRY(dev_alloc(I.allocs, v.lflowSum, NS)); HIP_TRY(dev_alloc(I.allocs, v.A2x[0], NS / 2)); HIP_TRY(dev_alloc(I.allocs, v.A2x[1], NS / 2));
+        {   /* link flow sums in batches - the plain single-GPU path (SF3D_OVERLAP_ACCEPT not 0, no quirk-1 compat rows): SF3D_LINKS_RING matrices
+             * instead of two and as many copies of an accepted head, R x 88 B per node.  Memory that is not there is no error: the model
+             * then runs with the two matrices and adds the sums inside every step */
+            const char* oe = getenv("SF3D_OVERLAP_ACCEPT");
+            I.overlapAccept = (oe && oe[0] == '0') ? 0 : 1;
+            I.ring = 0; I.pend.n = 0;
+            if (I.overlapAccept && world_ == 1 && !m.compat) {
+                const size_t keep = I.allocs.size(); const uint64_t bytesBefore = g_deviceBytes;
+                bool ok = true;
+                for (int k = 2; k < SF3D_LINKS_RING && ok; ++k) ok = dev_alloc(I.allocs, v.A2x[k], NS / 2) == hipSuccess;
+                for (int k = 0; k < SF3D_LINKS_RING && ok; ++k) ok = dev_alloc(I.allocs, v.Hring[k], N) == hipSuccess;
+                if (ok) I.ring = SF3D_LINKS_RING;
+                else {
+                    (void)hipGetLastError();
+                    while (I.allocs.size() > keep) { (void)hipFree(I.allocs.back()); I.allocs.pop_back(); }
+                    g_deviceBytes = bytesBefore;
+                    for (int k = 2; k < SF3D_LINKS_RING; ++k) v.A2x[k] = nullptr;
+                    for (int k = 0; k < SF3D_LINKS_RING; ++k) v.Hring[k] = nullptr;
+                }
+            }
+        }
         HIP_TRY(dev_alloc(I.allocs, v.b, N)); HIP_TRY(dev_alloc(I.allocs, v.C, N));
         for (int k = 0; k < SF3D_POOL; ++k) HIP_TRY(dev_alloc(I.allocs, v.X[k], N));
         HIP_TRY(dev_alloc(I.allocs, v.Se, N)); HIP_TRY(dev_alloc(I.allocs, v.K, N)); HIP_TRY(dev_alloc(I.allocs, v.SeHold, N));
@@ -1538,7 +1587,9 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         HIP_TRY(hipMemcpy(dcdesc, cdesc.data(), cdesc.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice));
         if (!sd.empty()) HIP_TRY(hipMemcpy(soils, sd.data(), sd.size() * sizeof(SoilDev), hipMemcpyHostToDevice));
         if (!m.roughness.empty()) HIP_TRY(hipMemcpy(roughness, m.roughness.data(), m.roughness.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(v.A2x[0], 0, NS * 8)); HIP_TRY(hipMemset(v.A2x[1], 0, NS * 8)); HIP_TRY(hipMemset(v.b, 0, N * 8)); HIP_TRY(hipMemset(v.C, 0, N * 8));
+        for (uint32_t k = 0; k < (I.ring ? I.ring : 2u); ++k) HIP_TRY(hipMemset(v.A2x[k], 0, NS * 8));
+        for (uint32_t k = 0; k < I.ring; ++k) HIP_TRY(hipMemset(v.Hring[k], 0, N * 8));
+        HIP_TRY(hipMemset(v.b, 0, N * 8)); HIP_TRY(hipMemset(v.C, 0, N * 8));
         HIP_TRY(hipMemset(v.flow, 0, N * 8)); HIP_TRY(hipMemset(v.bflowRate, 0, N * 8)); HIP_TRY(hipMemset(v.SeHold, 0, N * 8));
         for (int k = 0; k < SF3D_POOL; ++k) HIP_TRY(hipMemset(v.X[k], 0, N * 8));
         if (m.heat && I.heatAirP) hipLaunchKernelGGL(k_heat_static, dim3(v.nb), dim3(SF3D_BLOCK), 0, 0, v, I.heatAirP);
@@ -1548,6 +1599,7 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         mirror_.cur = 0; mirror_.hold = 0; mirror_.best = -1; mirror_.stage = ST_IDLE;
         mirror_.bestMBR = NODATA_D;
         mirror_.tCur = 0; mirror_.tOld = 0; mirror_.hStage = HS_IDLE;
+        mirror_.aRing = I.ring ? I.ring : 2u;
         built_ = true;
         m.graphDirty = false;
         m.stateDirty = m.sinkDirty = m.pondDirty = m.boundaryDirty = m.flowSumsDirty = m.ctrlDirty = true;

@@ -15,7 +15,7 @@ sf3d_error_t DeviceSolver::fetch_flows(HostModel& m)
 {
     Impl& I = *impl_;
     const size_t N = m.N;
-    if (I.stream2) { HIP_TRY(hipStreamSynchronize(I.stream2)); I.linksPending[0] = I.linksPending[1] = false; }     /* link flow sums of the last step */
+    HIP_TRY(I.flush_links());      /* link flow sums of the accepted steps still pending: added on the stream the copies below are queued on */
     HIP_TRY(hipMemcpyAsync(m.bflowSum.data(), I.v.bflowSum, N * 8, hipMemcpyDeviceToHost, I.stream));
     HIP_TRY(hipMemcpyAsync(m.bflowRate.data(), I.v.bflowRate, N * 8, hipMemcpyDeviceToHost, I.stream));
     if (I.dslot.empty()) {
@@ -735,17 +735,7 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
      * round (at 70 VGPRs only 1 792 of 2 048 blocks fit and the remaining 256 ran alone afterwards).  Every kernel walks the
      * chunk list with its own gridDim, and the fused reductions count gridDim partials, so any grid is valid. */
     auto resident = [&](const void* fn) -> dim3 {
-        uint32_t nbk = 0;
-        for (auto& r : I.residentBlocks) if (r.first == fn) nbk = r.second;
-        if (nbk == 0) {
-            int perCu = 0, dev = 0; hipDeviceProp_t prop;
-            nbk = SF3D_MAX_BLOCKS;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, fn, SF3D_BLOCK, 0) == hipSuccess && perCu > 0
-                && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                nbk = (uint32_t)perCu * (uint32_t)prop.multiProcessorCount;
-            if (I.residentGrids == 0) nbk = SF3D_MAX_BLOCKS;
-            I.residentBlocks.push_back({fn, nbk});
-        }
+        const uint32_t nbk = I.resident_blocks(fn);
         return dim3(v.nb < nbk ? v.nb : nbk);
     };
     if (heatOn && multi) I.useFused = 1;       /* the sharded heat step exists only in the fused-exchange form */
@@ -766,13 +756,10 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
     /* mode 2 samples: the sweeps of every 8th computeStep carry HIP events (eager launches); the other
      * steps replay hipGraphs, so the measurement costs ~1 % instead of ~6 % */
     const bool timedStep = I.timing == 1 || (I.timing == 2 && (I.stepSeq++ % 8 == 0));
-    if (I.overlapAccept < 0) { const char* oe = getenv("SF3D_OVERLAP_ACCEPT"); I.overlapAccept = (oe && oe[0] == '0') ? 0 : 1; }
-    /* single GPU only: a second stream per process is a second hardware queue, and ranks that share a GPU (functional
-     * multi-rank tests) oversubscribe the queues - their spinning exchange kernels then wait for time slices (measured: 45x slower) */
-    if (I.overlapAccept && !multi && !I.stream2) { HIP_TRY(hipStreamCreateWithFlags(&I.stream2, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&I.evLinks[0], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&I.evLinks[1], hipEventDisableTiming)); }
-    /* accepted step: link flow sums on a second stream next to the next step's k_props (untimed steps only, so that the
-     * per-kernel event timing of --time-all-kernels stays a sequence of exclusive launches) */
-    const bool overlap = I.overlapAccept && !multi && I.stream2 && !timedStep && I.timing != 1 && v.compatCv == nullptr;   /* (compat: k_compat_rows rewrites what the sums read) */
+    /* accepted step: its link flow sums are not added in the step - the step keeps its matrix and a copy of its head in a slot of the rings,
+     * and one pass adds the sums of up to SF3D_LINKS_RING such steps (k_links_flush).  Plain single-GPU path, untimed steps only, so
+     * that the per-kernel event timing of --time-all-kernels sees every kernel of a step inside the step */
+    const bool overlap = I.overlapAccept && !multi && I.ring && !timedStep && I.timing != 1 && v.compatCv == nullptr;   /* (compat: k_compat_rows rewrites what the sums read) */
     auto timed = [&](int kid, auto launch) {
         if (!timedStep || (I.timing == 2 && kid != KID_SWEEP && kid != KID_SWEEP_PAIR && kid != KID_SWEEP_RES)) { launch(); return; }
         hipEvent_t a, b;
@@ -789,13 +776,11 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
     }
     uint32_t stage = ST_ACCEPT;
     if (m.water) {
-    {   /* this step assembles into the copy of the matrix that the step before the last one used (k_step_begin flips Ctrl::aBuf): the
-         * link flow sums that read it - queued two steps ago on the second stream - must be done; so must they before this step's
-         * sweeps reuse the head buffer they read.  The sums of the LAST step run next to this whole step - unless this step adds its
-         * own sums inside the step (event-timed steps): then both must be done first. */
-        const uint32_t wb = (mirror_.aBuf ^ 1u) & 1u;
-        if (I.linksPending[wb]) { HIP_TRY(hipStreamWaitEvent(st, I.evLinks[wb], 0)); I.linksPending[wb] = false; }
-        if (!overlap && I.linksPending[wb ^ 1u]) { HIP_TRY(hipStreamWaitEvent(st, I.evLinks[wb ^ 1u], 0)); I.linksPending[wb ^ 1u] = false; }
+    {   /* this step assembles into the next slot of the ring (k_step_begin): if the sums of the step that used it are still pending the
+         * ring is full, and everything pending is added first.  So it is before a step that adds its own sums inside the step
+         * (event-timed steps): the sums are added in the order the steps were accepted in. */
+        const uint32_t ringSlots = mirror_.aRing < 2u ? 2u : mirror_.aRing;
+        if (I.pend.n && (!overlap || I.links_pending((mirror_.aBuf + 1u) % ringSlots))) HIP_TRY(I.flush_links());
     }
     {
     hipLaunchKernelGGL(k_step_begin, one, one, 0, st, v.ctrl, maxTimeStep);
@@ -1115,16 +1100,10 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
         for (uint32_t k = 0; k < I.predCount; ++k) I.pred[k] = I.hostCtrl->seqSweeps[k];
     }
     }
-    if (overlap && stage == ST_ACCEPT) {
-        /* the main stream is drained (the poll just read the control block): no dependency to express for the launch */
-        uint32_t lcap = 384u; if (const char* le = getenv("SF3D_LINKS_BLOCKS")) lcap = (uint32_t)atoi(le);      /* measured at C4: 2048 -1 %, 512 / 256 +1 %, 128 -4 % */
-        const dim3 lgrid(v.nb > lcap ? lcap : v.nb);        /* a streaming kernel: few enough waves that k_props fits next to it */
+    if (overlap && stage == ST_ACCEPT) {      /* what k_links_flush needs of this step: where its matrix and head are, and its dt */
         const Ctrl& hc = *I.hostCtrl;
-        const uint32_t rb = hc.acceptABuf & 1u;
-        if (v.ntStream) hipLaunchKernelGGL(k_accept_links<true>, lgrid, block, 0, I.stream2, v, hc.acceptBuf, rb, hc.acceptDt);
-        else hipLaunchKernelGGL(k_accept_links<false>, lgrid, block, 0, I.stream2, v, hc.acceptBuf, rb, hc.acceptDt);
-        HIP_TRY(hipEventRecord(I.evLinks[rb], I.stream2));
-        I.linksPending[rb] = true;
+        if (I.pend.n >= (uint32_t)SF3D_LINKS_RING) HIP_TRY(I.flush_links());      /* (never: a full ring was emptied before the step) */
+        I.pend.slot[I.pend.n] = hc.acceptABuf < (uint32_t)SF3D_LINKS_RING ? hc.acceptABuf : 0u; I.pend.dt[I.pend.n] = hc.acceptDt; ++I.pend.n;
     }
     }   /* if (m.water) */
 

@@ -211,8 +211,8 @@ sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const M
     HIP_TRY(maps_reserve(C.out, C.outCap, outN));
     if (!C.missing) HIP_TRY(hipMalloc((void**)&C.missing, sizeof(int)));
     HIP_TRY(hipMemsetAsync(C.missing, 0, sizeof(int), I.stream));
-    /* the link flow sums of the accepted step may still be added on the second stream */
-    if ((var == MV_WATER_INFLOW || var == MV_WATER_OUTFLOW) && I.stream2) HIP_TRY(hipStreamSynchronize(I.stream2));
+    /* the link flow sums of the last accepted steps may still be pending: added on this stream before the kernel that reads them */
+    if (var == MV_WATER_INFLOW || var == MV_WATER_OUTFLOW) HIP_TRY(I.flush_links());
 
     MapView mv{};
     mv.col = C.col; mv.thick = C.thick; mv.slope = C.slope; mv.geo = C.geo;

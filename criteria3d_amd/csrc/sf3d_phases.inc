@@ -975,31 +975,75 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_accept(DevView v)
 }
 
 
-/* The two halves of k_accept for the overlapped mode: the boundary sums stay in the step (the next step's k_props
- * overwrites bflowRate); the link sums - 1.5 GB of traffic at C4, 6 % VALU - run on a second stream next to the next
- * step's k_props (68 % VALU, little traffic), which must only finish before that step's first k_assemble rewrites A2. */
+/* The two halves of k_accept where the link flow sums are added in batches (plain single-GPU path): the boundary sums stay in the
+ * step (the next step's k_props overwrites bflowRate), and the step keeps a copy of its accepted head in the slot of the ring its
+ * matrix sits in.  The link sums - read and rewrite 160 B per node to add one term each - wait: k_links_flush adds the terms of up
+ * to SF3D_LINKS_RING accepted steps in one pass over the sums. */
 __global__ void __launch_bounds__(SF3D_BLOCK) k_accept_boundary(DevView v)
 {
     const Ctrl* c = v.ctrl;
     if (c->stage != ST_ACCEPT) return;
     const double dt = c->dt;
+    const double* __restrict__ X = v.X[c->cur];
+    double* __restrict__ Hk = v.Hring[c->aBuf];          /* the slot comes from the control block: the captured graphs carry no argument for it */
     FOR_EACH_CHUNK(v) {
         const uint32_t i = q * SF3D_CHUNK + lane_;
         if (NOT_MINE(v, i)) continue;
+        Hk[i] = X[i];
         if (v.btype[i] != SF3D_BND_NONE) v.bflowSum[i] += v.bflowRate[i] * dt;
     }
 }
-template <bool NT>
-__global__ void __launch_bounds__(SF3D_BLOCK) k_accept_links(DevView v, int xbuf, uint32_t abuf, double dt)
+/* The link flow sums of the accepted steps b.slot[0 .. n), in that order: per node and slot the expression of accept_links_row applied n
+ * times to a sum held in a register - the same operands in the same order, and a step whose coefficient is zero adds nothing (the sum, a
+ * -0.0 included, stays what it is) - so the sums have the bits n launches of k_accept would have left.  Matrix and head of step k come
+ * from slot b.slot[k] of the two rings (the pool buffer the head was accepted in is long recycled).  A sum no step touched is not stored.
+ * Slots [S0, S0 + H) of a node per call: whole pairs of the matrix.  No compat rows here: where DevView::compatCv exists the sums are
+ * added inside the step. */
+template <bool NT, int S0, int H>
+__device__ __forceinline__ void links_flush_slots(const DevView& v, const LinksBatch& b, const ChunkDesc& cd, uint32_t i)
 {
-    /* which head buffer, which copy of the matrix and which dt the accepted step had come as ARGUMENTS (the host has just polled
-     * them): this kernel runs next to the whole following computeStep, which overwrites those fields of the control block */
-    const double* __restrict__ X = v.X[xbuf];
-    const sf3d_d2* __restrict__ A2 = v.A2x[abuf & 1u];      /* the accepted step's matrix: the step in progress writes the other copy */
+    static_assert(S0 % 2 == 0 && H % 2 == 0 && S0 + H <= SF3D_SLOTS, "whole (2p, 2p+1) pairs of A2x");
+    uint32_t j[H];
+    double f[H];
+    uint32_t touched = 0u;
+    #pragma unroll
+    for (int t = 0; t < H; ++t) {
+        const int s = S0 + t;
+        if (cd.kind[s] != CK_MIXED) j[t] = i + cd.delta[s];
+        else if ((cd.sweepUniform >> s) & 1u) { const uint32_t jj = i + (uint32_t)cd.delta[s]; j[t] = jj < v.N ? jj : i; }   /* a node without the link has a zero coefficient */
+        else j[t] = v.lto[(size_t)s * v.N + i];
+        f[t] = load_stream<NT>(&v.lflowSum[(size_t)s * v.N + i]);
+    }
+    for (uint32_t k = 0; k < b.n; ++k) {
+        const sf3d_d2* __restrict__ A2 = v.A2x[b.slot[k]];
+        const double* __restrict__ X = v.Hring[b.slot[k]];
+        const double dt = b.dt[k];
+        double a[H], xj[H];
+        #pragma unroll
+        for (int p = 0; p < H / 2; ++p) { const sf3d_d2 t2 = load_coeff<NT>(&A2[(size_t)(S0 / 2 + p) * v.N + i]); a[2 * p] = t2.x; a[2 * p + 1] = t2.y; }   /* non-zero only where a link exists */
+        const double Hi = X[i];
+        #pragma unroll
+        for (int t = 0; t < H; ++t) xj[t] = X[j[t]];
+        #pragma unroll
+        for (int t = 0; t < H; ++t)
+            if (a[t] != 0.) { f[t] = f[t] + a[t] * (Hi - xj[t]) * dt; touched |= 1u << t; }
+    }
+    #pragma unroll
+    for (int t = 0; t < H; ++t)
+        if ((touched >> t) & 1u) store_stream<NT>(&v.lflowSum[(size_t)(S0 + t) * v.N + i], f[t]);
+}
+/* the ten slots in two groups, 4 + 6: all ten sums, coefficients, neighbour heads and indices across the loop over the steps take 108 VGPRs
+ * (4 waves per SIMD; held to 96 they spill), a group of six stays below the 88 of k_accept (5 waves).  The second group reads the
+ * node's own head again: 8 B of the 168 B a step costs per node, and from the cache */
+template <bool NT>
+__global__ void __launch_bounds__(SF3D_BLOCK) k_links_flush(DevView v, LinksBatch b)
+{
     FOR_EACH_CHUNK(v) {
         const uint32_t i = q * SF3D_CHUNK + lane_;
         if (NOT_MINE(v, i)) continue;
-        accept_links_row<NT>(v, A2, q, i, X, dt);
+        const ChunkDesc cd = v.cdesc[q];
+        links_flush_slots<NT, 0, 4>(v, b, cd, i);
+        links_flush_slots<NT, 4, SF3D_SLOTS - 4>(v, b, cd, i);
     }
 }
 

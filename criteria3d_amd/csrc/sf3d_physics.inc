@@ -155,7 +155,7 @@ __device__ __forceinline__ double tortuosity(double Se, double L) { return (L ==
 #endif
 
 /* the coefficient matrix of the computeStep in progress */
-__device__ __forceinline__ sf3d_d2* cur_A2(const DevView& v) { return v.A2x[v.ctrl->aBuf & 1u]; }
+__device__ __forceinline__ sf3d_d2* cur_A2(const DevView& v) { return v.A2x[v.ctrl->aBuf]; }      /* aBuf < Ctrl::aRing (k_step_begin) */
 
 __device__ __forceinline__ int free_buffer3(int cur, int hold, int best)
 {
