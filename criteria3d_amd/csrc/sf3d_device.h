@@ -603,6 +603,19 @@ struct SinkView {       /* k_sink_hour; the maps of one block share a base point
     int32_t lastEvapLayer;
     float flag;
 };
+struct SinkCrackDev {   /* what Crit3DProject::computeSoilCracking (criteria3DProject.cpp:978-1123) reads beyond the sink view.  It lies in device memory and is
+                         * read where the rain term needs it, so that its pointers hold no scalar registers during evaporation and transpiration */
+    const double* pond;                 /* the solver's pond [m] per node: getCriteria3DVar(surfacePond) */
+    const double* maxDepth;             /* [nSoils] the crack's depth [m] (:1030-1031) */
+    const int32_t* lastLayer;           /* [nSoils] getSoilLayerIndex(maxDepth) (:1078), < 0: the soil never cracks */
+    const double* layerDepth;           /* [nrLayers] */
+    float* precSurfaceWater;            /* [nCells] what computeSoilCracking returned [mm] */
+    double* crackWater;                 /* [nCells] the water that went into the crack's nodes [mm] */
+};
+struct SinkCrackView {  /* k_sink_hour_crack */
+    SinkView s;
+    const SinkCrackDev* k;
+};
 struct SinkSetup {      /* what sf3d_sink_initialize keeps for DeviceSolver::sink_alloc: host pointers */
     uint32_t nCells, nrLayers, nUnits, nSoils;
     int32_t lastEvapLayer;
@@ -625,6 +638,9 @@ struct SinkCall {       /* what sf3d_sink_compute_hour hands to DeviceSolver::si
     const float* dd;
     const float* liquid;
     const uint8_t* mine;
+    const double* crackMaxDepth;        /* soil cracking (sf3d_sink_set_cracking): host tables per soil, null = off */
+    const int32_t* crackLastLayer;
+    uint64_t crackVer;                  /* changes with every sf3d_sink_set_cracking */
 };
 /* the per-cell block of the sink maps: two double maps, then seven maps of 4-byte values */
 enum { SINK_MAP_EVAPORATION = 0, SINK_MAP_TRANSPIRATION = 1, SINK_MAP_DEM = 2, SINK_MAP_ET0 = 3, SINK_MAP_LAI = 4, SINK_MAP_DD = 5, SINK_MAP_LIQUID = 6,

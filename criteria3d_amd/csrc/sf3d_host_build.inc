@@ -185,6 +185,11 @@ struct SinkCache {
     float flag = -9999.f;
     bool computed = false;
     double lastMs = 0.;
+    SinkCrackDev crackDev{};            /* what the head of `crack` holds */
+    char* crack = nullptr;              /* soil cracking: SinkCrackDev, maxDepth [nSoils], layerDepth [nrLayers], crackWater [nCells] (doubles), lastLayer [nSoils], precSurfaceWater [nCells] */
+    uint64_t crackVer = 0;              /* the sf3d_sink_set_cracking the tables in `crack` were uploaded from */
+    bool crackComputed = false;         /* the last hour ran k_sink_hour_crack */
+    std::vector<double> layerDepth;
 };
 
 struct DeviceSolver::Impl {

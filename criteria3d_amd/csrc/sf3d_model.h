@@ -257,6 +257,8 @@ public:
     sf3d_error_t sink_hour(HostModel& m, const ParamsHost& p, const MapsInput& in, const SinkCall& call);
     sf3d_error_t sink_download_nodes(double* dst, uint32_t count);     /* the device model's numbering */
     sf3d_error_t sink_download_cells(int map, double* dst);
+    sf3d_error_t sink_download_crack(float* precSurfaceWater, double* crackWater);
+    bool sink_crack_computed() const;
     bool sink_computed() const;
     sf3d_error_t sink_free();
     double sink_kernel_ms() const;

@@ -55,7 +55,82 @@ __device__ __forceinline__ bool sink_root_layer(const SinkView& v, uint32_t c, u
     return true;
 }
 
-__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v)
+/* getCriteria3DVar(maxVolumetricWaterContent, node), project3D.cpp:2756-2810 */
+__device__ __forceinline__ double sink_max_vwc(const SinkView& v, int32_t n)
+{
+    const double w = ((uint32_t)n < v.ns) ? SF3D_VAL_INDEX_ERROR : v.soils[v.cls[n]].thetaS;
+    return map_sentinel(w) ? (double)SINK_NODATA : w;
+}
+
+/* voidVolumeList[layer] of computeSoilCracking's first loop (criteria3DProject.cpp:1058-1064) for a layer with a node and a horizon */
+__device__ __forceinline__ double sink_void_volume(const SinkView& v, int32_t n, int32_t si, int32_t h)
+{
+    const double soilFraction = v.horizonValues[((size_t)si * ROOT_MAX_HORIZONS + (uint32_t)h) * SINK_HORIZON_VALUES + SINK_H_FRACTION];
+    const double VWC = sink_vwc(v, n);
+    const double maxVWC = sink_max_vwc(v, n);
+    const double currentVoidVolume = dmax(0.0, maxVWC - VWC);
+    return currentVoidVolume * soilFraction;
+}
+
+/* Crit3DProject::computeSoilCracking (criteria3DProject.cpp:978-1123) behind its tests on the soil and the layer grid, which the host made
+ * (sf3d_sink_set_cracking: maxDepth, lastLayer).  The evaporation and transpiration subtractions of the column are in v.sink already; every
+ * addition is made on its own.  Returns the function's float; *crackWater: the sum of layerWater over the layers filled. */
+__device__ __forceinline__ float sink_soil_cracking(const SinkView& v, const SinkCrackDev& k, uint32_t c, int32_t s0, int32_t si, float precipitation, double* crackWater)
+{
+    const size_t nc = v.nCells;
+    const uint32_t nl = v.nrLayers;
+    const double* const thick = v.layerTables;
+    *crackWater = 0.;
+    if (si < 0) return precipitation;
+    double minimumPond = (((uint32_t)s0 < v.ns) ? k.pond[s0] : SF3D_VAL_INDEX_ERROR) * 1000;      /* getCriteria3DVar(surfacePond) [mm] */
+    if (map_sentinel(minimumPond)) minimumPond = (double)SINK_NODATA;
+    if (precipitation <= minimumPond) return precipitation;
+    const int32_t lastLayer = k.lastLayer[si];
+    if (lastLayer < 0) return precipitation;                              /* the soil never cracks */
+    const double maxDepth = k.maxDepth[si];
+    double crackDepth = 0.0, voidsVolumeSum = 0;
+    uint32_t layerIndex = 1;                                             /* :1045-1069 */
+    while (layerIndex < nl && k.layerDepth[layerIndex] <= maxDepth) {
+        const int32_t n = v.col[(size_t)layerIndex * nc + c];
+        if (n < 0) break;
+        const int32_t h = v.horizon[(size_t)si * nl + layerIndex];
+        if (h < 0) break;
+        voidsVolumeSum += sink_void_volume(v, n, si, h) * thick[layerIndex];
+        crackDepth += thick[layerIndex];
+        ++layerIndex;
+    }
+    if (crackDepth == 0.0) return precipitation;
+    const double avgVoidVolume = voidsVolumeSum / crackDepth;
+    if (avgVoidVolume <= 0.15) return precipitation;
+    const double ratio = (avgVoidVolume - 0.15) / (0.20 - 0.15);
+    const double crackRatio = (ratio < 0.0) ? 0.0 : ((1.0 < ratio) ? 1.0 : ratio);            /* std::clamp */
+    const double maxInfiltration = precipitation * crackRatio;
+    const double surfaceWater = dmax(precipitation - maxInfiltration, minimumPond);
+    const double potentialInfiltration = dmax(0.0, precipitation - surfaceWater);
+    const double area = v.area;
+    double residualDownWater = potentialInfiltration;
+    /* filling from the bottom (:1095-1119).  voidVolumeList is 0 in every layer the first loop did not reach: such a layer takes nothing */
+    for (int32_t l = (lastLayer < (int32_t)layerIndex - 1) ? lastLayer : (int32_t)layerIndex - 1; l > 0; --l) {
+        if (residualDownWater <= 0) break;
+        const int32_t n = v.col[(size_t)l * nc + c];
+        if (n < 0) continue;
+        const double layerThick_mm = thick[l] * 1000;
+        const double storage = dmin(sink_void_volume(v, n, si, v.horizon[(size_t)si * nl + l]), 0.05);
+        double layerWater = layerThick_mm * storage;
+        layerWater = dmin(layerWater, residualDownWater);
+        const double flow = area * (layerWater / 1000.);
+        const double flowRate = flow / 3600.;
+        if (flowRate > 0.0) {
+            v.sink[n] += flowRate;
+            residualDownWater -= layerWater;
+            *crackWater += layerWater;
+        }
+    }
+    return (float)(surfaceWater + residualDownWater);
+}
+
+/* one cell of the hour; CRACK: the rain term goes through sink_soil_cracking (k_sink_hour_crack), else precSurfaceWater = liquidWater */
+template <bool CRACK> __device__ __forceinline__ void sink_cell(const SinkView& v, const SinkCrackDev* k)
 {
     fm_init();
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -80,6 +155,7 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v)
     if (!cell) {
         if (s0 >= 0) v.sink[s0] = 0.;
         actualMaps[c] = (double)flag; actualMaps[nc + c] = (double)flag;
+        if constexpr (CRACK) { k->precSurfaceWater[c] = flag; k->crackWater[c] = (double)flag; }
         return;
     }
     double surfaceSink = 0.;
@@ -178,16 +254,25 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v)
         }
     }
 
-    /* ---- the rain term of assignPrecipitation (criteria3DProject.cpp:939-964), precSurfaceWater = liquidWater ---- */
+    /* ---- the rain term of assignPrecipitation (criteria3DProject.cpp:939-964); without cracking precSurfaceWater = liquidWater ---- */
     const float liquidWater = v.liquid[c];
+    float precSurfaceWater = liquidWater;
+    double crackWater = 0.;
     if (!snow_eqf(liquidWater, flag) && liquidWater > 0) {
-        const double surfaceFlow = area * (liquidWater / 1000.);
+        if constexpr (CRACK) precSurfaceWater = sink_soil_cracking(v, *k, c, s0, si, liquidWater, &crackWater);
+        const double surfaceFlow = area * (precSurfaceWater / 1000.);
         if ((surfaceFlow / 3600.) > 0.) surfaceSink += surfaceFlow / 3600.;
     }
     v.sink[s0] = surfaceSink;
     actualMaps[c] = actualEvaporationSum;
     actualMaps[nc + c] = actualTranspiration;
+    if constexpr (CRACK) { k->precSurfaceWater[c] = precSurfaceWater; k->crackWater[c] = crackWater; }
 }
+
+__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v) { sink_cell<false>(v, nullptr); }
+
+/* the hour with soil cracking (sf3d_sink_set_cracking) */
+__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour_crack(SinkCrackView k) { sink_cell<true>(k.s, k.k); }
 
 /* ---- host side: the per-cell block, one block of tables and the node array; calls go through the shared raster path at the end of
  * sf3d_maps.inc. */
@@ -196,7 +281,7 @@ enum { SINK_T_UNITS = 0, SINK_T_HORIZON_VALUES, SINK_T_THICK, SINK_T_EVAP_COEFF,
 sf3d_error_t DeviceSolver::sink_free()
 {
     if (!impl_) return SF3D_OK;
-    raster_release({impl_->sink.cells, impl_->sink.tables, impl_->sink.nodes});
+    raster_release({impl_->sink.cells, impl_->sink.tables, impl_->sink.nodes, impl_->sink.crack});
     impl_->sink = SinkCache();
     return SF3D_OK;
 }
@@ -214,6 +299,7 @@ sf3d_error_t DeviceSolver::sink_alloc(const SinkSetup& S)
     const void* src[SINK_T_END] = {S.units, S.horizonValues, S.thick, S.evapCoeff, S.layerEvapCoeff, S.horizon};
     const size_t srcBytes[SINK_T_END] = {S.nUnits * sizeof(SinkUnitDev), bytes[1], bytes[2], bytes[3], bytes[4], bytes[5]};
     RASTER_TRY(hipMalloc((void**)&K.cells, (size_t)SINK_MAP_WORDS * n * 4));
+    K.layerDepth.assign(S.layerDepth, S.layerDepth + nl);
     K.nCells = S.nCells; K.nrLayers = S.nrLayers; K.nUnits = S.nUnits; K.nSoils = S.nSoils; K.lastEvapLayer = S.lastEvapLayer; K.area = S.area; K.flag = S.flag;
     e = raster_tables(K.tables, K.off, SINK_T_END, bytes, src, srcBytes);
     if (e != SF3D_OK) return e;
@@ -275,7 +361,34 @@ sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const Ma
     v.area = K.area;
     v.ns = I.v.ns; v.nCells = K.nCells; v.nrLayers = K.nrLayers; v.nUnits = K.nUnits; v.nSoils = K.nSoils;
     v.lastEvapLayer = K.lastEvapLayer; v.flag = K.flag;
-    e = raster_launch(k_sink_hour, n, v, K.lastMs);
+    K.crackComputed = false;
+    if (!call.crackMaxDepth) e = raster_launch(k_sink_hour, n, v, K.lastMs);
+    else {
+        /* soil cracking: one block of its own - SinkCrackDev, maxDepth, layerDepth, crackWater (doubles), then lastLayer and precSurfaceWater (4 bytes) */
+        const size_t ns8 = K.nSoils, nl8 = K.nrLayers;
+        if (!K.crack) { RASTER_TRY(hipMalloc((void**)&K.crack, sizeof(SinkCrackDev) + (ns8 + nl8 + n) * 8 + (ns8 + n) * 4 + 8)); K.crackVer = 0; K.crackDev = SinkCrackDev{}; }
+        double* const maxDepth = (double*)(K.crack + sizeof(SinkCrackDev));
+        double* const layerDepth = maxDepth + ns8;
+        double* const crackWater = layerDepth + nl8;
+        int32_t* const lastLayer = (int32_t*)(crackWater + n);
+        float* const precSurfaceWater = (float*)(lastLayer + ns8);
+        if (K.crackVer != call.crackVer) {
+            RASTER_TRY(hipMemcpyAsync(maxDepth, call.crackMaxDepth, ns8 * 8, hipMemcpyHostToDevice, I.stream));
+            RASTER_TRY(hipMemcpyAsync(layerDepth, K.layerDepth.data(), nl8 * 8, hipMemcpyHostToDevice, I.stream));
+            RASTER_TRY(hipMemcpyAsync(lastLayer, call.crackLastLayer, ns8 * 4, hipMemcpyHostToDevice, I.stream));
+            RASTER_TRY(hipStreamSynchronize(I.stream));
+            K.crackVer = call.crackVer;
+        }
+        const SinkCrackDev d{I.v.pond, maxDepth, lastLayer, layerDepth, precSurfaceWater, crackWater};
+        if (std::memcmp(&d, &K.crackDev, sizeof d) != 0) {                /* (the pond array moves with a new model) */
+            K.crackDev = d;
+            RASTER_TRY(hipMemcpyAsync(K.crack, &K.crackDev, sizeof d, hipMemcpyHostToDevice, I.stream));
+        }
+        SinkCrackView k{};
+        k.s = v; k.k = (const SinkCrackDev*)K.crack;
+        e = raster_launch(k_sink_hour_crack, n, k, K.lastMs);
+        if (e == SF3D_OK) K.crackComputed = true;
+    }
     if (e == SF3D_OK) K.computed = true;
     return e;
 }
@@ -291,6 +404,20 @@ sf3d_error_t DeviceSolver::sink_download_cells(int map, double* dst)
 {
     const SinkCache& K = impl_->sink;
     return raster_download(dst, raster_cell_map(K.cells, K.nCells, map), (size_t)K.nCells * sizeof(double));
+}
+
+bool DeviceSolver::sink_crack_computed() const { return sink_computed() && impl_->sink.crack && impl_->sink.crackComputed; }
+
+sf3d_error_t DeviceSolver::sink_download_crack(float* precSurfaceWater, double* crackWater)
+{
+    const SinkCache& K = impl_->sink;
+    const size_t n = K.nCells;
+    const double* const water = (const double*)(K.crack + sizeof(SinkCrackDev)) + K.nSoils + K.nrLayers;
+    const float* const prec = (const float*)((const int32_t*)(water + n) + K.nSoils);
+    sf3d_error_t e = SF3D_OK;
+    if (precSurfaceWater) e = raster_download(precSurfaceWater, prec, n * sizeof(float));
+    if (e == SF3D_OK && crackWater) e = raster_download(crackWater, water, n * sizeof(double));
+    return e;
 }
 
 double DeviceSolver::sink_kernel_ms() const { return impl_ ? impl_->sink.lastMs : 0.; }

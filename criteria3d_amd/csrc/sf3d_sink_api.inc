@@ -8,6 +8,7 @@
 
 static_assert(sizeof(sf3d_sink_unit_t) == sizeof(SinkUnitDev) && sizeof(SinkUnitDev) == 24, "the sink unit table is copied as it is");
 static_assert(sizeof(sf3d_sink_soil_t) == 8 + 7 * 8 * SF3D_ROOT_MAX_HORIZONS, "sf3d_sink_soil_t has no padding");
+static_assert(sizeof(sf3d_sink_crack_soil_t) == 16 + 4 * 8 * SF3D_ROOT_MAX_HORIZONS, "sf3d_sink_crack_soil_t has no padding");
 static_assert(SF3D_ROOT_MAX_HORIZONS == ROOT_MAX_HORIZONS, "sf3d_root.h and sf3d_device.h disagree");
 
 namespace {
@@ -23,7 +24,17 @@ struct SinkHost {
     std::vector<SinkUnitDev> units;
     std::vector<double> horizonValues, layerDepth, thick, evapCoeff, layerEvapCoeff;
     std::vector<double> nodes;                 /* the last download, in the device model's numbering */
+    /* soil cracking (sf3d_sink_set_cracking): the horizons' depths and the computation depth it needs, and its per-soil tables */
+    double computationSoilDepth = 0.;
+    std::vector<int32_t> nrHorizons;
+    std::vector<double> upperDepth, lowerDepth;   /* [soil][SF3D_ROOT_MAX_HORIZONS] */
+    bool crackOn = false;
+    uint64_t crackVer = 0;
+    std::vector<double> crackMaxDepth;         /* [soil], -9999: never cracks */
+    std::vector<int32_t> crackLastLayer;       /* [soil], -9999: never cracks */
 } SK;
+
+uint64_t sinkCrackVersions = 0;                /* a new number for every table sf3d_sink_set_cracking leaves */
 
 void sinkClear() { SK = SinkHost(); (void)dev().sink_free(); }
 
@@ -80,7 +91,14 @@ sf3d_error_t sf3d_sink_initialize(uint32_t nrRows, uint32_t nrCols, const float*
 
     sinkClear();
     SK.nRows = nrRows; SK.nCols = nrCols; SK.nrLayers = nrLayers; SK.nUnits = nUnits; SK.nSoils = nSoils; SK.lastEvapLayer = lastEvapLayer;
-    SK.flag = flag; SK.area = cellSize * cellSize;
+    SK.flag = flag; SK.area = cellSize * cellSize; SK.computationSoilDepth = computationSoilDepth;
+    SK.nrHorizons.resize(nSoils);
+    SK.upperDepth.assign((size_t)nSoils * SF3D_ROOT_MAX_HORIZONS, 0.); SK.lowerDepth.assign((size_t)nSoils * SF3D_ROOT_MAX_HORIZONS, 0.);
+    for (uint32_t s = 0; s < nSoils; ++s) {
+        SK.nrHorizons[s] = soils[s].nrHorizons;
+        std::copy(soils[s].upperDepth, soils[s].upperDepth + soils[s].nrHorizons, SK.upperDepth.begin() + (size_t)s * SF3D_ROOT_MAX_HORIZONS);
+        std::copy(soils[s].lowerDepth, soils[s].lowerDepth + soils[s].nrHorizons, SK.lowerDepth.begin() + (size_t)s * SF3D_ROOT_MAX_HORIZONS);
+    }
     SK.dem.assign(dem, dem + n);
     SK.cropIndex.resize(n); SK.soilIndex.resize(n);
     for (uint32_t c = 0; c < n; ++c) { SK.cropIndex[c] = cropIndex[c] < 0 ? -1 : cropIndex[c]; SK.soilIndex[c] = soilIndex[c] < 0 ? -1 : soilIndex[c]; }
@@ -115,6 +133,55 @@ sf3d_error_t sf3d_sink_get_tables(double* evapCoeff, double* layerEvapCoeff, int
     return SF3D_OK;
 }
 
+/* The part of Crit3DProject::computeSoilCracking (criteria3DProject.cpp:1003-1035, :1078) that depends on the soil and the layer grid only.
+ * Every one of these exits returns the precipitation unchanged and has no side effect, so their place before or after the per-cell tests
+ * (soil index, pond, crackDepth, avgVoidVolume) changes no result: a soil that fails one never cracks. */
+sf3d_error_t sf3d_sink_set_cracking(uint32_t nSoils, const sf3d_sink_crack_soil_t* soils)
+{
+    if (!SK.on) return SF3D_MEMORY_ERROR;
+    if (!soils || nSoils == 0) { SK.crackOn = false; SK.crackMaxDepth.clear(); SK.crackLastLayer.clear(); return SF3D_OK; }
+    if (nSoils != SK.nSoils) return SF3D_PARAMETER_ERROR;
+    for (uint32_t s = 0; s < nSoils; ++s)
+        if (soils[s].nrHorizons < 0 || soils[s].nrHorizons > SF3D_ROOT_MAX_HORIZONS || soils[s].nrHorizons > SK.nrHorizons[s]) return SF3D_PARAMETER_ERROR;
+    const double MAX_CRACKING_DEPTH = 0.6, MIN_FINE_LAYER_DEPTH = 0.2, MIN_FINE_FRACTION = 0.5;
+    std::vector<double> maxDepthOf(nSoils, -9999.);
+    std::vector<int32_t> lastLayerOf(nSoils, -9999);
+    for (uint32_t s = 0; s < nSoils; ++s) {
+        const sf3d_sink_crack_soil_t& so = soils[s];
+        const double* upper = SK.upperDepth.data() + (size_t)s * SF3D_ROOT_MAX_HORIZONS;
+        const double* lower = SK.lowerDepth.data() + (size_t)s * SF3D_ROOT_MAX_HORIZONS;
+        const double soilDepth = std::min(SK.computationSoilDepth, so.totalDepth);
+        if (soilDepth <= MIN_FINE_LAYER_DEPTH) continue;
+        int lastFineHorizon = -9999;
+        double maxDepth = std::min(soilDepth, MAX_CRACKING_DEPTH);
+        int32_t h = 0;
+        while (h < so.nrHorizons && upper[h] < maxDepth) {
+            const double fineFraction = (so.clay[h] + so.silt[h] * 0.5) / 100 * (1 - so.coarseFragments[h]) * (1 - so.organicMatter[h]);
+            if (fineFraction < MIN_FINE_FRACTION) break;
+            lastFineHorizon = h;
+            ++h;
+        }
+        if (lastFineHorizon == -9999) continue;
+        maxDepth = std::min(lower[lastFineHorizon], MAX_CRACKING_DEPTH);
+        maxDepth = std::min(maxDepth, SK.computationSoilDepth);
+        if (maxDepth < MIN_FINE_LAYER_DEPTH) continue;
+        const int lastLayer = sinkLayerIndex(SK.nrLayers, SK.layerDepth.data(), SK.thick.data(), maxDepth);
+        if (lastLayer == -9999) continue;
+        maxDepthOf[s] = maxDepth; lastLayerOf[s] = lastLayer;
+    }
+    SK.crackMaxDepth = maxDepthOf; SK.crackLastLayer = lastLayerOf;
+    SK.crackOn = true; SK.crackVer = ++sinkCrackVersions;
+    return SF3D_OK;
+}
+
+sf3d_error_t sf3d_sink_get_crack_tables(double* maxDepth, int32_t* lastLayer)
+{
+    if (!SK.on || !SK.crackOn) return SF3D_MEMORY_ERROR;
+    if (maxDepth) std::copy(SK.crackMaxDepth.begin(), SK.crackMaxDepth.end(), maxDepth);
+    if (lastLayer) std::copy(SK.crackLastLayer.begin(), SK.crackLastLayer.end(), lastLayer);
+    return SF3D_OK;
+}
+
 sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const float* lai, const float* degreeDays, const float* liquidWater)
 {
     if (!SK.on) return SF3D_MEMORY_ERROR;
@@ -138,7 +205,8 @@ sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const fl
     HostModel& D = deviceModel();
     MapsInput in;
     mapsDeviceInput(in);
-    SinkCall call{et0, lai, degreeDays, liquidWater, mapsOwnedCells(nrCells)};
+    SinkCall call{et0, lai, degreeDays, liquidWater, mapsOwnedCells(nrCells), nullptr, nullptr, 0};
+    if (SK.crackOn) { call.crackMaxDepth = SK.crackMaxDepth.data(); call.crackLastLayer = SK.crackLastLayer.data(); call.crackVer = SK.crackVer; }
     return rasterFail("sink compute hour", dev().sink_hour(D, P, in, call));
 }
 
@@ -163,6 +231,13 @@ sf3d_error_t sf3d_sink_get_actual(uint32_t nrCells, double* evaporation, double*
     if (evaporation) e = dev().sink_download_cells(SINK_MAP_EVAPORATION, evaporation);
     if (e == SF3D_OK && transpiration) e = dev().sink_download_cells(SINK_MAP_TRANSPIRATION, transpiration);
     return rasterFail("sink get actual", e);
+}
+
+sf3d_error_t sf3d_sink_get_crack(uint32_t nrCells, float* precSurfaceWater, double* crackWater)
+{
+    if (!SK.on || !SK.crackOn || !dev().sink_crack_computed()) return SF3D_MEMORY_ERROR;
+    if (nrCells != SK.nRows * SK.nCols) return SF3D_PARAMETER_ERROR;
+    return rasterFail("sink get crack", dev().sink_download_crack(precSurfaceWater, crackWater));
 }
 
 sf3d_error_t sf3d_sink_apply(void)

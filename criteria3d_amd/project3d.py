@@ -153,6 +153,7 @@ def set_horizon(row: dict, textures) -> tuple:
             and (sand + silt + clay) <= 1.01):
         sand *= 100; silt *= 100; clay *= 100
     h["clay"] = clay
+    h["silt"] = silt                                                                                # texture.silt [%]: soil cracking reads it
     cls = usda_texture_class(sand, silt, clay)                                                     # :880-888
     h["class_usda"] = cls
     if cls == int(NODATA):
@@ -694,6 +695,15 @@ def soil_sink_table(soils) -> list:
                         waterContentWP=[theta_from_sign_psi(h, -1600.0) * f for h, f in zip(hz, frac)],
                         waterContentHH=[theta_from_sign_psi(h, -3000.0) * f for h, f in zip(hz, frac)]))
     return out
+
+
+def soil_crack_table(soils) -> list:
+    """the soils of load_all_soils as sinks.set_cracking takes them (sf3d_sink_crack_soil_t), same index as soil_sink_table: totalDepth and
+    per horizon texture.clay, texture.silt [%], coarseFragments and organicMatter [-], what Crit3DProject::computeSoilCracking reads
+    (criteria3DProject.cpp:1003-1018)"""
+    return [dict(totalDepth=float(s["total_depth"]), clay=[float(h["clay"]) for h in s["horizons"]], silt=[float(h["silt"]) for h in s["horizons"]],
+                 coarseFragments=[float(h["coarse"]) for h in s["horizons"]], organicMatter=[float(h["organic_matter"]) for h in s["horizons"]])
+            for s in soils]
 
 
 def project_model(inp: ProjectInputs, par: ProjectParameters | None = None) -> Model:

@@ -1,7 +1,7 @@
 """The hourly water sinks on the device (include/sf3d_sink.h, criteria3d_amd/csrc/sf3d_sink.inc): the cell loop of
 `Crit3DProject::assignETreal` (bin/CRITERIA3D/criteria3DProject.cpp:796-911) around `Project3D::assignEvaporation`
 (src/project3D/project3D.cpp:2377-2451) and `Project3D::assignTranspiration` (:2461-2610), and the rain term of `assignPrecipitation`
-(criteria3DProject.cpp:939-964) without soil cracking.
+(criteria3DProject.cpp:939-964), with `Crit3DProject::computeSoilCracking` (:978-1123) as an option (`set_cracking`).
 
 Three parts:
   * the binding (`bind`, `initialize`, `compute_hour`, `get_node_sinks`, `get_actual`, `apply` ...): k_sink_hour reads ET0, LAI and degree
@@ -10,7 +10,9 @@ Three parts:
   * `sink_hour`: root compute -> sink compute -> apply, the hour's hand-over to the solver;
   * `restate_sink_hour` (and `evaporation_coefficients`, `horizon_table`): both functions and the rain term in plain Python doubles with
     the reference's operation order, the C library's exp (python's `math`) and layerTranspiration rounded to float - the checker of the
-    CPU tests against the compiled-reference pin (tests/golden/water_sinks.npz).  A checker, never a fallback."""
+    CPU tests against the compiled-reference pin (tests/golden/water_sinks.npz).  A checker, never a fallback;
+  * `crack_tables` and `restate_soil_cracking`: the host part and the per-cell part of computeSoilCracking restated, the checker of
+    tests/golden/soil_cracking.npz; `restate_sink_hour(..., cracking=...)` calls the second in the rain term."""
 from __future__ import annotations
 
 import ctypes as C
@@ -42,8 +44,23 @@ class Soil(C.Structure):
     _fields_ = [("nrHorizons", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_double * MAX_HORIZONS) for n in HORIZON_FIELDS]
 
 
+CRACK_FIELDS = ("clay", "silt", "coarseFragments", "organicMatter")
+MAX_CRACKING_DEPTH = 0.6                        # criteria3DProject.cpp:980-985
+MIN_FINE_LAYER_DEPTH = 0.2
+MIN_VOID_VOLUME = 0.15
+MAX_VOID_VOLUME = 0.20
+MIN_FINE_FRACTION = 0.5
+MAX_STORAGE = 0.05
+
+
+class CrackSoil(C.Structure):
+    """sf3d_sink_crack_soil_t"""
+    _fields_ = [("nrHorizons", C.c_int32), ("reserved", C.c_int32), ("totalDepth", C.c_double)] + [(n, C.c_double * MAX_HORIZONS) for n in CRACK_FIELDS]
+
+
 punit = C.POINTER(Unit)
 psoil = C.POINTER(Soil)
+pcrack = C.POINTER(CrackSoil)
 # name -> (restype, argtypes): every symbol include/sf3d_sink.h declares
 SIGNATURES = {
     "sf3d_sink_initialize": (capi.u8, [capi.u32, capi.u32, pf32, capi.f32, capi.f64, capi.u32, pf64, pf64, capi.f64, pi32, pi32, capi.u32, punit, capi.u32, psoil]),
@@ -52,6 +69,9 @@ SIGNATURES = {
     "sf3d_sink_get_node_sinks": (capi.u8, [capi.u32, pf64]),
     "sf3d_sink_get_actual": (capi.u8, [capi.u32, pf64, pf64]),
     "sf3d_sink_apply": (capi.u8, []),
+    "sf3d_sink_set_cracking": (capi.u8, [capi.u32, pcrack]),
+    "sf3d_sink_get_crack_tables": (capi.u8, [pf64, pi32]),
+    "sf3d_sink_get_crack": (capi.u8, [capi.u32, pf32, pf64]),
     "sf3d_sink_kernel_ms": (capi.f64, []),
     "sf3d_sink_clean": (capi.u8, []),
 }
@@ -138,6 +158,45 @@ def apply(sf: capi.SF3D):
     sf.check(sf.lib.sf3d_sink_apply(), "sink_apply")
 
 
+def crack_soil_array(crack_soils):
+    """list of dicts (totalDepth; CRACK_FIELDS: one list per field) -> ctypes array of sf3d_sink_crack_soil_t (no check of the cap: the
+    library refuses more horizons than it holds)"""
+    arr = (CrackSoil * max(len(crack_soils), 1))()
+    for k, s in enumerate(crack_soils):
+        nh = len(s["clay"])
+        arr[k].nrHorizons, arr[k].totalDepth = nh, float(s["totalDepth"])
+        for name in CRACK_FIELDS:
+            for h in range(min(nh, MAX_HORIZONS)):
+                getattr(arr[k], name)[h] = float(s[name][h])
+    return arr
+
+
+def set_cracking(sf: capi.SF3D, crack_soils=None):
+    """sf3d_sink_set_cracking: soil cracking (computeSoilCracking) for the hours that follow; None or an empty list turns it off"""
+    bind(sf)
+    if not crack_soils:
+        sf.check(sf.lib.sf3d_sink_set_cracking(0, None), "sink_set_cracking")
+        return
+    sf.check(sf.lib.sf3d_sink_set_cracking(len(crack_soils), crack_soil_array(crack_soils)), "sink_set_cracking")
+
+
+def get_crack_tables(sf: capi.SF3D):
+    """what the host evaluated per soil: (maxDepth [m], lastLayer), -9999 where the soil never cracks"""
+    ns = sf._sink_soils
+    md, ll = np.zeros(ns), np.zeros(ns, np.int32)
+    sf.check(sf.lib.sf3d_sink_get_crack_tables(md.ctypes.data_as(pf64), ll.ctypes.data_as(pi32)), "sink_get_crack_tables")
+    return md, ll
+
+
+def get_crack(sf: capi.SF3D):
+    """(precSurfaceWater [mm] float32: what computeSoilCracking returned, crackWater [mm]: what went into the crack's nodes), the flag where
+    the cell was not computed"""
+    shape = sf._sink_shape
+    p, w = np.empty(shape, np.float32), np.empty(shape, np.float64)
+    sf.check(sf.lib.sf3d_sink_get_crack(p.size, p.ctypes.data_as(pf32), w.ctypes.data_as(pf64)), "sink_get_crack")
+    return p, w
+
+
 def kernel_ms(sf: capi.SF3D) -> float:
     return float(sf.lib.sf3d_sink_kernel_ms())
 
@@ -204,16 +263,150 @@ def horizon_table(soils, layer_depth):
     return t
 
 
+def crack_tables(soils, crack_soils, layer_depth, layer_thickness, computation_depth, reasons=None):
+    """The part of computeSoilCracking that depends on the soil and the layer grid only (criteria3DProject.cpp:1003-1035, :1078; the layer
+    index by getSoilLayerIndex, project3D.cpp:1764-1776): (maxDepth, lastLayer) per soil, -9999 where the soil never cracks.  `soils`: the
+    sink soils (upperDepth, lowerDepth); `reasons`: a list that receives one arm name per soil."""
+    nl = len(layer_depth)
+    max_depth_of, last_layer_of = np.full(len(soils), float(NODATA)), np.full(len(soils), NODATA, np.int32)
+    for s, (so, cs) in enumerate(zip(soils, crack_soils)):
+        def never(why):
+            if reasons is not None:
+                reasons.append(why)
+        soil_depth = min(computation_depth, cs["totalDepth"])
+        if soil_depth <= MIN_FINE_LAYER_DEPTH:
+            never("crack: soilDepth <= 0.2 by " + ("computationSoilDepth" if computation_depth <= MIN_FINE_LAYER_DEPTH else "totalDepth"))
+            continue
+        last_fine = NODATA
+        max_depth = min(soil_depth, MAX_CRACKING_DEPTH)
+        h = 0
+        while h < len(cs["clay"]) and so["upperDepth"][h] < max_depth:
+            fine = (cs["clay"][h] + cs["silt"][h] * 0.5) / 100 * (1 - cs["coarseFragments"][h]) * (1 - cs["organicMatter"][h])
+            if fine < MIN_FINE_FRACTION:
+                break
+            last_fine = h
+            h += 1
+        ended_by_horizon = h < len(cs["clay"]) and so["upperDepth"][h] < max_depth
+        if last_fine == NODATA:
+            never("crack: first horizon not fine")
+            continue
+        max_depth = min(so["lowerDepth"][last_fine], MAX_CRACKING_DEPTH)
+        max_depth = min(max_depth, computation_depth)
+        if max_depth < MIN_FINE_LAYER_DEPTH:
+            never("crack: fine horizon too thin")
+            continue
+        last_layer = NODATA
+        if nl > 0 and max_depth >= 0:
+            for layer in range(nl):
+                if max_depth <= layer_depth[layer] + layer_thickness[layer] * 0.5:
+                    last_layer = layer
+                    break
+        if last_layer == NODATA:
+            never("crack: lastLayer NODATA")
+            continue
+        max_depth_of[s], last_layer_of[s] = max_depth, last_layer
+        if reasons is not None:
+            reasons.append("crack: fine down to MAX_CRACKING_DEPTH" if max_depth == MAX_CRACKING_DEPTH else
+                           "crack: a second horizon ends the fine range" if ended_by_horizon and last_fine >= 0 else "crack: the soil ends the fine range")
+    return max_depth_of, last_layer_of
+
+
+def restate_soil_cracking(r, c, columns, water, max_water, minimum_pond, si, tables, soils, hz_of, layer_depth, layer_thickness, area, precipitation,
+                          additions, hit, reasons=None):
+    """The per-cell part of computeSoilCracking (criteria3DProject.cpp:988-1000, :1037-1122) behind crack_tables: `precipitation` a float32,
+    `water` / `max_water`: getCriteria3DVar(volumetricWaterContent / maxVolumetricWaterContent) of a node, `minimum_pond`:
+    getCriteria3DVar(surfacePond) of the surface node [mm].  Writes each filled node's flow rate into `additions`; returns (the function's
+    float32, the water that went into the crack [mm])."""
+    p = float(precipitation)
+    nl = len(layer_depth)
+    if si < 0:
+        hit("crack: no soil index")
+        return precipitation, 0.0
+    if p <= minimum_pond:
+        hit("crack: precipitation <= minimumPond")
+        return precipitation, 0.0
+    max_depth, last_layer = float(tables[0][si]), int(tables[1][si])
+    if last_layer == NODATA:
+        hit(reasons[si] if reasons else "crack: the soil never cracks")
+        return precipitation, 0.0
+    if reasons:
+        hit(reasons[si])
+    so = soils[si]
+
+    def void_volume(layer):
+        n = int(columns[layer][r][c])
+        fraction = so["soilFraction"][int(hz_of[si, layer])]
+        return max(0.0, max_water(n) - water(n)) * fraction
+    crack_depth, voids_sum = 0.0, 0.0
+    layer = 1
+    while layer < nl and layer_depth[layer] <= max_depth:
+        if int(columns[layer][r][c]) < 0:
+            hit("crack: hole at layer 1" if layer == 1 else "crack: a hole inside the range")
+            break
+        if int(hz_of[si, layer]) == NODATA:
+            hit("crack: horizon NODATA inside the range")
+            break
+        voids_sum += void_volume(layer) * layer_thickness[layer]
+        crack_depth += layer_thickness[layer]
+        layer += 1
+    reached = layer
+    if crack_depth == 0.0:
+        hit("crack: crackDepth == 0")
+        return precipitation, 0.0
+    avg_void = voids_sum / crack_depth
+    if avg_void <= MIN_VOID_VOLUME:
+        hit("crack: avgVoidVolume <= 0.15")
+        return precipitation, 0.0
+    ratio = (avg_void - MIN_VOID_VOLUME) / (MAX_VOID_VOLUME - MIN_VOID_VOLUME)
+    crack_ratio = 0.0 if ratio < 0.0 else (1.0 if 1.0 < ratio else ratio)
+    hit("crack: crackRatio clamped to 1" if 1.0 < ratio else "crack: crackRatio inside (0, 1)" if 0.0 < ratio < 1.0 else "crack: crackRatio at a bound")
+    max_infiltration = p * crack_ratio
+    surface_water = max(p - max_infiltration, minimum_pond)
+    if p - max_infiltration < minimum_pond:
+        hit("crack: surfaceWater raised to minimumPond")
+    potential = max(0.0, p - surface_water)
+    residual = potential
+    crack_water = 0.0
+    capped = below = False
+    broke = False
+    for l in range(last_layer, 0, -1):
+        if residual <= 0:
+            broke = True
+            break
+        n = int(columns[l][r][c])
+        if n < 0:
+            continue
+        void = void_volume(l) if l < reached else 0.0       # voidVolumeList is 0 where the first loop did not come
+        storage = min(void, MAX_STORAGE)
+        layer_water = min(layer_thickness[l] * 1000 * storage, residual)
+        flow_rate = area * (layer_water / 1000.) / 3600.
+        if flow_rate > 0.0:
+            additions[n] = flow_rate
+            residual -= layer_water
+            crack_water += layer_water
+            capped = capped or void > MAX_STORAGE
+            below = below or void < MAX_STORAGE
+    if capped and below:
+        hit("crack: storage capped in one layer and below the cap in another")
+    if broke:
+        hit("crack: rain used up before layer 1")
+    elif residual > 0:
+        hit("crack: residual left after layer 1")
+    return np.float32(surface_water + residual), crack_water
+
+
 def _covered_surface_fraction(lai):
     return 0.0 if lai < EPSILON else 1 - math.exp(-0.6 * lai)
 
 
 def restate_sink_hour(dem, flag, cell_size, columns, vwc, crop_index, soil_index, units, soils, layer_depth, layer_thickness, computation_depth,
-                      et0, lai, degree_days, liquid_water, roots, n_nodes, arms=None):
+                      et0, lai, degree_days, liquid_water, roots, n_nodes, arms=None, cracking=None):
     """One hour on plain doubles.  columns[layer][row][col]: the node, -1 where none; vwc[node]: getCriteria3DVar(volumetricWaterContent);
     roots: dict(length, first, last, density[layer]) of the hour (root.restate_root_maps or the root pin).  Returns dict(sinks_et: the
     node sinks after evaporation and transpiration, sinks: with the rain term, evaporation, transpiration).  `arms`: a dict that counts
-    the (cell, hour) pairs per arm, for the tests."""
+    the (cell, hour) pairs per arm, for the tests.  `cracking`: None, or dict(crack_soils, max_vwc[node], pond[node]: getCriteria3DVar(
+    maxVolumetricWaterContent / surfacePond [mm])) - then the rain term goes through restate_soil_cracking and the result also holds
+    prec_surface_water (float32) and crack_water, the flag where the cell is not computed."""
     dem = np.asarray(dem, np.float32)
     rows, cols = dem.shape
     nl = len(layer_depth)
@@ -235,6 +428,15 @@ def restate_sink_hour(dem, flag, cell_size, columns, vwc, crop_index, soil_index
 
     def water(n):
         return float(NODATA) if n < 0 else float(vwc[n])
+
+    if cracking is not None:
+        reasons = []
+        tables = crack_tables(soils, cracking["crack_soils"], layer_depth, layer_thickness, computation_depth, reasons)
+        prec_surface = np.full(dem.shape, fl, np.float32)
+        crack_water = np.full(dem.shape, float(fl), np.float64)
+
+        def max_water(n):
+            return float(NODATA) if n < 0 else float(cracking["max_vwc"][n])
 
     for r in range(rows):
         for c in range(cols):
@@ -303,13 +505,28 @@ def restate_sink_hour(dem, flag, cell_size, columns, vwc, crop_index, soil_index
                                                          float(np.float32(degree_days[r][c])), roots, area, sink, hit)
             # ---- the rain term
             lw = np.float32(liquid_water[r][c])
+            prec = lw
+            if cracking is not None:
+                prec_surface[r, c], crack_water[r, c] = lw, 0.0
             if not abs(float(lw) - fl) < EPSILON and lw > 0:
-                surface_flow = area * (float(lw) / 1000.)
+                if cracking is not None:
+                    wet = [int(columns[layer][r][c]) for layer in range(1, nl) if int(columns[layer][r][c]) >= 0 and sink[int(columns[layer][r][c])] != 0]
+                    prec, crack_water[r, c] = restate_soil_cracking(r, c, columns, water, max_water, float(cracking["pond"][s0]), si, tables, soils, hz_of,
+                                                                    layer_depth, layer_thickness, area, lw, rain, hit, reasons)
+                    prec_surface[r, c] = prec
+                    if any(rain[n] > 0 for n in wet):
+                        hit("crack: a filled layer already carries a subtraction")
+                surface_flow = area * (float(prec) / 1000.)
                 if surface_flow / 3600. > 0.:
                     rain[s0] = surface_flow / 3600.
+            elif cracking is not None:
+                hit("crack: liquidWater at the flag" if abs(float(lw) - fl) < EPSILON else "crack: liquidWater <= 0")
     total = sink.copy()
     total[rain > 0] = sink[rain > 0] + rain[rain > 0]
-    return dict(sinks_et=sink, sinks=total, evaporation=evaporation, transpiration=transpiration)
+    out = dict(sinks_et=sink, sinks=total, evaporation=evaporation, transpiration=transpiration)
+    if cracking is not None:
+        out.update(prec_surface_water=prec_surface, crack_water=crack_water)
+    return out
 
 
 def _restate_transpiration(r, c, columns, water, ci, si, units, soils, hz_of, nl, et0, current_lai, cov, dd, roots, area, sink, hit):

@@ -2,7 +2,10 @@
 launch), the sf3d_sink_compute_hour call with every input resident on the device (NULL maps: the crop, snow and root blocks), and
 sf3d_sink_apply, beside the path they replace, measured in the same run: sf3d_root_get_density of all layers (the download a host-side
 assembly starts with) plus the upload of N sinks through sf3d_set_node_water_sink_source node by node.  20 launches after 3 warm-ups.
-usage: python scripts/sink_timing.py [--launches 20] [--warmup 3] [--out profiles/sink_C5_timing.json]"""
+Then an hour of 10 mm rain with soil cracking (sf3d_sink_set_cracking: k_sink_hour_crack) and without, alternating, on the same inputs; the
+soil nodes are dry (-800 / -150 m in alternate layers) so that the two clay soils of the raster do crack.  --library times another build of
+the product library (the parent commit's, for one): a library without sf3d_sink_set_cracking gives the plain hour only.
+usage: python scripts/sink_timing.py [--launches 20] [--warmup 3] [--library libsf3d_hip.so] [--out profiles/sink_C5_timing.json]"""
 import argparse
 import hashlib
 import json
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "sink_C5_timing.json"))
+    ap.add_argument("--library", default=None, help="another build of the product library (default: the tree's)")
     a = ap.parse_args()
     from tests import crop_cases as cc
     from tests import sink_cases as sc
@@ -43,9 +47,17 @@ def main():
     soil_index = np.where(valid, r // 8 % 2, -1).astype(np.int32)          # the two deep soils of the pin
     dd = np.where(valid, (10.0 + ((r * 7 + c * 3) % 1500)), flag).astype(np.float32)
     lai = np.where(valid, 0.25 * ((r + 2 * c) % 17), flag).astype(np.float32)
-    sf = capi.load_product()
+    sf = capi.SF3D(Path(a.library).resolve()) if a.library else capi.load_product()
+    if not hasattr(sf.lib, "sf3d_sink_set_cracking"):         # a build from before soil cracking: bind what it has
+        for name in [k for k in sinks.SIGNATURES if "crack" in k]:
+            del sinks.SIGNATURES[name]
     sf.check(sf.lib.sf3d_reset_solver_state(), "reset")
     cm.build(sf, m, threads=1)
+    layer_of_node = np.repeat(np.arange(len(thick)), [int(np.count_nonzero(columns[l] >= 0)) for l in range(len(thick))])
+    assert len(layer_of_node) == m.n and np.all(np.diff(columns[columns >= 0]) > 0)      # layer-major numbering
+    psi = np.where(layer_of_node % 2 == 1, -800.0, -150.0)    # dry soil nodes
+    psi[:m.ns] = 0.0
+    sf.set_matric_potential_bulk(0, psi)
     sinks.set_columns(sf, columns, thick)
     crop_units = cc.load_pin()["unit_list"]
     snow.initialize(sf, dem, flag)
@@ -70,6 +82,31 @@ def main():
             kernel_us.append(sinks.kernel_ms(sf) * 1e3); call_ms.append((t1 - t0) * 1e3); apply_ms.append((t2 - t1) * 1e3)
     q = sinks.get_node_sinks(sf, m.n)
     evaporation, transpiration = sinks.get_actual(sf)
+    cracked = None
+    if hasattr(sf.lib, "sf3d_sink_set_cracking"):             # the cracked hour and the plain hour in turn, on the same inputs
+        from tests.golden.make_soil_cracking import TEXTURE
+        crack_soils = [dict(totalDepth=so["totalDepth"], clay=[t[0] for t in tx], silt=[t[1] for t in tx], coarseFragments=[1.0 - f for f in so["soilFraction"]],
+                            organicMatter=[t[2] for t in tx]) for so, tx in zip(soils, TEXTURE)]
+        crack_us, plain_us = [], []
+        rain = np.where(valid, 10.0, flag).astype(np.float32)      # [mm]: more than the ponds hold (2 mm), so that the dry clay does crack
+        for h in range(a.warmup + a.launches):
+            sinks.set_cracking(sf, crack_soils)
+            sinks.compute_hour(sf, None, None, None, rain)
+            if h >= a.warmup:
+                crack_us.append(sinks.kernel_ms(sf) * 1e3)
+            if h == a.warmup + a.launches - 1:
+                prec_surface, crack_water = sinks.get_crack(sf)
+                q_crack = sinks.get_node_sinks(sf, m.n)
+            sinks.set_cracking(sf, None)
+            sinks.compute_hour(sf, None, None, None, rain)
+            if h >= a.warmup:
+                plain_us.append(sinks.kernel_ms(sf) * 1e3)
+        q_plain = sinks.get_node_sinks(sf, m.n)
+        assert np.array_equal(q_plain[m.ns:], q[m.ns:])              # cracking off again: below the surface the plain hour's bits
+        q = q_plain
+        cracked = dict(rain_mm=10.0, k_sink_hour_crack=stats(crack_us, "kernel_us"), k_sink_hour_alternating=stats(plain_us, "kernel_us"),
+                       cells_cracking=int(np.count_nonzero((crack_water != flag) & (crack_water > 0))),
+                       nodes_filled=int(np.count_nonzero(q_crack[m.ns:] > q[m.ns:])))
     for h in range(max(3, a.launches // 4)):                  # the replaced path: the density download, then N single setters
         t0 = time.perf_counter()
         root.get_density(sf, -1)
@@ -86,7 +123,8 @@ def main():
                k_sink_hour=stats(kernel_us, "kernel_us"), compute_call_inputs_resident=stats(call_ms, "call_ms"), apply_call=stats(apply_ms, "call_ms"),
                replaced_path=dict(root_get_density_all_layers=stats(density_ms, "call_ms"), upload_of_n_sinks_through_the_setter=stats(setter_ms, "call_ms")),
                nodes_with_a_sink=int(np.count_nonzero(q)), cells_evaporating=int(np.count_nonzero((evaporation != flag) & (evaporation > 0))),
-               cells_transpiring=int(np.count_nonzero((transpiration != flag) & (transpiration > 0))), fingerprint=hashlib.sha256(src).hexdigest()[:16])
+               cells_transpiring=int(np.count_nonzero((transpiration != flag) & (transpiration > 0))), soil_cracking=cracked,
+               library=Path(a.library).name if a.library else "libsf3d_hip.so", fingerprint=hashlib.sha256(src).hexdigest()[:16])
     line = json.dumps(res)
     print(line)
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
