@@ -693,6 +693,44 @@ struct RadSetup {       /* what sf3d_rad_initialize hands to DeviceSolver::rad_a
     float flag, demMax;
 };
 
+/* ---- station transmissivity and its window (sf3d_transmissivity.inc, include/sf3d_transmissivity.h): one wave64 per point, a lane per
+ * evaluation of computeRadiationRsun, lane 0 of the wave adds up in the reference's order ---- */
+#define TR_MAX_WIDTH 63                 /* a lane per window slot: widths above 63 are refused */
+#define TR_WINDOW_SLOTS 24              /* estimateTransmissivityWindow: noon, the centre and 11 pairs of steps (MAX_STEPS = 23) */
+#define TR_MAX_POINTS 65536             /* the cap on nPoints of one call */
+#define TR_WAVE 64
+enum { TR_MODE_POINTS = 0, TR_MODE_WINDOW = 1 };
+struct TrPointDev {     /* a station: its own coordinates in doubles and the terms of its place (radsCellAt on its height, float(lat), float(lon), slope 0, aspect 180) */
+    double x, y, z;
+    RadCellDev cell;
+    int32_t inGrid;                     /* ! gis::isOutOfGridXY(x, y, dem.header): the shadow ray is marched */
+    int32_t pad;
+};
+struct TrView {         /* k_transmissivity_points */
+    RadGridDev grid;
+    const RadHourDev* hours;            /* [nSlots] radsHour of every slot's time, Linke and the settings filled in */
+    const uint8_t* hourOk;              /* [nSlots] 0: S_solpos refuses the slot's date (computeRadiationRsun returns false) */
+    const TrPointDev* points;           /* [nPoints] */
+    const float* measured;              /* [nPoints][nSlots], TR_MODE_POINTS */
+    uint8_t* written;                   /* [nPoints][nSlots] 1: the evaluation wrote; 0: it failed or was skipped */
+    float* elevationRefr;               /* [nPoints][nSlots] */
+    double* global;                     /* [nPoints][nSlots] radPoint.global, a double */
+    float* transmissivity;              /* [nPoints], TR_MODE_POINTS */
+    int32_t* windowSteps;               /* [nPoints], TR_MODE_WINDOW */
+    uint32_t nPoints;
+    int32_t nSlots, mode;
+    float clearSky;
+};
+struct TrCall {         /* what the entry points hand to DeviceSolver::tr_run: host pointers */
+    const RadHourDev* hours;
+    const uint8_t* hourOk;
+    const TrPointDev* points;
+    const float* measured;
+    uint32_t nPoints;
+    int32_t nSlots, mode;
+    float clearSky;
+};
+
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */
 enum { KID_PROPS = 0, KID_ASSEMBLE, KID_SWEEP, KID_POST, KID_RESTORE, KID_ACCEPT, KID_SWEEP_PAIR, KID_SWEEP_RES, KID_MAPS, KID_COUNT };
 

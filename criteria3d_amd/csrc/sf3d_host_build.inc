@@ -169,6 +169,11 @@ struct RadCache {
     double xll = 0., yll = 0., cellSize = 0.;
     float flag = -9999.f, demMax = -9999.f;
     double lastMs = 0.;
+    /* station transmissivity (sf3d_transmissivity.inc): the inputs, evaluations and results of the last call, in one block that grows */
+    char* tr = nullptr;
+    size_t trCap = 0, trOff[3] = {0, 0, 0};     /* trOff: global, elevationRefr, written */
+    uint32_t trPoints = 0, trSlots = 0;
+    double trMs = 0.;
 };
 
 /* hourly sinks (sf3d_sink.inc): the per-cell maps and the tables of include/sf3d_sink.h belong to the raster; the node array follows the

@@ -249,6 +249,13 @@ public:
     sf3d_error_t rad_free();
     double rad_kernel_ms() const;
     sf3d_error_t rad_trig(int which, uint32_t n, const double* x, const double* y, double* out);     /* test hook: the device build of sf3d_trig.inc */
+    /* station transmissivity and its window (sf3d_transmissivity.inc) on the raster of the radiation block (the caller has checked that it
+     * is allocated): one launch over call.nPoints x call.nSlots evaluations; the scratch is the radiation block's and goes with rad_free.
+     * tr_evaluated: the last call held this many points and slots, so tr_evaluations may copy them out */
+    sf3d_error_t tr_run(const TrCall& call, float* transmissivity, int32_t* windowSteps);
+    bool tr_evaluated(uint32_t nPoints, uint32_t nSlots) const;
+    sf3d_error_t tr_evaluations(uint8_t* written, float* elevationRefr, double* global);
+    double tr_kernel_ms() const;
     /* hourly evaporation, transpiration and rain sinks (sf3d_sink.inc): the per-cell maps and the tables belong to the raster as the other
      * blocks' do, the node array to the model on the device (release() frees it); sink_hour reads the accepted state after sync_to_device as
      * output_map does and the root block's maps, and, where a map of `call` is null, the crop / snow block's */

@@ -226,9 +226,12 @@ SF3D_RAD_FN void rad_separate(double clearSkyTransmissivity, double transmissivi
     td = Tt * Kd_reindl;
 }
 
-/* computeRadiationDemPoint + computeRadiationRsun for the cell (row, col); false: nothing is written.  out: sun elevation (refracted),
- * global, beam, diffuse, reflected */
-SF3D_RAD_FN bool rad_point(const RadGridDev& g, const RadHourDev& h, const RadCellDev& c, int row, int col, float transmissivityF, float out[5])
+/* computeRadiationRsun for a point at (x0, y0, z0) with the terms `c` of its place; false: nothing is written.  march: the shadow ray runs
+ * (! gis::isOutOfGridXY, solarRadiation.cpp:748: a cell centre is never out of the grid, a station may be).  elev: the refracted sun
+ * elevation; res: global, beam, diffuse, reflected as the doubles of TradPoint.  k_rad_hour (rad_point) and k_transmissivity_points
+ * (sf3d_transmissivity.inc) share this text */
+SF3D_RAD_FN bool rad_eval(const RadGridDev& g, const RadHourDev& h, const RadCellDev& c, double x0, double y0, double z0, bool march, double transmissivity,
+                          float& elev, double res[4])
 {
     RadSun sun;
     if (!rad_sun_position(h, c, sun)) return false;
@@ -240,17 +243,11 @@ SF3D_RAD_FN bool rad_point(const RadGridDev& g, const RadHourDev& h, const RadCe
     bool shadow = true;                             /* never set with shadowing off: see the head of this file */
     if (h.shadowing) {
         shadow = !lit;
-        if (lit) {
-            /* Crit3DRasterGrid::getXY, gis.cpp:473-477; the cell centre is never out of the grid */
-            const double x0 = g.xll + g.cellSize * ((double)col + 0.5);
-            const double y0 = g.yll + g.cellSize * ((double)(g.nRows - row) - 0.5);
-            shadow = rad_shadow(g, x0, y0, (double)c.height, sun);
-        }
+        if (lit && march) shadow = rad_shadow(g, x0, y0, z0, sun);
     }
-    out[0] = sun.elevationRefr;
-    if (!lit) { out[1] = 0.f; out[2] = 0.f; out[3] = 0.f; out[4] = 0.f; return true; }
+    elev = sun.elevationRefr;
+    if (!lit) { res[0] = 0.; res[1] = 0.; res[2] = 0.; res[3] = 0.; return true; }
 
-    double transmissivity = transmissivityF;
     if (h.realSky && transmissivity == RAD_NODATA) return false;
 
     const double linke = h.linke, albedoIn = h.albedo, clearSky = h.clearSky;
@@ -336,7 +333,20 @@ SF3D_RAD_FN bool rad_point(const RadGridDev& g, const RadHourDev& h, const RadCe
         }
         global = beam + diffuse + reflected;
     }
-    out[1] = (float)global; out[2] = (float)beam; out[3] = (float)diffuse; out[4] = (float)reflected;
+    res[0] = global; res[1] = beam; res[2] = diffuse; res[3] = reflected;
+    return true;
+}
+
+/* computeRadiationDemPoint + computeRadiationRsun for the cell (row, col); false: nothing is written.  out: sun elevation (refracted),
+ * global, beam, diffuse, reflected as the maps store them */
+SF3D_RAD_FN bool rad_point(const RadGridDev& g, const RadHourDev& h, const RadCellDev& c, int row, int col, float transmissivityF, float out[5])
+{
+    /* Crit3DRasterGrid::getXY, gis.cpp:473-477; the cell centre is never out of the grid */
+    const double x0 = g.xll + g.cellSize * ((double)col + 0.5);
+    const double y0 = g.yll + g.cellSize * ((double)(g.nRows - row) - 0.5);
+    double res[4];
+    if (!rad_eval(g, h, c, x0, y0, (double)c.height, true, (double)transmissivityF, out[0], res)) return false;
+    out[1] = (float)res[0]; out[2] = (float)res[1]; out[3] = (float)res[2]; out[4] = (float)res[3];
     return true;
 }
 
@@ -406,7 +416,7 @@ sf3d_error_t DeviceSolver::rad_trig(int which, uint32_t n, const double* x, cons
 sf3d_error_t DeviceSolver::rad_free()
 {
     if (!impl_) return SF3D_OK;
-    raster_release({impl_->rad.base});
+    raster_release({impl_->rad.base, impl_->rad.tr});
     impl_->rad = RadCache();
     return SF3D_OK;
 }

@@ -12,6 +12,7 @@ namespace {
 struct RadHost {
     bool on = false;
     uint32_t nRows = 0, nCols = 0;
+    double xll = 0., yll = 0., cellSize = 0.;  /* the raster's place: sf3d_transmissivity_api.inc asks where a station lies */
     sf3d_rad_settings_t set;
 } RD;
 
@@ -80,7 +81,7 @@ sf3d_error_t sf3d_rad_initialize(uint32_t nrRows, uint32_t nrCols, const float* 
     setup.xll = xllCorner; setup.yll = yllCorner; setup.cellSize = cellSize; setup.flag = flag; setup.demMax = demMax;
     const sf3d_error_t e = dev().rad_alloc(setup);
     if (e != SF3D_OK) { rasterFail("rad initialize", e); radClear(); return e; }
-    RD.nRows = nrRows; RD.nCols = nrCols; RD.set = s;
+    RD.nRows = nrRows; RD.nCols = nrCols; RD.xll = xllCorner; RD.yll = yllCorner; RD.cellSize = cellSize; RD.set = s;
     RD.on = true;
     return SF3D_OK;
 }

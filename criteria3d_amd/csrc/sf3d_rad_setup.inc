@@ -19,14 +19,13 @@ static inline int radsMonthDays(int y, int m)
 
 /* the cell's part of computeRadiationDemPoint / computeRadiationRsun / S_solpos (solarRadiation.cpp:734, 479-496, 534; solPos.cpp:327-344,
  * 886-890, 912-917).  slope and aspect: the maps' values (TILT_TYPE_DEM) or the fixed ones */
-static inline RadCellDev radsCell(float height, float lat, float lon, float slope, float aspect)
+static inline RadCellDev radsCellAt(double h, float lat, float lon, float slope, float aspect)
 {
     RadCellDev c;
-    c.height = height; c.lat = lat; c.lon = lon; c.slope = slope; c.aspect = aspect;
+    c.height = float(h); c.lat = lat; c.lon = lon; c.slope = slope; c.aspect = aspect;
     c.cl = float(std::cos(RADS_RADDEG * lat));
     c.sl = float(std::sin(RADS_RADDEG * lat));
-    /* pressureFromAltitude(double(height)) * 0.01, physics.cpp:39-47 */
-    const double h = height;
+    /* pressureFromAltitude(height) * 0.01, physics.cpp:39-47: the height is a double (a raster cell's is double(float), a station's its own) */
     const double pressure = 101325. * std::pow(1 + h * 0.0065 / 293.16, -9.80665 / (0.0065 * 287.058)) * 0.01;
     c.press = float(pressure);
     c.cp = std::cos(RADS_RADDEG * aspect);
@@ -47,6 +46,7 @@ static inline RadCellDev radsCell(float height, float lat, float lon, float slop
     c.ok = bad ? 0 : 1;
     return c;
 }
+static inline RadCellDev radsCell(float height, float lat, float lon, float slope, float aspect) { return radsCellAt(height, lat, lon, slope, aspect); }
 
 /* the call's part: the local-time shift of solarRadiation.cpp:714-726 (Crit3DTime::addSeconds, crit3dTime.cpp:145-165), validate(),
  * dom2doy() and the date-and-time part of geometry() (solPos.cpp:293-331, 373-382, 426-555), localtrig()'s declination terms and etrn.

@@ -52,3 +52,4 @@
 #include "sf3d_meteo.inc"
 #include "sf3d_sink.inc"
 #include "sf3d_rad.inc"
+#include "sf3d_transmissivity.inc"

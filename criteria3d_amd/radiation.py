@@ -597,11 +597,25 @@ def _separate(clear_sky, transmissivity, elev_deg, sin_elev_deg):
 def rad_point(grid: dict, h: dict, c: dict, row: int, col: int, transmissivity: float, sun_arms: list | None = None):
     """computeRadiationDemPoint + computeRadiationRsun -> (the five values or None when nothing is written, arm bits); sun_arms: a list that
     receives the SUN_ARMS bits of the cell's sun position"""
+    nrows = grid["dem"].shape[0]
+    x0 = grid["xll"] + grid["cellsize"] * (float(col) + 0.5)
+    y0 = grid["yll"] + grid["cellsize"] * (float(nrows - row) - 0.5)
+    v, arms = rad_eval(grid, h, c, x0, y0, float(c["height"]), True, transmissivity, sun_arms)
+    return (None if v is None else (v[0],) + tuple(f32(x) for x in v[1:])), arms
+
+
+def rad_eval(grid: dict, h: dict, c: dict, x0: float, y0: float, z0: float, march: bool, transmissivity: float, sun_arms: list | None = None,
+             sun_out: list | None = None):
+    """computeRadiationRsun for a point at (x0, y0, z0) -> ((elevationRefr, global, beam, diffuse, reflected) with the four radiations as
+    the doubles of TradPoint, or None when nothing is written, arm bits).  march: the shadow ray runs (the point is inside the DEM);
+    sun_out: a list that receives the sun position where it was computed (also when the evaluation then fails)"""
     sun = sun_position(h, c)
     if sun is None:
         return None, _ARM["false: S_solpos range check"]
     if sun_arms is not None:
         sun_arms.append(sun["sunArms"])
+    if sun_out is not None:
+        sun_out.append(sun)
     lit = False
     if sun["rise"] != NODATA and sun["set"] != NODATA and sun["elevationRefr"] != NODATA:
         lit = h["localTime"] >= sun["rise"] and h["localTime"] <= sun["set"] and sun["elevationRefr"] > 0
@@ -609,11 +623,8 @@ def rad_point(grid: dict, h: dict, c: dict, row: int, col: int, transmissivity: 
     shaded = True           # TsunPosition::shadow is never set with shadowing off and reads non-zero in the pin build (sf3d_rad.inc)
     if h["shadowing"]:
         shaded = not lit
-        if lit:
-            nrows = grid["dem"].shape[0]
-            x0 = grid["xll"] + grid["cellsize"] * (float(col) + 0.5)
-            y0 = grid["yll"] + grid["cellsize"] * (float(nrows - row) - 0.5)
-            shaded, a = shadow(grid, x0, y0, float(c["height"]), sun)
+        if lit and march:
+            shaded, a = shadow(grid, x0, y0, z0, sun)
             arms |= a
     if not lit:
         return (sun["elevationRefr"], 0.0, 0.0, 0.0, 0.0), arms
@@ -702,7 +713,7 @@ def rad_point(grid: dict, h: dict, c: dict, row: int, col: int, transmissivity: 
         else:
             reflected = _clamp(h["albedo"], 0.0, 1.0) * (bh + dh) * c["reflGeom"] / 2.
         glob = beam + diffuse + reflected
-    return (elev, f32(glob), f32(beam), f32(diffuse), f32(reflected)), arms
+    return (elev, glob, beam, diffuse, reflected), arms
 
 
 def restate_radiation_hour(dem, flag, xll, yll, cell_size, lat, lon, slope, aspect, when, transmissivity, settings: dict | None = None, previous=None,

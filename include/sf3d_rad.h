@@ -9,8 +9,9 @@
  * expected (the double sin / cos / tan of the device are faithful routines, not the C library's).  The global and beam irradiance and
  * the transmissivity are what sf3d_snow_compute_hour and sf3d_crop_compute_hour take; a caller downloads and passes them.
  *
- * With the caller: computeTransmissivity and its window estimate (per station, host), the Brooks point model and the meteo-point /
- * output-point variants, updateMinMaxRasterGrid, and the sun-position error return beyond leaving the cell untouched.
+ * computeTransmissivity and its window estimate are include/sf3d_transmissivity.h (per station, on the device, on this block's raster
+ * and settings).  With the caller: the station series behind them, the Brooks point model and the
+ * meteo-point / output-point variants, updateMinMaxRasterGrid, and the sun-position error return beyond leaving the cell untouched.
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.
  *

@@ -1,0 +1,290 @@
+"""Station transmissivity and its window on the device (include/sf3d_transmissivity.h, k_transmissivity_points) against the
+compiled-reference pin tests/golden/transmissivity.npz: every station of every case - the float transmissivity, nValid and the int window
+width; the evaluations of the device (written flags, elevation, the double global) against the host build of the same text
+(tests/transmissivity_host.cpp) bit for bit; 1 x 1, 3 x 3, 5 x 13, 65 x 23 and 300 x 23 stations x slots off the pin against the
+restatement (less than a wave, a partial block, a partial last block), which together reach every arm of the pin; a one-row raster and a
+station on the raster's last row and column; what needs the radiation block to be refused; no side effect on the radiation maps and the
+solver; the scratch survives sf3d_initialize and goes with sf3d_clean; and the chain points -> meteo interpolation -> radiation hour on
+the device against the same three steps with the values passed through the host."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from criteria3d_amd import capi, catchment as cm, meteo, radiation as rad, transmissivity as tr
+from tests import rad_cases
+from tests import transmissivity_cases as tc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return tc.load_pin()
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return tc.build_host(tmp_path_factory.mktemp("transmissivity_host"))
+
+
+@pytest.fixture(scope="module")
+def static(pin):
+    """latitude and longitude maps of the pin's rasters (the station calls read neither; sf3d_rad_initialize asks for them)"""
+    out = []
+    for r, info in enumerate(pin["rasters"]):
+        dem, flag, geo = tc.raster_of(pin, r)
+        header = dict(nrows=dem.shape[0], ncols=dem.shape[1], xllcorner=geo[0], yllcorner=geo[1], cellsize=geo[2])
+        out.append(rad.latlon_maps(header, dict(utmZone=info["utmZone"], startLatitude=info["startLatitude"]), dem=dem, flag=flag))
+    return out
+
+
+def _start(product, pin, static, r, settings):
+    dem, flag, geo = tc.raster_of(pin, r)
+    s = rad.settings_dict(settings)
+    zeros = np.zeros_like(dem)
+    rad.initialize(product, dem, geo[0], geo[1], geo[2], static[r][0], static[r][1], zeros, zeros,
+                   linke_map=dem if s["linkeMode"] == rad.MODE_MAP else None, albedo_map=dem if s["albedoMode"] == rad.MODE_MAP else None,
+                   settings=settings, flag=flag)
+
+
+def _same(got, want, what, dtype=np.float32):
+    same = tc.same_bits(got, want, dtype)
+    assert same.all(), (what, int((~same).sum()), np.argwhere(~same)[:4].tolist(), np.asarray(got)[~same][:4], np.asarray(want)[~same][:4])
+
+
+def _windows(product, case, stations):
+    return [tr.window(product, case["when"], case["step"], p) for p in stations]
+
+
+def test_every_station_of_every_pin_case(product, pin, static):
+    checked = 0
+    for k, c in enumerate(pin["cases"]):
+        _start(product, pin, static, c["raster"], c["settings"])
+        st = pin[f"stations{k}"]
+        if c["mode"] == tc.POINTS:
+            got, n_valid = tr.points(product, c["when"], c["width"], c["step"], st, pin[f"measured{k}"])
+            _same(got, pin[f"result{k}"], c["name"])
+            assert n_valid == int((np.abs(pin[f"result{k}"].astype(np.float64) + 9999.0) >= 1e-5).sum()) and (n_valid > 0) == bool(c["ret"]), c["name"]
+        else:
+            assert _windows(product, c, st) == pin[f"result{k}"].tolist(), c["name"]
+        checked += 1
+    rad.clean(product)
+    assert checked == len(pin["cases"]) >= 40
+
+
+def test_device_evaluations_equal_the_host_build_of_the_same_text_bit_for_bit(product, pin, static, host, tmp_path):
+    """written flags, sunPosition.elevationRefr and the double radPoint.global of every (station, slot): the pin's cases on the scaled
+    window and the small sets; one window call per case (the evaluations are the last call's)"""
+    dem, flag, geo = tc.raster_of(pin, 1)
+    idx, calls = tc.pin_calls(pin, 1)
+    calls = list(calls) + [(tc.SMALL[s][0], tc.SMALL[s][1], tc.POINTS, s[1], tc.SMALL[s][2], tc.small_set(s)[0], tc.small_set(s)[1]) for s in tc.SHAPES]
+    want = tc.run_host(host, tmp_path, dem, flag, geo, calls, tag="dev")
+    lit = 0
+    for (settings, when, mode, width, step, st, measured), h in zip(calls, want):
+        _start(product, pin, static, 1, settings)
+        if mode == tc.POINTS:
+            got, _ = tr.points(product, when, width, step, st, measured)
+            _same(got, h["result"], (when, width))
+            w, e, g = tr.evaluations(product, len(st), width)
+            rows = slice(None)
+        else:
+            assert tr.window(product, when, step, st[-1]) == int(h["result"][-1])
+            w, e, g = tr.evaluations(product, 1, tr.WINDOW_SLOTS)
+            rows = slice(len(st) - 1, len(st))
+        assert np.array_equal(w, h["written"][rows]), (when, width)
+        _same(e, h["elev"][rows], (when, width, "elevation"))
+        _same(g, h["glob"][rows], (when, width, "global"), np.float64)
+        lit += int((g > 0).sum())
+    rad.clean(product)
+    assert lit > 500                                                        # not vacuous: thousands of evaluations by day
+
+
+@pytest.mark.parametrize("shape", tc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_small_sets_equal_the_restatement(product, pin, static, shape):
+    ref, _ = tc.small_reference()
+    want, n_valid, arms, evals = ref[shape]
+    settings, when, step = tc.SMALL[shape]
+    st, measured = tc.small_set(shape)
+    _start(product, pin, static, 1, settings)
+    got, nv = tr.points(product, when, shape[1], step, st, measured)
+    _same(got, want, shape)
+    assert nv == n_valid
+    w, _, _ = tr.evaluations(product, *shape)
+    assert [int(w[p].sum()) for p in range(shape[0])] == [sum(v[0] for v in slots.values()) for slots in evals]
+    rad.clean(product)
+
+
+def test_small_windows_equal_the_restatement_and_the_runs_reach_every_arm(product, pin, static):
+    ref, windows = tc.small_reference()
+    st = tc.small_set((65, 23))[0]
+    union = 0
+    for shape in tc.SHAPES:
+        union |= int(np.bitwise_or.reduce(ref[shape][2]))
+    refused = 0
+    for (settings, when, step, count), (steps, arms) in zip(tc.SMALL_WINDOWS, windows):
+        _start(product, pin, static, 1, settings)
+        for p, want in zip(st[:count], steps):
+            if want is None:                                                # S_solpos refuses the station: the reference reads an unset sunPosition
+                out = ctypes.c_int32(-5)
+                q = tr.point_array(p)
+                assert product.lib.sf3d_transmissivity_window(*when, step, q.ctypes.data_as(tr.ppoint), ctypes.byref(out)) == capi.PARAMETER_ERROR
+                assert out.value == -5
+                refused += 1
+            else:
+                assert tr.window(product, when, step, p) == want, (when, p)
+        union |= int(np.bitwise_or.reduce(np.asarray(arms, np.int64)))
+    rad.clean(product)
+    assert refused > 0 and union == (1 << len(tr.ARMS)) - 1                 # what the kernel ran here reaches every arm of the pin
+
+
+def test_one_row_raster_and_a_station_on_the_last_row_and_column(product, pin):
+    g = rad_cases.small_raster((1, 300))
+    geo = rad_cases.GEO
+    rad.initialize(product, g["dem"], *geo, g["lat"], g["lon"], g["slope"], g["aspect"], flag=float(rad_cases.FLAG))
+    grid = tr.grid_of(g["dem"], rad_cases.FLAG, *geo)
+    header = dict(xllcorner=geo[0], yllcorner=geo[1], cellsize=geo[2])
+    x = geo[0] + geo[2] * np.array([0.5, 150.2, 299.5, 299.999, 300.0, -0.1])
+    y = geo[1] + geo[2] * np.array([0.5, 0.01, 0.999, 0.5, 0.5, 1.0])
+    st = tr.station_points(x, y, np.full(6, -9999.0), None, g["dem"], header, float(rad_cases.FLAG))
+    rng = np.random.default_rng(3)
+    for when, width, step in (((2021, 3, 20, 7, 30, 0), 13, 1800), ((2021, 3, 20, 16, 0, 0), 3, 3600)):
+        measured = np.round(rng.uniform(50, 600, (6, width))).astype(np.float32)
+        want, n_valid, _, model, _ = tr.restate_points(grid, None, when, width, step, st, measured)
+        got, nv = tr.points(product, when, width, step, st, measured)
+        _same(got, want, when)
+        assert nv == n_valid == 6
+    # the same on the pin's window: the last row and column's own cell, its outer corner (out of the DEM) and the point just inside it
+    dem, flag, geo = tc.raster_of(pin, 1)
+    rows, cols = dem.shape
+    lat, lon = rad.latlon_maps(dict(nrows=rows, ncols=cols, xllcorner=geo[0], yllcorner=geo[1], cellsize=geo[2]), dem=dem, flag=flag)
+    rad.initialize(product, dem, *geo, lat, lon, np.zeros_like(dem), np.zeros_like(dem), flag=flag)
+    x = geo[0] + geo[2] * np.array([cols - 0.5, cols, cols - 1e-9, cols - 0.5])
+    y = geo[1] + geo[2] * np.array([0.5, 0.0, 1e-9, rows - 0.5])
+    st = tr.station_points(x, y, np.array([-9999.0, 150.0, -9999.0, -9999.0]), None, dem, dict(xllcorner=geo[0], yllcorner=geo[1], cellsize=geo[2]), flag)
+    measured = np.round(rng.uniform(50, 600, (4, 13))).astype(np.float32)
+    when = (2021, 3, 20, 8, 0, 0)
+    want, n_valid, arms, _, _ = tr.restate_points(tr.grid_of(dem, flag, *geo), None, when, 13, 3600, st, measured)
+    got, nv = tr.points(product, when, 13, 3600, st, measured)
+    _same(got, want, "last row and column")
+    assert nv == n_valid and arms[1] & tr._A["station outside the DEM: no ray"] and arms[2] & tr._A["station inside the DEM"]
+    assert tr.points(product, when, 13, 3600, np.zeros((0, 5)), np.zeros((0, 13), np.float32))[1] == 0                   # nPoints == 0 is allowed
+    rad.clean(product)
+
+
+def test_what_needs_the_radiation_block_is_refused(product, pin, static):
+    dem, flag, geo = tc.raster_of(pin, 1)
+    k = next(k for k, c in enumerate(pin["cases"]) if c["raster"] == 1 and len(pin[f"stations{k}"]) == 7 and c["mode"] == tc.POINTS and c["width"] == 13)
+    st, measured, c = pin[f"stations{k}"], pin[f"measured{k}"], pin["cases"][k]
+    inside, far_east = st[[0, 1, 5]], st[[0, 6]]
+    out, nv = np.zeros(3, np.float32), ctypes.c_uint32(0)
+
+    def call(stations, m):
+        p = tr.point_array(stations)
+        return product.lib.sf3d_transmissivity_points(*c["when"], 13, c["step"], len(p), p.ctypes.data_as(tr.ppoint), np.ascontiguousarray(m).ctypes.data_as(capi.pf32),
+                                                      out.ctypes.data_as(capi.pf32), ctypes.byref(nv))
+    for settings in (dict(linkeMode=rad.MODE_MAP), dict(albedoMode=rad.MODE_MAP)):
+        _start(product, pin, static, 1, settings)
+        assert call(inside, measured[[0, 1, 5]]) == capi.OK                  # inside the raster the map yields NODATA, as the block already does
+        assert call(far_east, measured[[0, 6]]) == capi.PARAMETER_ERROR      # outside the reference indexes its map out of bounds
+        steps = ctypes.c_int32(0)
+        q = tr.point_array(st[6])
+        assert product.lib.sf3d_transmissivity_window(*c["when"], 3600, q.ctypes.data_as(tr.ppoint), ctypes.byref(steps)) == capi.PARAMETER_ERROR
+    _start(product, pin, static, 1, None)
+    assert call(far_east, measured[[0, 6]]) == capi.OK
+    w, e, g = np.zeros(26, np.uint8), np.zeros(26, np.float32), np.zeros(26)
+    ev = lambda n, width: product.lib.sf3d_transmissivity_get_evaluations(n, width, w.ctypes.data_as(tr.pu8), e.ctypes.data_as(capi.pf32), g.ctypes.data_as(capi.pd))
+    assert ev(2, 13) == capi.OK and ev(3, 13) == capi.PARAMETER_ERROR and ev(2, 11) == capi.PARAMETER_ERROR       # sizes other than the last call's
+    rad.clean(product)
+    assert ev(2, 13) == capi.MEMORY_ERROR and call(far_east, measured[[0, 6]]) == capi.MEMORY_ERROR
+
+
+def test_calls_leave_the_radiation_maps_and_the_solver_untouched(product, pin, static):
+    """the smallest catchment the raster blocks use for this, station calls between every two computeSteps: H, Se and the work counters of
+    the run without; and the five radiation maps of an hour are the same with station calls before and after it"""
+    rpin = rad_cases.load_pin()
+    k = next(k for k, c in enumerate(pin["cases"]) if c["raster"] == 1 and len(pin[f"stations{k}"]) == 7 and c["mode"] == tc.POINTS and c["width"] == 13)
+    st, measured, c = pin[f"stations{k}"], pin[f"measured{k}"], pin["cases"][k]
+
+    def start():
+        geo = rpin["geo"]
+        rad.initialize(product, rpin["dem"][1], geo[0], geo[1], geo[2], rpin["lat"][1], rpin["lon"][1], rpin["slope"][1], rpin["aspect"][1], flag=float(rpin["flag"]))
+
+    def run(with_calls):
+        m = cm.catchment_model(16, 16, 4)
+        product.check(product.lib.sf3d_reset_solver_state(), "reset")
+        cm.build(product, m, threads=1)
+        start()
+        rad.compute_hour(product, (2021, 3, 20, 7, 30, 0), rpin["transmissivity"][0])
+        product.set_sink_source_bulk(0, np.full(m.ns, cm.rain_rate(20.0, m.cell_area)))
+        t, n = 0.0, 0
+        while t < 3600.0:
+            dt = product.lib.sf3d_compute_step(3600.0 - t)
+            assert dt > 0.0
+            t += dt
+            if with_calls:
+                got, _ = tr.points(product, c["when"], 13, c["step"], st, measured)
+                _same(got, pin[f"result{k}"], "interleaved")
+                if n % 3 == 0:
+                    tr.window(product, c["when"], 1800, st[0])
+            n += 1
+        maps = np.stack([rad.get_map(product, name) for name in rad.MAPS])
+        s, counters = cm.snapshot(product, m), product.counters()
+        product.lib.sf3d_clean()
+        return s, counters, maps
+    (s0, c0, m0), (s1, c1, m1) = run(False), run(True)
+    assert np.array_equal(s0["H"], s1["H"]) and np.array_equal(s0["Se"], s1["Se"]) and c0 == c1
+    _same(m0, m1, "radiation maps")
+    assert np.count_nonzero(m0[1] > 0) > 100
+
+
+def test_scratch_survives_sf3d_initialize_and_goes_with_sf3d_clean(product, pin, static):
+    k = next(k for k, c in enumerate(pin["cases"]) if c["raster"] == 1 and len(pin[f"stations{k}"]) == 7 and c["mode"] == tc.POINTS and c["width"] == 13)
+    st, measured, c = pin[f"stations{k}"], pin[f"measured{k}"], pin["cases"][k]
+    _start(product, pin, static, 1, c["settings"])
+    got, _ = tr.points(product, c["when"], 13, c["step"], st, measured)
+    before = tr.evaluations(product, 7, 13)
+    m = cm.catchment_model(16, 16, 4)
+    product.check(product.lib.sf3d_reset_solver_state(), "reset")
+    cm.build(product, m, threads=1)                                   # sf3d_initialize inside
+    after = tr.evaluations(product, 7, 13)
+    assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(before, after)) and (before[2] > 0).any()
+    _same(tr.points(product, c["when"], 13, c["step"], st, measured)[0], got, "after sf3d_initialize")
+    product.lib.sf3d_clean()
+    w, e, g = before
+    assert product.lib.sf3d_transmissivity_get_evaluations(7, 13, w.ctypes.data_as(tr.pu8), e.ctypes.data_as(capi.pf32), g.ctypes.data_as(capi.pd)) == capi.MEMORY_ERROR
+
+
+def test_the_chain_on_the_device_equals_the_chain_through_the_host(product, pin):
+    """points -> meteo.interpolate("transmissivity", download=False) -> rad.compute_hour(None) against the same three steps with the
+    interpolated map downloaded and handed back in"""
+    rpin = rad_cases.load_pin()
+    dem, geo, flag = rpin["dem"][1], rpin["geo"], float(rpin["flag"])
+    k = next(k for k, c in enumerate(pin["cases"]) if c["name"] == "forty stations, the hour of sunrise")
+    c, measured = pin["cases"][k], pin[f"measured{k}"]
+    st = pin[f"stations{k}"]
+    when = (2021, 3, 20, 8, 30, 0)
+
+    def start():
+        rad.initialize(product, dem, geo[0], geo[1], geo[2], rpin["lat"][1], rpin["lon"][1], rpin["slope"][1], rpin["aspect"][1], flag=flag)
+        meteo.initialize(product, dem, geo[0], geo[1], geo[2], flag=flag)
+
+    def stations_of():
+        t, n_valid = tr.points(product, when, c["width"], c["step"], st, measured)
+        there = np.abs(t.astype(np.float64) + 9999.0) >= 1e-5
+        assert n_valid == there.sum() >= 10
+        return st[there, 0], st[there, 1], t[there]
+    start()
+    sx, sy, sv = stations_of()
+    meteo.interpolate(product, "transmissivity", "idw", sx, sy, sv, 600.0 * 500.0, download=False)
+    rad.compute_hour(product, when, None)
+    on_device = np.stack([rad.get_map(product, n) for n in rad.MAPS])
+    start()
+    sx, sy, sv = stations_of()
+    t_map = meteo.interpolate(product, "transmissivity", "idw", sx, sy, sv, 600.0 * 500.0)
+    meteo.clean(product)
+    rad.compute_hour(product, when, t_map)
+    _same(on_device, np.stack([rad.get_map(product, n) for n in rad.MAPS]), "chain")
+    assert np.count_nonzero(on_device[1] > 0) > 500
+    meteo.clean(product)
+    rad.clean(product)
