@@ -1,102 +1,13 @@
-/* part of sf3d_solver.hip (included there, in this order: physics, control, phases, host_build, host_step) - host side, part 1: row-strip partition, DeviceSolver::Impl, device selection and sync_to_device (graph derivation, chunk descriptors, patch lists, uploads) */
+/* part of sf3d_solver.hip (included there, in this order: physics, control, phases, host_plan, host_build, host_step) - host side, part 1: DeviceSolver::Impl, device selection, the switches of the build and sync_to_device (the stages of sf3d_host_plan.inc in their order, allocations, uploads; the multi-GPU windows, the resident loop's plan and the coupled-heat arrays in member functions of their own) */
 /* ======================================================================================= */
 /* host side                                                                                */
 /* ======================================================================================= */
 
 namespace {
 
-template <class F> void parallel_for(uint32_t n, F f)
-{
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt == 0) nt = 1;
-    if (nt > 16) nt = 16;
-    if (n < 65536 || nt == 1) { f(0u, n); return; }
-    std::vector<std::thread> th;
-    const uint32_t chunk = (n + nt - 1) / nt;
-    for (unsigned t = 0; t < nt; ++t) {
-        const uint32_t a = t * chunk, b = (a + chunk < n) ? a + chunk : n;
-        if (a >= b) break;
-        th.emplace_back([=] { f(a, b); });
-    }
-    for (auto& t : th) t.join();
-}
-
 const char* kKernelNames[KID_COUNT] = {"k_props", "k_assemble", "k_sweep", "k_post", "k_restore", "k_accept", "k_sweep_pair", "k_sweep_resident", "k_output_map"};
 
 }  // namespace
-
-/* ---- row-strip partition (host logic; also used by CPU tests through sf3d_dist_owner/halo) ----
- * Strip-local build: a rank may stage only the nodes its strip touches - the columns it owns (sf3d_dist_bounds says which surface
- * nodes those are) and the one-cell ring of columns around them, each column whole.  A node that never received its soil / surface
- * class is ABSENT (owner SF3D_OWNER_NONE): it joins no list, and a link to it from a node of another rank's halo is ignored.  What
- * must not happen is a link from one of THIS rank's nodes to an absent node - the caller forgot a halo column (or a class): that is
- * SF3D_MISSING_DATA_ERROR here instead of a wrong answer later.  With every node staged (the global build) nothing changes. */
-sf3d_error_t sf3d_partition_bounds(uint32_t ns, int world, uint32_t* bounds)
-{
-    if (world < 1 || world > SF3D_MAX_RANKS || !bounds) return SF3D_PARAMETER_ERROR;
-    for (int r = 0; r <= world; ++r) {
-        uint64_t b = (uint64_t)ns * r / world;
-        if (r > 0 && r < world) b = (b / SF3D_CHUNK) * SF3D_CHUNK;      /* cut at chunk boundaries */
-        bounds[r] = (uint32_t)b;
-    }
-    bounds[world] = ns;
-    for (int r = 1; r <= world; ++r) if (bounds[r] < bounds[r - 1]) bounds[r] = bounds[r - 1];
-    return SF3D_OK;
-}
-sf3d_error_t sf3d_compute_partition(const HostModel& m, int rank, int world, Partition& out)
-{
-    const uint32_t N = m.N, ns = m.ns;
-    if (world < 1 || world > SF3D_MAX_RANKS || rank < 0 || rank >= world) return SF3D_PARAMETER_ERROR;
-    out.world = world; out.rank = rank;
-    out.owner.assign(N, 0);
-    out.bounds.assign(world + 1, 0);
-    out.send.assign(world, {}); out.recv.assign(world, {});
-    out.missingFrom = out.missingTo = UINT32_MAX;
-    sf3d_partition_bounds(ns, world, out.bounds.data());
-    if (world == 1) return SF3D_OK;
-    auto present = [&](uint32_t i) { return m.hasClass[i] != 0; };
-    /* column id = surface ancestor through Up links (layer-major numbering: one pass suffices) */
-    std::vector<uint32_t> col(N, UINT32_MAX);
-    for (uint32_t i = 0; i < ns && i < N; ++i) col[i] = i;
-    for (int pass = 0; pass < 64; ++pass) {
-        bool changed = false, missing = false;
-        for (uint32_t i = ns; i < N; ++i) {
-            if (col[i] != UINT32_MAX || !present(i)) continue;
-            if (m.ltype[0][i] == SF3D_LINK_NONE) { col[i] = 0; changed = true; continue; }   /* orphan: rank 0 */
-            const uint32_t up = m.lto[0][i];
-            if (col[up] != UINT32_MAX) { col[i] = col[up]; changed = true; } else missing = true;
-        }
-        if (!missing || !changed) break;
-    }
-    for (uint32_t i = 0; i < N; ++i) {
-        if (!present(i)) { out.owner[i] = SF3D_OWNER_NONE; continue; }
-        const uint32_t cidx = col[i] == UINT32_MAX ? 0u : col[i];
-        int r = 0;
-        while (r + 1 < world && cidx >= out.bounds[r + 1]) ++r;
-        out.owner[i] = (uint8_t)r;
-    }
-    for (int s = 0; s < SF3D_SLOTS; ++s)
-        for (uint32_t i = 0; i < N; ++i) {
-            if (m.ltype[s][i] == SF3D_LINK_NONE || out.owner[i] == SF3D_OWNER_NONE) continue;
-            if (s >= 2 && s - 2 >= m.nLat[i]) continue;
-            const uint32_t j = m.lto[s][i];
-            const int a = out.owner[i], b = out.owner[j];
-            if (b == SF3D_OWNER_NONE) {          /* a link into what was never staged: harmless from another rank's halo node, an error from one of mine */
-                if (a == rank && out.missingFrom == UINT32_MAX) { out.missingFrom = i; out.missingTo = j; }
-                continue;
-            }
-            if (a == b) continue;
-            if (a == rank) out.recv[b].push_back(j);       /* my row i reads node j of rank b */
-            if (b == rank) out.send[a].push_back(j);       /* rank a's row i reads my node j   */
-        }
-    for (int r = 0; r < world; ++r) {
-        for (auto* v : {&out.send[r], &out.recv[r]}) {
-            std::sort(v->begin(), v->end());
-            v->erase(std::unique(v->begin(), v->end()), v->end());
-        }
-    }
-    return out.missingFrom == UINT32_MAX ? SF3D_OK : SF3D_MISSING_DATA_ERROR;
-}
 
 /* compiled shapes of k_sweep_resident: K (row, layer) chunks per wave x NW waves per block (PR NZ <= K NW); smallest first */
 struct ResShape { int K, NW; };
@@ -485,6 +396,483 @@ sf3d_error_t DeviceSolver::ensure_device()
     return SF3D_OK;
 }
 
+/* the SF3D_* switches the build block of sync_to_device reads, each parsed once at the top of that block.  Read again on every build and
+ * never cached: tests toggle them between models of one process */
+struct BuildSwitches {
+    bool slotAlign;                     /* SF3D_SLOT_ALIGN (0: off) */
+    int pairSweep;                      /* SF3D_PAIR_SWEEP: -1 unset (automatic: large grids only), 0 off, 1 on */
+    bool residentSweep;                 /* SF3D_RESIDENT_SWEEP; unset: on unless SF3D_PAIR_SWEEP=1 alone asks for the paired passes (tests, measurements) */
+    bool forceMasked;                   /* SF3D_PAIR_FORCE_MASKED=1: measurement: a full box through k_sweep_pair_masked */
+    uint32_t asmSoilBlocks;             /* SF3D_ASM_SOIL_BLOCKS: tuning (0: unset) */
+    int overlapAccept;                  /* SF3D_OVERLAP_ACCEPT */
+    int ntStream;                       /* SF3D_NT_STREAM: -1 unset (by the sweep's working set), 0, 1 */
+    double probeMin;                    /* SF3D_COURANT_PROBE */
+    double autoCost;                    /* SF3D_PAIR_AUTO_COST */
+    bool pairWSet; uint32_t pairW;      /* SF3D_PAIR_W */
+    double distTimeoutS;                /* SF3D_DIST_TIMEOUT_S */
+    int fusedDecide;                    /* SF3D_FUSED_DECIDE (Impl::useFused takes it where that is still unknown) */
+    int haloDirect;                     /* SF3D_HALO_DIRECT: -1 unset, 1 it is 1, 0 anything else */
+    uint32_t pairRecordsWish;           /* SF3D_PAIR_RECORDS: Impl::pairRecordsWish */
+    uint32_t residentPR;                /* SF3D_RESIDENT_PR: tests: this patch height or none (0: unset) */
+    uint32_t residentPost;              /* SF3D_RESIDENT_POST */
+    uint32_t heatRedBlack;              /* SF3D_HEAT_SWEEP=j: Jacobi */
+    bool heatDebug, heatGS;             /* SF3D_HEAT_DEBUG, SF3D_HEAT_GS=1 */
+};
+static BuildSwitches read_build_switches()
+{
+    BuildSwitches s;
+    const char* re = getenv("SF3D_SLOT_ALIGN");
+    s.slotAlign = !(re && re[0] == '0');
+    const char* pe = getenv("SF3D_PAIR_SWEEP");
+    s.pairSweep = pe ? (pe[0] == '0' ? 0 : 1) : -1;
+    const char* rse = getenv("SF3D_RESIDENT_SWEEP");
+    s.residentSweep = rse ? rse[0] != '0' : s.pairSweep != 1;
+    s.forceMasked = false;
+    if (const char* fm = getenv("SF3D_PAIR_FORCE_MASKED")) if (fm[0] == '1') s.forceMasked = true;
+    s.asmSoilBlocks = 0;
+    if (const char* be = getenv("SF3D_ASM_SOIL_BLOCKS")) s.asmSoilBlocks = (uint32_t)atoi(be);
+    const char* oe = getenv("SF3D_OVERLAP_ACCEPT");
+    s.overlapAccept = (oe && oe[0] == '0') ? 0 : 1;
+    const char* e = getenv("SF3D_NT_STREAM");
+    s.ntStream = e ? (e[0] != '0') : -1;
+    s.probeMin = 0.8;
+    if (const char* ce = getenv("SF3D_COURANT_PROBE")) { s.probeMin = atof(ce); if (ce[0] == '0' && ce[1] == 0) s.probeMin = -1.; if (ce[0] == 'a') s.probeMin = 0.; }
+    s.autoCost = 1.9;
+    if (const char* ae = getenv("SF3D_PAIR_AUTO_COST")) s.autoCost = atof(ae);
+    const char* we = getenv("SF3D_PAIR_W");
+    s.pairWSet = we != nullptr; s.pairW = we ? (uint32_t)atoi(we) : 0u;
+    {   double ts = 10.; if (const char* te = getenv("SF3D_DIST_TIMEOUT_S")) { ts = atof(te); if (!(ts >= 0.5)) ts = 0.5; if (ts > 600.) ts = 600.; }
+        s.distTimeoutS = ts; }
+    { const char* fe = getenv("SF3D_FUSED_DECIDE"); s.fusedDecide = (fe && fe[0] == '0') ? 0 : 1; }
+    s.haloDirect = -1;
+    if (const char* hd = getenv("SF3D_HALO_DIRECT")) s.haloDirect = hd[0] == '1' ? 1 : 0;
+    const char* pre = getenv("SF3D_PAIR_RECORDS");
+    s.pairRecordsWish = (pre && pre[0] == '0') ? 0u : ((pre && pre[0] == '1') ? 2u : 1u);
+    s.residentPR = 0; if (const char* pe = getenv("SF3D_RESIDENT_PR")) s.residentPR = (uint32_t)atoi(pe);
+    {   const char* pe2 = getenv("SF3D_RESIDENT_POST"); s.residentPost = (pe2 && pe2[0] == '0') ? 0u : 1u; }
+    const char* se = getenv("SF3D_HEAT_SWEEP");
+    s.heatRedBlack = (se && se[0] == 'j') ? 0u : 1u;
+    s.heatDebug = getenv("SF3D_HEAT_DEBUG") != nullptr;
+    s.heatGS = false;
+    if (const char* ge = getenv("SF3D_HEAT_GS")) if (ge[0] == '1') s.heatGS = true;
+    return s;
+}
+
+/* what the stages of one build share: it lives for the duration of the build block of sync_to_device */
+struct DeviceSolver::BuildState {
+    BuildSwitches sw;
+    LinkTables links;
+    std::vector<ChunkDesc> cdesc;
+    GridPlan grid;
+    ChunkLists lists;
+    EdgeRows edge;
+};
+
+/* The three device-side stages below are blocks of the build block of sync_to_device, moved as they stood: each begins by giving what it
+ * shares with the rest the names it has there.  Every HIP_TRY returns from the stage, and the caller hands that on at once. */
+
+/* multi GPU: the owner array, the send / receive lists, the in-kernel puts, where foreign neighbours arrive, k_sweep_bnd's chunks, the
+ * record hand-over of the paired pass and this rank's window */
+sf3d_error_t DeviceSolver::build_dist_window(BuildState& st)
+{
+    Impl& I = *impl_; DevView& v = I.v; const BuildSwitches& sw = st.sw;
+    const uint32_t N = I.N, ns = I.ns, nChunks = v.nChunks; const size_t NS = (size_t)N * SF3D_SLOTS;
+    const std::vector<uint8_t>& kind = st.links.kind; const std::vector<uint32_t>& to = st.links.to;
+    std::vector<ChunkDesc>& cdesc = st.cdesc; const std::vector<uint32_t>& listSurf = st.lists.listSurf;
+    const uint32_t pairNX = st.grid.NX, pairNY = st.grid.NY, pairNZ = st.grid.NZ, pairOwnLo = st.grid.ownLo, pairOwnHi = st.grid.ownHi;
+    const int32_t(&edgePeer)[2] = st.edge.edgePeer; const uint32_t(&edgePut)[2] = st.edge.edgePut, (&edgeGet)[2] = st.edge.edgeGet;
+    auto edge_rows_direct = [&]() -> bool { return plan_edge_rows_direct(I.part, st.grid, ns, world_, rank_, st.edge); };
+    uint8_t* downer; HIP_TRY(dev_alloc(I.allocs, downer, N));
+    HIP_TRY(hipMemcpy(downer, I.part.owner.data(), N, hipMemcpyHostToDevice));
+    v.owner = downer;
+    /* my window: mailboxes + payload areas for what each neighbour puts (2 parities x 2 fields) */
+    DistView& d = I.hostDist;
+    std::memset(&d, 0, sizeof(d));
+    d.world = world_; d.rank = rank_; d.owner = downer;
+    d.spinTicks = (long long)(sw.distTimeoutS * 1e8);
+    uint64_t off = 0;
+    uint32_t maxSend = 0;
+    for (int pr = 0; pr < world_; ++pr) {
+        d.recvCount[pr] = (uint32_t)I.part.recv[pr].size();
+        d.recvOff[pr] = off;
+        off += (uint64_t)d.recvCount[pr] * 2 * SF3D_DIST_FIELDS;
+        d.sendCount[pr] = (uint32_t)I.part.send[pr].size();
+        if (d.sendCount[pr] > maxSend) maxSend = d.sendCount[pr];
+        uint32_t *si, *ri;
+        HIP_TRY(dev_alloc(I.allocs, si, I.part.send[pr].size())); HIP_TRY(dev_alloc(I.allocs, ri, I.part.recv[pr].size()));
+        if (d.sendCount[pr]) HIP_TRY(hipMemcpy(si, I.part.send[pr].data(), (size_t)d.sendCount[pr] * 4, hipMemcpyHostToDevice));
+        if (d.recvCount[pr]) HIP_TRY(hipMemcpy(ri, I.part.recv[pr].data(), (size_t)d.recvCount[pr] * 4, hipMemcpyHostToDevice));
+        d.sendIdx[pr] = si; d.recvIdx[pr] = ri;
+    }
+    {   /* the send lists regrouped by chunk for the in-kernel puts */
+        struct Ent { uint32_t node; uint8_t peer; uint32_t slot; };
+        std::vector<Ent> ents;
+        for (int pr = 0; pr < world_; ++pr)
+            for (uint32_t k = 0; k < I.part.send[pr].size(); ++k) ents.push_back({I.part.send[pr][k], (uint8_t)pr, k});
+        std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.node != b.node ? a.node < b.node : a.peer < b.peer; });
+        std::vector<uint32_t> bstart(nChunks + 1, 0), bslot(ents.size());
+        std::vector<uint8_t> blane(ents.size()), bpeer(ents.size());
+        for (size_t k = 0; k < ents.size(); ++k) {
+            bstart[ents[k].node / SF3D_CHUNK + 1]++;
+            blane[k] = (uint8_t)(ents[k].node % SF3D_CHUNK); bpeer[k] = ents[k].peer; bslot[k] = ents[k].slot;
+        }
+        for (uint32_t q = 0; q < nChunks; ++q) bstart[q + 1] += bstart[q];
+        uint32_t *dbs, *dsl; uint8_t *dla, *dpe;
+        HIP_TRY(dev_alloc(I.allocs, dbs, bstart.size())); HIP_TRY(dev_alloc(I.allocs, dsl, bslot.size()));
+        HIP_TRY(dev_alloc(I.allocs, dla, blane.size())); HIP_TRY(dev_alloc(I.allocs, dpe, bpeer.size()));
+        HIP_TRY(hipMemcpy(dbs, bstart.data(), bstart.size() * 4, hipMemcpyHostToDevice));
+        if (!ents.empty()) {
+            HIP_TRY(hipMemcpy(dsl, bslot.data(), bslot.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dla, blane.data(), blane.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dpe, bpeer.data(), bpeer.size(), hipMemcpyHostToDevice));
+        }
+        d.bndStart = dbs; d.bndSlot = dsl; d.bndLane = dla; d.bndPeer = dpe;
+    }
+    if (I.useFused < 0) I.useFused = sw.fusedDecide;
+    v.haloDirect = I.useFused != 0 ? 1u : 0u;      /* the fused exchange only; SF3D_HALO_DIRECT=0 copies the halo after every sweep */
+    if (sw.haloDirect >= 0) v.haloDirect = (sw.haloDirect == 1 && I.useFused != 0) ? 1u : 0u;
+    if (v.haloDirect) {   /* where each foreign neighbour's value arrives in my window; chunks that have any are flagged */
+        std::vector<uint32_t> fsrc(NS, SF3D_FSRC_NONE);
+        for (uint32_t i = 0; i < N; ++i) {
+            if (I.part.owner[i] != rank_) continue;
+            for (int sl = 0; sl < SF3D_SLOTS; ++sl) {
+                const size_t e = (size_t)sl * N + i;
+                if (kind[e] == LK_NONE) continue;
+                const uint32_t j = to[e];
+                const int pr = I.part.owner[j];
+                if (pr == rank_) continue;
+                const auto& lst = I.part.recv[pr];
+                const auto it = std::lower_bound(lst.begin(), lst.end(), j);
+                if (it == lst.end() || *it != j) { snprintf(err_, sizeof(err_), "partition: node %u read by %u is missing from the halo list of rank %d", j, i, pr); return SF3D_TOPOGRAPHY_ERROR; }
+                fsrc[e] = ((uint32_t)pr << 27) | (uint32_t)(it - lst.begin());
+                cdesc[i / SF3D_CHUNK].pad0 = 1;
+            }
+        }
+        uint32_t* dfs; HIP_TRY(dev_alloc(I.allocs, dfs, NS));
+        HIP_TRY(hipMemcpy(dfs, fsrc.data(), NS * 4, hipMemcpyHostToDevice));
+        d.fsrc = dfs;
+    }
+    v.bndList = nullptr; v.nBnd = 0;
+    if (I.pairBlocks != 0) {
+        /* paired sweep on a strip: k_sweep_bnd's chunks = the owned chunks that read a neighbouring strip; they must be exactly
+         * the rows next to a halo row in every layer (what k_sweep_pair<DIST> leaves out), and the sweeps must take foreign
+         * neighbours from the window (the fused exchange) */
+        bool ok = v.haloDirect != 0;
+        std::vector<uint32_t> bnd;
+        if (ok && I.pairMasked) {      /* masked grid: no rows to reason with - every node gets its role (PairGrid::role) */
+            std::vector<uint8_t> role(N, 0);
+            for (uint32_t i = 0; i < N; ++i) if (I.part.owner[i] == rank_) role[i] = cdesc[i / SF3D_CHUNK].pad0 ? 2 : 1;
+            uint8_t* dr; HIP_TRY(dev_alloc(I.allocs, dr, N));
+            HIP_TRY(hipMemcpy(dr, role.data(), N, hipMemcpyHostToDevice));
+            v.pair.role = dr;
+            for (uint32_t q : listSurf) if (cdesc[q].pad0) bnd.push_back(q);
+        } else
+        for (uint32_t k = 0; k < listSurf.size() && ok; ++k) {
+            const uint32_t q = listSurf[k];
+            const uint32_t r = ((q * SF3D_CHUNK) % ns) / pairNX;
+            const bool edge = (pairOwnLo > 0 && r == pairOwnLo) || (pairOwnHi < pairNY && r + 1 == pairOwnHi);
+            const bool mineRow = r >= pairOwnLo && r < pairOwnHi;
+            if ((cdesc[q].pad0 != 0) != (edge && mineRow)) ok = false;
+            if (cdesc[q].pad0 && mineRow) bnd.push_back(q);
+        }
+        if (ok && !bnd.empty()) {
+            uint32_t* db; HIP_TRY(dev_alloc(I.allocs, db, bnd.size()));
+            HIP_TRY(hipMemcpy(db, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
+            v.bndList = db; v.nBnd = (uint32_t)bnd.size();
+        } else if (!ok || I.pairMasked || (pairOwnLo > 0 || pairOwnHi < pairNY)) { I.pairBlocks = 0; v.pair.NX = v.pair.NY = v.pair.NZ = 0; }
+    }
+    v.pair.records = 0u; d.recGet = nullptr; d.recPut = nullptr; I.pairRecordsWish = 0u;
+    if (I.pairBlocks != 0) {
+        if (I.pairMasked) {      /* masked grids: per-node tables - where an owned node's value goes, where a foreign node's arrives - instead of list walks */
+            std::vector<RecGet> rg(N, RecGet{SF3D_FSRC_NONE, 0u});
+            std::vector<RecPut> rp(N, RecPut{0u, 0u, 0u, 0u});
+            bool fits = true;
+            for (int pr = 0; pr < world_; ++pr) {
+                const uint64_t rc = d.recvCount[pr], sc = d.sendCount[pr];
+                for (uint32_t k = 0; k < rc; ++k) {
+                    const uint64_t o = d.recvOff[pr] + (uint64_t)DF_RECLO * rc + k;
+                    if (o + (uint64_t)2 * SF3D_DIST_FIELDS * rc >= 0xFFFFFFFFull) fits = false;
+                    rg[I.part.recv[pr][k]] = RecGet{(uint32_t)o, (uint32_t)rc};
+                }
+                for (uint32_t k = 0; k < sc; ++k) {
+                    RecPut& e = rp[I.part.send[pr][k]];
+                    if (e.nDest == 0u) {
+                        /* (sendOff: where MY values start in rank pr's window - known after the connect; the entry holds the position inside that area) */
+                        e.off0 = (uint32_t)((uint64_t)DF_RECLO * sc + k); e.cnt = (uint32_t)sc; e.peer = (uint32_t)pr;
+                    }
+                    e.nDest++;
+                }
+            }
+            if (fits) {
+                RecGet* dg; RecPut* dp;
+                HIP_TRY(dev_alloc(I.allocs, dg, N)); HIP_TRY(dev_alloc(I.allocs, dp, N));
+                HIP_TRY(hipMemcpy(dg, rg.data(), (size_t)N * sizeof(RecGet), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(dp, rp.data(), (size_t)N * sizeof(RecPut), hipMemcpyHostToDevice));
+                d.recGet = dg; d.recPut = dp;
+            }
+        }
+        /* record hand-over (one launch, one exchange per pass; SF3D_PAIR_RECORDS=0 keeps k_sweep_bnd and its second exchange; sf3d_dist_connect
+         * decides for all ranks) */
+        I.pairRecordsWish = sw.pairRecordsWish;
+        if (I.pairRecordsWish != 0u) {
+            /* every local node of another rank must be in that rank's halo list (it is: a node nobody here reads is not staged) - it would have no record */
+            bool all = true;
+            for (uint32_t i = 0; i < N && all; ++i) {
+                const int pr = I.part.owner[i];
+                if (pr == rank_ || pr == SF3D_OWNER_NONE) continue;
+                const auto& lst = I.part.recv[pr];
+                const auto it = std::lower_bound(lst.begin(), lst.end(), i);
+                if (it == lst.end() || *it != i) all = false;
+            }
+            /* regular strips whose edge rows lie in the lists as (layer) * NX + column from a base: the kernel addresses the records directly */
+            v.pair.recFast = 0u; v.pair.sidePeer[0] = v.pair.sidePeer[1] = -1; v.pair.recStride = pairNX;
+            if (all && !I.pairMasked && edge_rows_direct()) {
+                v.pair.recFast = 1u;
+                for (int side = 0; side < 2; ++side) { v.pair.sidePeer[side] = edgePeer[side]; v.pair.putBase[side] = edgePut[side]; v.pair.getBase[side] = edgeGet[side]; }
+            }
+            /* the hand-over exists where the records are addressed without list walks - that layout, or the per-node tables of the masked pass
+             * (above): with a walk through the chunk's send list per put and a look-up chain per wait it cost more than the second launch
+             * saves (profiles/r06_i_record_handover_on_strips_ab.txt, jobs 23 / 24) */
+            v.pair.records = (all && (I.pairMasked ? (d.recPut != nullptr && d.recGet != nullptr && pairNZ < 128u /* (bit 7 of the patches' depth byte flags the blocks at the cut) */) : v.pair.recFast != 0u)) ? 1u : 0u;
+        }
+    }
+    I.windowBytes = sizeof(DistWindow) + off * sizeof(double);
+    void* w = nullptr;
+    HIP_TRY(hipExtMallocWithFlags(&w, I.windowBytes, hipDeviceMallocFinegrained));
+    HIP_TRY(hipMemset(w, 0, I.windowBytes));
+    I.window = static_cast<DistWindow*>(w);
+    d.win[rank_] = I.window;
+    d.payload[rank_] = reinterpret_cast<double*>(reinterpret_cast<char*>(w) + sizeof(DistWindow));
+    HIP_TRY(dev_alloc(I.allocs, I.devDist, 1));
+    HIP_TRY(dev_alloc(I.allocs, I.distStats, 1 + 2 * SF3D_MAX_RANKS));
+    HIP_TRY(hipMemset(I.distStats, 0, sizeof(unsigned long long) * (1 + 2 * SF3D_MAX_RANKS)));
+    d.stats = I.distStats;
+    for (double& h : I.hopUs) h = 0.;
+    I.pushBlocks = (maxSend + SF3D_BLOCK - 1) / SF3D_BLOCK;
+    if (I.pushBlocks == 0) I.pushBlocks = 1;
+    if (I.pushBlocks > 256) I.pushBlocks = 256;
+    return SF3D_OK;
+}
+
+/* the resident sweep loop: its shape from the menu by the occupancy queries, its arrays, and on a strip where the halo rows arrive */
+sf3d_error_t DeviceSolver::build_resident_plan(const HostModel& m, BuildState& st)
+{
+    Impl& I = *impl_; DevView& v = I.v; const BuildSwitches& sw = st.sw;
+    const uint32_t N = I.N, ns = I.ns;
+    const std::vector<uint64_t>&pairNode = st.grid.node, &pairChunk = st.grid.chunk; const std::vector<int32_t>& pairIdxMap = st.grid.idxMap;
+    const uint32_t pairNX = st.grid.NX, pairNY = st.grid.NY, pairNZ = st.grid.NZ, pairOwnLo = st.grid.ownLo, pairOwnHi = st.grid.ownHi;
+    const int32_t(&edgePeer)[2] = st.edge.edgePeer; const uint32_t(&edgePut)[2] = st.edge.edgePut;
+    auto edge_rows_direct = [&]() -> bool { return plan_edge_rows_direct(I.part, st.grid, ns, world_, rank_, st.edge); };
+    {   /* resident sweep loop (k_sweep_resident, sf3d_resident.inc): a regular grid - or the rank's row strip of one - whose rows fit into the
+         * registers of the CUs: patch height PR (a divisor of the owned rows), K chunks per wave and NW waves per block from the menu of
+         * compiled shapes, every block resident at once (occupancy query).  SF3D_RESIDENT_SWEEP=0 turns it off, =1 is the default. */
+        v.res = ResGrid{};
+        I.resBlocks = 0; I.resLds = 0;
+        if (I.useFused < 0) I.useFused = sw.fusedDecide;
+        const bool asked = sw.residentSweep;      /* (SF3D_PAIR_SWEEP=1 alone asks for the paired passes: tests, measurements) */
+        const bool want = asked && I.useFused != 0 && !pairNode.empty() && pairIdxMap.empty() && (world_ == 1 || v.haloDirect);
+        if (want) {
+            const uint32_t ownRows = pairOwnHi - pairOwnLo, patchCols = pairNX / 64;
+            int cus = 256; { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, I.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount; }
+            const uint32_t onlyPR = sw.residentPR;      /* tests: this patch height or none */
+            for (uint32_t PR = 1; PR <= 8 && !v.res.on; ++PR) {
+                if (ownRows % PR != 0 || (onlyPR != 0 && PR != onlyPR)) continue;
+                const uint32_t blocks = patchCols * (ownRows / PR), T = PR * pairNZ;
+                const uint32_t lds = 2u * pairNZ * (PR + 2) * SF3D_RES_RS * 8u;
+                for (const ResShape& sh : kResShapes) {
+                    if ((uint32_t)(sh.K * sh.NW) < T || (uint32_t)sh.NW % PR != 0) continue;     /* (a wave's chunks: one row, layers a constant stride apart) */
+                    if (pairNZ * (2u * SF3D_RES_RS + 2u * PR) > (uint32_t)SF3D_RES_HM * sh.NW * 64u) continue;
+                    const void* fn = res_kernel(sh.K, sh.NW, world_ > 1);
+                    if (!fn) continue;
+                    if (lds > 48u * 1024u && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); continue; }
+                    int perCu = 0;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, fn, sh.NW * 64, lds) != hipSuccess || perCu < 1) { (void)hipGetLastError(); continue; }
+                    if (blocks > (uint32_t)perCu * (uint32_t)cus) continue;
+                    v.res.on = 1; v.res.NX = pairNX; v.res.NY = pairNY; v.res.NZ = pairNZ; v.res.PR = PR;
+                    v.res.patchCols = patchCols; v.res.rowGroups = ownRows / PR; v.res.ownLo = pairOwnLo; v.res.ownHi = pairOwnHi;
+                    v.res.K = (uint32_t)sh.K; v.res.NW = (uint32_t)sh.NW;
+                    I.resBlocks = blocks; I.resLds = lds; I.resCapacity = (uint32_t)perCu * (uint32_t)cus;
+                    break;
+                }
+            }
+        }
+        if (v.res.on) {
+            if (v.pair.nodeLat && v.pair.chunkCode && !v.pair.masked && v.pair.NX == pairNX) { v.res.nodeLat = v.pair.nodeLat; v.res.chunkCode = v.pair.chunkCode; }
+            else {
+                uint32_t* dn; uint64_t* dq;
+                std::vector<uint32_t> lat(pairNode.size());
+                for (size_t k = 0; k < pairNode.size(); ++k) lat[k] = (uint32_t)(pairNode[k] >> 8);
+                HIP_TRY(dev_alloc(I.allocs, dn, lat.size()));
+                HIP_TRY(hipMemcpy(dn, lat.data(), lat.size() * 4, hipMemcpyHostToDevice));
+                HIP_TRY(dev_alloc(I.allocs, dq, pairChunk.size()));
+                HIP_TRY(hipMemcpy(dq, pairChunk.data(), pairChunk.size() * 8, hipMemcpyHostToDevice));
+                v.res.nodeLat = dn; v.res.chunkCode = dq;
+            }
+            HIP_TRY(dev_alloc(I.allocs, v.res.bar, (size_t)SF3D_RES_LINE * 18)); HIP_TRY(hipMemset(v.res.bar, 0, (size_t)SF3D_RES_LINE * 18 * sizeof(unsigned int)));
+            HIP_TRY(dev_alloc(I.allocs, v.res.rec, (size_t)4 * N)); HIP_TRY(hipMemset(v.res.rec, 0, (size_t)4 * N * sizeof(unsigned long long)));
+            HIP_TRY(dev_alloc(I.allocs, v.res.prec, (size_t)8 * I.resBlocks)); HIP_TRY(hipMemset(v.res.prec, 0, (size_t)8 * I.resBlocks * sizeof(unsigned long long)));
+            HIP_TRY(dev_alloc(I.allocs, v.res.gpub, 8)); HIP_TRY(hipMemset(v.res.gpub, 0, 8 * sizeof(unsigned long long)));
+            HIP_TRY(dev_alloc(I.allocs, v.res.prec2, (size_t)8 * I.resBlocks)); HIP_TRY(hipMemset(v.res.prec2, 0, (size_t)8 * I.resBlocks * sizeof(unsigned long long)));
+            {   v.res.fusedPost = sw.residentPost;
+                if (m.heat) v.res.fusedPost = 0u; }      /* (with coupled heat k_post's successor kernels read what only k_post's launch orders: kept apart) */
+            HIP_TRY(dev_alloc(I.allocs, v.res.pub, 32)); HIP_TRY(hipMemset(v.res.pub, 0, 32 * sizeof(double)));
+            if (world_ > 1) {
+                /* where the cells of the foreign halo rows - the row above the strip (side 0), the row below it (side 1) - arrive in my window */
+                std::vector<uint32_t> hs((size_t)2 * pairNZ * pairNX, SF3D_FSRC_NONE);
+                v.res.sidePeer[0] = v.res.sidePeer[1] = -1;
+                bool oneRank = true;
+                for (uint32_t side = 0; side < 2; ++side) {
+                    if ((side == 0 && pairOwnLo == 0) || (side == 1 && pairOwnHi >= pairNY)) continue;
+                    const uint32_t r = side == 0 ? pairOwnLo - 1 : pairOwnHi;
+                    for (uint32_t l = 0; l < pairNZ; ++l)
+                        for (uint32_t cc = 0; cc < pairNX; ++cc) {
+                            const uint32_t j = l * ns + r * pairNX + cc;
+                            const int pr = I.part.owner[j];
+                            if (pr == rank_ || pr == SF3D_OWNER_NONE) continue;
+                            const auto& lst = I.part.recv[pr];
+                            const auto itp = std::lower_bound(lst.begin(), lst.end(), j);
+                            if (itp != lst.end() && *itp == j) {
+                                hs[((size_t)side * pairNZ + l) * pairNX + cc] = ((uint32_t)pr << 27) | (uint32_t)(itp - lst.begin());
+                                if (v.res.sidePeer[side] < 0) v.res.sidePeer[side] = pr; else if (v.res.sidePeer[side] != pr) oneRank = false;
+                            }
+                        }
+                }
+                uint32_t* dh; HIP_TRY(dev_alloc(I.allocs, dh, hs.size()));
+                HIP_TRY(hipMemcpy(dh, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+                v.res.haloSrc = dh;
+                v.res.recFast = 0u; v.res.putBase[0] = v.res.putBase[1] = 0u;
+                if (oneRank && edge_rows_direct() && edgePeer[0] == v.res.sidePeer[0] && edgePeer[1] == v.res.sidePeer[1]) {
+                    v.res.recFast = 1u; v.res.putBase[0] = edgePut[0]; v.res.putBase[1] = edgePut[1];
+                }
+                if (!oneRank) { v.res.on = 0; I.resBlocks = 0; }      /* (a halo row shared by two ranks: strips are cut between rows, so never - the kernel counts on it) */
+            }
+        }
+    }
+    return SF3D_OK;
+}
+
+/* coupled heat transport: state, system, per-node conductivities, boundary and link flux arrays; the colours of the heat sweep and the
+ * levels of the reference-order Gauss-Seidel */
+sf3d_error_t DeviceSolver::build_heat(HostModel& m, const ParamsHost& p, BuildState& st)
+{
+    Impl& I = *impl_; DevView& v = I.v; const BuildSwitches& sw = st.sw;
+    const uint32_t N = I.N, ns = I.ns, nChunks = v.nChunks; const size_t NS = (size_t)N * SF3D_SLOTS;
+    const std::vector<uint8_t>& kind = st.links.kind; const std::vector<uint32_t>& to = st.links.to;
+    const std::vector<uint32_t>& listSurf = st.lists.listSurf;
+    HeatDev& hv = v.heat;
+    hv = HeatDev{};
+    hv.on = 1; hv.water = m.water ? 1u : 0u; hv.vapor = m.heatVapor ? 1u : 0u; hv.advection = m.heatAdvection ? 1u : 0u;
+    hv.save = m.heatSave; hv.wf = p.heatWeightFactor;
+    double* tmp = nullptr;
+    for (int k = 0; k < 3; ++k) { HIP_TRY(dev_alloc(I.allocs, hv.TX[k], N)); HIP_TRY(hipMemset(hv.TX[k], 0, N * 8)); }
+    auto alloc0 = [&](double*& ptr, size_t cnt) -> hipError_t { hipError_t e = dev_alloc(I.allocs, ptr, cnt); if (e == hipSuccess) e = hipMemset(ptr, 0, cnt * 8); return e; };
+    HIP_TRY(alloc0(tmp, N)); hv.heatSink = tmp;
+    HIP_TRY(alloc0(hv.heatFlux, N)); HIP_TRY(alloc0(hv.invariant, N));
+    HIP_TRY(alloc0(hv.hC, N)); HIP_TRY(alloc0(hv.hcapTerm, N)); HIP_TRY(alloc0(hv.hb, N)); HIP_TRY(alloc0(hv.hD, N));
+    HIP_TRY(dev_alloc(I.allocs, hv.hA2, NS / 2)); HIP_TRY(hipMemset(hv.hA2, 0, NS * 8));
+    HIP_TRY(alloc0(hv.kHeat, N)); HIP_TRY(alloc0(hv.kIsoVap, N)); HIP_TRY(alloc0(hv.hAvg, N));
+    HIP_TRY(alloc0(hv.thetaOld, N)); HIP_TRY(alloc0(hv.thAvgC, N)); HIP_TRY(alloc0(hv.thNewC, N));
+    HIP_TRY(alloc0(tmp, N)); hv.airP = tmp; I.heatAirP = tmp;
+    HIP_TRY(alloc0(hv.wThLiq, N)); HIP_TRY(alloc0(hv.wThVap, N)); HIP_TRY(alloc0(hv.wTm, N));
+    const double** inputs[9] = {&hv.bHeightWind, &hv.bHeightT, &hv.bRoughH, &hv.bT, &hv.bRH, &hv.bWind, &hv.bNetIrr, &hv.bFixT, &hv.bFixDepth};
+    for (auto* pp : inputs) { HIP_TRY(alloc0(tmp, N)); *pp = tmp; }
+    double** outputs[6] = {&hv.bAero, &hv.bSoilCond, &hv.bSens, &hv.bLat, &hv.bRad, &hv.bAdv};
+    const std::vector<double>* outInit[6] = {&m.bAero, &m.bSoilCond, &m.bSens, &m.bLat, &m.bRad, &m.bAdv};   /* NODATA / 0 of setNodeBoundary */
+    for (int k = 0; k < 6; ++k) {
+        HIP_TRY(alloc0(*outputs[k], N)); I.heatOut[k] = *outputs[k];
+        HIP_TRY(hipMemcpy(*outputs[k], outInit[k]->data(), N * 8, hipMemcpyHostToDevice));
+    }
+    { double* wv = nullptr; HIP_TRY(alloc0(wv, NS)); hv.lwvFlux = reinterpret_cast<sf3d_f2*>(wv); }      /* 8 bytes per link: two floats */
+    const int nTypes = (m.heatSave == 2) ? SF3D_FLUX_TYPES : (m.heatSave == 1 ? 1 : 0);
+    {   /* never-linked slots hold 0 (calloc in the reference), linked slots NODATA (setNodeLink, soilFluxes3D.cpp:672-678) */
+        std::vector<double> init(NS, 0.);
+        for (size_t e = 0; e < NS; ++e) if (kind[e] != LK_NONE) init[e] = NODATA_D;
+        for (int t = 0; t < nTypes; ++t) {
+            HIP_TRY(dev_alloc(I.allocs, hv.lflux[t], NS));
+            HIP_TRY(hipMemcpy(hv.lflux[t], init.data(), NS * 8, hipMemcpyHostToDevice));
+        }
+    }
+    {   /* nodeDistance3D (soilPhysics.cpp:334-338) of every link between two soil nodes */
+        std::vector<double> d3(NS, 1.);
+        parallel_for(N, [&](uint32_t a, uint32_t b) {
+            for (uint32_t i = a; i < b; ++i)
+                for (int s = 0; s < SF3D_SLOTS; ++s) {
+                    const size_t e = (size_t)s * N + i;
+                    if (kind[e] != LK_SOIL_VERT && kind[e] != LK_SOIL_LAT) continue;
+                    const uint32_t j = to[e];
+                    const double dx = m.x[i] - m.x[j], dy = m.y[i] - m.y[j], dz = m.z[i] - m.z[j];
+                    double nrm = 0; nrm += dx * dx; nrm += dy * dy; nrm += dz * dz;
+                    d3[e] = std::sqrt(nrm);
+                }
+        });
+        HIP_TRY(alloc0(tmp, NS)); hv.hdist = tmp;
+        HIP_TRY(hipMemcpy(tmp, d3.data(), NS * 8, hipMemcpyHostToDevice));
+    }
+    {   /* colours of the heat sweep: layer = hops to the surface through the Up links (layer-major numbering: the node above has
+         * a smaller index); a halo node of a strip-local model that lost its Up link is never swept here */
+        std::vector<uint8_t> lp(N, 0);
+        for (uint32_t i = ns; i < N; ++i) if (kind[i] != LK_NONE && to[i] < i) lp[i] = (uint8_t)(lp[to[i]] + 1);
+        uint8_t* dlp; HIP_TRY(dev_alloc(I.allocs, dlp, N));
+        HIP_TRY(hipMemcpy(dlp, lp.data(), N, hipMemcpyHostToDevice));
+        hv.lpar = dlp;
+        /* (a rank of a sharded run: plus, in BOTH lists, the chunks that owe values to a neighbouring rank - every wave puts all the
+         * entries of its chunk in each half, the nodes of the other colour with the value they have at that moment) */
+        std::vector<uint8_t> owesHeat(nChunks, 0);
+        if (world_ > 1) for (int pr = 0; pr < world_; ++pr) for (uint32_t node : I.part.send[pr]) owesHeat[node / SF3D_CHUNK] = 1;
+        for (int col = 0; col < 2; ++col) {         /* col 0: odd layers (first half), col 1: even layers */
+            std::vector<uint32_t> cl;
+            for (uint32_t q : listSurf) {
+                const uint32_t i0 = q * SF3D_CHUNK, i1 = (i0 + SF3D_CHUNK < N) ? i0 + SF3D_CHUNK : N;
+                bool any = owesHeat[q] != 0;
+                for (uint32_t i = i0; i < i1 && !any; ++i) any = ((lp[i] & 1u) != 0u) == (col == 0);
+                if (any) cl.push_back(q);
+            }
+            uint32_t* dcl; HIP_TRY(dev_alloc(I.allocs, dcl, cl.size()));
+            if (!cl.empty()) HIP_TRY(hipMemcpy(dcl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
+            hv.colourList[col] = dcl; hv.nColour[col] = (uint32_t)cl.size();
+        }
+        hv.redBlack = sw.heatRedBlack;
+        /* only where layer parity really colours the vertical links (heat_two_colour_valid, sf3d_model.h).  A rank of a sharded run
+         * sees its strip only: its finding travels in its blob and dist_connect turns the two-colour sweep off on EVERY rank if any
+         * rank found a violation - all ranks must run the same protocol */
+        const bool colourable = heat_two_colour_valid(m);
+        I.heatJacobiOnly = !colourable;
+        if (hv.redBlack && !colourable) {
+            hv.redBlack = 0u;
+            if (sw.heatDebug) fprintf(stderr, "sf3d: heat sweep: the node numbering is not layer-major along the Up links - Jacobi instead of the two-colour sweep\n");
+        }
+    }
+    I.gsLevelStart.clear();
+    if (sw.heatGS) {
+        if (world_ > 1) { snprintf(err_, sizeof(err_), "SF3D_HEAT_GS=1 (reference-order Gauss-Seidel) is a single-GPU verification mode"); return SF3D_PARAMETER_ERROR; }
+        /* dependency levels of the serial sweep: a node waits for its linked heat nodes with a smaller index */
+        std::vector<uint32_t> level(N, 0u);
+        uint32_t maxLevel = 0;
+        for (uint32_t i = ns; i < N; ++i) {
+            uint32_t l = 0;
+            for (int sl = 0; sl < SF3D_SLOTS; ++sl) {
+                const size_t e = (size_t)sl * N + i;
+                if ((kind[e] == LK_SOIL_VERT || kind[e] == LK_SOIL_LAT) && to[e] < i && level[to[e]] + 1 > l) l = level[to[e]] + 1;
+            }
+            level[i] = l;
+            if (l > maxLevel) maxLevel = l;
+        }
+        std::vector<uint32_t> start(maxLevel + 2, 0u), order(N > ns ? N - ns : 0);
+        for (uint32_t i = ns; i < N; ++i) start[level[i] + 1]++;
+        for (uint32_t l = 0; l <= maxLevel; ++l) start[l + 1] += start[l];
+        std::vector<uint32_t> pos(start.begin(), start.end() - 1);
+        for (uint32_t i = ns; i < N; ++i) order[pos[level[i]]++] = i;
+        uint32_t* dord; HIP_TRY(dev_alloc(I.allocs, dord, order.size()));
+        if (!order.empty()) HIP_TRY(hipMemcpy(dord, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+        hv.gsOrder = dord; hv.gs = 1;
+        I.gsLevelStart = start;
+    }
+    m.heatStateDirty = m.heatSinkDirty = m.heatBoundaryDirty = true;
+    m.hostStaleHeat = false;
+    for (int t = 0; t < SF3D_FLUX_TYPES; ++t) m.lfluxValid[t] = false;
+    return SF3D_OK;
+}
+
 sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
 {
     { const sf3d_error_t e = ensure_device(); if (e != SF3D_OK) return e; }
@@ -497,6 +885,9 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
     const size_t NS = (size_t)N * SF3D_SLOTS;
 
     if (m.graphDirty || !built_) {
+        BuildState st;
+        st.sw = read_build_switches();
+        const BuildSwitches& sw = st.sw;
         /* a connected strip is frozen: its build arrays may be gone (trimHostStaging drops surf / hasClass / the link tables of the
          * strip-local copy), so this refusal comes BEFORE anything reads them (round 4's advice: an edit after connect segfaulted in
          * the validation loop below and left the peers in their 60 s all-gather time-outs) */
@@ -518,340 +909,21 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         v.qSplit = (ns + SF3D_CHUNK - 1) / SF3D_CHUNK;
         if (v.qSplit > v.nChunks) v.qSplit = v.nChunks;
 
-        /* derived static graph data: link kind and link distance (host, libm - exactly the
-         * reference's nodeDistance2D/3D arithmetic, soilPhysics.cpp:328-338) */
-        std::vector<uint8_t> kind(NS, LK_NONE);
-        std::vector<double> dist(NS, 0.), area(NS, 0.);
-        std::vector<uint32_t> to(NS, 0u);
-        std::atomic<bool> bad{false};
-        {   /* Slot alignment.  setNodeLink puts a node's k-th lateral link into slot 2 + k, so a node at the edge of a grid (fewer
-             * laterals) holds OTHER directions in its slots than its 63 chunk mates and the whole chunk falls back to per-lane link
-             * kinds and indices (two dependent round trips per group of links in the assembly instead of one: a quarter of the soil
-             * chunks of a 512-wide grid).  On the device such a node's laterals sit in the slots where the chunk's fullest node has the
-             * same neighbour offset and link kind, in the same relative order - the sums of a row are taken over the existing links in
-             * slot order, so every result keeps its bits.  Nodes that do not fit the pattern keep their own order. */
-            I.dslot.clear();
-            const char* re = getenv("SF3D_SLOT_ALIGN");
-            if (!(re && re[0] == '0')) {
-                std::vector<uint8_t> ds(NS);
-                for (int sl = 0; sl < SF3D_SLOTS; ++sl) std::memset(ds.data() + (size_t)sl * N, sl, N);
-                std::atomic<bool> moved{false};
-                const uint32_t nq = (N + SF3D_CHUNK - 1) / SF3D_CHUNK;
-                auto lateral_kind = [&](uint32_t i, int sl) -> int {      /* 0: no lateral link in host slot sl */
-                    if (sl - 2 >= m.nLat[i] || m.ltype[sl][i] == SF3D_LINK_NONE) return 0;
-                    const bool si = i >= ns, sj = m.lto[sl][i] >= ns;
-                    return (si && sj) ? 1 + (m.ltype[sl][i] == SF3D_LINK_LATERAL ? 0 : 1) : ((!si && !sj) ? 3 : 4);
-                };
-                parallel_for(nq, [&](uint32_t qa, uint32_t qb) {
-                    for (uint32_t q = qa; q < qb; ++q) {
-                        const uint32_t i0 = q * SF3D_CHUNK, i1 = (i0 + SF3D_CHUNK < N) ? i0 + SF3D_CHUNK : N;
-                        /* the pattern: the node with the most laterals, if they fill its slots 2 .. 2 + n - 1 */
-                        uint32_t tmpl = i0; int tn = -1;
-                        for (uint32_t i = i0; i < i1; ++i) {
-                            int n = 0; bool dense = true;
-                            for (int sl = 2; sl < SF3D_SLOTS; ++sl) { const bool on = lateral_kind(i, sl) != 0; if (on) { if (sl - 2 != n) dense = false; ++n; } }
-                            if (dense && n > tn) { tn = n; tmpl = i; }
-                        }
-                        if (tn <= 0) continue;
-                        int64_t td[SF3D_SLOTS]; int tk[SF3D_SLOTS];
-                        for (int p = 0; p < tn; ++p) { td[p] = (int64_t)m.lto[2 + p][tmpl] - (int64_t)tmpl; tk[p] = lateral_kind(tmpl, 2 + p); }
-                        for (uint32_t i = i0; i < i1; ++i) {
-                            if (i == tmpl) continue;
-                            uint8_t map[SF3D_SLOTS]; bool fits = true, differs = false; int p = 0;
-                            for (int sl = 2; sl < SF3D_SLOTS && fits; ++sl) {
-                                const int kk = lateral_kind(i, sl);
-                                map[sl] = (uint8_t)sl;
-                                if (!kk) continue;
-                                const int64_t dd = (int64_t)m.lto[sl][i] - (int64_t)i;
-                                while (p < tn && !(td[p] == dd && tk[p] == kk)) ++p;
-                                if (p >= tn) { fits = false; break; }
-                                map[sl] = (uint8_t)(2 + p); if (map[sl] != sl) differs = true;
-                                ++p;
-                            }
-                            if (!fits || !differs) continue;
-                            /* host slots without a link take the device slots that are left, so that the map stays a permutation */
-                            bool used[SF3D_SLOTS] = {false};
-                            for (int sl = 2; sl < SF3D_SLOTS; ++sl) if (lateral_kind(i, sl)) used[map[sl]] = true;
-                            int free_ = 2;
-                            for (int sl = 2; sl < SF3D_SLOTS; ++sl) {
-                                if (lateral_kind(i, sl)) continue;
-                                while (used[free_]) ++free_;
-                                map[sl] = (uint8_t)free_; used[free_] = true;
-                            }
-                            for (int sl = 2; sl < SF3D_SLOTS; ++sl) ds[(size_t)sl * N + i] = map[sl];
-                            moved = true;
-                        }
-                    }
-                });
-                if (moved) I.dslot.swap(ds);
-            }
-        }
-        const uint8_t* dslot = I.dslot.empty() ? nullptr : I.dslot.data();
-        parallel_for(N, [&](uint32_t a, uint32_t b) {
-            for (uint32_t i = a; i < b; ++i) {
-                const int nl = m.nLat[i];
-                for (int s = 0; s < SF3D_SLOTS; ++s) {
-                    if (s >= 2 && s - 2 >= nl) continue;            /* lateral loop bound, cpusolver.cpp:360 */
-                    if (m.ltype[s][i] == SF3D_LINK_NONE) continue;
-                    const uint32_t j = m.lto[s][i];
-                    const size_t e = (size_t)(dslot ? dslot[(size_t)s * N + i] : s) * N + i;
-                    to[e] = j; area[e] = m.larea[s][i];
-                    const bool si = i >= ns, sj = j >= ns;
-                    if (si && sj) {
-                        if (m.ltype[s][i] == SF3D_LINK_LATERAL) {
-                            kind[e] = LK_SOIL_LAT;
-                            const double dx = m.x[i] - m.x[j], dy = m.y[i] - m.y[j], dz = m.z[i] - m.z[j];
-                            double nrm = 0; nrm += dx * dx; nrm += dy * dy; nrm += dz * dz;
-                            dist[e] = std::sqrt(nrm);
-                        } else { kind[e] = LK_SOIL_VERT; dist[e] = std::fabs(m.z[i] - m.z[j]); }
-                    } else if (!si && !sj) {
-                        kind[e] = LK_RUNOFF;
-                        const double dx = m.x[i] - m.x[j], dy = m.y[i] - m.y[j];
-                        double nrm = 0; nrm += dx * dx; nrm += dy * dy;
-                        dist[e] = std::sqrt(nrm);
-                    } else {
-                        kind[e] = LK_INFILTRATION;
-                        const uint32_t su = sj ? i : j, so = sj ? j : i;
-                        dist[e] = m.z[su] - m.z[so];
-                    }
-                }
-                if (m.btype[i] == SF3D_BND_FREE_DRAINAGE && m.ltype[0][i] == SF3D_LINK_NONE
-                    && (m.presetPartition == nullptr || m.presetPartition->owner[i] == rank_)) bad = true;   /* assert water.cpp:682 (a strip-local model's halo nodes may have lost the link: their rows and boundaries are the neighbour's) */
-            }
-        });
-        if (bad) { snprintf(err_, sizeof(err_), "FreeDrainage node without an Up link"); return SF3D_BOUNDARY_ERROR; }
-
-        /* per (64-node chunk, slot) descriptors: uniform kind + uniform index offset => the kernels
-         * never read lto/lkind for that chunk and slot */
+        /* the graph analysis: the stages of sf3d_host_plan.inc, in their order (DESIGN.md 3) */
+        I.dslot = plan_slot_alignment(m, sw.slotAlign);
+        { const sf3d_error_t e = plan_link_tables(m, I.dslot, rank_, st.links, err_, sizeof(err_)); if (e != SF3D_OK) return e; }
+        const std::vector<uint8_t>& kind = st.links.kind; const std::vector<double>&dist = st.links.dist, &area = st.links.area; const std::vector<uint32_t>& to = st.links.to;
         const uint32_t nChunks = v.nChunks;
-        std::vector<ChunkDesc> cdesc(nChunks);
-        parallel_for(nChunks, [&](uint32_t qa, uint32_t qb) {
-            for (uint32_t q = qa; q < qb; ++q) {
-                const uint32_t i0 = q * SF3D_CHUNK, i1 = (i0 + SF3D_CHUNK < N) ? i0 + SF3D_CHUNK : N;
-                ChunkDesc d;
-                std::memset(&d, 0, sizeof(d));
-                d.rowType = (i1 <= ns) ? 0 : (i0 >= ns ? 1 : 2);
-                for (int s = 0; s < SF3D_SLOTS; ++s) {
-                    bool any = false, all = true, same = true, sameDelta = true;
-                    uint8_t k0 = LK_NONE; int64_t d0 = 0;
-                    for (uint32_t i = i0; i < i1; ++i) {
-                        const size_t e = (size_t)s * N + i;
-                        if (kind[e] == LK_NONE) { all = false; continue; }
-                        const int64_t dd = (int64_t)to[e] - (int64_t)i;
-                        if (!any) { any = true; k0 = kind[e]; d0 = dd; }
-                        else { if (kind[e] != k0 || dd != d0) same = false; if (dd != d0) sameDelta = false; }
-                    }
-                    const bool fits = d0 >= INT32_MIN && d0 <= INT32_MAX;
-                    uint8_t ck = CK_NONE;
-                    if (any) ck = (all && same && fits) ? k0 : (uint8_t)CK_MIXED;
-                    d.kind[s] = ck;
-                    d.ukind[s] = any ? ((same && fits) ? k0 : (uint8_t)CK_MIXED) : (uint8_t)CK_NONE;
-                    d.delta[s] = (ck != CK_NONE && ck != CK_MIXED) ? (int32_t)d0 : 0;
-                    if (ck == CK_MIXED && sameDelta && fits) { d.delta[s] = (int32_t)d0; d.sweepUniform |= (uint16_t)(1u << s); }
-                    if (any) {                                   /* one interface area for the whole chunk? */
-                        bool first = true, uni = true; double a0 = 0.;
-                        for (uint32_t i = i0; i < i1 && uni; ++i) {
-                            const size_t e = (size_t)s * N + i;
-                            if (kind[e] == LK_NONE) continue;
-                            if (first) { a0 = area[e]; first = false; }
-                            else if (area[e] != a0) uni = false;
-                        }
-                        if (uni) { d.areaUniform |= (uint16_t)(1u << s); d.area[s] = a0; }
-                        first = true; uni = true; double d0v = 0.;
-                        for (uint32_t i = i0; i < i1 && uni; ++i) {
-                            const size_t e = (size_t)s * N + i;
-                            if (kind[e] == LK_NONE) continue;
-                            if (first) { d0v = dist[e]; first = false; }
-                            else if (dist[e] != d0v) uni = false;
-                        }
-                        if (uni) { d.distUniform |= (uint16_t)(1u << s); d.dist[s] = d0v; }
-                    }
-                }
-                {   /* scalar-geometry path of k_assemble: full 64-node soil chunk, every slot empty or uniform soil-soil */
-                    bool su = d.rowType == 1 && i1 - i0 == SF3D_CHUNK, partial = false;
-                    for (int s = 0; s < SF3D_SLOTS && su; ++s) {
-                        if (d.kind[s] == CK_NONE) continue;
-                        if (d.kind[s] == CK_MIXED) partial = true;      /* same kind and offset wherever the link exists (ukind, sweepUniform), some nodes without it */
-                        su = (d.ukind[s] == LK_SOIL_VERT || d.ukind[s] == LK_SOIL_LAT) && (d.kind[s] != CK_MIXED || ((d.sweepUniform >> s) & 1u))
-                             && ((d.areaUniform >> s) & 1u) && ((d.distUniform >> s) & 1u);
-                    }
-                    d.soilUniform = su ? (partial ? 2 : 1) : 0;
-                }
-                cdesc[q] = d;
-            }
-        });
-
-        /* paired sweep (k_sweep_pair): is the graph a regular NX x NY x NZ grid in layer-major numbering, and which neighbour
-         * does every link slot of every node name?  (host logic; the same structure sf3d_get_regular_grid reports) */
-        std::vector<uint64_t> pairNode, pairChunk;
-        std::vector<int32_t> pairIdxMap;            /* non-empty: the graph is a layered masked grid, not a full box */
-        uint32_t pairNX = 0, pairNY = 0, pairNZ = 0;
-        {
-            const char* pe = getenv("SF3D_PAIR_SWEEP");
-            const int want = pe ? (pe[0] == '0' ? 0 : 1) : -1;          /* -1: automatic (large grids only, decided below) */
-            /* (world > 1: the rank's strip + halo rows in local numbering - or the whole grid with SF3D_DIST_LOCAL=0 - is such a grid when
-             * the strips are cut between rows; which rows are the rank's is found below, once the partition is known) */
-            const char* rse = getenv("SF3D_RESIDENT_SWEEP");
-            const bool wantResident = rse ? rse[0] != '0' : want != 1;      /* the resident sweep loop (below) needs the same description of the grid; SF3D_PAIR_SWEEP=1 alone asks for the paired passes */
-            bool regular = (want != 0 || wantResident) && ns >= 64 && N % ns == 0 && N / ns >= 2 && N < (1u << 28);   /* 32-bit byte offsets in the kernel */
-            if (const char* fm = getenv("SF3D_PAIR_FORCE_MASKED")) if (fm[0] == '1') regular = false;       /* measurement: a full box through k_sweep_pair_masked */
-            int64_t maxOff = 0;
-            if (regular) {
-                for (int sl = 2; sl < SF3D_SLOTS && regular; ++sl)
-                    for (uint32_t i = 0; i < N; ++i) {
-                        const size_t e = (size_t)sl * N + i;
-                        if (kind[e] == LK_NONE) continue;
-                        const int64_t o = std::llabs((int64_t)to[e] - (int64_t)i);
-                        if (o > maxOff) maxOff = o;
-                    }
-                const int64_t NX = maxOff - 1;
-                regular = NX >= 64 && NX % 64 == 0 && ns % (uint64_t)NX == 0 && ns / (uint64_t)NX >= 6;
-                if (regular) { pairNX = (uint32_t)NX; pairNY = (uint32_t)(ns / (uint64_t)NX); pairNZ = N / ns; }
-            }
-            if (regular) {
-                pairNode.assign(N, 0);
-                std::atomic<bool> irregular{false};
-                const int64_t NX = pairNX, NY = pairNY;
-                parallel_for(N, [&](uint32_t a, uint32_t b) {
-                    for (uint32_t i = a; i < b && !irregular.load(std::memory_order_relaxed); ++i) {
-                        const int64_t l = i / ns, r = (i % ns) / NX, cidx = i % NX;
-                        uint64_t code = 0; unsigned seen = 0;
-                        for (int sl = 0; sl < SF3D_SLOTS; ++sl) {
-                            const size_t e = (size_t)sl * N + i;
-                            uint64_t nib = SF3D_PAIR_NONE;
-                            if (kind[e] != LK_NONE) {
-                                const int64_t off = (int64_t)to[e] - (int64_t)i;
-                                if (sl == 0) { if (off != -(int64_t)ns) irregular = true; nib = SF3D_PAIR_UP; }
-                                else if (sl == 1) { if (off != (int64_t)ns) irregular = true; nib = SF3D_PAIR_DOWN; }
-                                else {
-                                    const int64_t rr = (off >= 0) ? (off + NX / 2) / NX : -((-off + NX / 2) / NX), cc = off - rr * NX;
-                                    if (rr < -1 || rr > 1 || cc < -1 || cc > 1 || (rr == 0 && cc == 0) || r + rr < 0 || r + rr >= NY || cidx + cc < 0 || cidx + cc >= NX
-                                        || (int64_t)(to[e] / ns) != l) { irregular = true; break; }
-                                    nib = (uint64_t)((rr + 1) * 3 + (cc + 1));
-                                    if (seen & (1u << nib)) irregular = true;      /* two links to one neighbour */
-                                    seen |= 1u << nib;
-                                }
-                            }
-                            code |= nib << (4 * sl);
-                        }
-                        pairNode[i] = code;
-                    }
-                });
-                regular = !irregular;
-            }
-            if (regular) {
-                pairChunk.assign(nChunks, 0);
-                for (uint32_t q = 0; q < nChunks; ++q) {
-                    bool same = (size_t)(q + 1) * SF3D_CHUNK <= N;
-                    for (uint32_t k = 1; k < SF3D_CHUNK && same; ++k) same = pairNode[(size_t)q * SF3D_CHUNK + k] == pairNode[(size_t)q * SF3D_CHUNK];
-                    if (same) pairChunk[q] = pairNode[(size_t)q * SF3D_CHUNK] | (1ull << 63);
-                }
-            } else { pairNode.clear(); pairNX = pairNY = pairNZ = 0; }
-            /* not a full box: a LAYERED MASKED grid?  (a DEM outline with holes, soil columns of different depth - what
-             * Project3D::setCrit3DTopography builds, project3D.cpp:941-1103.)  Every node gets (layer, row, column): layer = number of Up
-             * hops to the surface, row / column from the surface node's coordinates; every link must go to one of the 26 grid neighbours. */
-            if (!regular && want != 0 && ns >= 64 && N < (1u << 28) && m.x.size() == N && m.y.size() == N) {
-                bool ok = true;
-                std::vector<int32_t> lay(N, -1), row(N, -1), colv(N, -1);
-                double cell = 0.;
-                for (int sl = 2; sl < SF3D_SLOTS; ++sl)
-                    for (uint32_t i = 0; i < ns; ++i) {
-                        const size_t e = (size_t)sl * N + i;
-                        if (kind[e] == LK_NONE) continue;
-                        const double dx = std::fabs(m.x[to[e]] - m.x[i]), dy = std::fabs(m.y[to[e]] - m.y[i]);
-                        const double d = dx > 0 ? (dy > 0 ? std::min(dx, dy) : dx) : dy;
-                        if (d > 0 && (cell == 0. || d < cell)) cell = d;
-                    }
-                ok = cell > 0.;
-                double xmin = 0, ymin = 0, ymax = 0;
-                bool northFirst = false;
-                auto place_rc = [&](uint32_t i) -> bool {           /* row / column of a node from its coordinates */
-                    const double fc = (m.x[i] - xmin) / cell, fr = (northFirst ? (ymax - m.y[i]) : (m.y[i] - ymin)) / cell;
-                    const long long c = std::llround(fc), r = std::llround(fr);
-                    if (std::fabs(fc - (double)c) > 1e-6 || std::fabs(fr - (double)r) > 1e-6 || c < 0 || r < 0 || c > 60000 || r > 60000) return false;
-                    row[i] = (int32_t)r; colv[i] = (int32_t)c;
-                    return true;
-                };
-                if (ok) {
-                    xmin = m.x[0]; ymin = ymax = m.y[0];
-                    const uint32_t nb = world_ > 1 ? N : ns;         /* (a strip-local model may hold halo soil nodes whose surface node it does not hold) */
-                    for (uint32_t i = 1; i < nb; ++i) { xmin = std::min(xmin, m.x[i]); ymin = std::min(ymin, m.y[i]); ymax = std::max(ymax, m.y[i]); }
-                    northFirst = m.y[0] > m.y[ns - 1];
-                    for (uint32_t i = 0; i < ns && ok; ++i) { lay[i] = 0; ok = place_rc(i); }
-                }
-                std::vector<uint32_t> orphans;
-                for (uint32_t i = ns; i < N && ok; ++i) {           /* soil nodes: below the node their Up link names (layer-major: it has a smaller index) */
-                    if (kind[i] == LK_NONE || to[i] >= i || lay[to[i]] < 0) {
-                        /* a strip-local model: a HALO node may have lost its Up link (the node above it is read by none of this rank's rows) */
-                        if (world_ > 1 && m.presetPartition != nullptr && m.presetPartition->owner[i] != rank_) { orphans.push_back(i); continue; }
-                        ok = false; break;
-                    }
-                    lay[i] = lay[to[i]] + 1; row[i] = row[to[i]]; colv[i] = colv[to[i]];
-                }
-                for (int pass = 0; pass < 8 && ok && !orphans.empty(); ++pass) {
-                    /* such a node lies in the layer of the node that reads it through a lateral link, at the place its coordinates say */
-                    for (int sl = 2; sl < SF3D_SLOTS; ++sl)
-                        for (uint32_t i = 0; i < N; ++i) {
-                            const size_t e = (size_t)sl * N + i;
-                            if (kind[e] == LK_NONE || lay[i] < 0) continue;
-                            const uint32_t j = to[e];
-                            if (lay[j] < 0) { lay[j] = lay[i]; if (!place_rc(j)) ok = false; }
-                        }
-                    std::vector<uint32_t> left;
-                    for (uint32_t i : orphans) {
-                        if (lay[i] >= 0) continue;
-                        if (kind[i] != LK_NONE && to[i] < i && lay[to[i]] >= 0) { lay[i] = lay[to[i]] + 1; row[i] = row[to[i]]; colv[i] = colv[to[i]]; }
-                        else left.push_back(i);
-                    }
-                    if (left.size() == orphans.size()) break;
-                    orphans.swap(left);
-                }
-                for (uint32_t i : orphans) if (lay[i] < 0) ok = false;
-                int32_t mr = 0, mc = 0, ml = 0;
-                if (ok) for (uint32_t i = 0; i < N; ++i) { mr = std::max(mr, row[i]); mc = std::max(mc, colv[i]); ml = std::max(ml, lay[i]); }
-                const uint32_t gNX = ok ? (uint32_t)((mc + 64) / 64 * 64) : 0, gNY = (uint32_t)mr + 1, gNZ = (uint32_t)ml + 1;
-                if (ok && ((uint64_t)gNX * gNY * gNZ > (1ull << 30) || gNZ < 2 || gNY < 6)) ok = false;
-                std::vector<int32_t> idxMap;
-                if (ok) {
-                    idxMap.assign((size_t)gNX * gNY * gNZ, -1);
-                    for (uint32_t i = 0; i < N && ok; ++i) {
-                        int32_t& cellIdx = idxMap[((size_t)lay[i] * gNY + (size_t)row[i]) * gNX + (size_t)colv[i]];
-                        if (cellIdx >= 0) ok = false;                /* two nodes in one cell */
-                        cellIdx = (int32_t)i;
-                    }
-                }
-                if (ok) {
-                    pairNode.assign(N, 0);
-                    std::atomic<bool> bad{false};
-                    parallel_for(N, [&](uint32_t a, uint32_t b) {
-                        for (uint32_t i = a; i < b && !bad.load(std::memory_order_relaxed); ++i) {
-                            uint64_t code = 0; unsigned seen = 0;
-                            for (int sl = 0; sl < SF3D_SLOTS; ++sl) {
-                                const size_t e = (size_t)sl * N + i;
-                                uint64_t nib = SF3D_PAIR_NONE;
-                                if (kind[e] != LK_NONE) {
-                                    const uint32_t j = to[e];
-                                    const int32_t dl = lay[j] - lay[i], dr = row[j] - row[i], dc = colv[j] - colv[i];
-                                    if (sl == 0) { if (dl != -1 || dr != 0 || dc != 0) bad = true; nib = SF3D_PAIR_UP; }
-                                    else if (sl == 1) { if (dl != 1 || dr != 0 || dc != 0) bad = true; nib = SF3D_PAIR_DOWN; }
-                                    else {
-                                        if (dl != 0 || dr < -1 || dr > 1 || dc < -1 || dc > 1 || (dr == 0 && dc == 0)) { bad = true; break; }
-                                        nib = (uint64_t)((dr + 1) * 3 + (dc + 1));
-                                        if (seen & (1u << nib)) bad = true;
-                                        seen |= 1u << nib;
-                                    }
-                                }
-                                code |= nib << (4 * sl);
-                            }
-                            pairNode[i] = code;
-                        }
-                    });
-                    ok = !bad;
-                }
-                if (ok) { pairNX = gNX; pairNY = gNY; pairNZ = gNZ; pairIdxMap.swap(idxMap); pairChunk.assign(nChunks, 0); }
-                else { pairNode.clear(); }
-            }
-        }
+        st.cdesc = plan_chunk_descriptors(st.links, N, ns);
+        std::vector<ChunkDesc>& cdesc = st.cdesc;
+        /* (world > 1: the rank's strip + halo rows in local numbering - or the whole grid with SF3D_DIST_LOCAL=0 - is such a grid when
+         * the strips are cut between rows; which rows are the rank's is found below, once the partition is known.  The resident sweep loop
+         * needs the same description of the grid as the paired passes) */
+        const bool regular = (sw.pairSweep != 0 || sw.residentSweep) && !sw.forceMasked && plan_regular_box(st.links, m, st.grid);
+        if (!regular && sw.pairSweep != 0) plan_masked_grid(st.links, m, world_, rank_, st.grid);
+        const std::vector<uint64_t>&pairNode = st.grid.node, &pairChunk = st.grid.chunk;
+        const std::vector<int32_t>& pairIdxMap = st.grid.idxMap;            /* non-empty: the graph is a layered masked grid, not a full box */
+        const uint32_t &pairNX = st.grid.NX, &pairNY = st.grid.NY, &pairNZ = st.grid.NZ, &pairOwnLo = st.grid.ownLo, &pairOwnHi = st.grid.ownHi;
 
         /* ownership + chunk lists (identity lists on one GPU) */
         {
@@ -861,64 +933,22 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
                 if (pe != SF3D_OK) { snprintf(err_, sizeof(err_), "partition failed"); return pe; }
             }
         }
-        I.ownedNodes = N;
-        if (world_ > 1) { uint32_t cnt = 0; for (uint32_t i = 0; i < N; ++i) cnt += I.part.owner[i] == rank_; I.ownedNodes = cnt; }
-        std::vector<uint32_t> listSurf, listSoil;
-        for (uint32_t q = 0; q < nChunks; ++q) {
-            bool mine = world_ == 1;
-            if (!mine) {
-                const uint32_t i0 = q * SF3D_CHUNK, i1 = (i0 + SF3D_CHUNK < N) ? i0 + SF3D_CHUNK : N;
-                for (uint32_t i = i0; i < i1 && !mine; ++i) mine = I.part.owner[i] == rank_;
-            }
-            if (mine) (q < v.qSplit ? listSurf : listSoil).push_back(q);
-        }
+        st.lists = plan_chunk_lists(I.part, st.links, N, ns, world_, rank_);
+        I.ownedNodes = st.lists.ownedNodes;
+        I.propsNeed.swap(st.lists.propsNeed);
+        const std::vector<uint32_t>& listSurf = st.lists.listSurf;
         {
             const uint32_t per = SF3D_BLOCK / SF3D_CHUNK;
-            v.nListSurf = (uint32_t)listSurf.size();
-            v.nList = (uint32_t)(listSurf.size() + listSoil.size());
+            v.nListSurf = st.lists.nListSurf;
+            v.nList = st.lists.nList;
             auto blocks = [&](uint32_t chunks) { uint32_t b = (chunks + per - 1) / per; if (b > SF3D_MAX_BLOCKS) b = SF3D_MAX_BLOCKS; return b; };
             v.nb = blocks(v.nList); if (v.nb == 0) v.nb = 1;
             v.nbSurf = blocks(v.nListSurf); if (v.nbSurf == 0) v.nbSurf = 1;
-            v.nbSoil = blocks(v.nList - v.nListSurf);
+            v.nbSoil = blocks(v.nList - v.nListSurf);      /* grids of the two halves of k_assemble */
+            if (sw.asmSoilBlocks > 0 && sw.asmSoilBlocks < v.nbSoil) v.nbSoil = sw.asmSoilBlocks;   /* tuning */
             v.world = world_; v.rank = rank_;
         }
-        if (world_ > 1) {
-            /* chunks that owe values to a neighbouring rank go first: their halo puts are on the wire while the interior
-             * is still being computed, instead of being the last thing every sweep waits for */
-            std::vector<uint8_t> owes(nChunks, 0);
-            for (int pr = 0; pr < world_; ++pr) for (uint32_t node : I.part.send[pr]) owes[node / SF3D_CHUNK] = 1;
-            auto first = [&](uint32_t q) { return owes[q] != 0; };
-            std::stable_partition(listSurf.begin(), listSurf.end(), first);
-            std::stable_partition(listSoil.begin(), listSoil.end(), first);
-        }
-        listSurf.insert(listSurf.end(), listSoil.begin(), listSoil.end());
         v.pLo = 0; v.pHi = v.nList; v.aLo = v.nListSurf; v.aHi = v.nList;
-        /* An approximation queued in slabs (SF3D_SLAB_OVERLAP, sf3d_host_step.inc): the rows of the list entries [0, e) read the node
-         * properties of list entries [0, propsNeed[e - 1]) - the furthest node any of their links names, whatever the numbering
-         * (layer-major: one layer further).  One GPU: the list is the identity. */
-        I.propsNeed.clear();
-        if (world_ == 1 && v.nList == nChunks) {
-            I.propsNeed.assign(nChunks, 0);
-            parallel_for(nChunks, [&](uint32_t a, uint32_t b) {
-                for (uint32_t q = a; q < b; ++q) {
-                    uint32_t far = q;
-                    const uint32_t i0 = q * SF3D_CHUNK, i1 = (i0 + SF3D_CHUNK < N) ? i0 + SF3D_CHUNK : N;
-                    for (int sl = 0; sl < SF3D_SLOTS; ++sl)
-                        for (uint32_t i = i0; i < i1; ++i) {
-                            const size_t e = (size_t)sl * N + i;
-                            if (kind[e] != LK_NONE && to[e] / SF3D_CHUNK > far) far = to[e] / SF3D_CHUNK;
-                        }
-                    I.propsNeed[q] = far + 1;
-                }
-            });
-            for (uint32_t q = 1; q < nChunks; ++q) if (I.propsNeed[q] < I.propsNeed[q - 1]) I.propsNeed[q] = I.propsNeed[q - 1];
-        }
-        {   /* grids of the two halves of k_assemble */
-            const uint32_t per = SF3D_BLOCK / SF3D_CHUNK;
-            auto blocks = [&](uint32_t chunks) { uint32_t b = (chunks + per - 1) / per; if (b > SF3D_MAX_BLOCKS) b = SF3D_MAX_BLOCKS; return b; };
-            v.nbSoil = blocks(v.nList - v.nListSurf);
-            if (const char* be = getenv("SF3D_ASM_SOIL_BLOCKS")) { const uint32_t nb = (uint32_t)atoi(be); if (nb > 0 && nb < v.nbSoil) v.nbSoil = nb; }   /* tuning */
-        }
         double *z, *size, *pond, *sink, *bslope, *bsize, *prescribed, *roughness, *larea, *ldist;
         uint16_t* cls; uint8_t *btype, *lkind; uint32_t* lto; SoilDev* soils; ChunkDesc* dcdesc;
         HIP_TRY(dev_alloc(I.allocs, z, N)); HIP_TRY(dev_alloc(I.allocs, size, N));
@@ -932,8 +962,7 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         {   /* link flow sums in batches - the plain single-GPU path (SF3D_OVERLAP_ACCEPT not 0, no quirk-1 compat rows): SF3D_LINKS_RING matrices
              * instead of two and as many copies of an accepted head, R x 88 B per node.  Memory that is not there is no error: the model
              * then runs with the two matrices and adds the sums inside every step */
-            const char* oe = getenv("SF3D_OVERLAP_ACCEPT");
-            I.overlapAccept = (oe && oe[0] == '0') ? 0 : 1;
+            I.overlapAccept = sw.overlapAccept;
             I.ring = 0; I.pend.n = 0;
             if (I.overlapAccept && world_ == 1 && !m.compat) {
                 const size_t keep = I.allocs.size(); const uint64_t bytesBefore = g_deviceBytes;
@@ -962,143 +991,32 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         {   /* bytes one rank touches per sweep: 152 B per owned node.  Below the 256 MiB Infinity Cache the whole
              * sweep working set stays cached between sweeps and bypassing costs ~8 % (measured at 0.98 M nodes);
              * above it the coefficient stream would thrash x, b, z: bypass gains ~13 % at 5.2 M nodes */
-            const char* e = getenv("SF3D_NT_STREAM");
             const double sweepBytes = 152.0 * (double)v.nList * SF3D_CHUNK;
-            v.ntStream = e ? (e[0] != '0') : (sweepBytes > 256.0 * 1024 * 1024);
+            v.ntStream = sw.ntStream >= 0 ? sw.ntStream : (sweepBytes > 256.0 * 1024 * 1024);
         }
         {   /* early Courant check (k_courant_probe): on while the last Courant number is >= 0.8 (the reference doubles dt while it is below 0.5, so quiet runs sit between 0.5 and 1: C4 F20 measured 43.6 sim-h/s without the check, 42.5 with a threshold of 0.5, 43.3 with 0.8; C4 F60 hour 0 5.23 -> 5.39 / 5.43); SF3D_COURANT_PROBE=0 turns it off,
              * any other number is the threshold (0: before every approximation) */
-            v.probeMin = 0.8;
-            if (const char* ce = getenv("SF3D_COURANT_PROBE")) { v.probeMin = atof(ce); if (ce[0] == '0' && ce[1] == 0) v.probeMin = -1.; if (ce[0] == 'a') v.probeMin = 0.; }
+            v.probeMin = sw.probeMin;
         }
         I.pairBlocks = 0; I.pairMasked = false; v.pair.masked = 0;
-        uint32_t pairOwnLo = 0, pairOwnHi = pairNY;
-        if (!pairNode.empty() && world_ > 1) {
-            /* paired sweep on a strip: the rank must own whole rows of the grid, one contiguous run of them, the same in every layer */
-            bool ok = true;
-            std::vector<int8_t> rowMine(pairNY, -1);
-            for (uint32_t i = 0; i < N && ok && pairIdxMap.empty(); ++i) {      /* (masked grids are cut mid-row: PairGrid::role instead, below) */
-                const uint32_t r = (i % ns) / pairNX;
-                const int8_t mine = I.part.owner[i] == rank_ ? 1 : 0;
-                if (rowMine[r] < 0) rowMine[r] = mine; else if (rowMine[r] != mine) ok = false;
-            }
-            uint32_t lo = 0, hi = pairNY;
-            if (ok && pairIdxMap.empty()) {
-                while (lo < pairNY && rowMine[lo] != 1) ++lo;
-                hi = lo;
-                while (hi < pairNY && rowMine[hi] == 1) ++hi;
-                for (uint32_t r = hi; r < pairNY && ok; ++r) if (rowMine[r] == 1) ok = false;
-                if (hi <= lo) ok = false;
-            }
-            if (ok) { pairOwnLo = lo; pairOwnHi = hi; }
-            else { pairNode.clear(); pairChunk.clear(); pairNX = pairNY = pairNZ = 0; }
-        }
+        plan_strip_rows(I.part, N, ns, world_, rank_, st.grid);
         if (!pairNode.empty()) {
             /* the paired sweep pays where the sweep streams from HBM (ntStream: above the Infinity Cache) - below that the plain sweep
              * is cache-resident and faster; SF3D_PAIR_SWEEP=1 forces it on any regular grid (tests on small grids) */
-            const char* pe = getenv("SF3D_PAIR_SWEEP");
             /* (masked grids, k_sweep_pair_masked: measured at the Ravone project, 5.85 M nodes, 249 us per pair against 2 x 147 us of
              * k_sweep - profiles/README.md; a first version that read the link table was slower than two sweeps) */
-            bool on = pe ? (pe[0] != '0') : (v.ntStream != 0);      /* (SF3D_PAIR_SWEEP=0: the grid was only described for the resident sweep loop) */
+            bool on = sw.pairSweep >= 0 ? (sw.pairSweep != 0) : (v.ntStream != 0);      /* (SF3D_PAIR_SWEEP=0: the grid was only described for the resident sweep loop) */
             /* below the Infinity Cache the pass still pays where the patches fill the machine: one of four strips of C4 (1.31 M nodes) 59.4 us
              * per pair against 2 x 36.5, C3 (0.98 M nodes) 45.2 against 2 x 29.0 - cost 1.69 in the model below; one of eight strips of C4
              * (53.4 against 2 x 22.4 us: cost 3.1) and anything smaller keep single sweeps (profiles/r04_pair_W_sweep.txt).
              * SF3D_PAIR_AUTO_COST=x moves the threshold (0: only above the Infinity Cache, round 3's rule) */
-            double autoCost = 1.9;
-            if (const char* ae = getenv("SF3D_PAIR_AUTO_COST")) autoCost = atof(ae);
-            const bool tryAuto = !pe && !on && autoCost > 0.;
+            const double autoCost = sw.autoCost;
+            const bool tryAuto = sw.pairSweep < 0 && !on && autoCost > 0.;
             if (on || tryAuto) {
                 int cus = 256; { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, I.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount; }
-                uint32_t bestW = 0; double bestCost = 1e30;
-                const char* we = getenv("SF3D_PAIR_W");
-                /* masked grids: the non-empty patches (a patch owns rows pr (W - 2) .. + W - 3 and 64 columns) and the layers they reach */
-                std::vector<uint32_t> plist[4]; std::vector<uint8_t> pdepth[4];
-                auto widx = [](uint32_t W) -> int { return W == 6 ? 0 : (W == 8 ? 1 : (W == 10 ? 2 : 3)); };
-                if (!pairIdxMap.empty()) {
-                    std::vector<uint8_t> colDepth((size_t)pairNX * pairNY, 0);          /* deepest layer + 1 of every cell's column */
-                    for (uint32_t l = 0; l < pairNZ; ++l)
-                        for (size_t k = 0; k < colDepth.size(); ++k)
-                            if (pairIdxMap[(size_t)l * colDepth.size() + k] >= 0) colDepth[k] = (uint8_t)(l + 1);
-                    std::vector<uint8_t> colMine(colDepth.size(), 1);                   /* multi GPU: the column is this rank's (a patch must own at least one such) */
-                    if (world_ > 1) for (size_t k = 0; k < colMine.size(); ++k) colMine[k] = pairIdxMap[k] >= 0 && I.part.owner[(uint32_t)pairIdxMap[k]] == rank_;
-                    /* a band of W - 2 rows is covered from left to right: a patch starts at the first column that still holds a node
-                     * of the band (not at a multiple of 64: at the Ravone outline 921 patches instead of 974 at W = 10, fill 0.90
-                     * instead of 0.85); patch columns fit 12 bits of the list entry (wider grids keep to multiples of 64, below) */
-                    int wi = 0;
-                    for (uint32_t W : {6u, 8u, 10u, 14u}) {
-                        const uint32_t prs = (pairNY + W - 3) / (W - 2);
-                        std::vector<uint8_t> band(pairNX);
-                        for (uint32_t pr = 0; pr < prs; ++pr) {
-                            const int64_t r0 = (int64_t)pr * (W - 2) - 1;
-                            std::fill(band.begin(), band.end(), 0);
-                            for (int64_t r = r0 + 1; r < r0 + (int64_t)W - 1 && r < (int64_t)pairNY; ++r)
-                                for (uint32_t cc = 0; cc < pairNX; ++cc) if (colDepth[(size_t)r * pairNX + cc] && colMine[(size_t)r * pairNX + cc]) band[cc] = 1;
-                            uint32_t cc = 0;
-                            while (cc < pairNX) {
-                                if (!band[cc]) { ++cc; continue; }
-                                const uint32_t c0 = pairNX <= 4096 ? cc : cc / 64 * 64;
-                                uint8_t depth = 0;
-                                for (int64_t r = r0; r < r0 + (int64_t)W; ++r) {
-                                    if (r < 0 || r >= (int64_t)pairNY) continue;
-                                    for (int64_t x = (int64_t)c0 - 1; x < (int64_t)c0 + 65; ++x) {
-                                        if (x < 0 || x >= (int64_t)pairNX) continue;
-                                        const uint8_t d = colDepth[(size_t)r * pairNX + (size_t)x];
-                                        if (d > depth) depth = d;
-                                    }
-                                }
-                                /* multi GPU: bit 7 = a column of another rank lies in the patch's footprint (the patch, its ring and the outer ring of the staged
-                                 * old iterate): after the first pass of an approximation the block takes such cells' values from the window (k_sweep_pair_masked) */
-                                if (world_ > 1 && pairNZ < 128u)
-                                    for (int64_t r = r0 - 1; r < r0 + (int64_t)W + 1 && !(depth & 0x80u); ++r) {
-                                        if (r < 0 || r >= (int64_t)pairNY) continue;
-                                        for (int64_t x = (int64_t)c0 - 2; x < (int64_t)c0 + 66; ++x) {
-                                            if (x < 0 || x >= (int64_t)pairNX) continue;
-                                            const size_t k = (size_t)r * pairNX + (size_t)x;
-                                            if (colDepth[k] && !colMine[k]) { depth |= 0x80u; break; }
-                                        }
-                                    }
-                                plist[wi].push_back(pairNX <= 4096 ? ((pr << 12) | c0) : ((pr << 12) | (c0 / 64)));
-                                pdepth[wi].push_back(depth);
-                                cc = c0 + 64;
-                            }
-                        }
-                        {   /* workgroup b runs on XCD b % 8 and takes entry run(b % 8) + b / 8 of the list (k_sweep_pair_masked): inside every
-                             * XCD's contiguous run the DEEPEST patches go first (stable: spatial order among equals), so that what is left for
-                             * the tail round - 921 patches over 512 resident blocks at the Ravone project - are the shallow ones */
-                            const uint32_t nbk = (uint32_t)plist[wi].size(), per = nbk >> 3, rem = nbk & 7u;
-                            uint32_t at = 0;
-                            for (uint32_t x = 0; x < 8 && nbk >= 8; ++x) {
-                                const uint32_t len = per + (x < rem ? 1u : 0u);
-                                std::vector<uint32_t> ord(len);
-                                for (uint32_t k = 0; k < len; ++k) ord[k] = at + k;
-                                std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return pdepth[wi][a] > pdepth[wi][b]; });
-                                std::vector<uint32_t> pl(len); std::vector<uint8_t> pd(len);
-                                for (uint32_t k = 0; k < len; ++k) { pl[k] = plist[wi][ord[k]]; pd[k] = pdepth[wi][ord[k]]; }
-                                std::copy(pl.begin(), pl.end(), plist[wi].begin() + at); std::copy(pd.begin(), pd.end(), pdepth[wi].begin() + at);
-                                at += len;
-                            }
-                        }
-                        ++wi;
-                    }
-                }
-                const uint32_t ownRows = pairOwnHi - pairOwnLo;
-                for (uint32_t W : {6u, 8u, 10u, 14u}) {
-                    if (pairNY < W || (we && (uint32_t)atoi(we) != W)) continue;
-                    if (W == 8 && !we) continue;          /* W = 8 is not in the fitted cost model: SF3D_PAIR_W=8 only (DESIGN.md 12) */
-                    const uint64_t blocks = pairIdxMap.empty() ? (uint64_t)((ownRows + W - 3) / (W - 2)) * (pairNX / 64) : (uint64_t)plist[widx(W)].size();
-                    if (blocks == 0) continue;
-                    /* relative time per node of a pass, fitted to measurements on one MI355X (profiles/r04_pair_W_sweep.txt: the full C4
-                     * grid and one of two / of four strips of it at W = 6 / 10 / 14): redundant halo rows x tail round of the blocks x a
-                     * latency term in the waves a busy CU holds, and the square root of the share of CUs that have a block at all (a
-                     * strip of 128 rows gives W = 10 only 128 blocks for 256 CUs: 72 us against 59 us at W = 6) */
-                    const uint64_t perCU = (uint64_t)(4 * SF3D_PAIR_WAVES / (W + 1)), resident = perCU * cus;     /* blocks of W + 1 waves per CU (LDS allows as many) */
-                    double quant = 1., busyShare = 1., wavesPerCU = (double)(perCU * (W + 1));
-                    if (blocks >= resident) { const uint64_t rounds = (blocks + resident - 1) / resident; quant = (double)(rounds * resident) / (double)blocks; }
-                    else { const uint64_t busy = std::min<uint64_t>(blocks, (uint64_t)cus); busyShare = (double)busy / cus; wavesPerCU = (double)blocks / (double)busy * (W + 1); }
-                    const double cost = (1. + 0.6 / (double)(W - 2)) * quant * (1. + 3.26 / (busyShare * wavesPerCU)) / std::sqrt(busyShare);
-                    if (cost < bestCost) { bestCost = cost; bestW = W; }
-                }
-                if (tryAuto && !(bestCost < autoCost)) bestW = 0;
+                const PairPlan pp = plan_pair_patches(st.grid, I.part, world_, rank_, cus, SF3D_PAIR_WAVES, tryAuto, autoCost, sw.pairWSet, sw.pairW);
+                const uint32_t bestW = pp.bestW, ownRows = pairOwnHi - pairOwnLo;
+                const std::vector<uint32_t>(&plist)[4] = pp.plist; const std::vector<uint8_t>(&pdepth)[4] = pp.pdepth;
                 if (bestW) {
                     uint32_t* dn; uint64_t* dq;
                     {   /* the kernels decode the eight lateral nibbles only (slots 2 .. 9: bits 8 .. 39 of a node's code) */
@@ -1116,7 +1034,7 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
                     I.pairBlocks = v.pair.patchCols * v.pair.patchRows;
                     v.pair.masked = 0; I.pairMasked = false;
                     if (!pairIdxMap.empty()) {
-                        const int wi = widx(bestW);
+                        const int wi = pair_widx(bestW);
                         int32_t* dm; uint32_t* dl; uint8_t* dd;
                         HIP_TRY(dev_alloc(I.allocs, dm, pairIdxMap.size())); HIP_TRY(dev_alloc(I.allocs, dl, plist[wi].size())); HIP_TRY(dev_alloc(I.allocs, dd, pdepth[wi].size()));
                         HIP_TRY(hipMemcpy(dm, pairIdxMap.data(), pairIdxMap.size() * 4, hipMemcpyHostToDevice));
@@ -1128,291 +1046,8 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
                 }
             }
         }
-        /* multi GPU, regular row strips: are the edge rows laid out in the send / receive lists as (layer) * NX + column from a base?  Then the kernels
-         * that hand records over inside a launch (the paired pass, the resident loop) address them directly - no walk through a chunk's send list
-         * between a value and its store (that walk is the latency of a per-layer / per-iteration lock-step of two ranks' edge blocks) */
-        int32_t edgePeer[2] = {-1, -1}; uint32_t edgePut[2] = {0u, 0u}, edgeGet[2] = {0u, 0u};
-        auto edge_rows_direct = [&]() -> bool {
-            if (pairNX == 0 || pairOwnHi - pairOwnLo < 2) return false;
-            for (uint32_t side = 0; side < 2; ++side) {
-                if ((side == 0 && pairOwnLo == 0) || (side == 1 && pairOwnHi >= pairNY)) continue;
-                const uint32_t rEdge = side == 0 ? pairOwnLo : pairOwnHi - 1, rHalo = side == 0 ? pairOwnLo - 1 : pairOwnHi;
-                const int pr = I.part.owner[rHalo * pairNX];
-                if (pr == rank_ || pr == SF3D_OWNER_NONE || pr >= world_) return false;
-                const auto& sl = I.part.send[pr]; const auto& rl = I.part.recv[pr];
-                const auto si = std::lower_bound(sl.begin(), sl.end(), rEdge * pairNX), ri = std::lower_bound(rl.begin(), rl.end(), rHalo * pairNX);
-                if (si == sl.end() || ri == rl.end()) return false;
-                const size_t sb = (size_t)(si - sl.begin()), rb = (size_t)(ri - rl.begin());
-                for (uint32_t l = 0; l < pairNZ; ++l)
-                    for (uint32_t cc = 0; cc < pairNX; ++cc) {
-                        const size_t ks = sb + (size_t)l * pairNX + cc, kr = rb + (size_t)l * pairNX + cc;
-                        if (ks >= sl.size() || kr >= rl.size() || sl[ks] != l * ns + rEdge * pairNX + cc || rl[kr] != l * ns + rHalo * pairNX + cc
-                            || I.part.owner[l * ns + rHalo * pairNX + cc] != pr) return false;
-                    }
-                edgePeer[side] = pr; edgePut[side] = (uint32_t)sb; edgeGet[side] = (uint32_t)rb;
-            }
-            return true;
-        };
-        if (world_ > 1) {
-            uint8_t* downer; HIP_TRY(dev_alloc(I.allocs, downer, N));
-            HIP_TRY(hipMemcpy(downer, I.part.owner.data(), N, hipMemcpyHostToDevice));
-            v.owner = downer;
-            /* my window: mailboxes + payload areas for what each neighbour puts (2 parities x 2 fields) */
-            DistView& d = I.hostDist;
-            std::memset(&d, 0, sizeof(d));
-            d.world = world_; d.rank = rank_; d.owner = downer;
-            {   double ts = 10.; if (const char* te = getenv("SF3D_DIST_TIMEOUT_S")) { ts = atof(te); if (!(ts >= 0.5)) ts = 0.5; if (ts > 600.) ts = 600.; }
-                d.spinTicks = (long long)(ts * 1e8); }
-            uint64_t off = 0;
-            uint32_t maxSend = 0;
-            for (int pr = 0; pr < world_; ++pr) {
-                d.recvCount[pr] = (uint32_t)I.part.recv[pr].size();
-                d.recvOff[pr] = off;
-                off += (uint64_t)d.recvCount[pr] * 2 * SF3D_DIST_FIELDS;
-                d.sendCount[pr] = (uint32_t)I.part.send[pr].size();
-                if (d.sendCount[pr] > maxSend) maxSend = d.sendCount[pr];
-                uint32_t *si, *ri;
-                HIP_TRY(dev_alloc(I.allocs, si, I.part.send[pr].size())); HIP_TRY(dev_alloc(I.allocs, ri, I.part.recv[pr].size()));
-                if (d.sendCount[pr]) HIP_TRY(hipMemcpy(si, I.part.send[pr].data(), (size_t)d.sendCount[pr] * 4, hipMemcpyHostToDevice));
-                if (d.recvCount[pr]) HIP_TRY(hipMemcpy(ri, I.part.recv[pr].data(), (size_t)d.recvCount[pr] * 4, hipMemcpyHostToDevice));
-                d.sendIdx[pr] = si; d.recvIdx[pr] = ri;
-            }
-            {   /* the send lists regrouped by chunk for the in-kernel puts */
-                struct Ent { uint32_t node; uint8_t peer; uint32_t slot; };
-                std::vector<Ent> ents;
-                for (int pr = 0; pr < world_; ++pr)
-                    for (uint32_t k = 0; k < I.part.send[pr].size(); ++k) ents.push_back({I.part.send[pr][k], (uint8_t)pr, k});
-                std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.node != b.node ? a.node < b.node : a.peer < b.peer; });
-                std::vector<uint32_t> bstart(nChunks + 1, 0), bslot(ents.size());
-                std::vector<uint8_t> blane(ents.size()), bpeer(ents.size());
-                for (size_t k = 0; k < ents.size(); ++k) {
-                    bstart[ents[k].node / SF3D_CHUNK + 1]++;
-                    blane[k] = (uint8_t)(ents[k].node % SF3D_CHUNK); bpeer[k] = ents[k].peer; bslot[k] = ents[k].slot;
-                }
-                for (uint32_t q = 0; q < nChunks; ++q) bstart[q + 1] += bstart[q];
-                uint32_t *dbs, *dsl; uint8_t *dla, *dpe;
-                HIP_TRY(dev_alloc(I.allocs, dbs, bstart.size())); HIP_TRY(dev_alloc(I.allocs, dsl, bslot.size()));
-                HIP_TRY(dev_alloc(I.allocs, dla, blane.size())); HIP_TRY(dev_alloc(I.allocs, dpe, bpeer.size()));
-                HIP_TRY(hipMemcpy(dbs, bstart.data(), bstart.size() * 4, hipMemcpyHostToDevice));
-                if (!ents.empty()) {
-                    HIP_TRY(hipMemcpy(dsl, bslot.data(), bslot.size() * 4, hipMemcpyHostToDevice));
-                    HIP_TRY(hipMemcpy(dla, blane.data(), blane.size(), hipMemcpyHostToDevice));
-                    HIP_TRY(hipMemcpy(dpe, bpeer.data(), bpeer.size(), hipMemcpyHostToDevice));
-                }
-                d.bndStart = dbs; d.bndSlot = dsl; d.bndLane = dla; d.bndPeer = dpe;
-            }
-            if (I.useFused < 0) { const char* fe = getenv("SF3D_FUSED_DECIDE"); I.useFused = (fe && fe[0] == '0') ? 0 : 1; }
-            v.haloDirect = I.useFused != 0 ? 1u : 0u;      /* the fused exchange only; SF3D_HALO_DIRECT=0 copies the halo after every sweep */
-            if (const char* hd = getenv("SF3D_HALO_DIRECT")) v.haloDirect = (hd[0] == '1' && I.useFused != 0) ? 1u : 0u;
-            if (v.haloDirect) {   /* where each foreign neighbour's value arrives in my window; chunks that have any are flagged */
-                std::vector<uint32_t> fsrc(NS, SF3D_FSRC_NONE);
-                for (uint32_t i = 0; i < N; ++i) {
-                    if (I.part.owner[i] != rank_) continue;
-                    for (int sl = 0; sl < SF3D_SLOTS; ++sl) {
-                        const size_t e = (size_t)sl * N + i;
-                        if (kind[e] == LK_NONE) continue;
-                        const uint32_t j = to[e];
-                        const int pr = I.part.owner[j];
-                        if (pr == rank_) continue;
-                        const auto& lst = I.part.recv[pr];
-                        const auto it = std::lower_bound(lst.begin(), lst.end(), j);
-                        if (it == lst.end() || *it != j) { snprintf(err_, sizeof(err_), "partition: node %u read by %u is missing from the halo list of rank %d", j, i, pr); return SF3D_TOPOGRAPHY_ERROR; }
-                        fsrc[e] = ((uint32_t)pr << 27) | (uint32_t)(it - lst.begin());
-                        cdesc[i / SF3D_CHUNK].pad0 = 1;
-                    }
-                }
-                uint32_t* dfs; HIP_TRY(dev_alloc(I.allocs, dfs, NS));
-                HIP_TRY(hipMemcpy(dfs, fsrc.data(), NS * 4, hipMemcpyHostToDevice));
-                d.fsrc = dfs;
-            }
-            v.bndList = nullptr; v.nBnd = 0;
-            if (I.pairBlocks != 0) {
-                /* paired sweep on a strip: k_sweep_bnd's chunks = the owned chunks that read a neighbouring strip; they must be exactly
-                 * the rows next to a halo row in every layer (what k_sweep_pair<DIST> leaves out), and the sweeps must take foreign
-                 * neighbours from the window (the fused exchange) */
-                bool ok = v.haloDirect != 0;
-                std::vector<uint32_t> bnd;
-                if (ok && I.pairMasked) {      /* masked grid: no rows to reason with - every node gets its role (PairGrid::role) */
-                    std::vector<uint8_t> role(N, 0);
-                    for (uint32_t i = 0; i < N; ++i) if (I.part.owner[i] == rank_) role[i] = cdesc[i / SF3D_CHUNK].pad0 ? 2 : 1;
-                    uint8_t* dr; HIP_TRY(dev_alloc(I.allocs, dr, N));
-                    HIP_TRY(hipMemcpy(dr, role.data(), N, hipMemcpyHostToDevice));
-                    v.pair.role = dr;
-                    for (uint32_t q : listSurf) if (cdesc[q].pad0) bnd.push_back(q);
-                } else
-                for (uint32_t k = 0; k < listSurf.size() && ok; ++k) {
-                    const uint32_t q = listSurf[k];
-                    const uint32_t r = ((q * SF3D_CHUNK) % ns) / pairNX;
-                    const bool edge = (pairOwnLo > 0 && r == pairOwnLo) || (pairOwnHi < pairNY && r + 1 == pairOwnHi);
-                    const bool mineRow = r >= pairOwnLo && r < pairOwnHi;
-                    if ((cdesc[q].pad0 != 0) != (edge && mineRow)) ok = false;
-                    if (cdesc[q].pad0 && mineRow) bnd.push_back(q);
-                }
-                if (ok && !bnd.empty()) {
-                    uint32_t* db; HIP_TRY(dev_alloc(I.allocs, db, bnd.size()));
-                    HIP_TRY(hipMemcpy(db, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
-                    v.bndList = db; v.nBnd = (uint32_t)bnd.size();
-                } else if (!ok || I.pairMasked || (pairOwnLo > 0 || pairOwnHi < pairNY)) { I.pairBlocks = 0; v.pair.NX = v.pair.NY = v.pair.NZ = 0; }
-            }
-            v.pair.records = 0u; d.recGet = nullptr; d.recPut = nullptr; I.pairRecordsWish = 0u;
-            if (I.pairBlocks != 0) {
-                if (I.pairMasked) {      /* masked grids: per-node tables - where an owned node's value goes, where a foreign node's arrives - instead of list walks */
-                    std::vector<RecGet> rg(N, RecGet{SF3D_FSRC_NONE, 0u});
-                    std::vector<RecPut> rp(N, RecPut{0u, 0u, 0u, 0u});
-                    bool fits = true;
-                    for (int pr = 0; pr < world_; ++pr) {
-                        const uint64_t rc = d.recvCount[pr], sc = d.sendCount[pr];
-                        for (uint32_t k = 0; k < rc; ++k) {
-                            const uint64_t o = d.recvOff[pr] + (uint64_t)DF_RECLO * rc + k;
-                            if (o + (uint64_t)2 * SF3D_DIST_FIELDS * rc >= 0xFFFFFFFFull) fits = false;
-                            rg[I.part.recv[pr][k]] = RecGet{(uint32_t)o, (uint32_t)rc};
-                        }
-                        for (uint32_t k = 0; k < sc; ++k) {
-                            RecPut& e = rp[I.part.send[pr][k]];
-                            if (e.nDest == 0u) {
-                                /* (sendOff: where MY values start in rank pr's window - known after the connect; the entry holds the position inside that area) */
-                                e.off0 = (uint32_t)((uint64_t)DF_RECLO * sc + k); e.cnt = (uint32_t)sc; e.peer = (uint32_t)pr;
-                            }
-                            e.nDest++;
-                        }
-                    }
-                    if (fits) {
-                        RecGet* dg; RecPut* dp;
-                        HIP_TRY(dev_alloc(I.allocs, dg, N)); HIP_TRY(dev_alloc(I.allocs, dp, N));
-                        HIP_TRY(hipMemcpy(dg, rg.data(), (size_t)N * sizeof(RecGet), hipMemcpyHostToDevice));
-                        HIP_TRY(hipMemcpy(dp, rp.data(), (size_t)N * sizeof(RecPut), hipMemcpyHostToDevice));
-                        d.recGet = dg; d.recPut = dp;
-                    }
-                }
-                /* record hand-over (one launch, one exchange per pass; SF3D_PAIR_RECORDS=0 keeps k_sweep_bnd and its second exchange; sf3d_dist_connect
-                 * decides for all ranks) */
-                const char* pre = getenv("SF3D_PAIR_RECORDS");
-                I.pairRecordsWish = (pre && pre[0] == '0') ? 0u : ((pre && pre[0] == '1') ? 2u : 1u);
-                if (I.pairRecordsWish != 0u) {
-                    /* every local node of another rank must be in that rank's halo list (it is: a node nobody here reads is not staged) - it would have no record */
-                    bool all = true;
-                    for (uint32_t i = 0; i < N && all; ++i) {
-                        const int pr = I.part.owner[i];
-                        if (pr == rank_ || pr == SF3D_OWNER_NONE) continue;
-                        const auto& lst = I.part.recv[pr];
-                        const auto it = std::lower_bound(lst.begin(), lst.end(), i);
-                        if (it == lst.end() || *it != i) all = false;
-                    }
-                    /* regular strips whose edge rows lie in the lists as (layer) * NX + column from a base: the kernel addresses the records directly */
-                    v.pair.recFast = 0u; v.pair.sidePeer[0] = v.pair.sidePeer[1] = -1; v.pair.recStride = pairNX;
-                    if (all && !I.pairMasked && edge_rows_direct()) {
-                        v.pair.recFast = 1u;
-                        for (int side = 0; side < 2; ++side) { v.pair.sidePeer[side] = edgePeer[side]; v.pair.putBase[side] = edgePut[side]; v.pair.getBase[side] = edgeGet[side]; }
-                    }
-                    /* the hand-over exists where the records are addressed without list walks - that layout, or the per-node tables of the masked pass
-                     * (above): with a walk through the chunk's send list per put and a look-up chain per wait it cost more than the second launch
-                     * saves (profiles/r06_i_record_handover_on_strips_ab.txt, jobs 23 / 24) */
-                    v.pair.records = (all && (I.pairMasked ? (d.recPut != nullptr && d.recGet != nullptr && pairNZ < 128u /* (bit 7 of the patches' depth byte flags the blocks at the cut) */) : v.pair.recFast != 0u)) ? 1u : 0u;
-                }
-            }
-            I.windowBytes = sizeof(DistWindow) + off * sizeof(double);
-            void* w = nullptr;
-            HIP_TRY(hipExtMallocWithFlags(&w, I.windowBytes, hipDeviceMallocFinegrained));
-            HIP_TRY(hipMemset(w, 0, I.windowBytes));
-            I.window = static_cast<DistWindow*>(w);
-            d.win[rank_] = I.window;
-            d.payload[rank_] = reinterpret_cast<double*>(reinterpret_cast<char*>(w) + sizeof(DistWindow));
-            HIP_TRY(dev_alloc(I.allocs, I.devDist, 1));
-            HIP_TRY(dev_alloc(I.allocs, I.distStats, 1 + 2 * SF3D_MAX_RANKS));
-            HIP_TRY(hipMemset(I.distStats, 0, sizeof(unsigned long long) * (1 + 2 * SF3D_MAX_RANKS)));
-            d.stats = I.distStats;
-            for (double& h : I.hopUs) h = 0.;
-            I.pushBlocks = (maxSend + SF3D_BLOCK - 1) / SF3D_BLOCK;
-            if (I.pushBlocks == 0) I.pushBlocks = 1;
-            if (I.pushBlocks > 256) I.pushBlocks = 256;
-        }
-        {   /* resident sweep loop (k_sweep_resident, sf3d_resident.inc): a regular grid - or the rank's row strip of one - whose rows fit into the
-             * registers of the CUs: patch height PR (a divisor of the owned rows), K chunks per wave and NW waves per block from the menu of
-             * compiled shapes, every block resident at once (occupancy query).  SF3D_RESIDENT_SWEEP=0 turns it off, =1 is the default. */
-            v.res = ResGrid{};
-            I.resBlocks = 0; I.resLds = 0;
-            const char* re = getenv("SF3D_RESIDENT_SWEEP");
-            if (I.useFused < 0) { const char* fe = getenv("SF3D_FUSED_DECIDE"); I.useFused = (fe && fe[0] == '0') ? 0 : 1; }
-            const char* pse = getenv("SF3D_PAIR_SWEEP");
-            const bool asked = re ? re[0] != '0' : !(pse && pse[0] != '0');      /* (SF3D_PAIR_SWEEP=1 alone asks for the paired passes: tests, measurements) */
-            const bool want = asked && I.useFused != 0 && !pairNode.empty() && pairIdxMap.empty() && (world_ == 1 || v.haloDirect);
-            if (want) {
-                const uint32_t ownRows = pairOwnHi - pairOwnLo, patchCols = pairNX / 64;
-                int cus = 256; { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, I.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount; }
-                uint32_t onlyPR = 0; if (const char* pe = getenv("SF3D_RESIDENT_PR")) onlyPR = (uint32_t)atoi(pe);      /* tests: this patch height or none */
-                for (uint32_t PR = 1; PR <= 8 && !v.res.on; ++PR) {
-                    if (ownRows % PR != 0 || (onlyPR != 0 && PR != onlyPR)) continue;
-                    const uint32_t blocks = patchCols * (ownRows / PR), T = PR * pairNZ;
-                    const uint32_t lds = 2u * pairNZ * (PR + 2) * SF3D_RES_RS * 8u;
-                    for (const ResShape& sh : kResShapes) {
-                        if ((uint32_t)(sh.K * sh.NW) < T || (uint32_t)sh.NW % PR != 0) continue;     /* (a wave's chunks: one row, layers a constant stride apart) */
-                        if (pairNZ * (2u * SF3D_RES_RS + 2u * PR) > (uint32_t)SF3D_RES_HM * sh.NW * 64u) continue;
-                        const void* fn = res_kernel(sh.K, sh.NW, world_ > 1);
-                        if (!fn) continue;
-                        if (lds > 48u * 1024u && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); continue; }
-                        int perCu = 0;
-                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, fn, sh.NW * 64, lds) != hipSuccess || perCu < 1) { (void)hipGetLastError(); continue; }
-                        if (blocks > (uint32_t)perCu * (uint32_t)cus) continue;
-                        v.res.on = 1; v.res.NX = pairNX; v.res.NY = pairNY; v.res.NZ = pairNZ; v.res.PR = PR;
-                        v.res.patchCols = patchCols; v.res.rowGroups = ownRows / PR; v.res.ownLo = pairOwnLo; v.res.ownHi = pairOwnHi;
-                        v.res.K = (uint32_t)sh.K; v.res.NW = (uint32_t)sh.NW;
-                        I.resBlocks = blocks; I.resLds = lds; I.resCapacity = (uint32_t)perCu * (uint32_t)cus;
-                        break;
-                    }
-                }
-            }
-            if (v.res.on) {
-                if (v.pair.nodeLat && v.pair.chunkCode && !v.pair.masked && v.pair.NX == pairNX) { v.res.nodeLat = v.pair.nodeLat; v.res.chunkCode = v.pair.chunkCode; }
-                else {
-                    uint32_t* dn; uint64_t* dq;
-                    std::vector<uint32_t> lat(pairNode.size());
-                    for (size_t k = 0; k < pairNode.size(); ++k) lat[k] = (uint32_t)(pairNode[k] >> 8);
-                    HIP_TRY(dev_alloc(I.allocs, dn, lat.size()));
-                    HIP_TRY(hipMemcpy(dn, lat.data(), lat.size() * 4, hipMemcpyHostToDevice));
-                    HIP_TRY(dev_alloc(I.allocs, dq, pairChunk.size()));
-                    HIP_TRY(hipMemcpy(dq, pairChunk.data(), pairChunk.size() * 8, hipMemcpyHostToDevice));
-                    v.res.nodeLat = dn; v.res.chunkCode = dq;
-                }
-                HIP_TRY(dev_alloc(I.allocs, v.res.bar, (size_t)SF3D_RES_LINE * 18)); HIP_TRY(hipMemset(v.res.bar, 0, (size_t)SF3D_RES_LINE * 18 * sizeof(unsigned int)));
-                HIP_TRY(dev_alloc(I.allocs, v.res.rec, (size_t)4 * N)); HIP_TRY(hipMemset(v.res.rec, 0, (size_t)4 * N * sizeof(unsigned long long)));
-                HIP_TRY(dev_alloc(I.allocs, v.res.prec, (size_t)8 * I.resBlocks)); HIP_TRY(hipMemset(v.res.prec, 0, (size_t)8 * I.resBlocks * sizeof(unsigned long long)));
-                HIP_TRY(dev_alloc(I.allocs, v.res.gpub, 8)); HIP_TRY(hipMemset(v.res.gpub, 0, 8 * sizeof(unsigned long long)));
-                HIP_TRY(dev_alloc(I.allocs, v.res.prec2, (size_t)8 * I.resBlocks)); HIP_TRY(hipMemset(v.res.prec2, 0, (size_t)8 * I.resBlocks * sizeof(unsigned long long)));
-                {   const char* pe2 = getenv("SF3D_RESIDENT_POST"); v.res.fusedPost = (pe2 && pe2[0] == '0') ? 0u : 1u;
-                    if (m.heat) v.res.fusedPost = 0u; }      /* (with coupled heat k_post's successor kernels read what only k_post's launch orders: kept apart) */
-                HIP_TRY(dev_alloc(I.allocs, v.res.pub, 32)); HIP_TRY(hipMemset(v.res.pub, 0, 32 * sizeof(double)));
-                if (world_ > 1) {
-                    /* where the cells of the foreign halo rows - the row above the strip (side 0), the row below it (side 1) - arrive in my window */
-                    std::vector<uint32_t> hs((size_t)2 * pairNZ * pairNX, SF3D_FSRC_NONE);
-                    v.res.sidePeer[0] = v.res.sidePeer[1] = -1;
-                    bool oneRank = true;
-                    for (uint32_t side = 0; side < 2; ++side) {
-                        if ((side == 0 && pairOwnLo == 0) || (side == 1 && pairOwnHi >= pairNY)) continue;
-                        const uint32_t r = side == 0 ? pairOwnLo - 1 : pairOwnHi;
-                        for (uint32_t l = 0; l < pairNZ; ++l)
-                            for (uint32_t cc = 0; cc < pairNX; ++cc) {
-                                const uint32_t j = l * ns + r * pairNX + cc;
-                                const int pr = I.part.owner[j];
-                                if (pr == rank_ || pr == SF3D_OWNER_NONE) continue;
-                                const auto& lst = I.part.recv[pr];
-                                const auto itp = std::lower_bound(lst.begin(), lst.end(), j);
-                                if (itp != lst.end() && *itp == j) {
-                                    hs[((size_t)side * pairNZ + l) * pairNX + cc] = ((uint32_t)pr << 27) | (uint32_t)(itp - lst.begin());
-                                    if (v.res.sidePeer[side] < 0) v.res.sidePeer[side] = pr; else if (v.res.sidePeer[side] != pr) oneRank = false;
-                                }
-                            }
-                    }
-                    uint32_t* dh; HIP_TRY(dev_alloc(I.allocs, dh, hs.size()));
-                    HIP_TRY(hipMemcpy(dh, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-                    v.res.haloSrc = dh;
-                    v.res.recFast = 0u; v.res.putBase[0] = v.res.putBase[1] = 0u;
-                    if (oneRank && edge_rows_direct() && edgePeer[0] == v.res.sidePeer[0] && edgePeer[1] == v.res.sidePeer[1]) {
-                        v.res.recFast = 1u; v.res.putBase[0] = edgePut[0]; v.res.putBase[1] = edgePut[1];
-                    }
-                    if (!oneRank) { v.res.on = 0; I.resBlocks = 0; }      /* (a halo row shared by two ranks: strips are cut between rows, so never - the kernel counts on it) */
-                }
-            }
-        }
+        if (world_ > 1) { const sf3d_error_t e = build_dist_window(st); if (e != SF3D_OK) return e; }
+        { const sf3d_error_t e = build_resident_plan(m, st); if (e != SF3D_OK) return e; }
         if (m.compat) {      /* quirk-1 emulation: calloc'd like the reference's rows (soilFluxes3D.cpp:76-155) */
             HIP_TRY(dev_alloc(I.allocs, v.compatCv, (size_t)N * (SF3D_SLOTS + 2))); HIP_TRY(hipMemset(v.compatCv, 0, (size_t)N * (SF3D_SLOTS + 2) * 8));
             HIP_TRY(dev_alloc(I.allocs, v.compatCn, N)); HIP_TRY(hipMemset(v.compatCn, 0, N));
@@ -1437,120 +1072,7 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         v.cdesc = dcdesc;
 
         I.heatAirP = nullptr;
-        if (m.heat) {       /* coupled heat transport: state, system, per-node conductivities, boundary and link flux arrays */
-            HeatDev& hv = v.heat;
-            hv = HeatDev{};
-            hv.on = 1; hv.water = m.water ? 1u : 0u; hv.vapor = m.heatVapor ? 1u : 0u; hv.advection = m.heatAdvection ? 1u : 0u;
-            hv.save = m.heatSave; hv.wf = p.heatWeightFactor;
-            double* tmp = nullptr;
-            for (int k = 0; k < 3; ++k) { HIP_TRY(dev_alloc(I.allocs, hv.TX[k], N)); HIP_TRY(hipMemset(hv.TX[k], 0, N * 8)); }
-            auto alloc0 = [&](double*& ptr, size_t cnt) -> hipError_t { hipError_t e = dev_alloc(I.allocs, ptr, cnt); if (e == hipSuccess) e = hipMemset(ptr, 0, cnt * 8); return e; };
-            HIP_TRY(alloc0(tmp, N)); hv.heatSink = tmp;
-            HIP_TRY(alloc0(hv.heatFlux, N)); HIP_TRY(alloc0(hv.invariant, N));
-            HIP_TRY(alloc0(hv.hC, N)); HIP_TRY(alloc0(hv.hcapTerm, N)); HIP_TRY(alloc0(hv.hb, N)); HIP_TRY(alloc0(hv.hD, N));
-            HIP_TRY(dev_alloc(I.allocs, hv.hA2, NS / 2)); HIP_TRY(hipMemset(hv.hA2, 0, NS * 8));
-            HIP_TRY(alloc0(hv.kHeat, N)); HIP_TRY(alloc0(hv.kIsoVap, N)); HIP_TRY(alloc0(hv.hAvg, N));
-            HIP_TRY(alloc0(hv.thetaOld, N)); HIP_TRY(alloc0(hv.thAvgC, N)); HIP_TRY(alloc0(hv.thNewC, N));
-            HIP_TRY(alloc0(tmp, N)); hv.airP = tmp; I.heatAirP = tmp;
-            HIP_TRY(alloc0(hv.wThLiq, N)); HIP_TRY(alloc0(hv.wThVap, N)); HIP_TRY(alloc0(hv.wTm, N));
-            const double** inputs[9] = {&hv.bHeightWind, &hv.bHeightT, &hv.bRoughH, &hv.bT, &hv.bRH, &hv.bWind, &hv.bNetIrr, &hv.bFixT, &hv.bFixDepth};
-            for (auto* pp : inputs) { HIP_TRY(alloc0(tmp, N)); *pp = tmp; }
-            double** outputs[6] = {&hv.bAero, &hv.bSoilCond, &hv.bSens, &hv.bLat, &hv.bRad, &hv.bAdv};
-            const std::vector<double>* outInit[6] = {&m.bAero, &m.bSoilCond, &m.bSens, &m.bLat, &m.bRad, &m.bAdv};   /* NODATA / 0 of setNodeBoundary */
-            for (int k = 0; k < 6; ++k) {
-                HIP_TRY(alloc0(*outputs[k], N)); I.heatOut[k] = *outputs[k];
-                HIP_TRY(hipMemcpy(*outputs[k], outInit[k]->data(), N * 8, hipMemcpyHostToDevice));
-            }
-            { double* wv = nullptr; HIP_TRY(alloc0(wv, NS)); hv.lwvFlux = reinterpret_cast<sf3d_f2*>(wv); }      /* 8 bytes per link: two floats */
-            const int nTypes = (m.heatSave == 2) ? SF3D_FLUX_TYPES : (m.heatSave == 1 ? 1 : 0);
-            {   /* never-linked slots hold 0 (calloc in the reference), linked slots NODATA (setNodeLink, soilFluxes3D.cpp:672-678) */
-                std::vector<double> init(NS, 0.);
-                for (size_t e = 0; e < NS; ++e) if (kind[e] != LK_NONE) init[e] = NODATA_D;
-                for (int t = 0; t < nTypes; ++t) {
-                    HIP_TRY(dev_alloc(I.allocs, hv.lflux[t], NS));
-                    HIP_TRY(hipMemcpy(hv.lflux[t], init.data(), NS * 8, hipMemcpyHostToDevice));
-                }
-            }
-            {   /* nodeDistance3D (soilPhysics.cpp:334-338) of every link between two soil nodes */
-                std::vector<double> d3(NS, 1.);
-                parallel_for(N, [&](uint32_t a, uint32_t b) {
-                    for (uint32_t i = a; i < b; ++i)
-                        for (int s = 0; s < SF3D_SLOTS; ++s) {
-                            const size_t e = (size_t)s * N + i;
-                            if (kind[e] != LK_SOIL_VERT && kind[e] != LK_SOIL_LAT) continue;
-                            const uint32_t j = to[e];
-                            const double dx = m.x[i] - m.x[j], dy = m.y[i] - m.y[j], dz = m.z[i] - m.z[j];
-                            double nrm = 0; nrm += dx * dx; nrm += dy * dy; nrm += dz * dz;
-                            d3[e] = std::sqrt(nrm);
-                        }
-                });
-                HIP_TRY(alloc0(tmp, NS)); hv.hdist = tmp;
-                HIP_TRY(hipMemcpy(tmp, d3.data(), NS * 8, hipMemcpyHostToDevice));
-            }
-            {   /* colours of the heat sweep: layer = hops to the surface through the Up links (layer-major numbering: the node above has
-                 * a smaller index); a halo node of a strip-local model that lost its Up link is never swept here */
-                std::vector<uint8_t> lp(N, 0);
-                for (uint32_t i = ns; i < N; ++i) if (kind[i] != LK_NONE && to[i] < i) lp[i] = (uint8_t)(lp[to[i]] + 1);
-                uint8_t* dlp; HIP_TRY(dev_alloc(I.allocs, dlp, N));
-                HIP_TRY(hipMemcpy(dlp, lp.data(), N, hipMemcpyHostToDevice));
-                hv.lpar = dlp;
-                /* (a rank of a sharded run: plus, in BOTH lists, the chunks that owe values to a neighbouring rank - every wave puts all the
-                 * entries of its chunk in each half, the nodes of the other colour with the value they have at that moment) */
-                std::vector<uint8_t> owesHeat(nChunks, 0);
-                if (world_ > 1) for (int pr = 0; pr < world_; ++pr) for (uint32_t node : I.part.send[pr]) owesHeat[node / SF3D_CHUNK] = 1;
-                for (int col = 0; col < 2; ++col) {         /* col 0: odd layers (first half), col 1: even layers */
-                    std::vector<uint32_t> cl;
-                    for (uint32_t q : listSurf) {
-                        const uint32_t i0 = q * SF3D_CHUNK, i1 = (i0 + SF3D_CHUNK < N) ? i0 + SF3D_CHUNK : N;
-                        bool any = owesHeat[q] != 0;
-                        for (uint32_t i = i0; i < i1 && !any; ++i) any = ((lp[i] & 1u) != 0u) == (col == 0);
-                        if (any) cl.push_back(q);
-                    }
-                    uint32_t* dcl; HIP_TRY(dev_alloc(I.allocs, dcl, cl.size()));
-                    if (!cl.empty()) HIP_TRY(hipMemcpy(dcl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
-                    hv.colourList[col] = dcl; hv.nColour[col] = (uint32_t)cl.size();
-                }
-                const char* se = getenv("SF3D_HEAT_SWEEP");
-                hv.redBlack = (se && se[0] == 'j') ? 0u : 1u;
-                /* only where layer parity really colours the vertical links (heat_two_colour_valid, sf3d_model.h).  A rank of a sharded run
-                 * sees its strip only: its finding travels in its blob and dist_connect turns the two-colour sweep off on EVERY rank if any
-                 * rank found a violation - all ranks must run the same protocol */
-                const bool colourable = heat_two_colour_valid(m);
-                I.heatJacobiOnly = !colourable;
-                if (hv.redBlack && !colourable) {
-                    hv.redBlack = 0u;
-                    if (getenv("SF3D_HEAT_DEBUG")) fprintf(stderr, "sf3d: heat sweep: the node numbering is not layer-major along the Up links - Jacobi instead of the two-colour sweep\n");
-                }
-            }
-            I.gsLevelStart.clear();
-            if (const char* ge = getenv("SF3D_HEAT_GS")) if (ge[0] == '1') {
-                if (world_ > 1) { snprintf(err_, sizeof(err_), "SF3D_HEAT_GS=1 (reference-order Gauss-Seidel) is a single-GPU verification mode"); return SF3D_PARAMETER_ERROR; }
-                /* dependency levels of the serial sweep: a node waits for its linked heat nodes with a smaller index */
-                std::vector<uint32_t> level(N, 0u);
-                uint32_t maxLevel = 0;
-                for (uint32_t i = ns; i < N; ++i) {
-                    uint32_t l = 0;
-                    for (int sl = 0; sl < SF3D_SLOTS; ++sl) {
-                        const size_t e = (size_t)sl * N + i;
-                        if ((kind[e] == LK_SOIL_VERT || kind[e] == LK_SOIL_LAT) && to[e] < i && level[to[e]] + 1 > l) l = level[to[e]] + 1;
-                    }
-                    level[i] = l;
-                    if (l > maxLevel) maxLevel = l;
-                }
-                std::vector<uint32_t> start(maxLevel + 2, 0u), order(N > ns ? N - ns : 0);
-                for (uint32_t i = ns; i < N; ++i) start[level[i] + 1]++;
-                for (uint32_t l = 0; l <= maxLevel; ++l) start[l + 1] += start[l];
-                std::vector<uint32_t> pos(start.begin(), start.end() - 1);
-                for (uint32_t i = ns; i < N; ++i) order[pos[level[i]]++] = i;
-                uint32_t* dord; HIP_TRY(dev_alloc(I.allocs, dord, order.size()));
-                if (!order.empty()) HIP_TRY(hipMemcpy(dord, order.data(), order.size() * 4, hipMemcpyHostToDevice));
-                hv.gsOrder = dord; hv.gs = 1;
-                I.gsLevelStart = start;
-            }
-            m.heatStateDirty = m.heatSinkDirty = m.heatBoundaryDirty = true;
-            m.hostStaleHeat = false;
-            for (int t = 0; t < SF3D_FLUX_TYPES; ++t) m.lfluxValid[t] = false;
-        }
+        if (m.heat) { const sf3d_error_t e = build_heat(m, p, st); if (e != SF3D_OK) return e; }
 
         std::vector<SoilDev> sd(m.soils.size());
         for (size_t k = 0; k < sd.size(); ++k) {
@@ -1563,22 +1085,7 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         HIP_TRY(hipMemcpy(lto, to.data(), NS * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(lkind, kind.data(), NS, hipMemcpyHostToDevice));
         {   /* which end of a runoff link the early Courant check evaluates (DevView::probeMask) */
-            std::vector<uint8_t> pm(ns, 0);
-            parallel_for(ns, [&](uint32_t a, uint32_t b) {
-                for (uint32_t i = a; i < b; ++i)
-                    for (int sl = 2; sl < SF3D_SLOTS; ++sl) {
-                        const size_t e = (size_t)sl * N + i;
-                        if (kind[e] != LK_RUNOFF) continue;
-                        const uint32_t j = to[e];
-                        bool mineToDo = j > i;
-                        if (!mineToDo) {                     /* the other end does it - if it has the link back */
-                            bool back = false;
-                            for (int s2 = 2; s2 < SF3D_SLOTS && !back; ++s2) back = kind[(size_t)s2 * N + j] == LK_RUNOFF && to[(size_t)s2 * N + j] == i;
-                            mineToDo = !back || j == i;
-                        }
-                        if (mineToDo) pm[i] |= (uint8_t)(1u << (sl - 2));
-                    }
-            });
+            const std::vector<uint8_t> pm = plan_probe_mask(st.links, N, ns);
             /* the check looks at the lateral slots only; a caller may also link two surface nodes Up / Down (setNodeLink allows it and the
              * assembly counts that link's Courant term): the partial maximum would then refuse with another dt than checkCourant - off */
             for (int sl = 0; sl < 2 && v.probeMin >= 0.; ++sl)

@@ -8,6 +8,7 @@
 #ifndef SF3D_MODEL_H
 #define SF3D_MODEL_H
 
+#include <cstddef>
 #include <cstdint>
 #include <initializer_list>
 #include <vector>
@@ -283,6 +284,13 @@ private:
     template <class Arg> sf3d_error_t raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms);
     sf3d_error_t raster_tables(char*& tables, size_t* off, int count, const size_t* bytes, const void* const* src, const size_t* srcBytes);
     void raster_release(std::initializer_list<void*> blocks);
+    /* the three largest device-side stages of the build block of sync_to_device (sf3d_host_build.inc): the multi-GPU window set-up, the
+     * resident loop's plan with its occupancy queries, the coupled-heat arrays with their colouring and Gauss-Seidel levels.  BuildState
+     * is what one build's stages share */
+    struct BuildState;
+    sf3d_error_t build_dist_window(BuildState& st);
+    sf3d_error_t build_resident_plan(const HostModel& m, BuildState& st);
+    sf3d_error_t build_heat(HostModel& m, const ParamsHost& p, BuildState& st);
     struct Impl;
     Impl* impl_ = nullptr;
     Ctrl mirror_{};

@@ -43,6 +43,7 @@
 #include "sf3d_physics.inc"
 #include "sf3d_control.inc"
 #include "sf3d_phases.inc"
+#include "sf3d_host_plan.inc"
 #include "sf3d_host_build.inc"
 #include "sf3d_host_step.inc"
 #include "sf3d_maps.inc"

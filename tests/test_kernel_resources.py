@@ -1,7 +1,7 @@
 """Registers, scratch and LDS of the hot kernels, read from the code object inside the built product library (no GPU needed).
 
 The host side PLANS with these numbers - the patch-height cost model of the paired sweep assumes floor(4 * 6 / (W + 1)) blocks of W + 1
-waves per CU (sf3d_host_build.inc, "perCU"), the resident grids of k_props / k_assemble / k_post assume 5 / 4 / 8 waves per SIMD
+waves per CU (sf3d_host_plan.inc, "perCU"), the resident grids of k_props / k_assemble / k_post assume 5 / 4 / 8 waves per SIMD
  - and a change that makes a kernel spill or lose a resident block shows up as a slower bench line long after the edit.
 This test makes it show up at once."""
 import re
@@ -49,7 +49,7 @@ def _pick(kernels, pattern):
 
 def test_paired_sweeps_keep_the_blocks_per_cu_the_cost_model_counts_on(kernels):
     for W in (6, 10, 14):
-        per_cu = 4 * 6 // (W + 1)                 # sf3d_host_build.inc: perCU = 4 * SF3D_PAIR_WAVES / (W + 1)
+        per_cu = 4 * 6 // (W + 1)                 # sf3d_host_plan.inc: perCU = 4 * pairWaves / (W + 1), pairWaves = SF3D_PAIR_WAVES
         # k_sweep_pair<W, NT, DIST, RECORDS> (RECORDS: the strip variant that waits for the neighbours' records inside the launch), k_sweep_pair_masked<W, NT, DIST>
         for name, r in _pick(kernels, rf"k_sweep_pair(_masked<{W}, (true|false), (true|false)>|<{W}, (true|false), (true|false), (true|false)>)").items():
             assert r["threads"] == (W + 1) * 64, (name, r)

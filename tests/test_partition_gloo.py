@@ -28,7 +28,7 @@ def test_strips_are_row_blocks_cut_at_chunk_boundaries(product):
 
 
 def test_edge_rows_of_a_regular_strip_lie_in_the_lists_as_layer_times_nx_plus_column(product):
-    """What the in-launch record hand-overs count on (sf3d_host_build.inc edge_rows_direct): on a regular grid a rank's edge row
+    """What the in-launch record hand-overs count on (sf3d_host_plan.inc plan_edge_rows_direct): on a regular grid a rank's edge row
     lies in the neighbour's send / receive lists as base + layer * NX + column - the kernels of the paired pass and of the resident loop then
     store and poll their records without a walk through a chunk's send list.  A change of the partition's list order would not break a
     result (the host checks the layout and falls back to the two-launch form / the list walk), it would silently cost the speed: held here."""
