@@ -1,4 +1,4 @@
-/* part of sf3d_solver.hip (included there, in this order: physics, control, phases, host_plan, host_build, host_step) - host side, part 1: DeviceSolver::Impl, device selection, the switches of the build and sync_to_device (the stages of sf3d_host_plan.inc in their order, allocations, uploads; the multi-GPU windows, the resident loop's plan and the coupled-heat arrays in member functions of their own) */
+/* part of sf3d_solver.hip (included there, in this order: physics, control, phases, host_plan, host_build, host_step) - host side, part 1: DeviceSolver::Impl, device selection, the kernel selectors and launch_view, the switches of the build and of the step driver, and sync_to_device (the stages of sf3d_host_plan.inc in their order, allocations, uploads; the multi-GPU windows, the resident loop's plan and the coupled-heat arrays in member functions of their own) */
 /* ======================================================================================= */
 /* host side                                                                                */
 /* ======================================================================================= */
@@ -11,20 +11,44 @@ const char* kKernelNames[KID_COUNT] = {"k_props", "k_assemble", "k_sweep", "k_po
 
 /* compiled shapes of k_sweep_resident: K (row, layer) chunks per wave x NW waves per block (PR NZ <= K NW); smallest first */
 struct ResShape { int K, NW; };
-static const ResShape kResShapes[] = {{2, 5}, {2, 10}, {5, 8}};
 #define SF3D_RES_FOR_SHAPES(X) X(2, 5) X(2, 10) X(5, 8)
-static const void* res_kernel(int K, int NW, bool dist)
+#define SF3D_RES_SHAPE(k, w) {k, w},
+static const ResShape kResShapes[] = {SF3D_RES_FOR_SHAPES(SF3D_RES_SHAPE)};
+#undef SF3D_RES_SHAPE
+
+/* Every kernel of a step takes the device view by value.  A template family has one selector that returns the instantiation for run-time
+ * arguments - its rows are generated from one list, the template arguments are the macro's parameters - and everything is launched by
+ * launch_view.  nullptr: no such instantiation was compiled */
+typedef void (*ViewKernel)(DevView);
+static inline void launch_view(ViewKernel fn, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const DevView& v) { hipLaunchKernelGGL(fn, grid, block, lds, st, v); }
+static ViewKernel res_kernel(int K, int NW, bool dist)
 {
-#define SF3D_RES_PTR(k, w) if (K == k && NW == w) return dist ? (const void*)k_sweep_resident<k, w, true> : (const void*)k_sweep_resident<k, w, false>;
+#define SF3D_RES_PTR(k, w) if (K == k && NW == w) return dist ? k_sweep_resident<k, w, true> : k_sweep_resident<k, w, false>;
     SF3D_RES_FOR_SHAPES(SF3D_RES_PTR)
 #undef SF3D_RES_PTR
     return nullptr;
 }
-static void res_launch(int K, int NW, bool dist, uint32_t blocks, uint32_t lds, hipStream_t st, const DevView& v)
+/* patch heights of the paired pass (pair_widx, sf3d_host_plan.inc).  records: the hand-over of records inside the launch, on a strip only */
+#define SF3D_PAIR_FOR_HEIGHTS(X) X(6) X(8) X(10) X(14)
+static ViewKernel pair_kernel(uint32_t W, bool nt, bool dist, bool records, bool masked)
 {
-#define SF3D_RES_GO(k, w) if (K == k && NW == w) { if (dist) hipLaunchKernelGGL((k_sweep_resident<k, w, true>), dim3(blocks), dim3(w * 64), lds, st, v); else hipLaunchKernelGGL((k_sweep_resident<k, w, false>), dim3(blocks), dim3(w * 64), lds, st, v); return; }
-    SF3D_RES_FOR_SHAPES(SF3D_RES_GO)
-#undef SF3D_RES_GO
+#define SF3D_PAIR_PTR(w)                                                                                                                      \
+    if (W == w) {                                                                                                                             \
+        if (masked) return dist ? (nt ? k_sweep_pair_masked<w, true, true> : k_sweep_pair_masked<w, false, true>)                             \
+                                : (nt ? k_sweep_pair_masked<w, true, false> : k_sweep_pair_masked<w, false, false>);                          \
+        if (dist && records) return nt ? k_sweep_pair<w, true, true, true> : k_sweep_pair<w, false, true, true>;                              \
+        return dist ? (nt ? k_sweep_pair<w, true, true> : k_sweep_pair<w, false, true>) : (nt ? k_sweep_pair<w, true, false> : k_sweep_pair<w, false, false>); \
+    }
+    SF3D_PAIR_FOR_HEIGHTS(SF3D_PAIR_PTR)
+#undef SF3D_PAIR_PTR
+    return nullptr;
+}
+static ViewKernel sweep_kernel(int mode, bool nt)      /* k_sweep<MODE>: 0 separate decision kernels, 1 fused decision, 2 + in-kernel exchange */
+{
+#define SF3D_SWEEP_PTR(m) if (mode == m) return nt ? k_sweep<m, true> : k_sweep<m, false>;
+    SF3D_SWEEP_PTR(0) SF3D_SWEEP_PTR(1) SF3D_SWEEP_PTR(2)
+#undef SF3D_SWEEP_PTR
+    return nullptr;
 }
 
 __global__ void k_dist_ping(DistView d, unsigned long long token, long long timeoutTicks, int* out);
@@ -108,6 +132,19 @@ struct SinkCache {
     std::vector<double> layerDepth;
 };
 
+/* the SF3D_* switches the step driver acts on (sf3d_host_step.inc): read by read_step_switches when a model is built, back to these
+ * defaults at release() - tests toggle them between models of one process */
+struct StepSwitches {
+    bool residentGrids = true;          /* SF3D_RESIDENT_GRIDS (0: every kernel with the common 2 048-block grid) */
+    bool graphs = true;                 /* SF3D_GRAPHS (0: eager launches) */
+    bool asmNtOff = false;              /* SF3D_ASM_NT=0: tuning: cacheable stores of the rows */
+    bool pairOddSingle = true;          /* SF3D_PAIR_ODD_SINGLE (0: the paired pass queues pairs only) */
+    long residentFailAt = -1;           /* SF3D_RESIDENT_FAIL_TEST=n: tests: the resident launches of the process's n-th computeStep give up, once */
+    int heatDebug = 0;                  /* SF3D_HEAT_DEBUG: 0 unset, 1 set: one line per computeStep, 2: one per poll as well */
+    int slabs = 0;                      /* SF3D_SLAB_OVERLAP=S (2 .. 8, else 0), and its grids and the share of the soil rows in the first slab (0: equal slabs) */
+    uint32_t slabPropsBlocks = 512, slabAsmBlocks = 512; double slabFirst = 0.;
+};
+
 struct DeviceSolver::Impl {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -129,10 +166,12 @@ struct DeviceSolver::Impl {
     uint32_t lastHeatSteps = 1;            /* heat steps (accepted + halved) of the previous computeStep: look-ahead depth */
     double* heatOut[6] = {nullptr};       /* bAero, bSoilCond, bSens, bLat, bRad, bAdv (device) */
     double* heatAirP = nullptr;            /* filled by k_heat_static once z is on the device */
-    /* hipGraph cache: one instantiated graph per (with head part, number of queued sweeps) */
-    std::vector<std::pair<uint32_t, hipGraphExec_t>> graphs;
+    /* hipGraph cache: one instantiated graph per shape of a water batch or of a heat group (GraphKey, sf3d_host_plan.inc).  replay
+     * (sf3d_host_step.inc) launches the graph of `key` on st; the first time it captures what `enqueue` queues on st and instantiates it */
+    std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;
+    template <class F> hipError_t replay(const GraphKey& key, hipStream_t st, F enqueue);
     int useFused = -1;                     /* SF3D_FUSED_DECIDE=0 keeps the separate decision kernel */
-    int useGraphs = -1;                    /* -1 unknown, 0 off (SF3D_GRAPHS=0), 1 on */
+    StepSwitches sw;                       /* the switches of the step driver, read when the model is built */
     /* multi-GPU */
     Partition part;
     DistWindow* window = nullptr;          /* fine-grained, IPC-exported */
@@ -207,7 +246,7 @@ struct DeviceSolver::Impl {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, fn, SF3D_BLOCK, 0) == hipSuccess && perCu > 0
             && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             nbk = (uint32_t)perCu * (uint32_t)prop.multiProcessorCount;
-        if (residentGrids == 0) nbk = SF3D_MAX_BLOCKS;
+        if (!sw.residentGrids) nbk = SF3D_MAX_BLOCKS;
         residentBlocks.push_back({fn, nbk});
         return nbk;
     }
@@ -239,8 +278,6 @@ struct DeviceSolver::Impl {
     std::vector<uint32_t> propsNeed;       /* [nChunks] one GPU: the rows of chunks [0, q] read node properties of chunks [0, propsNeed[q]) */
     hipStream_t stream3 = nullptr;         /* slab overlap: the node properties of the next slab beside the rows of this one */
     hipEvent_t evSlab[8] = {};
-    int slabs = -1; uint32_t slabPropsBlocks = 0, slabAsmBlocks = 0; double slabFirst = 0.;
-    int residentGrids = -1;               /* SF3D_RESIDENT_GRIDS=0: every kernel with the common 2 048-block grid */
     uint32_t pairBlocks = 0;              /* grid of k_sweep_pair (0: the graph is no regular grid, or the paired sweep is off) */
     bool pairMasked = false;              /* the paired sweep runs as k_sweep_pair_masked (layered masked grid) */
     uint32_t resBlocks = 0, resLds = 0;   /* grid and dynamic LDS of k_sweep_resident (0: the rows of this grid do not fit on chip, or the resident loop is off) */
@@ -317,7 +354,6 @@ sf3d_error_t DeviceSolver::release()
         (void)hipStreamDestroy(I.stream3); I.stream3 = nullptr;
         for (auto& ev : I.evSlab) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
     }
-    I.slabs = -1;
     for (auto& p : I.pending) { I.freeEvents.push_back(p.a); I.freeEvents.push_back(p.b); }
     I.pending.clear();
     for (auto& g : I.graphs) hipGraphExecDestroy(g.second);
@@ -338,7 +374,7 @@ sf3d_error_t DeviceSolver::release()
     built_ = false;
     fatal_ = false;
     /* the SF3D_* mode switches are read again when the next model is built (tests toggle them between models of one process) */
-    I.overlapAccept = I.useFused = I.useGraphs = I.residentGrids = -1;
+    I.overlapAccept = I.useFused = -1; I.sw = StepSwitches();
     return SF3D_OK;
 }
 
@@ -410,7 +446,7 @@ struct BuildSwitches {
     double autoCost;                    /* SF3D_PAIR_AUTO_COST */
     bool pairWSet; uint32_t pairW;      /* SF3D_PAIR_W */
     double distTimeoutS;                /* SF3D_DIST_TIMEOUT_S */
-    int fusedDecide;                    /* SF3D_FUSED_DECIDE (Impl::useFused takes it where that is still unknown) */
+    int fusedDecide;                    /* SF3D_FUSED_DECIDE (Impl::useFused takes it at the head of the build) */
     int haloDirect;                     /* SF3D_HALO_DIRECT: -1 unset, 1 it is 1, 0 anything else */
     uint32_t pairRecordsWish;           /* SF3D_PAIR_RECORDS: Impl::pairRecordsWish */
     uint32_t residentPR;                /* SF3D_RESIDENT_PR: tests: this patch height or none (0: unset) */
@@ -455,6 +491,25 @@ static BuildSwitches read_build_switches()
     s.heatDebug = getenv("SF3D_HEAT_DEBUG") != nullptr;
     s.heatGS = false;
     if (const char* ge = getenv("SF3D_HEAT_GS")) if (ge[0] == '1') s.heatGS = true;
+    return s;
+}
+
+/* the switches of the step driver, each parsed once per model (sync_to_device keeps them in the solver's state) */
+static StepSwitches read_step_switches()
+{
+    StepSwitches s;
+    auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+    s.residentGrids = !off("SF3D_RESIDENT_GRIDS");
+    s.graphs = !off("SF3D_GRAPHS");
+    s.asmNtOff = off("SF3D_ASM_NT");
+    s.pairOddSingle = !off("SF3D_PAIR_ODD_SINGLE");
+    if (const char* fe = getenv("SF3D_RESIDENT_FAIL_TEST")) s.residentFailAt = strtol(fe, nullptr, 10);
+    if (const char* he = getenv("SF3D_HEAT_DEBUG")) s.heatDebug = he[0] == '2' ? 2 : 1;
+    { const char* e = getenv("SF3D_SLAB_OVERLAP"); s.slabs = e ? atoi(e) : 0; if (s.slabs > 8) s.slabs = 8; if (s.slabs < 2) s.slabs = 0; }
+    auto blocks_of = [](const char* e) -> uint32_t { const long n = e ? strtol(e, nullptr, 10) : 512L; return (uint32_t)(n < 1 ? 1 : (n > SF3D_MAX_BLOCKS ? SF3D_MAX_BLOCKS : n)); };      /* (0 or garbage would be a dim3(0) launch) */
+    s.slabPropsBlocks = blocks_of(getenv("SF3D_SLAB_PROPS_BLOCKS"));
+    s.slabAsmBlocks = blocks_of(getenv("SF3D_SLAB_ASM_BLOCKS"));
+    if (const char* fe = getenv("SF3D_SLAB_FIRST")) s.slabFirst = atof(fe);
     return s;
 }
 
@@ -528,7 +583,6 @@ sf3d_error_t DeviceSolver::build_dist_window(BuildState& st)
         }
         d.bndStart = dbs; d.bndSlot = dsl; d.bndLane = dla; d.bndPeer = dpe;
     }
-    if (I.useFused < 0) I.useFused = sw.fusedDecide;
     v.haloDirect = I.useFused != 0 ? 1u : 0u;      /* the fused exchange only; SF3D_HALO_DIRECT=0 copies the halo after every sweep */
     if (sw.haloDirect >= 0) v.haloDirect = (sw.haloDirect == 1 && I.useFused != 0) ? 1u : 0u;
     if (v.haloDirect) {   /* where each foreign neighbour's value arrives in my window; chunks that have any are flagged */
@@ -668,7 +722,6 @@ sf3d_error_t DeviceSolver::build_resident_plan(const HostModel& m, BuildState& s
          * compiled shapes, every block resident at once (occupancy query).  SF3D_RESIDENT_SWEEP=0 turns it off, =1 is the default. */
         v.res = ResGrid{};
         I.resBlocks = 0; I.resLds = 0;
-        if (I.useFused < 0) I.useFused = sw.fusedDecide;
         const bool asked = sw.residentSweep;      /* (SF3D_PAIR_SWEEP=1 alone asks for the paired passes: tests, measurements) */
         const bool want = asked && I.useFused != 0 && !pairNode.empty() && pairIdxMap.empty() && (world_ == 1 || v.haloDirect);
         if (want) {
@@ -682,7 +735,7 @@ sf3d_error_t DeviceSolver::build_resident_plan(const HostModel& m, BuildState& s
                 for (const ResShape& sh : kResShapes) {
                     if ((uint32_t)(sh.K * sh.NW) < T || (uint32_t)sh.NW % PR != 0) continue;     /* (a wave's chunks: one row, layers a constant stride apart) */
                     if (pairNZ * (2u * SF3D_RES_RS + 2u * PR) > (uint32_t)SF3D_RES_HM * sh.NW * 64u) continue;
-                    const void* fn = res_kernel(sh.K, sh.NW, world_ > 1);
+                    const void* fn = (const void*)res_kernel(sh.K, sh.NW, world_ > 1);
                     if (!fn) continue;
                     if (lds > 48u * 1024u && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); continue; }
                     int perCu = 0;
@@ -901,6 +954,8 @@ sf3d_error_t DeviceSolver::sync_to_device(HostModel& m, const ParamsHost& p)
         /* pull anything newer on the device before the arrays are re-created */
         if (built_) { if (m.hostStaleState) fetch_state(m); if (m.hostStaleFlows) fetch_flows(m); if (m.heat && m.hostStaleHeat && I.v.heat.on) fetch_heat(m); }
         release();
+        I.sw = read_step_switches();
+        if (I.useFused < 0) I.useFused = sw.fusedDecide;
         I.N = N; I.ns = ns;
         DevView& v = I.v;
         v = DevView{};

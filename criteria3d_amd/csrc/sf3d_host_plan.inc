@@ -1,7 +1,8 @@
 /* part of sf3d_solver.hip (included there just before sf3d_host_build.inc) - host side, part 0: the graph analysis of the device build as
- * plain functions over HostModel.  No HIP call, no solver object, no environment: this file also compiles with a plain C++ compiler after
- * sf3d_model.h (tests/plan_host.cpp holds every stage's claims against the link data).  What a stage reads from the environment or from the
- * device arrives as an argument; sync_to_device (sf3d_host_build.inc) calls the stages in the order they stand here. */
+ * plain functions over HostModel, and at its end the decisions of one computeStep as plain functions over scalars (plan_step).  No HIP call,
+ * no solver object, no environment: this file also compiles with a plain C++ compiler after sf3d_model.h (tests/plan_host.cpp holds every
+ * stage's claims against the link data, and the step's plan to the rules between its flags).  What a stage reads from the environment or
+ * from the device arrives as an argument; sync_to_device (sf3d_host_build.inc) calls the stages in the order they stand here. */
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -721,3 +722,120 @@ inline std::vector<uint8_t> plan_probe_mask(const LinkTables& t, uint32_t N, uin
     });
     return pm;
 }
+
+/* ---- one computeStep: which launch forms it takes (sf3d_host_step.inc), decided from scalars ----
+ * StepFacts is what the step driver reads to decide - copied from the solver's state, the device view, the control block of the last step
+ * and the switches; plan_step turns them into the mode flags the driver acts on.  tests/plan_host.cpp enumerates the boolean facts and holds
+ * the plan to the rules between the flags. */
+struct StepFacts {
+    bool multi = false;                 /* more than one rank */
+    bool heatOn = false;                /* coupled heat */
+    bool useFused = true;               /* SF3D_FUSED_DECIDE as the model holds it (the RCCL exchange turns it off) */
+    bool lineal = false, haveCg = false;            /* the caller asked for the linealia hook; the model has the conjugate gradients' arrays */
+    bool resAvail = false, resFusedPost = false;    /* the resident loop has a grid that fits; its launch does the post-solve part too */
+    bool haloDirect = false, rccl = false;
+    uint32_t nBnd = 0;                  /* chunks of the rows next to a neighbouring rank (k_sweep_bnd) */
+    bool pairAvail = false;             /* the paired pass has a grid */
+    int timing = 0; bool sampled = false;           /* kernel timing mode; mode 2: this is a sampled step */
+    bool overlapAccept = false, ring = false;       /* SF3D_OVERLAP_ACCEPT; the model has the rings of matrices and heads */
+    bool compat = false;                /* quirk-1 emulation: rows are stored raw and normalised by k_compat_rows after the Courant decision */
+    bool ntStream = false, asmNtOff = false;        /* streaming stores; SF3D_ASM_NT=0 */
+    double probeMin = -1., courant = 0.; uint32_t probeBudget = 0;      /* early Courant check: threshold, the Courant number and the budget the host saw last */
+    int slabs = 0; bool havePropsNeed = false; uint32_t nList = 0, nListSurf = 0;      /* SF3D_SLAB_OVERLAP and what it needs of the chunk list */
+    bool useGraphs = true, heatGs = false;          /* SF3D_GRAPHS; SF3D_HEAT_GS=1 */
+    long residentFailAt = -1; uint64_t residentSteps = 0;       /* SF3D_RESIDENT_FAIL_TEST and the computeSteps it counts in */
+};
+struct StepPlan {
+    bool useFused;                      /* what the model holds from now on: sharded heat exists only in the fused-exchange form */
+    bool fused, fusedMulti;             /* sweep + convergence decision in one launch (one GPU); + in-kernel halo puts and all-gather (several) */
+    bool linealOn;                      /* the linealia stand-in: device conjugate gradients */
+    bool resOn;                         /* all iterations of an approximation in ONE launch, the rows resident on chip (sf3d_resident.inc) */
+    bool resFusedPost;                  /* ... which also does k_post's work */
+    bool countsResidentStep, forceTimeout;          /* tests: this step counts for SF3D_RESIDENT_FAIL_TEST; its resident launches give up */
+    bool pairOn;                        /* k_sweep_pair instead of k_sweep (on a strip: + k_sweep_bnd) */
+    bool timedStep;                     /* launches carry HIP events: eager */
+    bool overlap;                       /* the accepted step's link flow sums are added later, in one pass over the rings (k_links_flush) */
+    bool compat, asmNT;
+    bool probeNow;                      /* early Courant check queued with the batches of this step */
+    bool slabOn;                        /* the slab experiment */
+    bool replayWater, replayHeat;       /* batches / heat groups are replayed from captured graphs (else launched eagerly) */
+};
+inline StepPlan plan_step(const StepFacts& f)
+{
+    StepPlan P;
+    P.useFused = f.useFused || (f.heatOn && f.multi);
+    P.fused = !f.multi && P.useFused;
+    P.fusedMulti = f.multi && P.useFused;
+    P.linealOn = f.lineal && f.haveCg && !f.multi && P.useFused;
+    /* the resident loop: grids that fit, fused decisions, window exchange */
+    P.resOn = f.resAvail && (P.fused || (P.fusedMulti && f.haloDirect && !f.rccl)) && !P.linealOn;
+    P.resFusedPost = P.resOn && f.resFusedPost;
+    P.countsResidentStep = P.resOn && !f.multi;
+    P.forceTimeout = P.countsResidentStep && f.residentFailAt >= 0 && (long)f.residentSteps == f.residentFailAt;
+    P.pairOn = !P.resOn && (P.fused || (P.fusedMulti && f.haloDirect && f.nBnd != 0)) && f.pairAvail && !P.linealOn;
+    /* mode 2 samples: the sweeps of every 8th computeStep carry HIP events (eager launches); the other steps replay captured graphs, so the
+     * measurement costs ~1 % instead of ~6 % */
+    P.timedStep = f.timing == 1 || (f.timing == 2 && f.sampled);
+    /* plain single-GPU path, untimed steps only, so that the per-kernel event timing sees every kernel of a step inside the step
+     * (compat: k_compat_rows rewrites what the sums read) */
+    P.overlap = f.overlapAccept && !f.multi && f.ring && !P.timedStep && f.timing != 1 && !f.compat;
+    P.compat = f.compat;
+    P.asmNT = f.ntStream && !f.asmNtOff;      /* SF3D_ASM_NT=0: tuning: cacheable stores of the rows */
+    /* queued while the Courant number the host saw last (end of the step before) is within reach of the threshold - far below it the two
+     * launches would be guarded no-ops in every approximation */
+    P.probeNow = f.probeMin >= 0. && !f.heatOn && !f.multi && !f.compat && f.courant >= 0.75 * f.probeMin && (f.probeBudget > 0 || f.probeMin == 0.);
+    P.slabOn = f.slabs >= 2 && !f.multi && !f.heatOn && P.useFused && !f.compat && !P.timedStep && f.timing != 1 && f.havePropsNeed
+               && f.nList > f.nListSurf + 64u * (uint32_t)f.slabs;
+    P.replayWater = f.useGraphs && !P.timedStep && !f.rccl;      /* event timing needs eager launches; RCCL calls are queued eagerly */
+    P.replayHeat = f.useGraphs && !f.heatGs;                     /* (a heat group carries no events: it is replayed in a timed step too) */
+    return P;
+}
+
+/* how many sweeps to queue for the `index`-th approximation of a step: what the same approximation of the previous step took, plus one
+ * (Ctrl::seqSweeps; a sweep queued in vain is a guarded no-op of ~4 us, one too few costs a poll; sweeps that a later batch queued simply
+ * continue an unfinished approximation); without a record, the last count plus two */
+inline uint32_t predicted_sweeps(uint32_t index, bool withHead, uint32_t predCount, const uint32_t* pred, uint32_t lastSweeps)
+{
+    uint32_t chunk;
+    if (withHead && index < predCount && index < 16u) { chunk = pred[index] + 1; if (chunk < 2) chunk = 2; }
+    else { chunk = lastSweeps + 2; if (chunk < 4) chunk = 4; }
+    if (chunk > 40) chunk = 40;
+    return chunk;
+}
+/* the paired pass, two Jacobi iterations per launch.  `chunk` = expected iterations + 1: floor(expected / 2) pairs, a single sweep when the
+ * expectation is odd (122 us instead of a 175 us pair whose second half would be thrown away), then one more pair as the margin (a guarded
+ * no-op when the expectation holds).  oddSingle off (SF3D_PAIR_ODD_SINGLE=0): pairs only.  The single sweep goes in front of pair
+ * number singleAfter (UINT32_MAX: there is none). */
+struct PairSchedule { uint32_t nPairs, singleAfter; };
+inline PairSchedule pair_schedule(uint32_t chunk, bool oddSingle)
+{
+    const uint32_t expected = chunk > 1 ? chunk - 1 : 1;
+    return {oddSingle ? expected / 2 + 1 : (chunk + 1) / 2, (oddSingle && (expected & 1u)) ? expected / 2 : UINT32_MAX};
+}
+/* sweeps per heat solve: one more than the last solve took, even: few graph shapes (a guarded no-op launch costs ~5 us) */
+inline uint32_t heat_chunk(uint32_t lastHeatSweeps)
+{
+    const uint32_t chunk = ((lastHeatSweeps + 1 + 1) / 2) * 2;
+    return chunk < 4 ? 4 : (chunk > 64 ? 64 : chunk);
+}
+/* Look-ahead: the previous step needed `lastBatches` approximations; that many guarded batches are queued before the first poll (a batch
+ * queued in vain costs ~25 no-op launches, a poll costs a full host round trip while the GPU idles).  Heat: as many guarded heat steps as
+ * the last computeStep needed; Gauss-Seidel has one launch per dependency level: the queue is kept short */
+inline uint32_t water_look_ahead(uint32_t lastBatches) { return lastBatches < 1 ? 1 : (lastBatches > 6 ? 6 : lastBatches); }
+inline uint32_t heat_look_ahead(uint32_t lastHeatSteps, bool gs) { return gs ? 1 : (lastHeatSteps < 1 ? 1 : (lastHeatSteps > 8 ? 8 : lastHeatSteps)); }
+
+/* what an instantiated graph is remembered under: everything that changes the launches of a water batch or of a heat group within the
+ * life of a model.  Counts have fields of their own, so no two of them can run into each other or into a flag */
+enum : uint32_t { GK_HEAT = 1u, GK_HEAD = 2u, GK_TAIL = 4u, GK_RES = 8u, GK_RES_POST = 16u, GK_RES_FAIL = 32u, GK_OVERLAP = 64u, GK_PAIR = 128u,
+                  GK_LINEAL = 256u, GK_PROBE = 512u, GK_SLAB = 1024u, GK_SAVE = 2048u };
+struct GraphKey {
+    uint32_t flags, sweeps, steps;
+    bool operator==(const GraphKey& o) const { return flags == o.flags && sweeps == o.sweeps && steps == o.steps; }
+};
+inline GraphKey water_graph_key(const StepPlan& P, bool withHead, bool withTail, uint32_t chunk)
+{
+    const uint32_t flags = (withHead ? GK_HEAD : 0u) | (withTail ? GK_TAIL : 0u) | (P.resOn ? GK_RES : 0u) | (P.resFusedPost ? GK_RES_POST : 0u) | (P.forceTimeout ? GK_RES_FAIL : 0u)
+                           | (P.overlap ? GK_OVERLAP : 0u) | (P.pairOn ? GK_PAIR : 0u) | (P.linealOn ? GK_LINEAL : 0u) | (P.probeNow ? GK_PROBE : 0u) | (P.slabOn ? GK_SLAB : 0u);
+    return {flags, P.resOn ? 0u : chunk, 0u};      /* (the resident loop: one launch whatever the number of iterations: one graph shape) */
+}
+inline GraphKey heat_graph_key(uint32_t steps, uint32_t chunk, bool save) { return {GK_HEAT | (save ? GK_SAVE : 0u), chunk, steps}; }

@@ -1,4 +1,4 @@
-/* part of sf3d_solver.hip (included there, in this order: physics, control, phases, host_build, host_step) - host side, part 2: read-backs, heat queries, the multi-GPU set-up (export / connect / finalize), device math probes, kernel timing and DeviceSolver::step (batch queueing, hipGraph replay, polling) */
+/* part of sf3d_solver.hip (included there, in this order: physics, control, phases, host_plan, host_build, host_step) - host side, part 2: read-backs, heat queries, the multi-GPU set-up (export / connect / finalize), device math probes, kernel timing, and the step driver: the one graph cache (Impl::replay), StepCtx (what the parts of a step share, and the queueing of node properties, a water batch, the slabs and a heat group), the water and heat poll loops (step_water, step_heat), the end of a step with the resident loop's retry (step_finish) and DeviceSolver::step, which plans (plan_step, sf3d_host_plan.inc) and calls them in turn */
 sf3d_error_t DeviceSolver::fetch_state(HostModel& m)
 {
     Impl& I = *impl_;
@@ -679,9 +679,6 @@ sf3d_error_t DeviceSolver::stats(int kid, uint64_t* launches, double* ms, uint64
     return SF3D_OK;
 }
 
-/* One computeStep (soilFluxes3D.cpp:1785-1821 -> CPUSolver::run -> waterMainLoop).
- * The host queues one approximation per batch - every kernel guarded by the device stage -
- * and polls the control block once per batch. */
 /* Profiler ranges (SURVEY.md 5: "add rocprofv3 markers").  SF3D_ROCTX=1 brackets every computeStep, every poll group of water
  * approximations and every poll group of heat sub-steps with roctx ranges (rocprofv3 --marker-trace shows them above the kernels: a
  * trace of config 5 + heat is ~40 000 launches per simulated hour).  The library is resolved at run time - librocprofiler-sdk-roctx,
@@ -717,131 +714,125 @@ struct RoctxRange {
 };
 }  // namespace
 
-sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep, double* dtOut)
+/* ---- the step driver ----
+ * One computeStep (soilFluxes3D.cpp:1785-1821 -> CPUSolver::run -> waterMainLoop).  The host queues one approximation per batch - every
+ * kernel guarded by the device stage - and polls the control block once per batch.  Which launch forms a step takes is decided by
+ * plan_step (sf3d_host_plan.inc) from scalars; StepCtx queues what the plan says; step_water and step_heat poll; step_finish ends the step. */
+
+/* The ~25 launches of a batch are replayed from an instantiated hipGraph (one per shape): small grids are bound by the host's launch
+ * rate otherwise.  Event timing needs eager launches. */
+template <class F> hipError_t DeviceSolver::Impl::replay(const GraphKey& key, hipStream_t st, F enqueue)
 {
-    RoctxRange stepRange("sf3d computeStep");
-    sf3d_error_t e = sync_to_device(m, p);
-    if (e != SF3D_OK) return e;
-    if (world_ > 1 && !connected_) { snprintf(err_, sizeof(err_), "multi-GPU model used before sf3d_dist_connect / sf3d_dist_finalize%s%.150s", distWhy_[0] ? ": " : "", distWhy_); return SF3D_SOLVER_ERROR; }
-    Impl& I = *impl_;
-    const DevView& v = I.v;
-    const dim3 grid(v.nb), block(SF3D_BLOCK), one(1);
-    const bool multi = world_ > 1;
-    const bool heatOn = v.heat.on != 0;
-    if (I.useFused < 0) { const char* e = getenv("SF3D_FUSED_DECIDE"); I.useFused = (e && e[0] == '0') ? 0 : 1; }
-    if (I.residentGrids < 0) { const char* e = getenv("SF3D_RESIDENT_GRIDS"); I.residentGrids = (e && e[0] == '0') ? 0 : 1; }
-    const bool compat = v.compatCv != nullptr;   /* quirk-1 emulation: rows are stored raw and normalised by k_compat_rows after the Courant decision */
+    for (auto& g : graphs) if (g.first == key) return hipGraphLaunch(g.second, st);
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return e;
+    enqueue();
+    e = hipStreamEndCapture(st, &graph);
+    if (e != hipSuccess) return e;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) return e;
+    graphs.push_back({key, exec});
+    return hipGraphLaunch(exec, st);
+}
+
+static ViewKernel assemble_kernel(bool fused, bool nt, bool heat)      /* (coupled heat with separate decision kernels: cacheable stores only) */
+{
+    if (heat) return fused ? (nt ? k_assemble<true, true, true> : k_assemble<true, false, true>) : k_assemble<false, false, true>;
+    return fused ? (nt ? k_assemble<true, true, false> : k_assemble<true, false, false>) : (nt ? k_assemble<false, true, false> : k_assemble<false, false, false>);
+}
+
+/* the device counters the attribution of event pairs reads, as of the last poll */
+struct StepCounts {
+    uint64_t counters[8], pairLaunches, singleLaunches, earlyCourant, residentLaunches;
+    explicit StepCounts(const Ctrl& c) : pairLaunches(c.pairLaunches), singleLaunches(c.singleLaunches), earlyCourant(c.earlyCourant), residentLaunches(c.residentLaunches)
+    { std::memcpy(counters, c.counters, sizeof(counters)); }
+};
+
+/* what the parts of one step share: the solver's state, the device view, the plan, the stream and the grids */
+struct DeviceSolver::StepCtx {
+    Impl& I;
+    const DevView& v;
+    const StepPlan P;
+    const hipStream_t st;
+    const bool multi, heatOn;
+    const dim3 grid, block, one, pgrid;
+    dim3 propsGrid, propsHeatGrid, acceptGrid;                          /* water part (water_grids) */
+    ViewKernel sweepFn = nullptr;                                       /* the resident loop's or the paired pass's kernel, where the plan has one */
+    dim3 gSaveWater, gBoundary, gHProps, gHAsm, gHPost, gHSave;         /* heat part (heat_grids) */
+    bool slabFailed = false;       /* a launch or an event call of the slab experiment failed: the batch is not trusted (checked after the enqueue) */
+
+    StepCtx(Impl& impl, const StepPlan& plan, bool multiRank)
+        : I(impl), v(impl.v), P(plan), st(impl.stream), multi(multiRank), heatOn(impl.v.heat.on != 0), grid(impl.v.nb), block(SF3D_BLOCK), one(1), pgrid(impl.pushBlocks ? impl.pushBlocks : 1) {}
+
     /* grids of the register-heavy kernels: exactly as many blocks as are resident at once - equal work per block, no tail
      * round (at 70 VGPRs only 1 792 of 2 048 blocks fit and the remaining 256 ran alone afterwards).  Every kernel walks the
      * chunk list with its own gridDim, and the fused reductions count gridDim partials, so any grid is valid. */
-    auto resident = [&](const void* fn) -> dim3 {
-        const uint32_t nbk = I.resident_blocks(fn);
+    dim3 resident(ViewKernel fn) const
+    {
+        const uint32_t nbk = I.resident_blocks((const void*)fn);
         return dim3(v.nb < nbk ? v.nb : nbk);
-    };
-    if (heatOn && multi) I.useFused = 1;       /* the sharded heat step exists only in the fused-exchange form */
-    const bool fused = !multi && I.useFused;   /* sweep + convergence decision in one launch (single GPU) */
-    const bool fusedMulti = multi && I.useFused; /* + in-kernel halo puts and all-gather (multi GPU) */
-    const bool linealOn = p.lineal && v.cgDiag != nullptr && !multi && I.useFused;     /* the linealia stand-in: device conjugate gradients */
-    /* all iterations of an approximation in ONE launch, the rows resident on chip (sf3d_resident.inc): grids that fit, fused decisions, window exchange */
-    const bool resOn = v.res.on && I.resBlocks != 0 && (fused || (fusedMulti && v.haloDirect && !I.rcclMode)) && !linealOn;
-    if (resOn && !multi) {      /* tests: SF3D_RESIDENT_FAIL_TEST=n makes the resident launches of the n-th computeStep give up, once */
-        static const long failAt = getenv("SF3D_RESIDENT_FAIL_TEST") ? strtol(getenv("SF3D_RESIDENT_FAIL_TEST"), nullptr, 10) : -1;
-        I.v.res.forceTimeout = (failAt >= 0 && (long)I.stepSeqAll == failAt) ? 1u : 0u;
-        ++I.stepSeqAll;
     }
-    const bool pairOn = !resOn && (fused || (fusedMulti && v.haloDirect && v.nBnd != 0)) && I.pairBlocks != 0 && !linealOn;   /* k_sweep_pair instead of k_sweep (on a strip: + k_sweep_bnd) */
-    const dim3 pgrid(I.pushBlocks ? I.pushBlocks : 1);
-    hipStream_t st = I.stream;
-
-    /* mode 2 samples: the sweeps of every 8th computeStep carry HIP events (eager launches); the other
-     * steps replay hipGraphs, so the measurement costs ~1 % instead of ~6 % */
-    const bool timedStep = I.timing == 1 || (I.timing == 2 && (I.stepSeq++ % 8 == 0));
-    /* accepted step: its link flow sums are not added in the step - the step keeps its matrix and a copy of its head in a slot of the rings,
-     * and one pass adds the sums of up to SF3D_LINKS_RING such steps (k_links_flush).  Plain single-GPU path, untimed steps only, so
-     * that the per-kernel event timing of --time-all-kernels sees every kernel of a step inside the step */
-    const bool overlap = I.overlapAccept && !multi && I.ring && !timedStep && I.timing != 1 && v.compatCv == nullptr;   /* (compat: k_compat_rows rewrites what the sums read) */
-    auto timed = [&](int kid, auto launch) {
-        if (!timedStep || (I.timing == 2 && kid != KID_SWEEP && kid != KID_SWEEP_PAIR && kid != KID_SWEEP_RES)) { launch(); return; }
+    void launch(ViewKernel fn, dim3 g) const { launch_view(fn, g, block, 0, st, v); }
+    template <class F> void timed(int kid, F queue)
+    {
+        if (!P.timedStep || (I.timing == 2 && kid != KID_SWEEP && kid != KID_SWEEP_PAIR && kid != KID_SWEEP_RES)) { queue(); return; }
         hipEvent_t a, b;
         if (I.freeEvents.size() >= 2) { a = I.freeEvents.back(); I.freeEvents.pop_back(); b = I.freeEvents.back(); I.freeEvents.pop_back(); }
-        else { hipEventCreate(&a); hipEventCreate(&b); }
-        hipEventRecord(a, st); launch(); hipEventRecord(b, st);
+        else { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
+        (void)hipEventRecord(a, st); queue(); (void)hipEventRecord(b, st);
         I.pending.push_back({a, b, kid});
-    };
+    }
+    void timed_launch(int kid, ViewKernel fn, dim3 g) { timed(kid, [&] { launch(fn, g); }); }
 
-    if (heatOn) {                           /* computeStep head, soilFluxes3D.cpp:1787-1791 */
-        if (v.heat.save == 2) hipLaunchKernelGGL(k_heat_reset_water_fluxes, grid, block, 0, st, v);
-        hipLaunchKernelGGL(k_heat_conductance, grid, block, 0, st, v);
-        for (int t = 0; t < SF3D_FLUX_TYPES; ++t) m.lfluxValid[t] = false;
-    }
-    uint32_t stage = ST_ACCEPT;
-    if (m.water) {
-    {   /* this step assembles into the next slot of the ring (k_step_begin): if the sums of the step that used it are still pending the
-         * ring is full, and everything pending is added first.  So it is before a step that adds its own sums inside the step
-         * (event-timed steps): the sums are added in the order the steps were accepted in. */
-        const uint32_t ringSlots = mirror_.aRing < 2u ? 2u : mirror_.aRing;
-        if (I.pend.n && (!overlap || I.links_pending((mirror_.aBuf + 1u) % ringSlots))) HIP_TRY(I.flush_links());
-    }
+    /* the kernels and grids of the water part; false: the plan names a kernel that was not compiled */
+    bool water_grids()
     {
-    hipLaunchKernelGGL(k_step_begin, one, one, 0, st, v.ctrl, maxTimeStep);
-    stage = ST_APPROX;                      /* k_step_begin opens the first attempt */
-    uint64_t before[8], atStart[8];
-    std::memcpy(before, mirror_.counters, sizeof(before));
-    std::memcpy(atStart, mirror_.counters, sizeof(atStart));
-    int guard = 0;
-    uint64_t pairBefore = mirror_.pairLaunches, singleBefore = mirror_.singleLaunches, earlyBefore = mirror_.earlyCourant, resBefore = mirror_.residentLaunches;
+        propsGrid = resident(k_props<0, false>); propsHeatGrid = resident(k_props<0, true>);
+        acceptGrid = resident(v.ntStream ? k_accept<true> : k_accept<false>);
+        if (P.resOn) sweepFn = res_kernel((int)v.res.K, (int)v.res.NW, multi);
+        else if (P.pairOn) sweepFn = pair_kernel(v.pair.W, v.ntStream != 0, multi, v.pair.records != 0, I.pairMasked);
+        return sweepFn != nullptr || !(P.resOn || P.pairOn);
+    }
+    void heat_grids()
+    {
+        gSaveWater = resident(v.ntStream ? k_heat_save_water<true> : k_heat_save_water<false>); gBoundary = resident(k_heat_boundary);
+        gHProps = resident(k_heat_props); gHAsm = resident(v.ntStream ? k_heat_assemble<true> : k_heat_assemble<false>);
+        gHPost = resident(k_heat_post); gHSave = resident(k_heat_save);
+    }
 
-
-    const dim3 propsGrid = resident((const void*)k_props<0, false>), propsHeatGrid = resident((const void*)k_props<0, true>);
-    const dim3 acceptGrid = v.ntStream ? resident((const void*)k_accept<true>) : resident((const void*)k_accept<false>);
-    /* one approximation's worth of guarded kernels */
-    auto enqueue_props = [&] {
-            if (heatOn && multi) {      /* sharded heat always uses the fused exchange; halo conductivities are recomputed locally */
-                timed(KID_PROPS, [&] { hipLaunchKernelGGL((k_props<2, true>), grid, block, 0, st, v); });
-                hipLaunchKernelGGL(k_halo_copy<0>, pgrid, block, 0, st, v);
-                hipLaunchKernelGGL(k_heat_halo_water, pgrid, block, 0, st, v);
-            }
-            else if (heatOn) timed(KID_PROPS, [&] { hipLaunchKernelGGL((k_props<0, true>), propsHeatGrid, block, 0, st, v); });
-            else if (multi && fusedMulti) { timed(KID_PROPS, [&] { hipLaunchKernelGGL((k_props<2, false>), grid, block, 0, st, v); }); hipLaunchKernelGGL(k_halo_copy<0>, pgrid, block, 0, st, v); }
-            else timed(KID_PROPS, [&] { hipLaunchKernelGGL((k_props<0, false>), propsGrid, block, 0, st, v); });
-            if (multi && !fusedMulti) {
-                hipLaunchKernelGGL(k_push_kf, pgrid, block, 0, st, v);
-                if (I.rcclMode) I.rccl_halo(st, 2);
-                hipLaunchKernelGGL(k_sync_kf, one, block, 0, st, v);
-            }
-    };
-    static const bool asmNtOff = getenv("SF3D_ASM_NT") && getenv("SF3D_ASM_NT")[0] == '0';      /* tuning: cacheable stores of the rows */
-    const bool asmNT = v.ntStream && !asmNtOff;
-    /* early Courant check: queued with the batches of a step while the Courant number the host saw last (end of the step before) is
-     * within reach of the threshold - far below it the two launches would be guarded no-ops in every approximation */
-    const bool probeNow = v.probeMin >= 0. && !heatOn && !multi && !compat && mirror_.courant >= 0.75 * v.probeMin && (mirror_.probeBudget > 0 || v.probeMin == 0.);
+    /* node properties of one approximation */
+    void enqueue_props()
+    {
+        if (heatOn && multi) {      /* sharded heat always uses the fused exchange; halo conductivities are recomputed locally */
+            timed_launch(KID_PROPS, k_props<2, true>, grid);
+            launch(k_halo_copy<0>, pgrid);
+            launch(k_heat_halo_water, pgrid);
+        }
+        else if (heatOn) timed_launch(KID_PROPS, k_props<0, true>, propsHeatGrid);
+        else if (multi && P.fusedMulti) { timed_launch(KID_PROPS, k_props<2, false>, grid); launch(k_halo_copy<0>, pgrid); }
+        else timed_launch(KID_PROPS, k_props<0, false>, propsGrid);
+        if (multi && !P.fusedMulti) {
+            launch(k_push_kf, pgrid);
+            if (I.rcclMode) I.rccl_halo(st, 2);
+            launch(k_sync_kf, one);
+        }
+    }
     /* SF3D_SLAB_OVERLAP=S (experiment, one GPU, no heat): an approximation's node properties and rows queued in S slabs of the chunk
      * list - the rows of slab k (k_assemble: waits for memory at 4 waves per SIMD, VALU half busy) next to the properties of slab
      * k + 1 (k_props: dependent pow chains, a third of the byte roof) on a second stream, both with reduced grids so that their
      * waves share the SIMDs.  What a slab of rows needs of the properties is Impl::propsNeed (sf3d_host_build.inc); the surface rows
      * and the Courant decision go with the last slab.  Same arithmetic per node, a maximum is a maximum: same bits. */
-    if (I.slabs < 0) {
-        const char* e = getenv("SF3D_SLAB_OVERLAP"); I.slabs = e ? atoi(e) : 0; if (I.slabs > 8) I.slabs = 8; if (I.slabs < 2) I.slabs = 0;
-        auto blocks_of = [](const char* e) -> uint32_t { const long n = e ? strtol(e, nullptr, 10) : 512L; return (uint32_t)(n < 1 ? 1 : (n > SF3D_MAX_BLOCKS ? SF3D_MAX_BLOCKS : n)); };      /* (0 or garbage would be a dim3(0) launch) */
-        I.slabPropsBlocks = blocks_of(getenv("SF3D_SLAB_PROPS_BLOCKS"));
-        I.slabAsmBlocks = blocks_of(getenv("SF3D_SLAB_ASM_BLOCKS"));
-        const char* fe = getenv("SF3D_SLAB_FIRST"); I.slabFirst = fe ? atof(fe) : 0.;      /* share of the soil rows in the first slab (0: equal slabs) */
-    }
-    const bool slabOn = I.slabs >= 2 && !multi && !heatOn && I.useFused && !compat && !timedStep && I.timing != 1 && !I.propsNeed.empty()
-                        && v.nList > v.nListSurf + 64u * (uint32_t)I.slabs;
-    if (slabOn && !I.stream3) {
-        HIP_TRY(hipStreamCreateWithFlags(&I.stream3, hipStreamNonBlocking));
-        for (auto& ev : I.evSlab) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
-    bool slabFailed = false;       /* a launch or an event call of the slab experiment failed: the batch is not trusted (checked after the enqueue) */
-    auto enqueue_slabs = [&](bool asmNTnow) {
+    void enqueue_slabs()
+    {
         auto chk = [&](hipError_t e) { if (e != hipSuccess) slabFailed = true; };
-        const int S = I.slabs;
+        const int S = I.sw.slabs;
         const uint32_t soil = v.nList - v.nListSurf;
         uint32_t aEnd[8], pEnd[8];
         for (int k = 0; k < S; ++k) {
             double share = (double)(k + 1) / S;
-            if (I.slabFirst > 0. && I.slabFirst < 1.) share = (k + 1 == S) ? 1. : I.slabFirst + (1. - I.slabFirst) * (double)k / (double)(S - 1);
+            if (I.sw.slabFirst > 0. && I.sw.slabFirst < 1.) share = (k + 1 == S) ? 1. : I.sw.slabFirst + (1. - I.sw.slabFirst) * (double)k / (double)(S - 1);
             aEnd[k] = (k + 1 == S) ? v.nList : v.nListSurf + (uint32_t)(share * soil);
             pEnd[k] = (k + 1 == S) ? v.nList : I.propsNeed[aEnd[k] - 1];
             if (k > 0 && pEnd[k] < pEnd[k - 1]) pEnd[k] = pEnd[k - 1];
@@ -849,12 +840,12 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
         DevView w = v;
         /* properties of slab 0 on the solver's stream, of the others on the second one behind it */
         w.pLo = 0; w.pHi = pEnd[0];
-        hipLaunchKernelGGL((k_props<0, false>), propsGrid, block, 0, st, w); chk(hipGetLastError());
+        launch_view(k_props<0, false>, propsGrid, block, 0, st, w); chk(hipGetLastError());
         chk(hipEventRecord(I.evSlab[0], st));
         chk(hipStreamWaitEvent(I.stream3, I.evSlab[0], 0));
         for (int k = 1; k < S; ++k) {
             w.pLo = pEnd[k - 1]; w.pHi = pEnd[k];
-            if (w.pHi > w.pLo) { hipLaunchKernelGGL((k_props<0, false>), dim3(I.slabPropsBlocks), block, 0, I.stream3, w); chk(hipGetLastError()); }
+            if (w.pHi > w.pLo) { launch_view(k_props<0, false>, dim3(I.sw.slabPropsBlocks), block, 0, I.stream3, w); chk(hipGetLastError()); }
             chk(hipEventRecord(I.evSlab[k], I.stream3));
         }
         /* rows: slab k waits for the properties of slab k; the last one carries the surface rows and the decision */
@@ -863,330 +854,231 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
             const bool last = k + 1 == S;
             if (k > 0) chk(hipStreamWaitEvent(st, I.evSlab[k], 0));
             w.aLo = k == 0 ? v.nListSurf : aEnd[k - 1]; w.aHi = aEnd[k];
-            if (!last) {
-                w.nbSurf = 0; w.nbSoil = I.slabAsmBlocks;
-                if (asmNTnow) hipLaunchKernelGGL((k_assemble<false, true, false>), dim3(w.nbSoil), block, 0, st, w); else hipLaunchKernelGGL((k_assemble<false, false, false>), dim3(w.nbSoil), block, 0, st, w);
-            } else {
-                w.nbSurf = v.nbSurf; w.nbSoil = v.nbSoil;
-                if (asmNTnow) hipLaunchKernelGGL((k_assemble<true, true, false>), dim3(w.nbSurf + w.nbSoil), block, 0, st, w); else hipLaunchKernelGGL((k_assemble<true, false, false>), dim3(w.nbSurf + w.nbSoil), block, 0, st, w);
-            }
+            if (!last) { w.nbSurf = 0; w.nbSoil = I.sw.slabAsmBlocks; }
+            else { w.nbSurf = v.nbSurf; w.nbSoil = v.nbSoil; }
+            launch_view(assemble_kernel(last, P.asmNT, false), dim3(w.nbSurf + w.nbSoil), block, 0, st, w);
         }
-    };
-    auto enqueue_batch = [&](bool withHead, bool withTail, bool skipProps, uint32_t chunk) {
-        if (withHead && slabOn && !skipProps) {
-            if (probeNow) {
-                hipLaunchKernelGGL(k_props_surface, dim3(v.nbSurf), block, 0, st, v);
-                if (asmNT) hipLaunchKernelGGL(k_courant_probe<true>, dim3(v.nbSurf), block, 0, st, v); else hipLaunchKernelGGL(k_courant_probe<false>, dim3(v.nbSurf), block, 0, st, v);
-            }
-            enqueue_slabs(asmNT);
-        } else
+    }
+    /* one approximation's worth of guarded kernels: with its head (node properties, rows, Courant decision), `chunk` sweeps, the
+     * post-solve part; with its tail, restore-best and the flow sums of the accepted step: once per poll group */
+    void enqueue_batch(bool withHead, bool withTail, uint32_t chunk)
+    {
         if (withHead) {
-            if (probeNow) {     /* early Courant check: two small guarded launches (the device looks at the Courant number of the moment) */
-                hipLaunchKernelGGL(k_props_surface, dim3(v.nbSurf), block, 0, st, v);
-                if (asmNT) hipLaunchKernelGGL(k_courant_probe<true>, dim3(v.nbSurf), block, 0, st, v); else hipLaunchKernelGGL(k_courant_probe<false>, dim3(v.nbSurf), block, 0, st, v);
+            if (P.probeNow) {     /* early Courant check: two small guarded launches (the device looks at the Courant number of the moment) */
+                launch(k_props_surface, dim3(v.nbSurf));
+                launch(P.asmNT ? k_courant_probe<true> : k_courant_probe<false>, dim3(v.nbSurf));
             }
-            if (!skipProps) enqueue_props();
-            if (heatOn && I.useFused) timed(KID_ASSEMBLE, [&] { if (asmNT) hipLaunchKernelGGL((k_assemble<true, true, true>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); else hipLaunchKernelGGL((k_assemble<true, false, true>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); });
-            else if (heatOn) { timed(KID_ASSEMBLE, [&] { hipLaunchKernelGGL((k_assemble<false, false, true>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); }); hipLaunchKernelGGL(k_decide_courant, one, block, 0, st, v); }
-            else if (I.useFused) timed(KID_ASSEMBLE, [&] { if (asmNT) hipLaunchKernelGGL((k_assemble<true, true, false>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); else hipLaunchKernelGGL((k_assemble<true, false, false>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); });
+            if (P.slabOn) enqueue_slabs();
             else {
-                timed(KID_ASSEMBLE, [&] { if (asmNT) hipLaunchKernelGGL((k_assemble<false, true, false>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); else hipLaunchKernelGGL((k_assemble<false, false, false>), dim3(v.nbSurf + v.nbSoil), block, 0, st, v); });
-                if (I.rcclMode) { hipLaunchKernelGGL(k_local_reduce, one, block, 0, st, v, 1); I.rccl_gather(st); }
-                hipLaunchKernelGGL(k_decide_courant, one, block, 0, st, v);
+                enqueue_props();
+                timed_launch(KID_ASSEMBLE, assemble_kernel(P.useFused, P.asmNT, heatOn), dim3(v.nbSurf + v.nbSoil));
+                if (!P.useFused) {
+                    if (!heatOn && I.rcclMode) { hipLaunchKernelGGL(k_local_reduce, one, block, 0, st, v, 1); I.rccl_gather(st); }
+                    launch(k_decide_courant, one);
+                }
             }
+            if (P.compat) launch(k_compat_rows, grid);
         }
-        if (withHead && compat) hipLaunchKernelGGL(k_compat_rows, grid, block, 0, st, v);
-        if (linealOn) {     /* conjugate gradients instead of Jacobi sweeps: `chunk` counts Jacobi sweeps, CG needs far fewer iterations */
-            hipLaunchKernelGGL(k_cg_init, grid, block, 0, st, v);
-            for (uint32_t k = 0; k < chunk; ++k) {
-                timed(KID_SWEEP, [&] { hipLaunchKernelGGL(k_cg_matvec, grid, block, 0, st, v); hipLaunchKernelGGL(k_cg_update, grid, block, 0, st, v);
-                                       hipLaunchKernelGGL(k_cg_dir, grid, block, 0, st, v); });
-            }
-            hipLaunchKernelGGL(k_cg_finish, grid, block, 0, st, v);
-        } else
-        if (resOn) timed(KID_SWEEP_RES, [&] { res_launch((int)v.res.K, (int)v.res.NW, multi, I.resBlocks, I.resLds, st, v); });
-        else
-        if (pairOn) {      /* two Jacobi iterations per launch (regular grid, one GPU).  `chunk` = expected iterations + 1: floor(expected / 2)
-                            * pairs, a single sweep when the expectation is odd (122 us instead of a 175 us pair whose second half
-                            * would be thrown away), then one more pair as the margin (a guarded no-op when the expectation holds) */
-            const dim3 pgr(I.pairBlocks), pbl((v.pair.W + 1) * 64);
-            const uint32_t expected = chunk > 1 ? chunk - 1 : 1;
-            static const bool oddSingle = !(getenv("SF3D_PAIR_ODD_SINGLE") && getenv("SF3D_PAIR_ODD_SINGLE")[0] == '0');
-            const uint32_t nPairs = oddSingle ? expected / 2 + 1 : (chunk + 1) / 2, singleAfter = (oddSingle && (expected & 1u)) ? expected / 2 : UINT32_MAX;
-            for (uint32_t k = 0; k < nPairs; ++k) {
-                if (k == singleAfter) timed(KID_SWEEP, [&] {
-                    if (multi) { if (v.ntStream) hipLaunchKernelGGL((k_sweep<2, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_sweep<2, false>), grid, block, 0, st, v); }
-                    else if (v.ntStream) hipLaunchKernelGGL((k_sweep<1, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_sweep<1, false>), grid, block, 0, st, v); });
+        if (P.linealOn) {     /* conjugate gradients instead of Jacobi sweeps: `chunk` counts Jacobi sweeps, CG needs far fewer iterations */
+            launch(k_cg_init, grid);
+            for (uint32_t k = 0; k < chunk; ++k) timed(KID_SWEEP, [&] { launch(k_cg_matvec, grid); launch(k_cg_update, grid); launch(k_cg_dir, grid); });
+            launch(k_cg_finish, grid);
+        }
+        else if (P.resOn) timed(KID_SWEEP_RES, [&] { launch_view(sweepFn, dim3(I.resBlocks), dim3(v.res.NW * 64), I.resLds, st, v); });
+        else if (P.pairOn) {      /* two Jacobi iterations per launch (pair_schedule) */
+            const dim3 pgr(I.pairBlocks), pbl((v.pair.W + 1) * 64), bgr((v.nBnd + SF3D_BLOCK / SF3D_CHUNK - 1) / (SF3D_BLOCK / SF3D_CHUNK));
+            const PairSchedule s = pair_schedule(chunk, I.sw.pairOddSingle);
+            for (uint32_t k = 0; k < s.nPairs; ++k) {
+                if (k == s.singleAfter) timed_launch(KID_SWEEP, sweep_kernel(multi ? 2 : 1, v.ntStream != 0), grid);
                 timed(KID_SWEEP_PAIR, [&] {
-                    if (multi) {      /* a strip: the pass (x' everywhere, x'' away from the neighbours) + the rows next to the neighbours */
-                        if (I.pairMasked) switch (v.pair.W * 2 + (v.ntStream ? 1 : 0)) {
-                            case 12: hipLaunchKernelGGL((k_sweep_pair_masked<6, false, true>), pgr, pbl, 0, st, v); break;
-                            case 13: hipLaunchKernelGGL((k_sweep_pair_masked<6, true, true>), pgr, pbl, 0, st, v); break;
-                            case 16: hipLaunchKernelGGL((k_sweep_pair_masked<8, false, true>), pgr, pbl, 0, st, v); break;
-                            case 17: hipLaunchKernelGGL((k_sweep_pair_masked<8, true, true>), pgr, pbl, 0, st, v); break;
-                            case 20: hipLaunchKernelGGL((k_sweep_pair_masked<10, false, true>), pgr, pbl, 0, st, v); break;
-                            case 21: hipLaunchKernelGGL((k_sweep_pair_masked<10, true, true>), pgr, pbl, 0, st, v); break;
-                            case 28: hipLaunchKernelGGL((k_sweep_pair_masked<14, false, true>), pgr, pbl, 0, st, v); break;
-                            default: hipLaunchKernelGGL((k_sweep_pair_masked<14, true, true>), pgr, pbl, 0, st, v); break;
-                        }
-                        else if (v.pair.records) switch (v.pair.W * 2 + (v.ntStream ? 1 : 0)) {
-                            case 12: hipLaunchKernelGGL((k_sweep_pair<6, false, true, true>), pgr, pbl, 0, st, v); break;
-                            case 13: hipLaunchKernelGGL((k_sweep_pair<6, true, true, true>), pgr, pbl, 0, st, v); break;
-                            case 16: hipLaunchKernelGGL((k_sweep_pair<8, false, true, true>), pgr, pbl, 0, st, v); break;
-                            case 17: hipLaunchKernelGGL((k_sweep_pair<8, true, true, true>), pgr, pbl, 0, st, v); break;
-                            case 20: hipLaunchKernelGGL((k_sweep_pair<10, false, true, true>), pgr, pbl, 0, st, v); break;
-                            case 21: hipLaunchKernelGGL((k_sweep_pair<10, true, true, true>), pgr, pbl, 0, st, v); break;
-                            case 28: hipLaunchKernelGGL((k_sweep_pair<14, false, true, true>), pgr, pbl, 0, st, v); break;
-                            default: hipLaunchKernelGGL((k_sweep_pair<14, true, true, true>), pgr, pbl, 0, st, v); break;
-                        }
-                        else switch (v.pair.W * 2 + (v.ntStream ? 1 : 0)) {
-                            case 12: hipLaunchKernelGGL((k_sweep_pair<6, false, true>), pgr, pbl, 0, st, v); break;
-                            case 13: hipLaunchKernelGGL((k_sweep_pair<6, true, true>), pgr, pbl, 0, st, v); break;
-                            case 16: hipLaunchKernelGGL((k_sweep_pair<8, false, true>), pgr, pbl, 0, st, v); break;
-                            case 17: hipLaunchKernelGGL((k_sweep_pair<8, true, true>), pgr, pbl, 0, st, v); break;
-                            case 20: hipLaunchKernelGGL((k_sweep_pair<10, false, true>), pgr, pbl, 0, st, v); break;
-                            case 21: hipLaunchKernelGGL((k_sweep_pair<10, true, true>), pgr, pbl, 0, st, v); break;
-                            case 28: hipLaunchKernelGGL((k_sweep_pair<14, false, true>), pgr, pbl, 0, st, v); break;
-                            default: hipLaunchKernelGGL((k_sweep_pair<14, true, true>), pgr, pbl, 0, st, v); break;
-                        }
-                        if (v.pair.records) return;      /* record hand-over: every row got both iterations in that launch */
-                        const dim3 bgr((v.nBnd + SF3D_BLOCK / SF3D_CHUNK - 1) / (SF3D_BLOCK / SF3D_CHUNK));
-                        if (v.ntStream) hipLaunchKernelGGL(k_sweep_bnd<true>, bgr, block, 0, st, v); else hipLaunchKernelGGL(k_sweep_bnd<false>, bgr, block, 0, st, v);
-                        return;
-                    }
-                    if (I.pairMasked) {
-                        switch (v.pair.W * 2 + (v.ntStream ? 1 : 0)) {
-                            case 12: hipLaunchKernelGGL((k_sweep_pair_masked<6, false, false>), pgr, pbl, 0, st, v); break;
-                            case 13: hipLaunchKernelGGL((k_sweep_pair_masked<6, true, false>), pgr, pbl, 0, st, v); break;
-                            case 16: hipLaunchKernelGGL((k_sweep_pair_masked<8, false, false>), pgr, pbl, 0, st, v); break;
-                            case 17: hipLaunchKernelGGL((k_sweep_pair_masked<8, true, false>), pgr, pbl, 0, st, v); break;
-                            case 20: hipLaunchKernelGGL((k_sweep_pair_masked<10, false, false>), pgr, pbl, 0, st, v); break;
-                            case 21: hipLaunchKernelGGL((k_sweep_pair_masked<10, true, false>), pgr, pbl, 0, st, v); break;
-                            case 28: hipLaunchKernelGGL((k_sweep_pair_masked<14, false, false>), pgr, pbl, 0, st, v); break;
-                            default: hipLaunchKernelGGL((k_sweep_pair_masked<14, true, false>), pgr, pbl, 0, st, v); break;
-                        }
-                        return;
-                    }
-                    switch (v.pair.W * 2 + (v.ntStream ? 1 : 0)) {
-                        case 12: hipLaunchKernelGGL((k_sweep_pair<6, false, false>), pgr, pbl, 0, st, v); break;
-                        case 13: hipLaunchKernelGGL((k_sweep_pair<6, true, false>), pgr, pbl, 0, st, v); break;
-                        case 16: hipLaunchKernelGGL((k_sweep_pair<8, false, false>), pgr, pbl, 0, st, v); break;
-                        case 17: hipLaunchKernelGGL((k_sweep_pair<8, true, false>), pgr, pbl, 0, st, v); break;
-                        case 20: hipLaunchKernelGGL((k_sweep_pair<10, false, false>), pgr, pbl, 0, st, v); break;
-                        case 21: hipLaunchKernelGGL((k_sweep_pair<10, true, false>), pgr, pbl, 0, st, v); break;
-                        case 28: hipLaunchKernelGGL((k_sweep_pair<14, false, false>), pgr, pbl, 0, st, v); break;
-                        default: hipLaunchKernelGGL((k_sweep_pair<14, true, false>), pgr, pbl, 0, st, v); break;
-                    }
+                    launch_view(sweepFn, pgr, pbl, 0, st, v);
+                    /* a strip: the pass (x' everywhere, x'' away from the neighbours) + the rows next to the neighbours - unless records were handed
+                     * over: every row got both iterations in that launch */
+                    if (multi && !v.pair.records) launch(v.ntStream ? k_sweep_bnd<true> : k_sweep_bnd<false>, bgr);
                 });
             }
-        } else
-        for (uint32_t k = 0; k < chunk; ++k) {
-            if (fused) { timed(KID_SWEEP, [&] { if (v.ntStream) hipLaunchKernelGGL((k_sweep<1, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_sweep<1, false>), grid, block, 0, st, v); }); continue; }
-            if (fusedMulti) { timed(KID_SWEEP, [&] { if (v.ntStream) hipLaunchKernelGGL((k_sweep<2, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_sweep<2, false>), grid, block, 0, st, v); }); continue; }
-            timed(KID_SWEEP, [&] { if (v.ntStream) hipLaunchKernelGGL((k_sweep<0, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_sweep<0, false>), grid, block, 0, st, v); });
-            if (multi) hipLaunchKernelGGL(k_push_x, pgrid, block, 0, st, v);
-            if (I.rcclMode) { I.rccl_halo(st, 1); hipLaunchKernelGGL(k_local_reduce, one, block, 0, st, v, 3); I.rccl_gather(st); }
-            hipLaunchKernelGGL(k_decide_sweep, one, block, 0, st, v);
         }
-        if (I.useFused) {
+        else for (uint32_t k = 0; k < chunk; ++k) {
+            timed_launch(KID_SWEEP, sweep_kernel(P.fused ? 1 : (P.fusedMulti ? 2 : 0), v.ntStream != 0), grid);
+            if (P.useFused) continue;
+            if (multi) launch(k_push_x, pgrid);
+            if (I.rcclMode) { I.rccl_halo(st, 1); hipLaunchKernelGGL(k_local_reduce, one, block, 0, st, v, 3); I.rccl_gather(st); }
+            launch(k_decide_sweep, one);
+        }
+        if (P.useFused) {
             /* (the resident sweep loop does k_post's work in its own launch when the solve ends well - sf3d_resident.inc; k_post follows only as the
-             * guard of the cases it leaves out would: none - a solve that ends badly goes back to ST_APPROX, not to ST_POST) */
-            if (!(resOn && v.res.fusedPost)) timed(KID_POST, [&] { hipLaunchKernelGGL(k_post<true>, grid, block, 0, st, v); });
-            if (multi && v.haloDirect && !(resOn && v.res.fusedPost)) hipLaunchKernelGGL(k_halo_copy<1>, pgrid, block, 0, st, v);      /* (the resident launch with its fused post-solve part stores the halo of its result itself) */
+             * guard of the cases it leaves out would: none - a solve that ends badly goes back to ST_APPROX, not to ST_POST; and with its fused
+             * post-solve part the resident launch stores the halo of its result itself) */
+            if (!P.resFusedPost) timed_launch(KID_POST, k_post<true>, grid);
+            if (multi && v.haloDirect && !P.resFusedPost) launch(k_halo_copy<1>, pgrid);
         }
         else {
-            timed(KID_POST, [&] { hipLaunchKernelGGL(k_post<false>, grid, block, 0, st, v); });
+            timed_launch(KID_POST, k_post<false>, grid);
             if (I.rcclMode) { hipLaunchKernelGGL(k_local_reduce, one, block, 0, st, v, 2); I.rccl_gather(st); }
-            hipLaunchKernelGGL(k_decide_balance, one, block, 0, st, v);
+            launch(k_decide_balance, one);
         }
-        if (withTail) {     /* restore-best and the flow sums of the accepted step: once per poll group */
-            if (heatOn && I.useFused) timed(KID_RESTORE, [&] { hipLaunchKernelGGL((k_restore<true, true>), grid, block, 0, st, v); });
-            else if (I.useFused) timed(KID_RESTORE, [&] { hipLaunchKernelGGL((k_restore<true, false>), grid, block, 0, st, v); });
-            else {
-                timed(KID_RESTORE, [&] { if (heatOn) hipLaunchKernelGGL((k_restore<false, true>), grid, block, 0, st, v); else hipLaunchKernelGGL((k_restore<false, false>), grid, block, 0, st, v); });
+        if (withTail) {
+            timed_launch(KID_RESTORE, P.useFused ? (heatOn ? k_restore<true, true> : k_restore<true, false>) : (heatOn ? k_restore<false, true> : k_restore<false, false>), grid);
+            if (!P.useFused) {
                 if (I.rcclMode) { hipLaunchKernelGGL(k_local_reduce, one, block, 0, st, v, 2); I.rccl_gather(st); }
-                hipLaunchKernelGGL(k_decide_restore, one, block, 0, st, v);
+                launch(k_decide_restore, one);
             }
-            if (overlap) hipLaunchKernelGGL(k_accept_boundary, grid, block, 0, st, v);
-            else timed(KID_ACCEPT, [&] { if (v.ntStream) hipLaunchKernelGGL(k_accept<true>, acceptGrid, block, 0, st, v); else hipLaunchKernelGGL(k_accept<false>, acceptGrid, block, 0, st, v); });
+            if (P.overlap) launch(k_accept_boundary, grid);
+            else timed_launch(KID_ACCEPT, v.ntStream ? k_accept<true> : k_accept<false>, acceptGrid);
         }
-    };
+    }
+    hipError_t launch_batch(bool withHead, bool withTail, uint32_t chunk)
+    {
+        if (!P.replayWater) { enqueue_batch(withHead, withTail, chunk); return hipSuccess; }
+        return I.replay(water_graph_key(P, withHead, withTail, chunk), st, [&] { enqueue_batch(withHead, withTail, chunk); });
+    }
+    /* one poll group of the heat part = `steps` guarded heat steps: boundary, node properties, rows, a run of sweeps, balance, flux bookkeeping */
+    void enqueue_heat(uint32_t steps, uint32_t chunk)
+    {
+        for (uint32_t bq = 0; bq < steps; ++bq) {
+            launch(k_heat_boundary, gBoundary);
+            launch(k_heat_props, gHProps);
+            launch(v.ntStream ? k_heat_assemble<true> : k_heat_assemble<false>, gHAsm);
+            if (v.heat.gs) {
+                for (uint32_t k = 0; k < chunk; ++k) {
+                    launch(k_heat_gs_begin, grid);
+                    for (size_t l = 0; l + 1 < I.gsLevelStart.size(); ++l) {
+                        const uint32_t first = I.gsLevelStart[l], cnt = I.gsLevelStart[l + 1] - first;
+                        if (cnt) hipLaunchKernelGGL(k_heat_gs_level, dim3((cnt + SF3D_BLOCK - 1) / SF3D_BLOCK), block, 0, st, v, first, cnt);
+                    }
+                    hipLaunchKernelGGL(k_heat_gs_decide, one, one, 0, st, v.ctrl);
+                }
+            } else
+            for (uint32_t k = 0; k < chunk; ++k) {
+                if (v.heat.redBlack) { launch(v.ntStream ? k_heat_sweep<0, true> : k_heat_sweep<0, false>, grid); launch(v.ntStream ? k_heat_sweep<1, true> : k_heat_sweep<1, false>, grid); }
+                else launch(k_heat_sweep<-1, false>, grid);
+            }
+            launch(k_heat_post, gHPost);
+            if (v.heat.save != 0) launch(k_heat_save, gHSave);
+        }
+    }
+    hipError_t launch_heat(uint32_t steps, uint32_t chunk)
+    {
+        if (!P.replayHeat) { enqueue_heat(steps, chunk); return hipSuccess; }
+        return I.replay(heat_graph_key(steps, chunk, v.heat.save != 0), st, [&] { enqueue_heat(steps, chunk); });
+    }
+    /* attribute event pairs only to launches that really ran: how many of each kernel ran comes from the device counters (c: now,
+     * before: at the last poll); guarded no-op launches are the shortest of a group */
+    void attribute_events(const Ctrl& c, const StepCounts& before)
+    {
+        uint64_t ran[KID_COUNT];
+        ran[KID_PROPS] = ran[KID_ASSEMBLE] = (c.counters[2] - before.counters[2]) - (c.earlyCourant - before.earlyCourant);      /* (an attempt the early check refused ran neither) */
+        ran[KID_SWEEP] = P.pairOn ? c.singleLaunches - before.singleLaunches : (P.resOn ? 0 : c.counters[3] - before.counters[3]);
+        ran[KID_SWEEP_RES] = c.residentLaunches - before.residentLaunches;
+        ran[KID_SWEEP_PAIR] = c.pairLaunches - before.pairLaunches;
+        ran[KID_POST] = c.counters[7] - before.counters[7];
+        ran[KID_RESTORE] = c.counters[6] - before.counters[6];
+        ran[KID_ACCEPT] = c.counters[1] - before.counters[1];
+        std::vector<float> el[KID_COUNT];
+        for (auto& pr : I.pending) {
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, pr.a, pr.b) == hipSuccess) el[pr.kid].push_back(t);
+            I.freeEvents.push_back(pr.a); I.freeEvents.push_back(pr.b);
+        }
+        I.pending.clear();
+        for (int k = 0; k < KID_COUNT; ++k) {
+            std::sort(el[k].begin(), el[k].end(), [](float x, float y) { return x > y; });
+            for (size_t q = 0; q < el[k].size() && q < ran[k]; ++q) { I.ms[k] += el[k][q]; I.launches[k]++; }
+        }
+    }
+};
 
-    /* Look-ahead: the previous step needed `lastBatches` approximations; queue that many guarded
-     * batches before the first poll (a batch queued in vain costs ~25 no-op launches, a poll costs
-     * a full host round trip while the GPU idles).  After the first poll continue one at a time. */
-    /* The ~25 launches of a batch are replayed from an instantiated hipGraph (one per shape): small
-     * grids are bound by the host's launch rate otherwise.  Event timing needs eager launches. */
-    if (I.useGraphs < 0) { const char* e = getenv("SF3D_GRAPHS"); I.useGraphs = (e && e[0] == '0') ? 0 : 1; }
-    /* how many sweeps to queue for the `index`-th approximation of this step: what the same approximation of the previous step took,
-     * plus one (Ctrl::seqSweeps; a sweep queued in vain is a guarded no-op of ~4 us, one too few costs a poll; sweeps that a later
-     * batch queued simply continue an unfinished approximation); without a record, the last count plus two */
-    auto predicted_sweeps = [&](uint32_t index, bool withHead) -> uint32_t {
-        uint32_t chunk;
-        if (withHead && index < I.predCount && index < 16u) { chunk = I.pred[index] + 1; if (chunk < 2) chunk = 2; }
-        else { chunk = I.lastSweeps + 2; if (chunk < 4) chunk = 4; }
-        if (chunk > 40) chunk = 40;
-        return chunk;
-    };
-    auto launch_batch = [&](bool withHead, bool withTail, bool skipProps, uint32_t chunk) -> hipError_t {
-        if (!I.useGraphs || timedStep || I.rcclMode) { enqueue_batch(withHead, withTail, skipProps, chunk); return hipSuccess; }   /* (RCCL calls are queued eagerly) */
-        if (resOn) chunk = 0;       /* (one launch whatever the number of iterations: one graph shape) */
-        const uint32_t key = ((resOn && v.res.fusedPost) ? 1u << 28 : 0u) | (v.res.forceTimeout ? 1u << 27 : 0u) | (resOn ? 1u << 26 : 0u) | (withHead ? 1u : 0u) | (withTail ? 2u : 0u) | (chunk << 2) | (skipProps ? 1u << 20 : 0u) | (overlap ? 1u << 21 : 0u) | (pairOn ? 1u << 22 : 0u) | (linealOn ? 1u << 23 : 0u) | (probeNow ? 1u << 24 : 0u) | (slabOn ? 1u << 25 : 0u);
-        for (auto& g : I.graphs) if (g.first == key) return hipGraphLaunch(g.second, st);
-        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-        if (e != hipSuccess) return e;
-        enqueue_batch(withHead, withTail, skipProps, chunk);
-        e = hipStreamEndCapture(st, &graph);
-        if (e != hipSuccess) return e;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (e != hipSuccess) return e;
-        I.graphs.push_back({key, exec});
-        return hipGraphLaunch(exec, st);
-    };
-
-    uint32_t look = I.lastBatches < 1 ? 1 : (I.lastBatches > 6 ? 6 : I.lastBatches);
+/* the water part: look-ahead batches (water_look_ahead), then one batch per poll until the step is accepted or fails */
+sf3d_error_t DeviceSolver::step_water(StepCtx& c, double maxTimeStep, uint32_t& stage)
+{
+    Impl& I = c.I; const DevView& v = c.v; const StepPlan& P = c.P; hipStream_t st = c.st;
+    if (!c.water_grids()) { snprintf(err_, sizeof(err_), "no kernel was compiled for the sweep form of this model (%s)", P.resOn ? "resident loop" : "paired pass"); fatal_ = true; return SF3D_SOLVER_ERROR; }
+    {   /* this step assembles into the next slot of the ring (k_step_begin): if the sums of the step that used it are still pending the
+         * ring is full, and everything pending is added first.  So it is before a step that adds its own sums inside the step
+         * (event-timed steps): the sums are added in the order the steps were accepted in. */
+        const uint32_t ringSlots = mirror_.aRing < 2u ? 2u : mirror_.aRing;
+        if (I.pend.n && (!P.overlap || I.links_pending((mirror_.aBuf + 1u) % ringSlots))) HIP_TRY(I.flush_links());
+    }
+    hipLaunchKernelGGL(k_step_begin, c.one, c.one, 0, st, v.ctrl, maxTimeStep);
+    stage = ST_APPROX;                      /* k_step_begin opens the first attempt */
+    StepCounts before(mirror_);
+    const uint64_t approxAtStart = mirror_.counters[2];
+    int guard = 0;
+    if (P.slabOn && !I.stream3) {
+        HIP_TRY(hipStreamCreateWithFlags(&I.stream3, hipStreamNonBlocking));
+        for (auto& ev : I.evSlab) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    uint32_t look = water_look_ahead(I.lastBatches);
     uint32_t batchIndex = 0;
     while (true) {
         RoctxRange pollRange(look > 1 ? "sf3d water: look-ahead batches of approximations + poll" : "sf3d water: one approximation batch + poll");
         for (uint32_t bq = 0; bq < look; ++bq) {
             const bool head = bq > 0 || stage == ST_APPROX;
-            HIP_TRY(launch_batch(head, bq + 1 == look, false, predicted_sweeps(batchIndex, head)));
+            HIP_TRY(c.launch_batch(head, bq + 1 == look, predicted_sweeps(batchIndex, head, I.predCount, I.pred, I.lastSweeps)));
             if (head) ++batchIndex;
         }
         look = 1;
         HIP_TRY(hipGetLastError());
-        if (slabFailed) { I.slabs = 0; snprintf(err_, sizeof(err_), "SF3D_SLAB_OVERLAP: a launch or an event call of the slab experiment failed - its rows may have read stale node properties"); (void)hipStreamSynchronize(st); fatal_ = true; return SF3D_SOLVER_ERROR; }
+        if (c.slabFailed) { I.sw.slabs = 0; snprintf(err_, sizeof(err_), "SF3D_SLAB_OVERLAP: a launch or an event call of the slab experiment failed - its rows may have read stale node properties"); (void)hipStreamSynchronize(st); fatal_ = true; return SF3D_SOLVER_ERROR; }
         HIP_TRY(hipMemcpyAsync(I.hostCtrl, v.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        const Ctrl& c = *I.hostCtrl;
+        const Ctrl& hc = *I.hostCtrl;
+        if (P.timedStep) c.attribute_events(hc, before);
+        before = StepCounts(hc);
 
-        if (timedStep) {
-            /* attribute event pairs only to launches that really ran: how many of each kernel ran
-             * comes from the device counters; guarded no-op launches are the shortest of a group */
-            uint64_t ran[KID_COUNT];
-            ran[KID_PROPS] = ran[KID_ASSEMBLE] = (c.counters[2] - before[2]) - (c.earlyCourant - earlyBefore);      /* (an attempt the early check refused ran neither) */
-            ran[KID_SWEEP] = pairOn ? c.singleLaunches - singleBefore : (resOn ? 0 : c.counters[3] - before[3]);
-            ran[KID_SWEEP_RES] = c.residentLaunches - resBefore;
-            ran[KID_SWEEP_PAIR] = c.pairLaunches - pairBefore;
-            ran[KID_POST] = c.counters[7] - before[7];
-            ran[KID_RESTORE] = c.counters[6] - before[6];
-            ran[KID_ACCEPT] = c.counters[1] - before[1];
-            std::vector<float> el[KID_COUNT];
-            for (auto& pr : I.pending) {
-                float t = 0.f;
-                if (hipEventElapsedTime(&t, pr.a, pr.b) == hipSuccess) el[pr.kid].push_back(t);
-                I.freeEvents.push_back(pr.a); I.freeEvents.push_back(pr.b);
-            }
-            I.pending.clear();
-            for (int k = 0; k < KID_COUNT; ++k) {
-                std::sort(el[k].begin(), el[k].end(), [](float x, float y) { return x > y; });
-                for (size_t q = 0; q < el[k].size() && q < ran[k]; ++q) { I.ms[k] += el[k][q]; I.launches[k]++; }
-            }
-        }
-        std::memcpy(before, c.counters, sizeof(before));
-        pairBefore = c.pairLaunches; singleBefore = c.singleLaunches; earlyBefore = c.earlyCourant; resBefore = c.residentLaunches;
-
-        stage = c.stage;
-        if (stage != ST_SWEEP && c.iter > 0) I.lastSweeps = c.iter;
+        stage = hc.stage;
+        if (stage != ST_SWEEP && hc.iter > 0) I.lastSweeps = hc.iter;
         if (stage == ST_ACCEPT || stage == ST_FAIL) break;   /* ST_ACCEPT: bookkeeping done and k_accept has run */
         if (++guard > 1000000) { snprintf(err_, sizeof(err_), "step state machine did not terminate (stage %u)", stage); return SF3D_SOLVER_ERROR; }
     }
     {   /* approximations this step took (rejected attempts included) = batches the next one will queue up front */
-        const uint64_t used = I.hostCtrl->counters[2] - atStart[2];
+        const uint64_t used = I.hostCtrl->counters[2] - approxAtStart;
         I.lastBatches = used < 1 ? 1u : (uint32_t)used;
         I.predCount = I.hostCtrl->seqCount < 16u ? I.hostCtrl->seqCount : 16u;
         for (uint32_t k = 0; k < I.predCount; ++k) I.pred[k] = I.hostCtrl->seqSweeps[k];
     }
-    }
-    if (overlap && stage == ST_ACCEPT) {      /* what k_links_flush needs of this step: where its matrix and head are, and its dt */
+    if (P.overlap && stage == ST_ACCEPT) {      /* what k_links_flush needs of this step: where its matrix and head are, and its dt */
         const Ctrl& hc = *I.hostCtrl;
         if (I.pend.n >= (uint32_t)SF3D_LINKS_RING) HIP_TRY(I.flush_links());      /* (never: a full ring was emptied before the step) */
         I.pend.slot[I.pend.n] = hc.acceptABuf < (uint32_t)SF3D_LINKS_RING ? hc.acceptABuf : 0u; I.pend.dt[I.pend.n] = hc.acceptDt; ++I.pend.n;
     }
-    }   /* if (m.water) */
+    return SF3D_OK;
+}
 
-    if (heatOn && stage == ST_ACCEPT) {
-        /* heat part of computeStep (soilFluxes3D.cpp:1802-1818): every kernel is guarded by Ctrl::hStage; one batch =
-         * boundary, node properties, rows, a run of sweeps, balance, flux bookkeeping; polled once per batch */
-        hipLaunchKernelGGL(k_heat_begin, one, one, 0, st, v.ctrl, maxTimeStep, m.water ? 1 : 0);
-        const dim3 gSaveWater = v.ntStream ? resident((const void*)k_heat_save_water<true>) : resident((const void*)k_heat_save_water<false>), gBoundary = resident((const void*)k_heat_boundary),
-                   gHProps = resident((const void*)k_heat_props), gHAsm = v.ntStream ? resident((const void*)k_heat_assemble<true>) : resident((const void*)k_heat_assemble<false>),
-                   gHPost = resident((const void*)k_heat_post), gHSave = resident((const void*)k_heat_save);
-        hipLaunchKernelGGL(k_heat_save_water_props, resident((const void*)k_heat_save_water_props), block, 0, st, v);
-        if (v.ntStream) hipLaunchKernelGGL(k_heat_save_water<true>, gSaveWater, block, 0, st, v); else hipLaunchKernelGGL(k_heat_save_water<false>, gSaveWater, block, 0, st, v);
-        int hguard = 0;
-        uint32_t lookH = I.lastHeatSteps < 1 ? 1 : (I.lastHeatSteps > 8 ? 8 : I.lastHeatSteps);
-        if (v.heat.gs) lookH = 1;              /* one launch per dependency level: keep the queue short */
-        if (I.useGraphs < 0) { const char* e = getenv("SF3D_GRAPHS"); I.useGraphs = (e && e[0] == '0') ? 0 : 1; }
-        /* one poll group = lookH guarded heat steps (look-ahead: as many as the last computeStep needed, <= 8), replayed
-         * from an instantiated hipGraph per shape like the water batches */
-        auto enqueue_heat = [&](uint32_t steps, uint32_t chunk) {
-            for (uint32_t bq = 0; bq < steps; ++bq) {
-                hipLaunchKernelGGL(k_heat_boundary, gBoundary, block, 0, st, v);
-                hipLaunchKernelGGL(k_heat_props, gHProps, block, 0, st, v);
-                if (v.ntStream) hipLaunchKernelGGL(k_heat_assemble<true>, gHAsm, block, 0, st, v); else hipLaunchKernelGGL(k_heat_assemble<false>, gHAsm, block, 0, st, v);
-                if (v.heat.gs) {
-                    for (uint32_t k = 0; k < chunk; ++k) {
-                        hipLaunchKernelGGL(k_heat_gs_begin, grid, block, 0, st, v);
-                        for (size_t l = 0; l + 1 < I.gsLevelStart.size(); ++l) {
-                            const uint32_t first = I.gsLevelStart[l], cnt = I.gsLevelStart[l + 1] - first;
-                            if (cnt) hipLaunchKernelGGL(k_heat_gs_level, dim3((cnt + SF3D_BLOCK - 1) / SF3D_BLOCK), block, 0, st, v, first, cnt);
-                        }
-                        hipLaunchKernelGGL(k_heat_gs_decide, one, one, 0, st, v.ctrl);
-                    }
-                } else
-                for (uint32_t k = 0; k < chunk; ++k) {
-                    if (v.heat.redBlack) {
-                        if (v.ntStream) { hipLaunchKernelGGL((k_heat_sweep<0, true>), grid, block, 0, st, v); hipLaunchKernelGGL((k_heat_sweep<1, true>), grid, block, 0, st, v); }
-                        else { hipLaunchKernelGGL((k_heat_sweep<0, false>), grid, block, 0, st, v); hipLaunchKernelGGL((k_heat_sweep<1, false>), grid, block, 0, st, v); }
-                    }
-                    else hipLaunchKernelGGL((k_heat_sweep<-1, false>), grid, block, 0, st, v);
-                }
-                hipLaunchKernelGGL(k_heat_post, gHPost, block, 0, st, v);
-                if (v.heat.save != 0) hipLaunchKernelGGL(k_heat_save, gHSave, block, 0, st, v);
-            }
-        };
-        auto launch_heat = [&](uint32_t steps, uint32_t chunk) -> hipError_t {
-            if (!I.useGraphs || v.heat.gs) { enqueue_heat(steps, chunk); return hipSuccess; }
-            const uint32_t key = 0x80000000u | (chunk << 8) | (steps << 1) | (v.heat.save != 0 ? 1u : 0u);
-            for (auto& g : I.graphs) if (g.first == key) return hipGraphLaunch(g.second, st);
-            hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e != hipSuccess) return e;
-            enqueue_heat(steps, chunk);
-            e = hipStreamEndCapture(st, &graph);
-            if (e != hipSuccess) return e;
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            hipGraphDestroy(graph);
-            if (e != hipSuccess) return e;
-            I.graphs.push_back({key, exec});
-            return hipGraphLaunch(exec, st);
-        };
-        RoctxRange heatRange("sf3d heat part of computeStep");
-        while (true) {
-            RoctxRange heatPoll("sf3d heat: sub-steps + poll");
-            uint32_t chunk = ((I.lastHeatSweeps + 1 + 1) / 2) * 2;      /* one more than the last solve took, even: few graph shapes (a guarded no-op launch costs ~5 us) */
-            if (chunk < 4) chunk = 4;
-            if (chunk > 64) chunk = 64;
-            HIP_TRY(launch_heat(lookH, chunk));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(I.hostCtrl, v.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            const Ctrl& c = *I.hostCtrl;
-            if (c.hSweepsLast > 0) I.lastHeatSweeps = c.hSweepsLast;
-            if (getenv("SF3D_HEAT_DEBUG") && getenv("SF3D_HEAT_DEBUG")[0] == '2') fprintf(stderr, "gpu heatLoop stage %u next dt %g outer %g/%g sweeps %u MBR %.6e storage %.12e sink %.6e courant %.6e\n", c.hStage, c.hDt, c.hOuterDt, c.hOuterSum, c.hSweepsLast, c.heatCur.MBR, c.heatCur.storage, c.heatCur.sinkSource, c.hCourant);
-            if (c.hStage == HS_FINISHED) { I.lastHeatSteps = c.hRows + c.hPad; break; }
-            if (c.hStage == HS_IDLE) { snprintf(err_, sizeof(err_), "heat step did not start (water stage %u)", c.stage); stage = ST_FAIL; fatal_ = true; break; }
-            if (++hguard > 1000000) { snprintf(err_, sizeof(err_), "heat state machine did not terminate (stage %u)", c.hStage); return SF3D_SOLVER_ERROR; }
-        }
-        if (getenv("SF3D_HEAT_DEBUG")) fprintf(stderr, "heat: water dt %g: %u heat steps accepted, %u halved, last dt %g, last sweeps %u, courant %g, MBR %g\n", I.hostCtrl->dtWater, I.hostCtrl->hRows, I.hostCtrl->hPad, I.hostCtrl->hDt, I.hostCtrl->hSweepsLast, I.hostCtrl->hCourant, I.hostCtrl->heatCur.MBR);
-        m.hostStaleHeat = true;
-    } else if (!m.water) {
+/* heat part of computeStep (soilFluxes3D.cpp:1802-1818): every kernel is guarded by Ctrl::hStage; polled once per group of heat steps
+ * (heat_look_ahead), which is replayed from an instantiated hipGraph per shape like the water batches */
+sf3d_error_t DeviceSolver::step_heat(StepCtx& c, HostModel& m, double maxTimeStep, uint32_t& stage)
+{
+    Impl& I = c.I; const DevView& v = c.v; hipStream_t st = c.st;
+    hipLaunchKernelGGL(k_heat_begin, c.one, c.one, 0, st, v.ctrl, maxTimeStep, m.water ? 1 : 0);
+    c.heat_grids();
+    c.launch(k_heat_save_water_props, c.resident(k_heat_save_water_props));
+    c.launch(v.ntStream ? k_heat_save_water<true> : k_heat_save_water<false>, c.gSaveWater);
+    int hguard = 0;
+    const uint32_t lookH = heat_look_ahead(I.lastHeatSteps, v.heat.gs != 0);
+    RoctxRange heatRange("sf3d heat part of computeStep");
+    while (true) {
+        RoctxRange heatPoll("sf3d heat: sub-steps + poll");
+        HIP_TRY(c.launch_heat(lookH, heat_chunk(I.lastHeatSweeps)));
+        HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(I.hostCtrl, v.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        const Ctrl& hc = *I.hostCtrl;
+        if (hc.hSweepsLast > 0) I.lastHeatSweeps = hc.hSweepsLast;
+        if (I.sw.heatDebug == 2) fprintf(stderr, "gpu heatLoop stage %u next dt %g outer %g/%g sweeps %u MBR %.6e storage %.12e sink %.6e courant %.6e\n", hc.hStage, hc.hDt, hc.hOuterDt, hc.hOuterSum, hc.hSweepsLast, hc.heatCur.MBR, hc.heatCur.storage, hc.heatCur.sinkSource, hc.hCourant);
+        if (hc.hStage == HS_FINISHED) { I.lastHeatSteps = hc.hRows + hc.hPad; break; }
+        if (hc.hStage == HS_IDLE) { snprintf(err_, sizeof(err_), "heat step did not start (water stage %u)", hc.stage); stage = ST_FAIL; fatal_ = true; break; }
+        if (++hguard > 1000000) { snprintf(err_, sizeof(err_), "heat state machine did not terminate (stage %u)", hc.hStage); return SF3D_SOLVER_ERROR; }
     }
+    if (I.sw.heatDebug) fprintf(stderr, "heat: water dt %g: %u heat steps accepted, %u halved, last dt %g, last sweeps %u, courant %g, MBR %g\n", I.hostCtrl->dtWater, I.hostCtrl->hRows, I.hostCtrl->hPad, I.hostCtrl->hDt, I.hostCtrl->hSweepsLast, I.hostCtrl->hCourant, I.hostCtrl->heatCur.MBR);
+    m.hostStaleHeat = true;
+    return SF3D_OK;
+}
+
+/* the end of a step: the resident loop's retry, or the control block, the error texts and the result */
+sf3d_error_t DeviceSolver::step_finish(HostModel& m, ParamsHost& p, double maxTimeStep, double* dtOut, uint32_t stage)
+{
+    Impl& I = *impl_; const DevView& v = I.v; hipStream_t st = I.stream;
     if (world_ == 1 && stage == ST_FAIL && I.hostCtrl->barTimeout && !I.hostCtrl->distError && I.resBlocks != 0) {
         /* The resident sweep loop gave up: a block waited seconds for the records of another one - its blocks were not on the device together (a
          * GPU shared with another process's long kernels).  Nothing of the step was accepted: put the control block of the step's start back (mirror_
@@ -1218,3 +1110,44 @@ sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep,
     return (stage == ST_ACCEPT) ? SF3D_OK : SF3D_SOLVER_ERROR;
 }
 
+/* bring the model up to date, plan, water part, heat part, finish */
+sf3d_error_t DeviceSolver::step(HostModel& m, ParamsHost& p, double maxTimeStep, double* dtOut)
+{
+    RoctxRange stepRange("sf3d computeStep");
+    sf3d_error_t e = sync_to_device(m, p);
+    if (e != SF3D_OK) return e;
+    if (world_ > 1 && !connected_) { snprintf(err_, sizeof(err_), "multi-GPU model used before sf3d_dist_connect / sf3d_dist_finalize%s%.150s", distWhy_[0] ? ": " : "", distWhy_); return SF3D_SOLVER_ERROR; }
+    Impl& I = *impl_;
+    StepFacts f;
+    {
+        const DevView& v = I.v; const StepSwitches& sw = I.sw;
+        f.multi = world_ > 1; f.heatOn = v.heat.on != 0; f.useFused = I.useFused != 0;
+        f.lineal = p.lineal; f.haveCg = v.cgDiag != nullptr;
+        f.resAvail = v.res.on && I.resBlocks != 0; f.resFusedPost = v.res.fusedPost != 0;
+        f.haloDirect = v.haloDirect != 0; f.rccl = I.rcclMode; f.nBnd = v.nBnd; f.pairAvail = I.pairBlocks != 0;
+        f.timing = I.timing; f.sampled = I.timing == 2 && (I.stepSeq++ % 8 == 0);
+        f.overlapAccept = I.overlapAccept != 0; f.ring = I.ring != 0; f.compat = v.compatCv != nullptr;
+        f.ntStream = v.ntStream != 0; f.asmNtOff = sw.asmNtOff;
+        f.probeMin = v.probeMin; f.courant = mirror_.courant; f.probeBudget = mirror_.probeBudget;
+        f.slabs = sw.slabs; f.havePropsNeed = !I.propsNeed.empty(); f.nList = v.nList; f.nListSurf = v.nListSurf;
+        f.useGraphs = sw.graphs; f.heatGs = v.heat.gs != 0;
+        f.residentFailAt = sw.residentFailAt; f.residentSteps = I.stepSeqAll;
+    }
+    StepCtx c(I, plan_step(f), f.multi);
+    I.useFused = c.P.useFused ? 1 : 0;
+    if (c.P.countsResidentStep) { I.v.res.forceTimeout = c.P.forceTimeout ? 1u : 0u; ++I.stepSeqAll; }
+
+    if (c.heatOn) {                         /* computeStep head, soilFluxes3D.cpp:1787-1791 */
+        if (c.v.heat.save == 2) c.launch(k_heat_reset_water_fluxes, c.grid);
+        c.launch(k_heat_conductance, c.grid);
+        for (int t = 0; t < SF3D_FLUX_TYPES; ++t) m.lfluxValid[t] = false;
+    }
+    uint32_t stage = ST_ACCEPT;
+    if (m.water) { e = step_water(c, maxTimeStep, stage); if (e != SF3D_OK) return e; }
+    if (c.heatOn && stage == ST_ACCEPT) { e = step_heat(c, m, maxTimeStep, stage); if (e != SF3D_OK) return e; }
+    else if (!m.water) {
+        HIP_TRY(hipMemcpyAsync(I.hostCtrl, c.v.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
+    }
+    return step_finish(m, p, maxTimeStep, dtOut, stage);
+}

@@ -291,6 +291,13 @@ private:
     sf3d_error_t build_dist_window(BuildState& st);
     sf3d_error_t build_resident_plan(const HostModel& m, BuildState& st);
     sf3d_error_t build_heat(HostModel& m, const ParamsHost& p, BuildState& st);
+    /* the parts of step (sf3d_host_step.inc): the water part and the heat part each queue guarded launches and poll the control block
+     * until their state machine ends (`stage`: where the water part ended); step_finish takes the step again where the resident loop gave
+     * up, and otherwise hands the step's results and errors to the caller.  StepCtx is what the parts of one step share */
+    struct StepCtx;
+    sf3d_error_t step_water(StepCtx& c, double maxTimeStep, uint32_t& stage);
+    sf3d_error_t step_heat(StepCtx& c, HostModel& m, double maxTimeStep, uint32_t& stage);
+    sf3d_error_t step_finish(HostModel& m, ParamsHost& p, double maxTimeStep, double* dt, uint32_t stage);
     struct Impl;
     Impl* impl_ = nullptr;
     Ctrl mirror_{};

@@ -298,6 +298,137 @@ static uint32_t best_w(uint32_t NX, uint32_t NY, uint32_t ownRows, bool tryAuto)
     return plan_pair_patches(g, Partition(), 1, 0, 256, 6, tryAuto, 1.9, false, 0).bestW;
 }
 
+/* ---- the step's plan (plan_step and the functions beside it) ---- */
+#include <map>
+#include <tuple>
+
+typedef std::tuple<uint32_t, uint32_t, uint32_t> KeyTuple;
+static KeyTuple key_tuple(const GraphKey& k) { return KeyTuple(k.flags, k.sweeps, k.steps); }
+/* the launches a water batch queues, as far as they can differ within the life of a model (heat, ranks, the decision form, compat rows,
+ * streaming stores and the odd-single rule are fixed with the model): the head part, the form and the number of the sweeps, the post-solve
+ * part, the tail part */
+typedef std::tuple<int, int, uint32_t, uint32_t, int, int> BatchShape;
+static BatchShape batch_shape(const StepPlan& P, bool head, bool tail, uint32_t chunk, bool oddSingle)
+{
+    const int headPart = head ? 1 + (P.probeNow ? 1 : 0) + (P.slabOn ? 2 : 0) : 0, tailPart = tail ? (P.overlap ? 2 : 1) : 0;
+    if (P.linealOn) return BatchShape(headPart, 4, chunk, 0u, 1, tailPart);
+    if (P.resOn) return BatchShape(headPart, 3, P.forceTimeout ? 1u : 0u, 0u, P.resFusedPost ? 0 : 1, tailPart);
+    if (P.pairOn) { const PairSchedule s = pair_schedule(chunk, oddSingle); return BatchShape(headPart, 2, s.nPairs, s.singleAfter, 1, tailPart); }
+    return BatchShape(headPart, 1, chunk, 0u, 1, tailPart);
+}
+typedef std::tuple<bool, bool, bool, bool, bool, bool, bool, bool> PlanShape;      /* what of a plan a water batch's launches depend on */
+
+static unsigned g_seen[12];
+static void check_plan(const StepFacts& f, std::set<PlanShape>& shapes)
+{
+    const StepPlan P = plan_step(f);
+    const bool one = !f.multi;
+    CHECK((int)P.linealOn + (int)P.resOn + (int)P.pairOn <= 1, "two sweep forms at once");
+    CHECK(!(P.linealOn || P.resOn || P.pairOn) || P.useFused, "a sweep form without fused decisions");
+    CHECK(P.useFused == (f.useFused || (f.heatOn && f.multi)), "useFused");
+    CHECK(P.fused == (one && P.useFused) && P.fusedMulti == (f.multi && P.useFused), "fused / fusedMulti");
+    CHECK(!P.linealOn || (one && f.lineal && f.haveCg), "conjugate gradients");
+    CHECK(!(f.multi && (P.resOn || P.pairOn)) || f.haloDirect, "a strip's resident loop or paired pass without the direct halo");
+    CHECK(!(f.multi && P.resOn) || !f.rccl, "the resident loop under RCCL");
+    CHECK(!(f.multi && P.pairOn) || f.nBnd != 0, "a strip's paired pass without boundary chunks");
+    CHECK((!P.resOn || f.resAvail) && (!P.pairOn || f.pairAvail), "a sweep form the model has no grid for");
+    CHECK(P.resFusedPost == (P.resOn && f.resFusedPost), "resFusedPost");
+    if (one && P.useFused && !P.linealOn) CHECK(P.resOn == f.resAvail && P.pairOn == (!f.resAvail && f.pairAvail), "one GPU: the resident loop where it fits, else the paired pass where it has a grid");
+    CHECK(P.linealOn == (f.lineal && f.haveCg && one && P.useFused), "conjugate gradients wherever they are asked for and possible");
+    CHECK(P.timedStep == (f.timing == 1 || (f.timing == 2 && f.sampled)), "timedStep");
+    CHECK(P.overlap == (one && f.ring && f.overlapAccept && !P.timedStep && f.timing != 1 && !f.compat), "overlap");
+    CHECK(!P.slabOn || (one && !f.heatOn && P.useFused && !f.compat && !P.timedStep && f.slabs >= 2 && f.nList > f.nListSurf + 64u * (uint32_t)f.slabs), "slabOn");
+    CHECK(P.slabOn || !(one && !f.heatOn && P.useFused && !f.compat && !P.timedStep && f.slabs >= 2 && f.havePropsNeed && f.nList > f.nListSurf + 64u * (uint32_t)f.slabs), "slabOn off");
+    CHECK(P.probeNow == (!f.heatOn && one && !f.compat && f.probeMin >= 0. && f.courant >= 0.75 * f.probeMin && (f.probeBudget > 0 || f.probeMin == 0.)), "probeNow");
+    CHECK(P.replayWater == (f.useGraphs && !P.timedStep && !f.rccl), "replayWater");
+    CHECK(P.replayHeat == (f.useGraphs && !f.heatGs), "replayHeat");
+    CHECK(P.compat == f.compat && P.asmNT == (f.ntStream && !f.asmNtOff), "compat / asmNT");
+    CHECK(P.countsResidentStep == (P.resOn && one), "countsResidentStep");
+    CHECK(P.forceTimeout == (P.countsResidentStep && f.residentFailAt >= 0 && (long)f.residentSteps == f.residentFailAt), "forceTimeout");
+    const bool flags[12] = {P.linealOn, P.resOn, P.pairOn, P.overlap, P.slabOn, P.probeNow, P.replayWater, P.replayHeat, P.forceTimeout, P.resFusedPost, P.timedStep, P.fusedMulti && P.pairOn};
+    for (int k = 0; k < 12; ++k) g_seen[k] += flags[k];
+    shapes.insert(PlanShape(P.resOn, P.resFusedPost, P.forceTimeout, P.overlap, P.pairOn, P.linealOn, P.probeNow, P.slabOn));
+}
+
+static void check_step_plan()
+{
+    std::set<PlanShape> shapes;
+    for (unsigned bits = 0; bits < (1u << 17); ++bits) {      /* every combination of the boolean facts */
+        StepFacts f;
+        unsigned b = bits;
+        for (bool* q : {&f.multi, &f.heatOn, &f.useFused, &f.lineal, &f.haveCg, &f.resAvail, &f.resFusedPost, &f.haloDirect, &f.rccl, &f.pairAvail, &f.sampled,
+                        &f.overlapAccept, &f.ring, &f.compat, &f.havePropsNeed, &f.useGraphs, &f.heatGs}) { *q = b & 1u; b >>= 1; }
+        f.nBnd = 5; f.probeMin = 0.8; f.courant = 1.; f.probeBudget = 1; f.nListSurf = 10; f.nList = 1000;
+        for (int timing = 0; timing < 3; ++timing) for (int slabs : {0, 2, 8}) for (uint32_t spare : {0u, 1u}) {      /* spare 0: a chunk list too short for the slabs */
+            StepFacts g = f; g.timing = timing; g.slabs = slabs; g.nList = g.nListSurf + 64u * (uint32_t)slabs + spare;
+            check_plan(g, shapes);
+        }
+        for (double probeMin : {-1., 0., 0.8}) for (double side : {-0.01, 0.01}) for (uint32_t budget : {0u, 1u}) {
+            StepFacts g = f; g.probeMin = probeMin; g.courant = 0.75 * probeMin + side; g.probeBudget = budget;
+            check_plan(g, shapes);
+        }
+        for (uint32_t nBnd : {0u, 5u}) for (long failAt : {-1L, 0L, 3L}) for (uint64_t steps : {0ull, 3ull}) {
+            StepFacts g = f; g.nBnd = nBnd; g.residentFailAt = failAt; g.residentSteps = steps;
+            check_plan(g, shapes);
+        }
+    }
+    for (int nt = 0; nt < 2; ++nt) for (int off = 0; off < 2; ++off) { StepFacts f; f.ntStream = nt; f.asmNtOff = off; check_plan(f, shapes); }
+    for (int k = 0; k < 12; ++k) CHECK(g_seen[k] > 0, "flag %d is never set", k);      /* none of the claims above holds because a flag is dead */
+
+    /* graph keys: two batches that queue different launches have different keys, and no water key is a heat key */
+    std::map<KeyTuple, BatchShape> water[2];
+    for (const PlanShape& s : shapes) {
+        StepPlan P = plan_step(StepFacts());
+        std::tie(P.resOn, P.resFusedPost, P.forceTimeout, P.overlap, P.pairOn, P.linealOn, P.probeNow, P.slabOn) = s;
+        for (int odd = 0; odd < 2; ++odd) for (int head = 0; head < 2; ++head) for (int tail = 0; tail < 2; ++tail) for (uint32_t chunk = 0; chunk <= 40; ++chunk) {
+            const KeyTuple k = key_tuple(water_graph_key(P, head, tail, chunk));
+            const BatchShape shape = batch_shape(P, head, tail, chunk, odd);
+            const auto at = water[odd].emplace(k, shape);
+            CHECK(at.second || at.first->second == shape, "two water batches with other launches under one key (flags %x, %u sweeps)", std::get<0>(k), std::get<1>(k));
+        }
+    }
+    CHECK(shapes.size() > 20 && water[0].size() > 1000, "%zu plans, %zu keys", shapes.size(), water[0].size());
+    std::set<KeyTuple> heat;
+    for (uint32_t steps = 1; steps <= 8; ++steps) for (uint32_t chunk = 4; chunk <= 64; ++chunk) for (int save = 0; save < 2; ++save) {
+        const KeyTuple k = key_tuple(heat_graph_key(steps, chunk, save));
+        CHECK(heat.insert(k).second, "two heat groups under one key");
+        CHECK(!water[0].count(k) && !water[1].count(k), "a heat group under a water batch's key");
+        GraphKey a = heat_graph_key(steps, chunk, save), b = a;
+        CHECK(a == b, "a key differs from itself");
+        b.steps ^= 1u; CHECK(!(a == b), "keys with other step counts compare equal");
+    }
+
+    /* the paired pass's schedule */
+    for (uint32_t chunk = 2; chunk <= 40; ++chunk) {
+        const uint32_t expected = chunk - 1;
+        const PairSchedule s = pair_schedule(chunk, true);
+        if (expected & 1u) {
+            CHECK(s.singleAfter < s.nPairs && 2 * s.singleAfter + 1 == expected, "chunk %u: %u pairs and the single sweep are not %u iterations", chunk, s.singleAfter, expected);
+            CHECK(s.nPairs - s.singleAfter == 1, "chunk %u: %u pairs after the single sweep", chunk, s.nPairs - s.singleAfter);
+        }
+        else CHECK(s.singleAfter == UINT32_MAX && 2 * (s.nPairs - 1) == expected, "chunk %u: %u pairs for %u iterations and the margin", chunk, s.nPairs, expected);
+        const PairSchedule p = pair_schedule(chunk, false);
+        CHECK(p.singleAfter == UINT32_MAX && 2 * p.nPairs >= chunk && 2 * p.nPairs <= chunk + 1, "chunk %u: %u pairs", chunk, p.nPairs);
+    }
+    CHECK(pair_schedule(0, true).nPairs == 1 && pair_schedule(1, true).nPairs == 1 && pair_schedule(1, true).singleAfter == 0, "the smallest chunks");
+
+    /* predicted counts and look-ahead depths */
+    const uint32_t edge[] = {0u, 1u, 2u, 3u, 7u, 38u, 39u, 40u, 41u, 62u, 63u, 64u, 1000u, UINT32_MAX - 1, UINT32_MAX};
+    for (uint32_t last : edge) {
+        uint32_t pred[16];
+        for (uint32_t& q : pred) q = last;
+        for (uint32_t count : {0u, 1u, 16u, 40u}) for (uint32_t index : {0u, 1u, 15u, 16u, 100u}) for (int head = 0; head < 2; ++head) {
+            const uint32_t n = predicted_sweeps(index, head, count, pred, last);
+            const bool record = head && index < count && index < 16u;
+            CHECK(n >= (record ? 2u : 4u) && n <= 40u, "predicted_sweeps %u (record %d, last %u)", n, record, last);
+            if (last < 30u) CHECK(n == std::max(last + (record ? 1u : 2u), record ? 2u : 4u), "predicted_sweeps %u after %u", n, last);
+        }
+        const uint32_t h = heat_chunk(last);
+        CHECK(h % 2 == 0 && h >= 4 && h <= 64 && (last >= 63u || h > last || h == 4), "heat chunk %u after %u sweeps", h, last);
+        CHECK(water_look_ahead(last) == std::min(std::max(last, 1u), 6u) && heat_look_ahead(last, false) == std::min(std::max(last, 1u), 8u) && heat_look_ahead(last, true) == 1, "look-ahead after %u", last);
+    }
+}
+
 int main()
 {
     Partition one; one.owner.clear();
@@ -410,5 +541,7 @@ int main()
     CHECK(best_w(512, 512, 512, true) == 10 && best_w(512, 512, 512, false) == 10, "C4: W = %u", best_w(512, 512, 512, true));
     CHECK(best_w(512, 66, 64, true) == 0 && best_w(512, 66, 64, false) == 6, "a strip of C4: W = %u", best_w(512, 66, 64, false));
     printf("ok cost model\n");
+    check_step_plan();
+    printf("ok step plan\n");
     return 0;
 }

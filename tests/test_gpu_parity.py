@@ -267,6 +267,44 @@ def test_random_irregular_models_with_every_fast_path_forced(product, oracle, se
     oracle.lib.sf3d_clean(); product.lib.sf3d_clean()
 
 
+def test_every_entry_of_the_paired_pass_kernel_table_gives_the_bits_of_single_sweeps(product):
+    """The step driver picks the paired pass's kernel from a table generated over the patch heights (pair_kernel, sf3d_host_build.inc):
+    every single-GPU entry - W = 6, 8, 10, 14 x streaming stores off / on x k_sweep_pair / k_sweep_pair_masked - on one small box, each a
+    model of its own with SF3D_PAIR_SWEEP=1.  A 30 mm hour capped at 40 steps under sf3d_kernel_timing(2): the sampled steps launch
+    eagerly with events, the others replay graphs.  H, Se, every accepted dt and the work counters must be the bits of the same hour
+    with SF3D_PAIR_SWEEP=0, and the pass must really have run in all sixteen.
+    The box is 64 x 14 x 3: 14 rows are the fewest at which plan_pair_patches accepts W = 14 when asked (it wants NY >= W; held on the
+    CPU by calling it for 64 x 13 / 14 / 16 x 3 boxes, full and masked: bestW = 0 at 13 rows, 14 at 14 and 16), and at 14 rows the last
+    patch of every height is a short one (4 + 4 + 4 + 2, 6 + 6 + 2, 8 + 6, 12 + 2 owned rows)."""
+    from tests.scenarios import env
+    m = cm.catchment_model(64, 14, 3)
+
+    def hour(**switches):
+        with env(**switches):
+            product.check(product.lib.sf3d_reset_solver_state(), "reset")
+            cm.build(product, m, threads=4)
+            product.check(product.lib.sf3d_kernel_timing(2), "timing")
+            _, dts = cm.run_hour(product, m, 30.0, max_steps=40)
+            stats = product.kernel_stats()
+            product.lib.sf3d_kernel_timing(0)
+            out = (np.array(dts), cm.snapshot(product, m), product.counters(), stats)
+            product.lib.sf3d_clean()
+        return out
+
+    rd, rs, rc, rstats = hour(SF3D_PAIR_SWEEP="0")
+    assert len(rd) == 40 or rd.sum() >= 3600.0
+    assert rstats["k_sweep_pair"][0] == 0, rstats
+    for W in (6, 8, 10, 14):
+        for nt in ("0", "1"):
+            for masked in (False, True):
+                mode = dict(SF3D_PAIR_SWEEP="1", SF3D_PAIR_W=str(W), SF3D_NT_STREAM=nt, **({"SF3D_PAIR_FORCE_MASKED": "1"} if masked else {}))
+                gd, gs, gc, stats = hour(**mode)
+                assert stats["k_sweep_pair"][0] > 0, (mode, stats)          # no falling back to single sweeps
+                assert np.array_equal(gd, rd), mode
+                assert np.array_equal(gs["H"], rs["H"]) and np.array_equal(gs["Se"], rs["Se"]), mode
+                assert gc == rc, (mode, gc, rc)
+
+
 def test_sf3d_devices_picks_the_gpu_of_an_unmodified_caller():
     """SF3D_DEVICES: which GPU a caller that never calls sf3d_set_device runs on - entry LOCAL_RANK of the list; a device
     that does not exist is a SolverError at the first device call, not a silent device 0"""

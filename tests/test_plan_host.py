@@ -29,7 +29,7 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
-GROUPS = ["box 64 x 6 x 2", "refusal", "neither", "box 128 x 8 x 3", "box 192 x 6 x 2", "masked 70 x 7", "cost model"]
+GROUPS = ["box 64 x 6 x 2", "refusal", "neither", "box 128 x 8 x 3", "box 192 x 6 x 2", "masked 70 x 7", "cost model", "step plan"]
 
 
 def build_host(directory, sanitize=False):
