@@ -375,6 +375,7 @@ void sinkClear();                               /* sf3d_sink_api.inc: the sink m
 void meteoClear();                              /* sf3d_meteo_api.inc: the meteo maps, as the root maps */
 void rootClear();                               /* sf3d_root_api.inc: the root maps and the density table, as the crop maps */
 void cropClear();                               /* sf3d_crop_api.inc: the ET0 / crop maps, as the snow maps */
+void hourClear();                               /* sf3d_hour_api.inc: the partial sums of the hour's totals */
 void snowClear();                               /* sf3d_snow_api.inc: the snow maps belong to the raster - sf3d_clean frees them, sf3d_initialize keeps them */
 
 /* the model's part of sf3d_clean */
@@ -396,6 +397,7 @@ const char* sf3d_backend_name(void) { return "hip"; }
 
 sf3d_error_t sf3d_clean(void)                                       /* soilFluxes3D.cpp:218-304 */
 {
+    hourClear();
     snowClear();
     cropClear();
     rootClear();
@@ -1192,3 +1194,4 @@ sf3d_error_t sf3d_device_pow(uint32_t count, const double* x, const double* y, d
 #include "sf3d_sink_api.inc"
 #include "sf3d_rad_api.inc"
 #include "sf3d_transmissivity_api.inc"
+#include "sf3d_hour_api.inc"

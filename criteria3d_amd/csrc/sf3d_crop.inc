@@ -239,14 +239,23 @@ sf3d_error_t DeviceSolver::crop_hour(const float* const in[5], float clearSky, f
     RASTER_TRY(hipSetDevice(I.device));
     if (in)
         for (int k = 0; k < 5; ++k) RASTER_TRY(hipMemcpyAsync(K.base + (size_t)(CROP_MAP_IN + k) * n, in[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
+    const float* d[5];
+    for (int k = 0; k < 5; ++k) d[k] = in ? K.base + (size_t)(CROP_MAP_IN + k) * n : snow_hour_input(I.snow, k);      /* null: the maps the last snow hour read */
+    return crop_launch(d, clearSky, flag, mine);
+}
+
+/* the hour on five input maps that are on the device: slots of this block, the snow hour's inputs (crop_hour) or maps of the meteo and
+ * radiation blocks (hour_et0, sf3d_hour.inc) */
+sf3d_error_t DeviceSolver::crop_launch(const float* const in[5], float clearSky, float flag, const uint8_t* mine)
+{
+    CropCache& K = impl_->crop;
     CropView v{};
-    const sf3d_error_t e = raster_mask(mine, n, &v.mine);
+    const sf3d_error_t e = raster_mask(mine, K.nCells, &v.mine);
     if (e != SF3D_OK) return e;
     crop_view(v, K, flag);
-    if (!in)                                    /* the maps sf3d_snow_compute_hour uploaded */
-        for (int k = 0; k < 5; ++k) v.in[k] = snow_hour_input(I.snow, k);
+    for (int k = 0; k < 5; ++k) v.in[k] = in[k];
     v.clearSky = clearSky;
-    return raster_launch(k_et0_hour, n, v, K.lastMs[0]);
+    return raster_launch(k_et0_hour, K.nCells, v, K.lastMs[0]);
 }
 
 sf3d_error_t DeviceSolver::crop_day(int dateDoy, int currentDoy, double latitude, float flag, const uint8_t* mine)

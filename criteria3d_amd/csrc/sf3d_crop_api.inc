@@ -86,7 +86,8 @@ sf3d_error_t sf3d_crop_compute_hour(uint32_t nrCells, const float* airTemperatur
     int given = 0;
     for (int k = 0; k < 5; ++k) given += in[k] ? 1 : 0;
     if (given != 0 && given != 5) return SF3D_PARAMETER_ERROR;
-    if (given == 0 && !(rasterFeeds(SN, CR.nRows, CR.nCols) && dev().snow_hour_done(nrCells))) return SF3D_PARAMETER_ERROR;
+    /* (after sf3d_hour_snow the snow hour's inputs are maps of the meteo and radiation blocks: they are gone once one of those is freed) */
+    if (given == 0 && !(rasterFeeds(SN, CR.nRows, CR.nCols) && dev().snow_inputs_held(nrCells))) return SF3D_PARAMETER_ERROR;
     return rasterFail("crop compute hour", dev().crop_hour(given ? in : nullptr, clearSkyTransmissivity, CR.flag, mapsOwnedCells(nrCells)));
 }
 

@@ -641,6 +641,7 @@ struct SinkCall {       /* what sf3d_sink_compute_hour hands to DeviceSolver::si
     const double* crackMaxDepth;        /* soil cracking (sf3d_sink_set_cracking): host tables per soil, null = off */
     const int32_t* crackLastLayer;
     uint64_t crackVer;                  /* changes with every sf3d_sink_set_cracking */
+    bool liquidFromMeteo;               /* sf3d_hour_sinks without a snow hour: a null `liquid` is the meteo block's precipitation map */
 };
 /* the per-cell block of the sink maps: two double maps, then seven maps of 4-byte values */
 enum { SINK_MAP_EVAPORATION = 0, SINK_MAP_TRANSPIRATION = 1, SINK_MAP_DEM = 2, SINK_MAP_ET0 = 3, SINK_MAP_LAI = 4, SINK_MAP_DD = 5, SINK_MAP_LIQUID = 6,
@@ -729,6 +730,48 @@ struct TrCall {         /* what the entry points hand to DeviceSolver::tr_run: h
     uint32_t nPoints;
     int32_t nSlots, mode;
     float clearSky;
+};
+
+/* ---- the hour, device to device (sf3d_hour.inc, include/sf3d_hour.h): one thread per raster cell ---- */
+struct HourRelhumView { /* k_hour_relhum: the meteo block's maps */
+    const float* airT;
+    const float* dewT;
+    float* out;                         /* the relative humidity map */
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    uint32_t nCells;
+    float flag;
+};
+#define HOUR_TOTALS 3                   /* precipitation, evaporation, transpiration */
+struct HourTotalsView { /* k_hour_totals; pass 0: the cells' terms -> one partial per block and total; pass 1: one block adds the partials by index */
+    const int32_t* col;                 /* the surface row of the column table */
+    const float* liquid;                /* the liquid water map the last sink hour read */
+    const double* actual;               /* the sink block's actual evaporation [nCells], then transpiration [nCells] */
+    const float* dem;                   /* the sink block's DEM */
+    const uint8_t* mine;
+    double* partials;                   /* [HOUR_TOTALS][nBlocks] */
+    double* totals;                     /* [HOUR_TOTALS] */
+    double area;
+    uint32_t nCells, nBlocks, pass;
+    float flag;
+};
+struct HourPondUnitDev { double maximumPond, laiMax; int32_t isCrop, pad; };      /* landUnitList[u].pond, cropList[u].LAImax, isCrop(u) */
+struct HourPondView {   /* k_hour_pond */
+    const int32_t* col;                 /* the surface row of the column table */
+    const double* tanSlope;             /* tan(slopeDegree * DEG_TO_RAD), the host's */
+    const int32_t* unit;                /* the land unit, -1: none, or no slope */
+    const float* lai;                   /* the crop block's LAI map; null without computeCrop */
+    const HourPondUnitDev* units;
+    float* out;                         /* the day's pond per cell, -9999 where the reference leaves the node's pond alone */
+    const uint8_t* mine;
+    uint32_t nCells;
+    float laiFlag;
+};
+struct HourPondSetup {  /* what sf3d_hour_set_ponds keeps for DeviceSolver::hour_pond: host pointers */
+    const double* tanSlope;
+    const int32_t* unit;
+    const HourPondUnitDev* units;
+    uint32_t nCells, nUnits;
+    uint64_t ver;                       /* changes with every sf3d_hour_set_ponds */
 };
 
 /* kernels instrumented by sf3d_kernel_timing (ids index the arrays in the solver) */

@@ -69,7 +69,16 @@ struct MapsCache {
 };
 
 /* hourly snow model (sf3d_snow.inc): the maps of include/sf3d_snow.h; they belong to the raster and stay when the model is released */
-struct SnowCache { float* base = nullptr; uint32_t nCells = 0; double lastMs = 0.; bool hourDone = false; };
+struct SnowCache {
+    float* base = nullptr; uint32_t nCells = 0; double lastMs = 0.; bool hourDone = false;
+    /* the eight input maps the last hour read (snow_hour_input): slots of this block after a host-fed hour, the meteo and radiation blocks'
+     * maps after sf3d_hour_snow (`feeds`: the FEED_* blocks they lie in; inputsHeld goes when one of those is freed) */
+    const float* in[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int feeds = 0;
+    bool inputsHeld = false;
+};
+/* the blocks another block may hold pointers into (DeviceSolver::raster_unbind, sf3d_hour.inc) */
+enum { FEED_METEO = 1, FEED_RAD = 2, FEED_SNOW = 4 };
 /* hourly ET0 and daily crop maps (sf3d_crop.inc): the maps of include/sf3d_crop.h and the crop table; as the snow maps, they belong to the raster */
 struct CropCache { float* base = nullptr; CropUnitDev* units = nullptr; uint32_t nCells = 0, nUnits = 0; double lastMs[2] = {0., 0.}; };
 
@@ -104,6 +113,9 @@ struct RadCache {
     double xll = 0., yll = 0., cellSize = 0.;
     float flag = -9999.f, demMax = -9999.f;
     double lastMs = 0.;
+    bool hourDone = false;              /* an hour has written the outputs (rad_hour_done) */
+    const float* trRead = nullptr;      /* the transmissivity map the last hour read: this block's copy or the meteo block's map (null once that is freed) */
+    bool trFromMeteo = false;
     /* station transmissivity (sf3d_transmissivity.inc): the inputs, evaluations and results of the last call, in one block that grows */
     char* tr = nullptr;
     size_t trCap = 0, trOff[3] = {0, 0, 0};     /* trOff: global, elevationRefr, written */
@@ -130,6 +142,18 @@ struct SinkCache {
     uint64_t crackVer = 0;              /* the sf3d_sink_set_cracking the tables in `crack` were uploaded from */
     bool crackComputed = false;         /* the last hour ran k_sink_hour_crack */
     std::vector<double> layerDepth;
+    const float* liquidRead = nullptr;  /* the liquid water map the last hour read: this block's, the snow block's or the meteo block's (null once that is freed) */
+    int liquidFrom = 0;                 /* FEED_SNOW / FEED_METEO, 0: this block's */
+};
+
+/* the hour, device to device (sf3d_hour.inc): the block partials and the three totals of k_hour_totals, in one block that grows, and the
+ * static maps of the day's ponds */
+struct HourCache {
+    double* sums = nullptr; size_t sumsCap = 0;
+    char* pond = nullptr;               /* the day's ponds: tanSlope [nCells] (doubles), the unit table, then unit [nCells] and the pond map [nCells] (4 bytes) */
+    uint32_t pondCells = 0;
+    uint64_t pondVer = 0;               /* the sf3d_hour_set_ponds `pond` was uploaded from (0: none) */
+    double lastMs[3] = {0., 0., 0.};    /* k_hour_relhum, k_hour_totals, k_hour_pond */
 };
 
 /* the SF3D_* switches the step driver acts on (sf3d_host_step.inc): read by read_step_switches when a model is built, back to these
@@ -298,6 +322,7 @@ struct DeviceSolver::Impl {
     MeteoCache meteo;
     SinkCache sink;
     RadCache rad;
+    HourCache hour;
 };
 
 /* on failure: message, then drain the solver stream (async copies from pageable host vectors may still be in flight and the

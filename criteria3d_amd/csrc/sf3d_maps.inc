@@ -246,7 +246,10 @@ sf3d_error_t DeviceSolver::output_map(HostModel& m, const ParamsHost& p, const M
  * (the output maps and the sinks).  What one block reads from another it asks of that block's accessors, which stand in the owning
  * block's file beside the predicate that makes the read safe: snow_hour_done / snow_hour_input, snow_liquid_water (sf3d_snow.inc),
  * crop_allocated / crop_et0, crop_lai, crop_degree_days (sf3d_crop.inc), root_computed (sf3d_root.inc; its maps go to the sink kernel
- * as one block), meteo_produced / meteo_map (sf3d_meteo.inc: the transmissivity map the radiation block reads). */
+ * as one block), meteo_produced / meteo_map (sf3d_meteo.inc: the transmissivity map the radiation block reads; the four maps of the hour:
+ * sf3d_hour.inc), rad_hour_done / rad_global, rad_beam, rad_transmissivity_read (sf3d_rad.inc).  A block that frees its maps says so
+ * (raster_unbind, sf3d_hour.inc): what another block had recorded of them - the snow hour's inputs, the transmissivity map the radiation
+ * hour read, the liquid water the sink hour read - is forgotten, and the next reader is refused instead of launched on a freed pointer. */
 
 /* a block of per-cell maps whose first two are 8-byte maps and the others 4-byte ones (RootCache::cells, SinkCache::cells) */
 static void* raster_cell_map(char* cells, size_t nCells, int map)

@@ -229,6 +229,7 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_meteo_idw(MeteoView v)
 sf3d_error_t DeviceSolver::meteo_free()
 {
     if (!impl_) return SF3D_OK;
+    raster_unbind(FEED_METEO);
     raster_release({impl_->meteo.base, impl_->meteo.stations});
     impl_->meteo = MeteoCache();
     return SF3D_OK;
@@ -295,6 +296,15 @@ sf3d_error_t DeviceSolver::meteo_download(int var, float* dst)
 {
     const MeteoCache& K = impl_->meteo;
     return raster_download(dst, K.base + (1 + (size_t)K.nProxies + (size_t)var) * K.nCells, (size_t)K.nCells * sizeof(float));
+}
+
+/* a map of the caller's in the place of an interpolation */
+sf3d_error_t DeviceSolver::meteo_upload(int var, const float* src)
+{
+    MeteoCache& K = impl_->meteo;
+    const sf3d_error_t e = raster_upload(K.base + (1 + (size_t)K.nProxies + (size_t)var) * K.nCells, src, (size_t)K.nCells * sizeof(float));
+    if (e == SF3D_OK) K.produced[var] = true;
+    return e;
 }
 
 /* what the radiation block reads of this one: the map of a variable, safe once meteo_produced says the block is on the caller's raster

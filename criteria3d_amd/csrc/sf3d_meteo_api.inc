@@ -72,6 +72,13 @@ sf3d_error_t sf3d_meteo_get_map(int variable, uint32_t nrCells, float* map)
     return rasterFail("meteo get map", dev().meteo_download(variable, map));
 }
 
+sf3d_error_t sf3d_meteo_set_map(int variable, uint32_t nrCells, const float* map)
+{
+    if (!MT.on) return SF3D_MEMORY_ERROR;
+    if (variable < 0 || variable >= SF3D_METEO_VARIABLES || !map || nrCells != MT.nRows * MT.nCols) return SF3D_PARAMETER_ERROR;
+    return rasterFail("meteo set map", dev().meteo_upload(variable, map));
+}
+
 double sf3d_meteo_kernel_ms(void) { return dev().meteo_kernel_ms(); }
 
 sf3d_error_t sf3d_meteo_clean(void)

@@ -209,6 +209,7 @@ public:
     sf3d_error_t snow_download(int map, float* dst);
     sf3d_error_t snow_hour(const float* const in[8], const SnowParamsDev& p, float flag, const uint8_t* mine);
     bool snow_hour_done(uint32_t nCells) const;
+    bool snow_inputs_held(uint32_t nCells) const;      /* ... and the input maps of that hour are still where it read them */
     sf3d_error_t snow_free();
     double snow_kernel_ms() const;
     /* hourly ET0 / daily crop maps (sf3d_crop.inc): CROP_MAPS maps of nCells on the device and the crop table, independent of the node
@@ -239,6 +240,7 @@ public:
                              const float* const* proxyMaps);
     sf3d_error_t meteo_interpolate(const MeteoCall& call, const uint8_t* mine, float* out);
     sf3d_error_t meteo_download(int var, float* dst);
+    sf3d_error_t meteo_upload(int var, const float* src);      /* the caller's map in the place of an interpolation: meteo_produced holds afterwards */
     sf3d_error_t meteo_free();
     double meteo_kernel_ms() const;
     bool meteo_produced(int var, uint32_t nRows, uint32_t nCols) const;   /* the block is on this raster and holds an interpolation of `var` */
@@ -247,6 +249,7 @@ public:
     sf3d_error_t rad_alloc(const RadSetup& setup);
     sf3d_error_t rad_hour(const RadHourDev& hour, const float* transmissivity, const uint8_t* mine);
     sf3d_error_t rad_download(int which, float* dst);
+    bool rad_hour_done(uint32_t nRows, uint32_t nCols) const;    /* an hour has run on this raster and the transmissivity map it read is still there */
     sf3d_error_t rad_free();
     double rad_kernel_ms() const;
     sf3d_error_t rad_trig(int which, uint32_t n, const double* x, const double* y, double* out);     /* test hook: the device build of sf3d_trig.inc */
@@ -270,6 +273,18 @@ public:
     bool sink_computed() const;
     sf3d_error_t sink_free();
     double sink_kernel_ms() const;
+    /* the hour, device to device (sf3d_hour.inc, include/sf3d_hour.h): the snow and ET0 kernels on the maps the meteo and radiation blocks
+     * hold (the caller has asked meteo_produced and rad_hour_done), the relative humidity map from the dew point map, the hour's three
+     * totals, the day's pond per cell (computeCrop: with the crop block's LAI map; the caller has asked crop_allocated).  which of
+     * hour_kernel_ms: 0 k_hour_relhum, 1 k_hour_totals, 2 k_hour_pond */
+    sf3d_error_t hour_snow(const float* surfaceWater, const SnowParamsDev& p, float flag, const uint8_t* mine);
+    sf3d_error_t hour_et0(float clearSky, float flag, const uint8_t* mine);
+    sf3d_error_t hour_relhum(const uint8_t* mine, float* out);
+    bool hour_totals_ready(uint32_t nCells) const;     /* a sink hour has run on nCells cells and the liquid water map it read is still there */
+    sf3d_error_t hour_totals(HostModel& m, const ParamsHost& p, const MapsInput& in, const uint8_t* mine, double totals[3]);
+    sf3d_error_t hour_pond(HostModel& m, const ParamsHost& p, const MapsInput& in, const HourPondSetup& setup, bool computeCrop, float laiFlag, const uint8_t* mine, float* out);
+    sf3d_error_t hour_free();
+    double hour_kernel_ms(int which) const;
 
 private:
     DeviceSolver() = default;
@@ -284,6 +299,10 @@ private:
     template <class Arg> sf3d_error_t raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms);
     sf3d_error_t raster_tables(char*& tables, size_t* off, int count, const size_t* bytes, const void* const* src, const size_t* srcBytes);
     void raster_release(std::initializer_list<void*> blocks);
+    /* block `who` (FEED_*) is about to free its maps: what other blocks hold of them is forgotten, so their next reader is refused */
+    void raster_unbind(int who);
+    sf3d_error_t snow_launch(const float* const in[8], int feeds, const SnowParamsDev& p, float flag, const uint8_t* mine);
+    sf3d_error_t crop_launch(const float* const in[5], float clearSky, float flag, const uint8_t* mine);
     /* the three largest device-side stages of the build block of sync_to_device (sf3d_host_build.inc): the multi-GPU window set-up, the
      * resident loop's plan with its occupancy queries, the coupled-heat arrays with their colouring and Gauss-Seidel levels.  BuildState
      * is what one build's stages share */

@@ -416,6 +416,7 @@ sf3d_error_t DeviceSolver::rad_trig(int which, uint32_t n, const double* x, cons
 sf3d_error_t DeviceSolver::rad_free()
 {
     if (!impl_) return SF3D_OK;
+    raster_unbind(FEED_RAD);
     raster_release({impl_->rad.base, impl_->rad.tr});
     impl_->rad = RadCache();
     return SF3D_OK;
@@ -473,8 +474,25 @@ sf3d_error_t DeviceSolver::rad_hour(const RadHourDev& hour, const float* transmi
     v.grid.nRows = (int32_t)K.nRows; v.grid.nCols = (int32_t)K.nCols; v.grid.flag = K.flag; v.grid.demMax = K.demMax;
     v.hour = hour;
     v.nCells = K.nCells;
-    return raster_launch(k_rad_hour, n, v, K.lastMs);
+    const sf3d_error_t el = raster_launch(k_rad_hour, n, v, K.lastMs);
+    if (el == SF3D_OK) { K.hourDone = true; K.trRead = v.transmissivity; K.trFromMeteo = !transmissivity; }
+    return el;
 }
+
+/* ---- what the other blocks read from this one (sf3d_hour.inc), once rad_hour_done says an hour has run on their raster and the
+ * transmissivity map it read is still there: the global and beam maps, and that transmissivity map - this block's copy, or the meteo
+ * block's map when the hour was called with none */
+bool DeviceSolver::rad_hour_done(uint32_t nRows, uint32_t nCols) const
+{
+    return impl_ && impl_->rad.base && impl_->rad.hourDone && impl_->rad.trRead && impl_->rad.nRows == nRows && impl_->rad.nCols == nCols;
+}
+static const float* rad_output(const RadCache& K, int which)
+{
+    return (const float*)((const double*)K.base + (size_t)RAD_DOUBLE_MAPS * K.nCells) + (size_t)(RAD_MAP_OUT + which) * K.nCells;
+}
+static const float* rad_global(const RadCache& K) { return rad_output(K, 1); }              /* SF3D_RAD_GLOBAL */
+static const float* rad_beam(const RadCache& K) { return rad_output(K, 2); }                /* SF3D_RAD_BEAM */
+static const float* rad_transmissivity_read(const RadCache& K) { return K.trRead; }
 
 sf3d_error_t DeviceSolver::rad_download(int which, float* dst)
 {

@@ -350,7 +350,9 @@ sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const Ma
     v.et0 = call.et0 ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_ET0) : crop_et0(I.crop);
     v.lai = call.lai ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_LAI) : crop_lai(I.crop);
     v.dd = call.dd ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_DD) : crop_degree_days(I.crop);
-    v.liquid = call.liquid ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_LIQUID) : snow_liquid_water(I.snow);
+    v.liquid = call.liquid ? (const float*)raster_cell_map(K.cells, n, SINK_MAP_LIQUID)
+               : call.liquidFromMeteo ? meteo_map(I.meteo, METEO_PRECIPITATION) : snow_liquid_water(I.snow);
+    K.liquidRead = nullptr; K.liquidFrom = 0;
     v.rootCells = R.cells;
     v.rootTable = (const double*)(R.tables + R.off[ROOT_T_TABLE]); v.rootRows = R.nRows;
     v.units = (const SinkUnitDev*)(K.tables + K.off[SINK_T_UNITS]);
@@ -389,7 +391,10 @@ sf3d_error_t DeviceSolver::sink_hour(HostModel& m, const ParamsHost& p, const Ma
         e = raster_launch(k_sink_hour_crack, n, k, K.lastMs);
         if (e == SF3D_OK) K.crackComputed = true;
     }
-    if (e == SF3D_OK) K.computed = true;
+    if (e == SF3D_OK) {
+        K.computed = true;
+        K.liquidRead = v.liquid; K.liquidFrom = call.liquid ? 0 : call.liquidFromMeteo ? FEED_METEO : FEED_SNOW;      /* what k_hour_totals sums (sf3d_hour.inc) */
+    }
     return e;
 }
 

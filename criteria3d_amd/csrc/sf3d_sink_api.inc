@@ -58,6 +58,8 @@ sf3d_error_t sinkFetch()
     return rasterFail("sink nodes", dev().sink_download_nodes(SK.nodes.data(), count));
 }
 
+sf3d_error_t sinkComputeHour(uint32_t nrCells, const float* et0, const float* lai, const float* degreeDays, const float* liquidWater, bool rainFromMeteo);
+
 }  // namespace
 
 extern "C" {
@@ -184,13 +186,27 @@ sf3d_error_t sf3d_sink_get_crack_tables(double* maxDepth, int32_t* lastLayer)
 
 sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const float* lai, const float* degreeDays, const float* liquidWater)
 {
+    return sinkComputeHour(nrCells, et0, lai, degreeDays, liquidWater, false);
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* sf3d_sink_compute_hour; rainFromMeteo (sf3d_hour_sinks of include/sf3d_hour.h): where no snow hour was done on this raster a null
+ * liquidWater is the precipitation map of the meteo block (assignPrecipitation:943 with isSnow false) */
+sf3d_error_t sinkComputeHour(uint32_t nrCells, const float* et0, const float* lai, const float* degreeDays, const float* liquidWater, bool rainFromMeteo)
+{
     if (!SK.on) return SF3D_MEMORY_ERROR;
     if (nrCells != SK.nRows * SK.nCols) return SF3D_PARAMETER_ERROR;
     NEED_INIT_E;
     if (!MP.set || MP.nCells != nrCells || MP.nLayers != SK.nrLayers) return SF3D_TOPOGRAPHY_ERROR;
     if (MP.maxNode >= 0 && (uint32_t)MP.maxNode >= M.N) return SF3D_TOPOGRAPHY_ERROR;
     if ((!et0 || !lai || !degreeDays) && !(rasterFeeds(CR, SK.nRows, SK.nCols) && dev().crop_allocated(nrCells))) return SF3D_PARAMETER_ERROR;
-    if (!liquidWater && !(rasterFeeds(SN, SK.nRows, SK.nCols) && dev().snow_hour_done(nrCells))) return SF3D_PARAMETER_ERROR;
+    const bool fromSnow = rasterFeeds(SN, SK.nRows, SK.nCols) && dev().snow_hour_done(nrCells);
+    const bool fromMeteo = !liquidWater && !fromSnow && rainFromMeteo && rasterFeeds(MT, SK.nRows, SK.nCols)
+                           && dev().meteo_produced(METEO_PRECIPITATION, SK.nRows, SK.nCols);
+    if (!liquidWater && !fromSnow && !fromMeteo) return SF3D_PARAMETER_ERROR;
     if (!(rasterFeeds(RT, SK.nRows, SK.nCols) && dev().root_computed(nrCells, SK.nrLayers))) return SF3D_PARAMETER_ERROR;
     if (!SK.uploaded || !dev().sink_allocated()) {
         SinkSetup S{};
@@ -205,10 +221,14 @@ sf3d_error_t sf3d_sink_compute_hour(uint32_t nrCells, const float* et0, const fl
     HostModel& D = deviceModel();
     MapsInput in;
     mapsDeviceInput(in);
-    SinkCall call{et0, lai, degreeDays, liquidWater, mapsOwnedCells(nrCells), nullptr, nullptr, 0};
+    SinkCall call{et0, lai, degreeDays, liquidWater, mapsOwnedCells(nrCells), nullptr, nullptr, 0, fromMeteo};
     if (SK.crackOn) { call.crackMaxDepth = SK.crackMaxDepth.data(); call.crackLastLayer = SK.crackLastLayer.data(); call.crackVer = SK.crackVer; }
     return rasterFail("sink compute hour", dev().sink_hour(D, P, in, call));
 }
+
+}  // namespace
+
+extern "C" {
 
 sf3d_error_t sf3d_sink_get_node_sinks(uint32_t nrNodes, double* sinks)
 {

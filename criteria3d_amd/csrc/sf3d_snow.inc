@@ -260,6 +260,7 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_snow_hour(SnowView v)
 sf3d_error_t DeviceSolver::snow_free()
 {
     if (!impl_) return SF3D_OK;
+    raster_unbind(FEED_SNOW);
     raster_release({impl_->snow.base});
     impl_->snow = SnowCache();
     return SF3D_OK;
@@ -296,16 +297,31 @@ sf3d_error_t DeviceSolver::snow_hour(const float* const in[8], const SnowParamsD
     RASTER_TRY(hipSetDevice(I.device));
     for (int k = 0; k < 8; ++k)
         if (in[k]) RASTER_TRY(hipMemcpyAsync(S.base + (size_t)(SNOW_MAP_IN + k) * n, in[k], n * sizeof(float), hipMemcpyHostToDevice, I.stream));
+    const float* d[8];
+    for (int k = 0; k < 8; ++k) d[k] = in[k] ? S.base + (size_t)(SNOW_MAP_IN + k) * n : nullptr;
+    return snow_launch(d, 0, p, flag, mine);
+}
+
+/* the hour on eight input maps that are on the device: slots of this block (snow_hour) or maps of the FEED_* blocks in `feeds`
+ * (hour_snow, sf3d_hour.inc); in[7], the surface water, may be null */
+sf3d_error_t DeviceSolver::snow_launch(const float* const in[8], int feeds, const SnowParamsDev& p, float flag, const uint8_t* mine)
+{
+    SnowCache& S = impl_->snow;
+    const size_t n = S.nCells;
     SnowView v{};
     const sf3d_error_t e = raster_mask(mine, n, &v.mine);
     if (e != SF3D_OK) return e;
     for (int k = 0; k < 7; ++k) v.st[k] = S.base + (size_t)(SNOW_MAP_STATE + k) * n;
     for (int k = 0; k < 6; ++k) v.out[k] = S.base + (size_t)(SNOW_MAP_OUT + k) * n;
-    for (int k = 0; k < 8; ++k) v.in[k] = in[k] ? S.base + (size_t)(SNOW_MAP_IN + k) * n : nullptr;
+    for (int k = 0; k < 8; ++k) v.in[k] = in[k];
     v.dem = S.base + (size_t)SNOW_MAP_DEM * n;
     v.nCells = S.nCells; v.flag = flag; v.p = p;
     const sf3d_error_t el = raster_launch(k_snow_hour, n, v, S.lastMs);
-    if (el == SF3D_OK) S.hourDone = true;                  /* the input maps of this hour stay in the block (sf3d_crop_compute_hour may read them) */
+    if (el == SF3D_OK) {                                   /* the input maps of this hour stay where they are (sf3d_crop_compute_hour may read them) */
+        S.hourDone = true;
+        for (int k = 0; k < 8; ++k) S.in[k] = in[k];
+        S.feeds = feeds; S.inputsHeld = true;
+    }
     return el;
 }
 
@@ -313,12 +329,14 @@ sf3d_error_t DeviceSolver::snow_hour(const float* const in[8], const SnowParamsD
 enum { SNOW_OUT_LIQUID_WATER = 5 };                        /* SF3D_SNOW_OUT_LIQUID_WATER of include/sf3d_snow.h */
 
 bool DeviceSolver::snow_hour_done(uint32_t nCells) const { return impl_ && impl_->snow.base && impl_->snow.hourDone && impl_->snow.nCells == nCells; }
+/* the maps snow_hour_input serves are still there: none of the blocks the last hour read in place has been freed since */
+bool DeviceSolver::snow_inputs_held(uint32_t nCells) const { return snow_hour_done(nCells) && impl_->snow.inputsHeld; }
 
-/* input k of k_et0_hour among the maps the last hour uploaded: air temperature, relative humidity, wind, global radiation, transmissivity */
+/* input k of k_et0_hour among the maps the last hour read: air temperature, relative humidity, wind, global radiation, transmissivity */
 static const float* snow_hour_input(const SnowCache& S, int k)
 {
     static const int snowInput[5] = {0, 2, 3, 4, 6};
-    return S.base + (size_t)(SNOW_MAP_IN + snowInput[k]) * S.nCells;
+    return S.in[snowInput[k]];
 }
 
 static const float* snow_liquid_water(const SnowCache& S) { return S.base + (size_t)(SNOW_MAP_OUT + SNOW_OUT_LIQUID_WATER) * S.nCells; }

@@ -54,3 +54,4 @@
 #include "sf3d_sink.inc"
 #include "sf3d_rad.inc"
 #include "sf3d_transmissivity.inc"
+#include "sf3d_hour.inc"

@@ -57,6 +57,7 @@ SIGNATURES = {
     "sf3d_meteo_initialize": (capi.u8, [capi.u32, capi.u32, pf32, capi.f32, capi.f64, capi.f64, capi.f64, capi.u32, ppf32]),
     "sf3d_meteo_interpolate": (capi.u8, [capi.i32, capi.i32, capi.u32, pf64, pf64, pf32, capi.f32, psettings, pf32]),
     "sf3d_meteo_get_map": (capi.u8, [capi.i32, capi.u32, pf32]),
+    "sf3d_meteo_set_map": (capi.u8, [capi.i32, capi.u32, pf32]),
     "sf3d_meteo_kernel_ms": (capi.f64, []),
     "sf3d_meteo_clean": (capi.u8, []),
 }
@@ -121,6 +122,12 @@ def get_map(sf: capi.SF3D, var) -> np.ndarray:
     out = np.empty(sf._meteo_shape, np.float32)
     sf.check(sf.lib.sf3d_meteo_get_map(raster.index(var, VARIABLES), out.size, out.ctypes.data_as(pf32)), "meteo_get_map")
     return out
+
+
+def set_map(sf: capi.SF3D, var, values) -> None:
+    """a map the caller holds in the place of an interpolation of the variable"""
+    v = raster.f32(values, sf._meteo_shape, "meteo")
+    sf.check(sf.lib.sf3d_meteo_set_map(raster.index(var, VARIABLES), v.size, v.ctypes.data_as(pf32)), "meteo_set_map")
 
 
 def interpolate_hour(sf: capi.SF3D, stations: dict, method, settings: dict | None = None) -> dict:

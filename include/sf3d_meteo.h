@@ -93,6 +93,10 @@ sf3d_error_t sf3d_meteo_interpolate(int variable, int method, uint32_t nStations
 /* the map the last sf3d_meteo_interpolate of the variable left on the device (the flag everywhere before the first) */
 sf3d_error_t sf3d_meteo_get_map(int variable, uint32_t nrCells, float* map);
 
+/* a map the caller holds (read from a file, computed elsewhere) in the place of an interpolation of the variable: it goes to the device
+ * as it is, every cell of every rank, and counts as produced for the blocks that read this one in place (sf3d_rad.h, sf3d_hour.h) */
+sf3d_error_t sf3d_meteo_set_map(int variable, uint32_t nrCells, const float* map);
+
 /* event-timed duration [ms] of the last k_meteo_idw launch when sf3d_kernel_timing is on, else 0 */
 double sf3d_meteo_kernel_ms(void);
 
