@@ -573,6 +573,49 @@ struct MeteoCall {      /* what sf3d_meteo_interpolate hands to DeviceSolver::me
     MeteoProxyDev proxy[METEO_MAX_PROXIES];
 };
 
+/* ---- topographic distance on the meteo block's raster (sf3d_topodist.inc, include/sf3d_topodist.h): the maps of
+ * gis::topographicDistanceMap, one thread per cell and a station per blockIdx.y, and interpolate() under getUseTD() ---- */
+#define TOPODIST_MAX_STEPS 65536        /* SF3D_TOPODIST_MAX_STEPS: the host refuses a point whose walk from any cell can be longer */
+#define TOPODIST_LOOP_CAP (2 * TOPODIST_MAX_STEPS)      /* the device's own bound on a walk: station to station (k_topodist_matrix) */
+struct TopoGridDev {    /* the DEM with its header, as Crit3DRasterGrid::getValueFromXY and gis::getRowColFromXY read it */
+    const float* dem;
+    double xll, yll, cellSize, invCellSize;
+    int32_t nRows, nCols;
+    float flag;
+};
+struct TopoMapsView {   /* k_topodist_maps */
+    TopoGridDev g;
+    const double* sx;                   /* the points of the call, in device memory */
+    const double* sy;
+    const double* sz;
+    float* maps;                        /* [nPoints][nCells] */
+    const uint8_t* mine;                /* null: every cell; else 1 on the cells this rank computes */
+    uint32_t nCells, nPoints;
+};
+struct TopoIdwView {    /* k_meteo_idw_td: k_meteo_idw's view and what the distances of computeDistances need beyond it */
+    MeteoView m;
+    const double* sz;
+    const int32_t* mapIndex;            /* per station: its map, -1: none (topographicDistance == nullptr) */
+    const float* maps;
+    double invCellSize;
+    int32_t kh;                         /* getTopoDist_Kh(); 0 also where the variable is not a TD variable */
+};
+struct TopoMatrixView { /* k_topodist_matrix */
+    TopoGridDev g;
+    const double* sx;
+    const double* sy;
+    const double* sz;
+    const int32_t* mapIndex;
+    const float* maps;
+    float* matrix;                      /* [nPoints][nPoints]: matrix[j * n + i], station i seen from station j */
+    uint32_t nCells, nPoints;
+};
+struct TopoCall {       /* what sf3d_topodist_interpolate adds to a MeteoCall: host pointers */
+    const double* z;
+    const int32_t* mapIndex;
+    int32_t kh;
+};
+
 /* ---- hourly evaporation, transpiration and rain sinks (sf3d_sink.inc, include/sf3d_sink.h): one thread per raster cell walks its column ---- */
 #define SINK_HORIZON_VALUES 5           /* per horizon: waterContentHH, FC, WP, SAT, getSoilFraction() */
 enum { SINK_H_HH = 0, SINK_H_FC = 1, SINK_H_WP = 2, SINK_H_SAT = 3, SINK_H_FRACTION = 4 };

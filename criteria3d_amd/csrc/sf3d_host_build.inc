@@ -103,6 +103,13 @@ struct MeteoCache {
     float flag = -9999.f;
     bool produced[METEO_VARIABLES] = {false};      /* the variable's map holds an interpolation (meteo_produced) */
     double lastMs = 0.;
+    /* topographic distance (sf3d_topodist.inc): the maps of the last topo_compute, sized to that call, and the point tables of a call
+     * (x, y, z: doubles; mapIndex: int32; the station matrix: METEO_MAX_STATIONS floats a row, allocated with the first matrix) */
+    float* topoMaps = nullptr;          /* topoPoints x nCells floats */
+    char* topoTables = nullptr;
+    float* topoMatrix = nullptr;
+    uint32_t topoPoints = 0, topoMatrixCap = 0;
+    double topoMs[3] = {0., 0., 0.};    /* k_topodist_maps, k_meteo_idw_td, k_topodist_matrix */
 };
 
 /* hourly radiation maps (sf3d_rad.inc): the five outputs, the static maps of include/sf3d_rad.h and the hour's transmissivity; they belong to

@@ -307,10 +307,10 @@ sf3d_error_t DeviceSolver::raster_mask(const uint8_t* mine, size_t nCells, const
     return SF3D_OK;
 }
 
-template <class Arg> sf3d_error_t DeviceSolver::raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms)
+template <class Arg> sf3d_error_t DeviceSolver::raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms, uint32_t gridY)
 {
     Impl& I = *impl_;
-    const dim3 grid((uint32_t)((count + SF3D_BLOCK - 1) / SF3D_BLOCK));
+    const dim3 grid((uint32_t)((count + SF3D_BLOCK - 1) / SF3D_BLOCK), gridY);
     hipEvent_t ev[2] = {nullptr, nullptr};
     if (I.timing) { RASTER_TRY(hipEventCreate(&ev[0])); RASTER_TRY(hipEventCreate(&ev[1])); RASTER_TRY(hipEventRecord(ev[0], I.stream)); }
     hipLaunchKernelGGL(kernel, grid, dim3(SF3D_BLOCK), 0, I.stream, arg);

@@ -9,6 +9,8 @@
  *       neighbourhood by insertion with the strict < of sortPointsByDistance (:121-159) - then the 10 x 10 direction terms and the sums, all
  *       in the order of that list;
  *   retrend (:1288-1351), single detrending, and the tail of interpolate().
+ * The methods take the distance vector of computeDistances as a template argument (MeteoPlainDistance here, TopoDistance in
+ * sf3d_topodist.inc) and meteo_cell is interpolate() for one cell: k_meteo_idw and k_meteo_idw_td run the same text.
  * The bar is the compiled reference's bits (tests/golden/meteo_idw.npz): the reference's types at every step (float distances, float
  * S = 1 / d, float products of two distances, double sums) in its order, -ffp-contract=off, IEEE sqrtf and float / double division (the
  * compiler's default for HIP: no fast-math flag, no approximate-division flag in the build).  No exp, log, pow or atan2; no atomics, no
@@ -25,20 +27,37 @@
 #define METEO_LIST 10                         /* SHEPARD_MAX_NRPOINTS */
 #define METEO_MIN 5                           /* SHEPARD_MIN_NRPOINTS */
 
+/* the per-cell text also compiles for the host (tests/topodist_host.cpp defines SF3D_METEO_HOST and the qualifier) */
+#ifndef SF3D_METEO_FN
+#define SF3D_METEO_FN __device__ __forceinline__
+#define SF3D_METEO_MEMBER __device__ __forceinline__     /* a member function: the host build cannot say `static` there */
+#endif
+
+SF3D_METEO_FN bool meteo_eqf(float a, float b) { return __builtin_fabs((double)a - (double)b) < METEO_EPSILON; }      /* isEqual(float, float), basicMath.h:25 */
+
 /* gis::computeDistance(x, y, float(utm.x), float(utm.y)), gis.cpp:685-691 */
-__device__ __forceinline__ float meteo_distance(float x, float y, double sx, double sy)
+SF3D_METEO_FN float meteo_distance(float x, float y, double sx, double sy)
 {
     const float dx = (float)sx - x;
     const float dy = (float)sy - y;
     return __builtin_sqrtf(dx * dx + dy * dy);
 }
 
+/* the distance vector of computeDistances (interpolation.cpp:208-256), one station at a time: dist(i).  This one is the plain distance
+ * of k_meteo_idw; sf3d_topodist.inc has the one with topographic distance.  The methods below take either. */
+struct MeteoPlainDistance {
+    const double* sx;
+    const double* sy;
+    float x, y;
+    SF3D_METEO_MEMBER float operator()(uint32_t i) const { return meteo_distance(x, y, sx[i], sy[i]); }
+};
+
 /* inverseDistanceWeighted, interpolation.cpp:1031-1051 */
-__device__ __forceinline__ float meteo_idw(const double* sx, const double* sy, const float* sv, uint32_t n, float x, float y)
+template <class Dist> SF3D_METEO_FN float meteo_idw(const Dist& dist, const float* sv, uint32_t n)
 {
     double sum = 0, sumWeights = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        const float d = meteo_distance(x, y, sx[i], sy[i]);
+        const float d = dist(i);
         if ((double)d > METEO_EPSILON) {
             const double dist_km = (double)d / 10000.;
             const double weight = 1.0 / (dist_km * dist_km * dist_km);
@@ -50,7 +69,7 @@ __device__ __forceinline__ float meteo_idw(const double* sx, const double* sy, c
 }
 
 /* shepardSearchNeighbour, then shepardIdw (modified == false) or modifiedShepardIdw with radius == NODATA on entry */
-__device__ __forceinline__ float meteo_shepard(const double* sx, const double* sy, const float* sv, uint32_t nStations, float x, float y, float radius0, bool modified)
+template <class Dist> SF3D_METEO_FN float meteo_shepard(const Dist& dist, const double* sx, const double* sy, const float* sv, uint32_t nStations, float x, float y, float radius0, bool modified)
 {
     float ld[METEO_LIST];
     uint32_t li[METEO_LIST];
@@ -58,7 +77,7 @@ __device__ __forceinline__ float meteo_shepard(const double* sx, const double* s
     for (int s = 0; s < METEO_LIST; ++s) { ld[s] = __builtin_inff(); li[s] = 0; }
     uint32_t inside = 0;
     for (uint32_t i = 0; i < nStations; ++i) {
-        const float d = meteo_distance(x, y, sx[i], sy[i]);
+        const float d = dist(i);
         inside += (d <= radius0 && d > 0) ? 1u : 0u;
     }
     const bool few = inside < METEO_MIN;
@@ -66,7 +85,7 @@ __device__ __forceinline__ float meteo_shepard(const double* sx, const double* s
     const int keep = few ? METEO_MIN : METEO_LIST;
     int n = 0;
     for (uint32_t i = 0; i < nStations; ++i) {
-        const float d = meteo_distance(x, y, sx[i], sy[i]);
+        const float d = dist(i);
         const bool in = d <= radius0 && d > 0;
         if (sorted) {
             /* sortPointsByDistance: ! isEqual(d, 0) (d is never near NODATA); of all stations (few) or of the neighbourhood */
@@ -160,8 +179,79 @@ __device__ __forceinline__ float meteo_shepard(const double* sx, const double* s
     return (float)result;
 }
 
-__global__ void __launch_bounds__(SF3D_BLOCK) k_meteo_idw(MeteoView v)
+/* gis::getUtmXYFromRowCol, gis.cpp:806-810, then the float x, y of interpolate() */
+SF3D_METEO_FN void meteo_cell_xy(const MeteoView& v, uint32_t c, float& x, float& y)
 {
+    const int row = (int)(c / v.nCols), col = (int)(c - (uint32_t)row * v.nCols);
+    const double xd = v.xll + v.cellSize * (col + 0.5);
+    const double yd = v.yll + v.cellSize * ((int)v.nRows - row - 0.5);
+    x = (float)xd; y = (float)yd;
+}
+
+/* interpolate() (interpolation.cpp:2502-2560) on DEM cell c of height z at the float (x, y), with the distances `dist` */
+template <class Dist> SF3D_METEO_FN float meteo_cell(const MeteoView& v, uint32_t c, float z, float x, float y, const Dist& dist,
+                                                      const double* sx, const double* sy, const float* sv, uint32_t nStations)
+{
+    const float flag = v.flag;
+    float result;
+    if (v.var == METEO_PRECIPITATION && v.allZero) result = 0.f;
+    else {
+        if (v.method == METEO_IDW) result = meteo_idw(dist, sv, nStations);
+        else result = meteo_shepard(dist, sx, sy, sv, nStations, x, y, v.radius0, v.method == METEO_SHEPARD_MODIFIED);
+        if (meteo_eqf(result, (float)METEO_NODATA)) result = (float)METEO_NODATA;
+        else {
+            if (v.useDetrending) {
+                float add = 0.f;                                        /* retrend of a variable that is not detrended */
+                if (v.detrendingVar) {
+                    double retrendValue = 0.;
+#pragma unroll
+                    for (int p = 0; p < METEO_MAX_PROXIES; ++p) {
+                        if (p < (int)v.nProxies && v.proxy[p].active) {
+                            const float f = v.proxyMap[p] ? v.proxyMap[p][c] : z;
+                            const double myProxyValue = (f != flag) ? (double)f : (double)METEO_NODATA;           /* getProxyValuesXY */
+                            if (myProxyValue != METEO_NODATA) {
+                                const float proxySlope = v.proxy[p].slope;
+                                if (v.proxy[p].isHeight) {
+                                    if (v.proxy[p].inversion) {
+                                        const float LR_H0 = v.proxy[p].lapseRateH0, LR_H1 = v.proxy[p].lapseRateH1, LR_Below = v.proxy[p].inversionLapseRate;
+                                        if (myProxyValue <= LR_H1) {
+                                            const double a = myProxyValue - LR_H0;
+                                            retrendValue += ((a > 0) ? a : 0) * LR_Below;
+                                        } else retrendValue += ((LR_H1 - LR_H0) * LR_Below) + (myProxyValue - LR_H1) * proxySlope;   /* a float product first */
+                                    } else retrendValue += ((myProxyValue > 0) ? myProxyValue : 0) * proxySlope;
+                                } else retrendValue += myProxyValue * proxySlope;
+                            }
+                        }
+                    }
+                    add = (float)retrendValue;
+                }
+                result += add;
+            }
+            /* the switch of interpolate(), with the comparisons of std::min / std::max */
+            if (v.var == METEO_PRECIPITATION) result = (result < v.rainfallThreshold) ? 0.f : result;
+            else if (v.var == METEO_AIR_REL_HUMIDITY) {
+                const float m = (100.f < result) ? 100.f : result;
+                result = (0.f < m) ? m : 0.f;
+            } else if (v.var == METEO_WIND_SCALAR_INTENSITY || v.var == METEO_GLOBAL_IRRADIANCE || v.var == METEO_ATM_TRANSMISSIVITY)
+                result = (result < 0.f) ? 0.f : result;
+        }
+    }
+    return result;
+}
+
+#ifndef SF3D_METEO_HOST
+/* The first argument of the running kernel, read where it lies in the kernel argument segment.  meteo_cell takes the view by reference;
+ * a reference to the by-value parameter makes the compiler copy the whole struct at the kernel's entry - every proxy held in scalar
+ * registers across the neighbour search, 40 of them spilled - while a reference into the segment loads each field where it is used,
+ * as the kernel did when this text stood in its body. */
+template <class View> __device__ __forceinline__ const View& meteo_kernel_argument()
+{
+    return *(const View*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+__global__ void __launch_bounds__(SF3D_BLOCK) k_meteo_idw(MeteoView)
+{
+    const MeteoView& v = meteo_kernel_argument<MeteoView>();
     __shared__ double sx[METEO_MAX_STATIONS], sy[METEO_MAX_STATIONS];
     __shared__ float sv[METEO_MAX_STATIONS];
     const uint32_t nStations = v.nStations < METEO_MAX_STATIONS ? v.nStations : METEO_MAX_STATIONS;
@@ -169,57 +259,12 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_meteo_idw(MeteoView v)
     __syncthreads();
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= v.nCells) return;
-    const float flag = v.flag;
-    float result = flag;
+    float result = v.flag;
     const float z = v.dem[c];
-    if (!(v.mine && !v.mine[c]) && !snow_eqf(z, flag)) {
-        if (v.var == METEO_PRECIPITATION && v.allZero) result = 0.f;
-        else {
-            /* gis::getUtmXYFromRowCol, gis.cpp:806-810, then the float x, y of interpolate() */
-            const int row = (int)(c / v.nCols), col = (int)(c - (uint32_t)row * v.nCols);
-            const double xd = v.xll + v.cellSize * (col + 0.5);
-            const double yd = v.yll + v.cellSize * ((int)v.nRows - row - 0.5);
-            const float x = (float)xd, y = (float)yd;
-            if (v.method == METEO_IDW) result = meteo_idw(sx, sy, sv, nStations, x, y);
-            else result = meteo_shepard(sx, sy, sv, nStations, x, y, v.radius0, v.method == METEO_SHEPARD_MODIFIED);
-            if (snow_eqf(result, (float)METEO_NODATA)) result = (float)METEO_NODATA;
-            else {
-                if (v.useDetrending) {
-                    float add = 0.f;                                        /* retrend of a variable that is not detrended */
-                    if (v.detrendingVar) {
-                        double retrendValue = 0.;
-#pragma unroll
-                        for (int p = 0; p < METEO_MAX_PROXIES; ++p) {
-                            if (p < (int)v.nProxies && v.proxy[p].active) {
-                                const float f = v.proxyMap[p] ? v.proxyMap[p][c] : z;
-                                const double myProxyValue = (f != flag) ? (double)f : (double)METEO_NODATA;           /* getProxyValuesXY */
-                                if (myProxyValue != METEO_NODATA) {
-                                    const float proxySlope = v.proxy[p].slope;
-                                    if (v.proxy[p].isHeight) {
-                                        if (v.proxy[p].inversion) {
-                                            const float LR_H0 = v.proxy[p].lapseRateH0, LR_H1 = v.proxy[p].lapseRateH1, LR_Below = v.proxy[p].inversionLapseRate;
-                                            if (myProxyValue <= LR_H1) {
-                                                const double a = myProxyValue - LR_H0;
-                                                retrendValue += ((a > 0) ? a : 0) * LR_Below;
-                                            } else retrendValue += ((LR_H1 - LR_H0) * LR_Below) + (myProxyValue - LR_H1) * proxySlope;   /* a float product first */
-                                        } else retrendValue += ((myProxyValue > 0) ? myProxyValue : 0) * proxySlope;
-                                    } else retrendValue += myProxyValue * proxySlope;
-                                }
-                            }
-                        }
-                        add = (float)retrendValue;
-                    }
-                    result += add;
-                }
-                /* the switch of interpolate(), with the comparisons of std::min / std::max */
-                if (v.var == METEO_PRECIPITATION) result = (result < v.rainfallThreshold) ? 0.f : result;
-                else if (v.var == METEO_AIR_REL_HUMIDITY) {
-                    const float m = (100.f < result) ? 100.f : result;
-                    result = (0.f < m) ? m : 0.f;
-                } else if (v.var == METEO_WIND_SCALAR_INTENSITY || v.var == METEO_GLOBAL_IRRADIANCE || v.var == METEO_ATM_TRANSMISSIVITY)
-                    result = (result < 0.f) ? 0.f : result;
-            }
-        }
+    if (!(v.mine && !v.mine[c]) && !meteo_eqf(z, v.flag)) {
+        float x, y;
+        meteo_cell_xy(v, c, x, y);
+        result = meteo_cell(v, c, z, x, y, MeteoPlainDistance{sx, sy, x, y}, sx, sy, sv, nStations);
     }
     v.out[c] = result;
 }
@@ -230,7 +275,7 @@ sf3d_error_t DeviceSolver::meteo_free()
 {
     if (!impl_) return SF3D_OK;
     raster_unbind(FEED_METEO);
-    raster_release({impl_->meteo.base, impl_->meteo.stations});
+    raster_release({impl_->meteo.base, impl_->meteo.stations, impl_->meteo.topoMaps, impl_->meteo.topoTables, impl_->meteo.topoMatrix});       /* the topographic distance maps go with their raster */
     impl_->meteo = MeteoCache();
     return SF3D_OK;
 }
@@ -258,7 +303,8 @@ sf3d_error_t DeviceSolver::meteo_alloc(uint32_t nRows, uint32_t nCols, const flo
     return raster_upload(K.base + (1 + (size_t)nProxies) * n, empty.data(), empty.size() * sizeof(float));
 }
 
-sf3d_error_t DeviceSolver::meteo_interpolate(const MeteoCall& call, const uint8_t* mine, float* out)
+/* the station table of a call on the device and the view of its launch: what k_meteo_idw and k_meteo_idw_td (sf3d_topodist.inc) share */
+sf3d_error_t DeviceSolver::meteo_view(const MeteoCall& call, const uint8_t* mine, MeteoView& v)
 {
     Impl& I = *impl_;
     MeteoCache& K = I.meteo;
@@ -272,8 +318,8 @@ sf3d_error_t DeviceSolver::meteo_interpolate(const MeteoCall& call, const uint8_
         RASTER_TRY(hipMemcpyAsync(dsy, call.y, call.nStations * sizeof(double), hipMemcpyHostToDevice, I.stream));
         RASTER_TRY(hipMemcpyAsync(dsv, call.value, call.nStations * sizeof(float), hipMemcpyHostToDevice, I.stream));
     }
-    MeteoView v{};
-    sf3d_error_t e = raster_mask(mine, n, &v.mine);
+    v = MeteoView{};
+    const sf3d_error_t e = raster_mask(mine, n, &v.mine);
     if (e != SF3D_OK) return e;
     v.dem = K.base;
     for (uint32_t p = 0; p < METEO_MAX_PROXIES; ++p) {
@@ -286,6 +332,16 @@ sf3d_error_t DeviceSolver::meteo_interpolate(const MeteoCall& call, const uint8_
     v.nCells = K.nCells; v.nRows = K.nRows; v.nCols = K.nCols; v.nStations = call.nStations; v.nProxies = call.nProxies;
     v.var = call.var; v.method = call.method; v.allZero = call.allZero; v.useDetrending = call.useDetrending; v.detrendingVar = call.detrendingVar;
     v.flag = K.flag; v.radius0 = call.radius0; v.rainfallThreshold = call.rainfallThreshold;
+    return SF3D_OK;
+}
+
+sf3d_error_t DeviceSolver::meteo_interpolate(const MeteoCall& call, const uint8_t* mine, float* out)
+{
+    MeteoCache& K = impl_->meteo;
+    const size_t n = K.nCells;
+    MeteoView v;
+    sf3d_error_t e = meteo_view(call, mine, v);
+    if (e != SF3D_OK) return e;
     e = raster_launch(k_meteo_idw, n, v, K.lastMs);
     if (e == SF3D_OK) K.produced[call.var] = true;
     if (e != SF3D_OK || !out) return e;
@@ -316,3 +372,4 @@ bool DeviceSolver::meteo_produced(int var, uint32_t nRows, uint32_t nCols) const
 static const float* meteo_map(const MeteoCache& K, int var) { return K.base + (1 + (size_t)K.nProxies + (size_t)var) * K.nCells; }
 
 double DeviceSolver::meteo_kernel_ms() const { return impl_ ? impl_->meteo.lastMs : 0.; }
+#endif

@@ -15,15 +15,42 @@ namespace {
 struct MeteoHost {
     bool on = false;
     uint32_t nRows = 0, nCols = 0, nProxies = 0;
+    double xll = 0., yll = 0., cellSize = 0.;      /* the header: what sf3d_topodist_api.inc bounds a walk with */
 } MT;
 
-void meteoClear() { MT = MeteoHost(); (void)dev().meteo_free(); }
+void topoHostClear();                          /* sf3d_topodist_api.inc: the topographic distance maps go with their raster */
+
+void meteoClear() { MT = MeteoHost(); topoHostClear(); (void)dev().meteo_free(); }
 
 /* computeShepardInitialRadius(area, nrPoints, SHEPARD_AVG_NRPOINTS), interpolation.cpp:800-803: float products, PI of commonConstants.h:249 */
 float meteoInitialRadius(float area, uint32_t allPointsNr)
 {
     const unsigned minPointsNr = 8;
     return float(std::sqrt((minPointsNr * area) / (float(3.1415926535898) * allPointsNr)));
+}
+
+/* the checks of a call and what the device needs of it: sf3d_meteo_interpolate, and sf3d_topodist_interpolate (sf3d_topodist_api.inc),
+ * the one caller that may set useTopographicDistance */
+sf3d_error_t meteoPrepare(int variable, int method, uint32_t nStations, const double* x, const double* y, const float* value, float boundingBoxArea,
+                          const sf3d_meteo_settings_t* settings, bool topographicDistance, MeteoCall& call)
+{
+    /* the checks that need no raster come first: a caller learns of an unsupported option before it has one */
+    if (variable < 0 || variable >= SF3D_METEO_VARIABLES || method < SF3D_METEO_IDW || method > SF3D_METEO_SHEPARD_MODIFIED || !settings) return SF3D_PARAMETER_ERROR;
+    if (nStations > SF3D_METEO_MAX_STATIONS || (nStations > 0 && (!x || !y || !value))) return SF3D_PARAMETER_ERROR;
+    if (settings->nProxies < 0 || settings->nProxies > SF3D_METEO_MAX_PROXIES) return SF3D_PARAMETER_ERROR;
+    if (settings->useMultipleDetrending || settings->useLocalDetrending || (settings->useTopographicDistance && !topographicDistance) || settings->useKriging ||
+        settings->useSupplementalStations || settings->useCrossValidationIndex || settings->updateMinMax) return SF3D_PARAMETER_ERROR;
+    if (!MT.on) return SF3D_MEMORY_ERROR;
+    if ((uint32_t)settings->nProxies > MT.nProxies) return SF3D_PARAMETER_ERROR;
+    call = MeteoCall{};
+    call.x = x; call.y = y; call.value = value;
+    call.nStations = nStations; call.nProxies = (uint32_t)settings->nProxies;
+    call.var = variable; call.method = method; call.allZero = settings->allZero != 0; call.useDetrending = settings->useDetrending != 0;
+    call.detrendingVar = variable == SF3D_METEO_AIR_TEMPERATURE || variable == SF3D_METEO_AIR_DEW_TEMPERATURE;      /* getUseDetrendingVar */
+    call.radius0 = meteoInitialRadius(boundingBoxArea, nStations);
+    call.rainfallThreshold = settings->rainfallThreshold;
+    for (int p = 0; p < settings->nProxies; ++p) std::memcpy(&call.proxy[p], &settings->proxy[p], sizeof(MeteoProxyDev));
+    return SF3D_OK;
 }
 
 }  // namespace
@@ -39,6 +66,7 @@ sf3d_error_t sf3d_meteo_initialize(uint32_t nrRows, uint32_t nrCols, const float
     const sf3d_error_t e = dev().meteo_alloc(nrRows, nrCols, dem, flag, xllCorner, yllCorner, cellSize, nProxies, proxyMaps);
     if (e != SF3D_OK) { rasterFail("meteo initialize", e); meteoClear(); return e; }
     MT.nRows = nrRows; MT.nCols = nrCols; MT.nProxies = nProxies;
+    MT.xll = xllCorner; MT.yll = yllCorner; MT.cellSize = cellSize;
     MT.on = true;
     return SF3D_OK;
 }
@@ -46,22 +74,9 @@ sf3d_error_t sf3d_meteo_initialize(uint32_t nrRows, uint32_t nrCols, const float
 sf3d_error_t sf3d_meteo_interpolate(int variable, int method, uint32_t nStations, const double* x, const double* y, const float* value, float boundingBoxArea,
                                     const sf3d_meteo_settings_t* settings, float* out)
 {
-    /* the checks that need no raster come first: a caller learns of an unsupported option before it has one */
-    if (variable < 0 || variable >= SF3D_METEO_VARIABLES || method < SF3D_METEO_IDW || method > SF3D_METEO_SHEPARD_MODIFIED || !settings) return SF3D_PARAMETER_ERROR;
-    if (nStations > SF3D_METEO_MAX_STATIONS || (nStations > 0 && (!x || !y || !value))) return SF3D_PARAMETER_ERROR;
-    if (settings->nProxies < 0 || settings->nProxies > SF3D_METEO_MAX_PROXIES) return SF3D_PARAMETER_ERROR;
-    if (settings->useMultipleDetrending || settings->useLocalDetrending || settings->useTopographicDistance || settings->useKriging ||
-        settings->useSupplementalStations || settings->useCrossValidationIndex || settings->updateMinMax) return SF3D_PARAMETER_ERROR;
-    if (!MT.on) return SF3D_MEMORY_ERROR;
-    if ((uint32_t)settings->nProxies > MT.nProxies) return SF3D_PARAMETER_ERROR;
-    MeteoCall call{};
-    call.x = x; call.y = y; call.value = value;
-    call.nStations = nStations; call.nProxies = (uint32_t)settings->nProxies;
-    call.var = variable; call.method = method; call.allZero = settings->allZero != 0; call.useDetrending = settings->useDetrending != 0;
-    call.detrendingVar = variable == SF3D_METEO_AIR_TEMPERATURE || variable == SF3D_METEO_AIR_DEW_TEMPERATURE;      /* getUseDetrendingVar */
-    call.radius0 = meteoInitialRadius(boundingBoxArea, nStations);
-    call.rainfallThreshold = settings->rainfallThreshold;
-    for (int p = 0; p < settings->nProxies; ++p) std::memcpy(&call.proxy[p], &settings->proxy[p], sizeof(MeteoProxyDev));
+    MeteoCall call;
+    const sf3d_error_t e = meteoPrepare(variable, method, nStations, x, y, value, boundingBoxArea, settings, false, call);
+    if (e != SF3D_OK) return e;
     return rasterFail("meteo interpolate", dev().meteo_interpolate(call, mapsOwnedCells((size_t)MT.nRows * MT.nCols), out));
 }
 

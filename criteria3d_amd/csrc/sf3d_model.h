@@ -244,6 +244,17 @@ public:
     sf3d_error_t meteo_free();
     double meteo_kernel_ms() const;
     bool meteo_produced(int var, uint32_t nRows, uint32_t nCols) const;   /* the block is on this raster and holds an interpolation of `var` */
+    /* topographic distance on the meteo block's raster (sf3d_topodist.inc; the caller has checked that the raster is there and the call
+     * against the caps and the maps held): the maps of gis::topographicDistanceMap, interpolate() under getUseTD() into the meteo block's
+     * slot of the variable, and the station matrix.  The maps go with the raster (meteo_free).  which of topo_kernel_ms: 0 k_topodist_maps,
+     * 1 k_meteo_idw_td, 2 k_topodist_matrix */
+    sf3d_error_t topo_compute(uint32_t nPoints, const double* x, const double* y, const double* z, const uint8_t* mine);
+    sf3d_error_t topo_download(uint32_t index, float* dst);
+    sf3d_error_t topo_upload(uint32_t index, const float* src);
+    sf3d_error_t topo_interpolate(const MeteoCall& call, const TopoCall& topo, const uint8_t* mine, float* out);
+    sf3d_error_t topo_matrix(uint32_t nPoints, const double* x, const double* y, const double* z, const int32_t* mapIndex, float* matrix);
+    sf3d_error_t topo_free();
+    double topo_kernel_ms(int which) const;
     /* hourly r.sun radiation maps (sf3d_rad.inc): the five outputs and the static maps, independent of the node model as the other raster
      * blocks; transmissivity == nullptr: k_rad_hour reads the map the meteo block holds (the caller asks meteo_produced first) */
     sf3d_error_t rad_alloc(const RadSetup& setup);
@@ -296,7 +307,10 @@ private:
     sf3d_error_t raster_upload(void* dev, const void* host, size_t bytes);
     sf3d_error_t raster_download(void* host, const void* dev, size_t bytes);
     sf3d_error_t raster_mask(const uint8_t* mine, size_t nCells, const uint8_t** dev);
-    template <class Arg> sf3d_error_t raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms);
+    template <class Arg> sf3d_error_t raster_launch(void (*kernel)(Arg), size_t count, const Arg& arg, double& ms, uint32_t gridY = 1);
+    sf3d_error_t meteo_view(const MeteoCall& call, const uint8_t* mine, MeteoView& v);       /* sf3d_meteo.inc: the station table and the view of a call */
+    sf3d_error_t topo_tables(uint32_t n, const double* x, const double* y, const double* z, const int32_t* mapIndex,
+                             const double*& dx, const double*& dy, const double*& dz, const int32_t*& dm);      /* sf3d_topodist.inc: a call's point tables */
     sf3d_error_t raster_tables(char*& tables, size_t* off, int count, const size_t* bytes, const void* const* src, const size_t* srcBytes);
     void raster_release(std::initializer_list<void*> blocks);
     /* block `who` (FEED_*) is about to free its maps: what other blocks hold of them is forgotten, so their next reader is refused */

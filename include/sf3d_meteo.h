@@ -14,7 +14,8 @@
  * With the caller: everything that produces the point list - quality control, checkPrecipitationZero, preInterpolation with its
  * regressions and detrendPoints (once per variable and hour, on N points): the calls take detrended values and the fitted slopes.  Also
  * multiple and local detrending, topographic distance, kriging, supplemental stations (every station is primary), the cross-validation
- * index and updateMinMaxRasterGrid: a settings struct that asks for one of them is refused (SF3D_PARAMETER_ERROR).
+ * index and updateMinMaxRasterGrid: a settings struct that asks for one of them is refused (SF3D_PARAMETER_ERROR).  Topographic distance
+ * has entry points of its own on this block's raster: sf3d_topodist.h.
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.  The meteo
  * state belongs to the raster as the snow, crop and root maps do: it does not need sf3d_initialize and survives it, uses the device
