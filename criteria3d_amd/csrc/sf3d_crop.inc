@@ -18,7 +18,12 @@
  *    updateDailyTemperatures does not look at the DEM at all;
  *  - transmissivity / clearSkyTransmissivity is a float division, widened afterwards;
  *  - the degree days are accumulated in float (the map's += float(dailyDD));
- *  - computeSimpleLAI starts the leaf fall of a TREE from LAImax * 0.75, whatever the LAI was. */
+ *  - computeSimpleLAI starts the leaf fall of a TREE from LAImax * 0.75, whatever the LAI was.
+ * The per-cell text compiles for the host too (tests/crop_host.cpp defines SF3D_CROP_HOST). */
+
+#ifndef SF3D_CROP_HOST
+#define SF3D_CROP_FN __device__ __forceinline__
+#endif
 
 #define CROP_NODATA (-9999.0)
 #define CROP_TYPE_HERBACEOUS_ANNUAL 0        /* speciesType, agrolib/crop/crop.h:14 */
@@ -26,8 +31,8 @@
 #define CROP_TYPE_TREE 4
 
 /* ET0_Penman_hourly, meteo.cpp:550-609 */
-__device__ __forceinline__ double crop_et0_penman_hourly(double heigth, double normalizedTransmissivity, double globalIrradiance, double airTemp,
-                                                         double airHum, double windSpeed10)
+SF3D_CROP_FN double crop_et0_penman_hourly(double heigth, double normalizedTransmissivity, double globalIrradiance, double airTemp, double airHum,
+                                           double windSpeed10)
 {
     const double es = 611 * fexp(17.502 * airTemp / (airTemp + 240.97)) / 1000.;          /* saturationVaporPressure */
     const double ea = airHum * es / 100.0;
@@ -56,11 +61,9 @@ __device__ __forceinline__ double crop_et0_penman_hourly(double heigth, double n
     return (sum > 0) ? sum : 0;                                                            /* MAXVALUE(., 0) */
 }
 
-__global__ void __launch_bounds__(SF3D_BLOCK) k_et0_hour(CropView v)
+/* one cell of k_et0_hour */
+SF3D_CROP_FN void crop_et0_cell(const CropView& v, uint32_t c)
 {
-    fm_init();
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= v.nCells) return;
     const float flag = v.flag;
     if (v.mine && !v.mine[c]) { v.et0[c] = flag; return; }          /* another rank's column: its extremes stay, its ET0 says "not here" */
     const float height = v.dem[c];
@@ -80,8 +83,18 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_et0_hour(CropView v)
     v.st[3][c] = snow_eqf(currentTmax, flag) ? temperature : ((currentTmax < temperature) ? temperature : currentTmax);     /* std::max */
 }
 
+#ifndef SF3D_CROP_HOST
+__global__ void __launch_bounds__(SF3D_BLOCK) k_et0_hour(CropView v)
+{
+    fm_init();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    crop_et0_cell(v, c);
+}
+#endif
+
 /* Crit3DCrop::isInsideTypicalCycle, crop.cpp:314-344 */
-__device__ __forceinline__ bool crop_inside_typical_cycle(const CropUnitDev& u, int doy)
+SF3D_CROP_FN bool crop_inside_typical_cycle(const CropUnitDev& u, int doy)
 {
     const int daysFromSowing = (doy - u.sowingDoy) % 365;
     if (daysFromSowing >= 0) return daysFromSowing < u.plantCycle;
@@ -89,7 +102,7 @@ __device__ __forceinline__ bool crop_inside_typical_cycle(const CropUnitDev& u, 
 }
 
 /* leafDevelopment::getLAICriteria, development.cpp:132-154 */
-__device__ __forceinline__ double crop_lai_criteria(const CropUnitDev& u, double myDegreeDays)
+SF3D_CROP_FN double crop_lai_criteria(const CropUnitDev& u, double myDegreeDays)
 {
     const double c4 = (u.type == CROP_TYPE_TREE) ? 15.0 : 9.0;
     if (myDegreeDays <= u.degreeDaysIncrease)
@@ -98,7 +111,7 @@ __device__ __forceinline__ double crop_lai_criteria(const CropUnitDev& u, double
 }
 
 /* Crit3DCrop::computeSimpleLAI, crop.cpp:177-224 */
-__device__ __forceinline__ double crop_simple_lai(const CropUnitDev& u, double myDegreeDays, double latitude, int currentDoy)
+SF3D_CROP_FN double crop_simple_lai(const CropUnitDev& u, double myDegreeDays, double latitude, int currentDoy)
 {
     /* one inlined copy of the curve serves both branches: sown crops enter it past the emergence offset, the others with degree days > 0 */
     const bool sowing = u.type == CROP_TYPE_HERBACEOUS_ANNUAL || u.type == CROP_TYPE_HORTICULTURAL;       /* isSowingCrop */
@@ -125,20 +138,10 @@ __device__ __forceinline__ double crop_simple_lai(const CropUnitDev& u, double m
     return currentLAI;
 }
 
-/* k_crop_day with dateDoy < 0: initializeCropFromDegreeDays (criteria3DProject.cpp:524-573) - the degree days are in place, LAI from them */
-__global__ void __launch_bounds__(SF3D_BLOCK) k_crop_day(CropView v)
+/* one cell of k_crop_day; units: the crop table (v.nUnits entries).  dateDoy < 0: initializeCropFromDegreeDays
+ * (criteria3DProject.cpp:524-573) - the degree days are in place, LAI from them */
+SF3D_CROP_FN void crop_day_cell(const CropView& v, const CropUnitDev* units, uint32_t c)
 {
-    __shared__ CropUnitDev units[CROP_MAX_UNITS];
-    {   /* the crop table: consecutive words from memory into LDS, read from there (every lane its own unit) */
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(v.units);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(units);
-        const uint32_t words = v.nUnits * (uint32_t)(sizeof(CropUnitDev) / 4);
-        for (uint32_t k = threadIdx.x; k < words; k += blockDim.x) dst[k] = src[k];
-    }
-    fm_init();
-    __syncthreads();
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= v.nCells) return;
     if (v.mine && !v.mine[c]) return;           /* another rank's column: untouched */
     const float flag = v.flag;
     const bool fromMap = v.dateDoy < 0;
@@ -175,6 +178,23 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_crop_day(CropView v)
     }
     v.st[0][c] = dd; v.st[1][c] = lai;
     v.st[2][c] = flag; v.st[3][c] = flag;                                     /* emptyGrid on the daily extremes (from a map: initializeCropMaps) */
+}
+
+#ifndef SF3D_CROP_HOST
+__global__ void __launch_bounds__(SF3D_BLOCK) k_crop_day(CropView v)
+{
+    __shared__ CropUnitDev units[CROP_MAX_UNITS];
+    {   /* the crop table: consecutive words from memory into LDS, read from there (every lane its own unit) */
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(v.units);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(units);
+        const uint32_t words = v.nUnits * (uint32_t)(sizeof(CropUnitDev) / 4);
+        for (uint32_t k = threadIdx.x; k < words; k += blockDim.x) dst[k] = src[k];
+    }
+    fm_init();
+    __syncthreads();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    crop_day_cell(v, units, c);
 }
 
 /* ---- host side: one device block of CROP_MAPS x nCells 4-byte values and the crop table; calls go through the shared raster path at the
@@ -273,3 +293,4 @@ sf3d_error_t DeviceSolver::crop_day(int dateDoy, int currentDoy, double latitude
 
 /* which: 0 k_et0_hour, 1 k_crop_day */
 double DeviceSolver::crop_kernel_ms(int which) const { return (impl_ && (which == 0 || which == 1)) ? impl_->crop.lastMs[which] : 0.; }
+#endif

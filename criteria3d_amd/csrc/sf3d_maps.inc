@@ -20,7 +20,15 @@ enum : int32_t {                          /* criteria3DVariable, agrolib/meteo/m
     MV_SURFACE_POND = 14, MV_MIN_VWC = 15, MV_MAX_VWC = 16
 };
 
-__device__ __forceinline__ double map_theta(const SoilDev& s, double Se) { return (Se * (s.thetaS - s.thetaR)) + s.thetaR; }   /* soilPhysics.cpp:38-42 */
+/* map_theta and map_sentinel also serve the host build of the sink text (tests/sink_host.cpp defines SF3D_MAPS_HOST: these two, nothing else) */
+#ifndef SF3D_MAPS_HOST
+#define SF3D_MAPS_FN __device__ __forceinline__
+#endif
+SF3D_MAPS_FN double map_theta(const SoilDev& s, double Se) { return (Se * (s.thetaS - s.thetaR)) + s.thetaR; }   /* soilPhysics.cpp:38-42 */
+/* the sentinels getCriteria3DVar turns into NODATA (INDEX_ERROR, MEMORY_ERROR, TOPOGRAPHY_ERROR, MISSING_DATA_ERROR of commonConstants.h) */
+SF3D_MAPS_FN bool map_sentinel(double v) { return v == -1111. || v == -2222. || v == -3333. || v == -9999.; }
+
+#ifndef SF3D_MAPS_HOST
 /* thetaFromSignedPsi for a soil node and psi < 0 (soilPhysics.cpp:50-61) */
 __device__ __forceinline__ double map_theta_at(const SoilDev& s, double absPsi, uint32_t wrc) { return map_theta(s, se_from_psi(s, absPsi, wrc)); }
 
@@ -65,8 +73,6 @@ __device__ __forceinline__ double map_node_value(const MapView& m, int32_t var, 
         default: return SF3D_VAL_MISSING_DATA_ERROR;
     }
 }
-/* the sentinels getCriteria3DVar turns into NODATA (INDEX_ERROR, MEMORY_ERROR, TOPOGRAPHY_ERROR, MISSING_DATA_ERROR of commonConstants.h) */
-__device__ __forceinline__ bool map_sentinel(double v) { return v == -1111. || v == -2222. || v == -3333. || v == -9999.; }
 
 __global__ void __launch_bounds__(SF3D_BLOCK) k_output_map(MapView m)
 {
@@ -326,3 +332,4 @@ template <class Arg> sf3d_error_t DeviceSolver::raster_launch(void (*kernel)(Arg
     }
     return SF3D_OK;
 }
+#endif

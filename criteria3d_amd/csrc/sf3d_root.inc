@@ -20,7 +20,12 @@
  *  - cylindricalDistribution normalises the lower half of its 2 m values only;
  *  - PI is 3.1415926535898 (commonConstants.h:249);
  *  - the early returns leave zeros in the density and NODATA in firstRootLayer / lastRootLayer (Crit3DRoot::clear);
- *  - a GAMMA_DISTRIBUTION unit becomes a cardioid (root.cpp:530-533). */
+ *  - a GAMMA_DISTRIBUTION unit becomes a cardioid (root.cpp:530-533).
+ * The per-cell and per-row text compiles for the host too (tests/root_host.cpp defines SF3D_ROOT_HOST). */
+
+#ifndef SF3D_ROOT_HOST
+#define SF3D_ROOT_FN __device__ __forceinline__
+#endif
 
 #define ROOT_NODATA (-9999)
 #define ROOT_EPSILON 0.00001
@@ -33,7 +38,7 @@
 #define ROOT_LOG_005 (-2.995732273553991)     /* log(0.05) */
 
 /* root::getRootLengthDD, root.cpp:139-170 */
-__device__ __forceinline__ double root_length_dd(const RootUnitDev& u, double actualRootDepthMax, double currentDD)
+SF3D_ROOT_FN double root_length_dd(const RootUnitDev& u, double actualRootDepthMax, double currentDD)
 {
     if (currentDD <= 1) return 0.;
     const double maxRootLength = actualRootDepthMax - u.rootDepthMin;
@@ -53,19 +58,9 @@ __device__ __forceinline__ double root_length_dd(const RootUnitDev& u, double ac
     return currentRootLength;
 }
 
-__global__ void __launch_bounds__(SF3D_BLOCK) k_root_cell(RootView v)
+/* one cell of k_root_cell; units: the unit table (v.nUnits entries) */
+SF3D_ROOT_FN void root_cell(const RootView& v, const RootUnitDev* units, uint32_t c)
 {
-    __shared__ RootUnitDev units[CROP_MAX_UNITS];
-    {   /* the unit table: consecutive words from memory into LDS, read from there (every lane its own unit) */
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(v.units);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(units);
-        const uint32_t words = v.nUnits * (uint32_t)(sizeof(RootUnitDev) / 4);
-        for (uint32_t k = threadIdx.x; k < words; k += blockDim.x) dst[k] = src[k];
-    }
-    fm_init();
-    __syncthreads();
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= v.nCells) return;
     const float flag = v.flag;
     double length = (double)flag, depth = (double)flag;
     int32_t first = (int32_t)flag, last = (int32_t)flag, key = -1;
@@ -105,11 +100,8 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_root_cell(RootView v)
 }
 
 /* one row of the density table: computeRootDensity3D on a fresh Crit3DRoot whose currentRootLength rounds to rowN rooted atoms */
-__global__ void __launch_bounds__(SF3D_BLOCK) k_root_table(RootTableView t)
+SF3D_ROOT_FN void root_table_row(const RootTableView& t, uint32_t r)
 {
-    fm_init();
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= t.nRows) return;
     const RootUnitDev u = t.units[t.rowUnit[r]];
     const uint32_t s = (uint32_t)t.rowSoil[r];
     const int n = t.rowN[r];
@@ -205,15 +197,45 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_root_table(RootTableView t)
 }
 
 /* the density maps of layers layer0 .. layer0 + layerCount - 1: out[k][cell] = table[layer0 + k][key[cell]], the flag where the cell has no key */
-__global__ void __launch_bounds__(SF3D_BLOCK) k_root_gather(RootView v)
+SF3D_ROOT_FN void root_gather_cell(const RootView& v, uint32_t c)
 {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= v.nCells) return;
     const int32_t key = v.key[c];
     const bool has = key >= 0 && (uint32_t)key < v.nRows;
     const double flag = (double)v.flag;
     for (uint32_t k = 0; k < v.layerCount; ++k)
         v.out[(size_t)k * v.nCells + c] = has ? v.table[(size_t)(v.layer0 + k) * v.nRows + (uint32_t)key] : flag;
+}
+
+#ifndef SF3D_ROOT_HOST
+__global__ void __launch_bounds__(SF3D_BLOCK) k_root_cell(RootView v)
+{
+    __shared__ RootUnitDev units[CROP_MAX_UNITS];
+    {   /* the unit table: consecutive words from memory into LDS, read from there (every lane its own unit) */
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(v.units);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(units);
+        const uint32_t words = v.nUnits * (uint32_t)(sizeof(RootUnitDev) / 4);
+        for (uint32_t k = threadIdx.x; k < words; k += blockDim.x) dst[k] = src[k];
+    }
+    fm_init();
+    __syncthreads();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    root_cell(v, units, c);
+}
+
+__global__ void __launch_bounds__(SF3D_BLOCK) k_root_table(RootTableView t)
+{
+    fm_init();
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= t.nRows) return;
+    root_table_row(t, r);
+}
+
+__global__ void __launch_bounds__(SF3D_BLOCK) k_root_gather(RootView v)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    root_gather_cell(v, c);
 }
 
 /* ---- host side: the per-cell block, one block of tables and the gathered density maps; calls go through the shared raster path at the end
@@ -350,3 +372,4 @@ bool DeviceSolver::root_computed(uint32_t nCells, uint32_t nrLayers) const
 /* which: 0 k_root_cell, 1 k_root_table, 2 k_root_gather */
 double DeviceSolver::root_kernel_ms(int which) const { return (impl_ && which >= 0 && which < 3) ? impl_->root.lastMs[which] : 0.; }
 uint32_t DeviceSolver::root_table_rows() const { return impl_ ? impl_->root.nRows : 0; }
+#endif

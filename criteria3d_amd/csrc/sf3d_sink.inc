@@ -16,14 +16,19 @@
  *  - the water content is read again, unchanged, in each of the up to three evaporation iterations;
  *  - a layer without a node takes part in the evaporation loop with the water content NODATA (nothing evaporates) and is skipped by
  *    transpiration; a layer without a horizon is skipped by both;
- *  - waterStress is 1 - 0 / 0 = NaN when every root layer was skipped: both comparisons are false and nothing is redistributed. */
+ *  - waterStress is 1 - 0 / 0 = NaN when every root layer was skipped: both comparisons are false and nothing is redistributed.
+ * The per-cell text compiles for the host too (tests/sink_host.cpp defines SF3D_SINK_HOST). */
+
+#ifndef SF3D_SINK_HOST
+#define SF3D_SINK_FN __device__ __forceinline__
+#endif
 
 #define SINK_NODATA (-9999)
 #define SINK_EPSILON 0.00001
 #define SINK_DBL_EPSILON 2.220446049250313e-16
 
 /* getCriteria3DVar(volumetricWaterContent, node), project3D.cpp:2756-2810 */
-__device__ __forceinline__ double sink_vwc(const SinkView& v, int32_t n)
+SF3D_SINK_FN double sink_vwc(const SinkView& v, int32_t n)
 {
     if (n < 0) return (double)SINK_NODATA;                                 /* getNodeWaterContent: INDEX_ERROR -> NODATA */
     const double w = ((uint32_t)n < v.ns) ? (v.H[n] - v.z[n]) : map_theta(v.soils[v.cls[n]], v.Se[n]);
@@ -32,8 +37,8 @@ __device__ __forceinline__ double sink_vwc(const SinkView& v, int32_t n)
 
 /* one root layer of assignTranspiration's first loop (:2525-2572): false when the layer is skipped; else the layer's root density, whether it
  * is stressed, and layerTranspiration as the float the reference stores */
-__device__ __forceinline__ bool sink_root_layer(const SinkView& v, uint32_t c, uint32_t layer, int32_t si, int32_t key, const SinkUnitDev& u,
-                                                double maxTranspiration, double& density, bool& stressed, float& layerTranspiration)
+SF3D_SINK_FN bool sink_root_layer(const SinkView& v, uint32_t c, uint32_t layer, int32_t si, int32_t key, const SinkUnitDev& u, double maxTranspiration,
+                                  double& density, bool& stressed, float& layerTranspiration)
 {
     const int32_t n = v.col[(size_t)layer * v.nCells + c];
     if (n < 0) return false;
@@ -56,14 +61,14 @@ __device__ __forceinline__ bool sink_root_layer(const SinkView& v, uint32_t c, u
 }
 
 /* getCriteria3DVar(maxVolumetricWaterContent, node), project3D.cpp:2756-2810 */
-__device__ __forceinline__ double sink_max_vwc(const SinkView& v, int32_t n)
+SF3D_SINK_FN double sink_max_vwc(const SinkView& v, int32_t n)
 {
     const double w = ((uint32_t)n < v.ns) ? SF3D_VAL_INDEX_ERROR : v.soils[v.cls[n]].thetaS;
     return map_sentinel(w) ? (double)SINK_NODATA : w;
 }
 
 /* voidVolumeList[layer] of computeSoilCracking's first loop (criteria3DProject.cpp:1058-1064) for a layer with a node and a horizon */
-__device__ __forceinline__ double sink_void_volume(const SinkView& v, int32_t n, int32_t si, int32_t h)
+SF3D_SINK_FN double sink_void_volume(const SinkView& v, int32_t n, int32_t si, int32_t h)
 {
     const double soilFraction = v.horizonValues[((size_t)si * ROOT_MAX_HORIZONS + (uint32_t)h) * SINK_HORIZON_VALUES + SINK_H_FRACTION];
     const double VWC = sink_vwc(v, n);
@@ -75,7 +80,7 @@ __device__ __forceinline__ double sink_void_volume(const SinkView& v, int32_t n,
 /* Crit3DProject::computeSoilCracking (criteria3DProject.cpp:978-1123) behind its tests on the soil and the layer grid, which the host made
  * (sf3d_sink_set_cracking: maxDepth, lastLayer).  The evaporation and transpiration subtractions of the column are in v.sink already; every
  * addition is made on its own.  Returns the function's float; *crackWater: the sum of layerWater over the layers filled. */
-__device__ __forceinline__ float sink_soil_cracking(const SinkView& v, const SinkCrackDev& k, uint32_t c, int32_t s0, int32_t si, float precipitation, double* crackWater)
+SF3D_SINK_FN float sink_soil_cracking(const SinkView& v, const SinkCrackDev& k, uint32_t c, int32_t s0, int32_t si, float precipitation, double* crackWater)
 {
     const size_t nc = v.nCells;
     const uint32_t nl = v.nrLayers;
@@ -130,11 +135,8 @@ __device__ __forceinline__ float sink_soil_cracking(const SinkView& v, const Sin
 }
 
 /* one cell of the hour; CRACK: the rain term goes through sink_soil_cracking (k_sink_hour_crack), else precSurfaceWater = liquidWater */
-template <bool CRACK> __device__ __forceinline__ void sink_cell(const SinkView& v, const SinkCrackDev* k)
+template <bool CRACK> SF3D_SINK_FN void sink_cell(const SinkView& v, const SinkCrackDev* k, uint32_t c)
 {
-    fm_init();
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= v.nCells) return;
     const size_t nc = v.nCells;
     const uint32_t nl = v.nrLayers;
     const float flag = v.flag;
@@ -269,10 +271,23 @@ template <bool CRACK> __device__ __forceinline__ void sink_cell(const SinkView& 
     if constexpr (CRACK) { k->precSurfaceWater[c] = precSurfaceWater; k->crackWater[c] = crackWater; }
 }
 
-__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v) { sink_cell<false>(v, nullptr); }
+#ifndef SF3D_SINK_HOST
+__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour(SinkView v)
+{
+    fm_init();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    sink_cell<false>(v, nullptr, c);
+}
 
 /* the hour with soil cracking (sf3d_sink_set_cracking) */
-__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour_crack(SinkCrackView k) { sink_cell<true>(k.s, k.k); }
+__global__ void __launch_bounds__(SF3D_BLOCK) k_sink_hour_crack(SinkCrackView k)
+{
+    fm_init();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= k.s.nCells) return;
+    sink_cell<true>(k.s, k.k, c);
+}
 
 /* ---- host side: the per-cell block, one block of tables and the node array; calls go through the shared raster path at the end of
  * sf3d_maps.inc. */
@@ -426,3 +441,4 @@ sf3d_error_t DeviceSolver::sink_download_crack(float* precSurfaceWater, double* 
 }
 
 double DeviceSolver::sink_kernel_ms() const { return impl_ ? impl_->sink.lastMs : 0.; }
+#endif

@@ -1,10 +1,12 @@
 /* part of sf3d_api.cpp (included at its end, after the meteo entry points) - the C entry points of include/sf3d_sink.h.  The host keeps the
- * raster and the tables until the first hour uploads them (no device is needed before), evaluates what needs the C library's exp
- * (initializeEvaporationCoefficient) and getHorizonIndex of every (soil, layer), hands the column table of sf3d_maps.h to the device in the
- * numbering of the model it works on, and moves the node sinks between that numbering and the caller's. */
+ * raster and the tables until the first hour uploads them (no device is needed before); what needs the C library's exp
+ * (initializeEvaporationCoefficient), getHorizonIndex of every (soil, layer) and the crack tables come from sf3d_sink_setup.inc.  It hands
+ * the column table of sf3d_maps.h to the device in the numbering of the model it works on, and moves the node sinks between that numbering
+ * and the caller's. */
 #include <cmath>
 
 #include "sf3d_sink.h"
+#include "sf3d_sink_setup.inc"
 
 static_assert(sizeof(sf3d_sink_unit_t) == sizeof(SinkUnitDev) && sizeof(SinkUnitDev) == 24, "the sink unit table is copied as it is");
 static_assert(sizeof(sf3d_sink_soil_t) == 8 + 7 * 8 * SF3D_ROOT_MAX_HORIZONS, "sf3d_sink_soil_t has no padding");
@@ -38,17 +40,6 @@ uint64_t sinkCrackVersions = 0;                /* a new number for every table s
 
 void sinkClear() { SK = SinkHost(); (void)dev().sink_free(); }
 
-const double kMaxEvaporationDepth = 0.25;      /* MAX_EVAPORATION_DEPTH, commonConstants.h:116 */
-
-/* Project3D::getSoilLayerIndex, project3D.cpp:1764-1776 */
-int sinkLayerIndex(uint32_t nrLayers, const double* layerDepth, const double* layerThickness, double depth)
-{
-    if (nrLayers == 0 || depth < 0) return -9999;
-    for (uint32_t layer = 0; layer < nrLayers; ++layer)
-        if (depth <= layerDepth[layer] + layerThickness[layer] * 0.5) return (int)layer;
-    return -9999;
-}
-
 /* the node sinks of the last hour from the device into SK.nodes */
 sf3d_error_t sinkFetch()
 {
@@ -76,20 +67,10 @@ sf3d_error_t sf3d_sink_initialize(uint32_t nrRows, uint32_t nrCols, const float*
     const uint32_t n = nrRows * nrCols;
     for (uint32_t c = 0; c < n; ++c)
         if ((cropIndex[c] >= 0 && (uint32_t)cropIndex[c] >= nUnits) || (soilIndex[c] >= 0 && (uint32_t)soilIndex[c] >= nSoils)) return SF3D_PARAMETER_ERROR;
-    /* initializeEvaporationCoefficient, project3D.cpp:2331-2368 */
-    int lastEvapLayer = sinkLayerIndex(nrLayers, layerDepth, layerThickness, kMaxEvaporationDepth);
-    if (computationSoilDepth < kMaxEvaporationDepth) lastEvapLayer = sinkLayerIndex(nrLayers, layerDepth, layerThickness, computationSoilDepth);
-    if (lastEvapLayer == -9999) return SF3D_PARAMETER_ERROR;
-    std::vector<double> evapCoeff(nrLayers, 0.), layerEvapCoeff(nrLayers, 0.);
-    double coeffSum = 0;
-    for (int layer = 1; layer <= lastEvapLayer; layer++) {
-        const double depthCoeff = std::max((layerDepth[layer] - layerDepth[1]) / (kMaxEvaporationDepth - layerDepth[1]), 0.0);
-        evapCoeff[layer] = exp(-2 * depthCoeff);
-        layerEvapCoeff[layer] = evapCoeff[layer] * (layerThickness[layer] / 0.04);
-        coeffSum += layerEvapCoeff[layer];
-    }
-    const double invCoeffSum = 1.0 / coeffSum;
-    for (int layer = 1; layer <= lastEvapLayer; layer++) layerEvapCoeff[layer] *= invCoeffSum;
+    SinkTablesHost T;
+    const sf3d_error_t et = sinkBuildTables(nrLayers, layerDepth, layerThickness, computationSoilDepth, nUnits, units, nSoils, soils, T);
+    if (et != SF3D_OK) return et;
+    const int lastEvapLayer = T.lastEvapLayer;
 
     sinkClear();
     SK.nRows = nrRows; SK.nCols = nrCols; SK.nrLayers = nrLayers; SK.nUnits = nUnits; SK.nSoils = nSoils; SK.lastEvapLayer = lastEvapLayer;
@@ -104,23 +85,9 @@ sf3d_error_t sf3d_sink_initialize(uint32_t nrRows, uint32_t nrCols, const float*
     SK.dem.assign(dem, dem + n);
     SK.cropIndex.resize(n); SK.soilIndex.resize(n);
     for (uint32_t c = 0; c < n; ++c) { SK.cropIndex[c] = cropIndex[c] < 0 ? -1 : cropIndex[c]; SK.soilIndex[c] = soilIndex[c] < 0 ? -1 : soilIndex[c]; }
-    SK.units.resize(nUnits);
-    for (uint32_t u = 0; u < nUnits; ++u) SK.units[u] = SinkUnitDev{units[u].kcMax, units[u].fRAW, units[u].isWaterSurplusResistant ? 1 : 0, 0};
-    SK.horizon.assign((size_t)nSoils * nrLayers, -1);
-    SK.horizonValues.assign((size_t)nSoils * SF3D_ROOT_MAX_HORIZONS * SINK_HORIZON_VALUES, 0.);
-    for (uint32_t s = 0; s < nSoils; ++s) {
-        const sf3d_sink_soil_t& so = soils[s];
-        for (int32_t h = 0; h < so.nrHorizons; ++h) {
-            double* hz = SK.horizonValues.data() + ((size_t)s * SF3D_ROOT_MAX_HORIZONS + h) * SINK_HORIZON_VALUES;
-            hz[SINK_H_HH] = so.waterContentHH[h]; hz[SINK_H_FC] = so.waterContentFC[h]; hz[SINK_H_WP] = so.waterContentWP[h];
-            hz[SINK_H_SAT] = so.waterContentSAT[h]; hz[SINK_H_FRACTION] = so.soilFraction[h];
-        }
-        for (uint32_t l = 0; l < nrLayers; ++l)                           /* Crit3DSoil::getHorizonIndex(layerDepth[l]), soil.cpp:192-201 */
-            for (int32_t h = 0; h < so.nrHorizons; ++h)
-                if (layerDepth[l] >= so.upperDepth[h] && layerDepth[l] <= (so.lowerDepth[h] + 0.00001)) { SK.horizon[(size_t)s * nrLayers + l] = h; break; }
-    }
+    SK.units = T.units; SK.horizon = T.horizon; SK.horizonValues = T.horizonValues;
     SK.layerDepth.assign(layerDepth, layerDepth + nrLayers); SK.thick.assign(layerThickness, layerThickness + nrLayers);
-    SK.evapCoeff = evapCoeff; SK.layerEvapCoeff = layerEvapCoeff;
+    SK.evapCoeff = T.evapCoeff; SK.layerEvapCoeff = T.layerEvapCoeff;
     SK.on = true;
     return SF3D_OK;
 }
@@ -135,9 +102,7 @@ sf3d_error_t sf3d_sink_get_tables(double* evapCoeff, double* layerEvapCoeff, int
     return SF3D_OK;
 }
 
-/* The part of Crit3DProject::computeSoilCracking (criteria3DProject.cpp:1003-1035, :1078) that depends on the soil and the layer grid only.
- * Every one of these exits returns the precipitation unchanged and has no side effect, so their place before or after the per-cell tests
- * (soil index, pond, crackDepth, avgVoidVolume) changes no result: a soil that fails one never cracks. */
+/* the per-soil tables of soil cracking: sinkCrackTables of sf3d_sink_setup.inc */
 sf3d_error_t sf3d_sink_set_cracking(uint32_t nSoils, const sf3d_sink_crack_soil_t* soils)
 {
     if (!SK.on) return SF3D_MEMORY_ERROR;
@@ -145,32 +110,10 @@ sf3d_error_t sf3d_sink_set_cracking(uint32_t nSoils, const sf3d_sink_crack_soil_
     if (nSoils != SK.nSoils) return SF3D_PARAMETER_ERROR;
     for (uint32_t s = 0; s < nSoils; ++s)
         if (soils[s].nrHorizons < 0 || soils[s].nrHorizons > SF3D_ROOT_MAX_HORIZONS || soils[s].nrHorizons > SK.nrHorizons[s]) return SF3D_PARAMETER_ERROR;
-    const double MAX_CRACKING_DEPTH = 0.6, MIN_FINE_LAYER_DEPTH = 0.2, MIN_FINE_FRACTION = 0.5;
-    std::vector<double> maxDepthOf(nSoils, -9999.);
-    std::vector<int32_t> lastLayerOf(nSoils, -9999);
-    for (uint32_t s = 0; s < nSoils; ++s) {
-        const sf3d_sink_crack_soil_t& so = soils[s];
-        const double* upper = SK.upperDepth.data() + (size_t)s * SF3D_ROOT_MAX_HORIZONS;
-        const double* lower = SK.lowerDepth.data() + (size_t)s * SF3D_ROOT_MAX_HORIZONS;
-        const double soilDepth = std::min(SK.computationSoilDepth, so.totalDepth);
-        if (soilDepth <= MIN_FINE_LAYER_DEPTH) continue;
-        int lastFineHorizon = -9999;
-        double maxDepth = std::min(soilDepth, MAX_CRACKING_DEPTH);
-        int32_t h = 0;
-        while (h < so.nrHorizons && upper[h] < maxDepth) {
-            const double fineFraction = (so.clay[h] + so.silt[h] * 0.5) / 100 * (1 - so.coarseFragments[h]) * (1 - so.organicMatter[h]);
-            if (fineFraction < MIN_FINE_FRACTION) break;
-            lastFineHorizon = h;
-            ++h;
-        }
-        if (lastFineHorizon == -9999) continue;
-        maxDepth = std::min(lower[lastFineHorizon], MAX_CRACKING_DEPTH);
-        maxDepth = std::min(maxDepth, SK.computationSoilDepth);
-        if (maxDepth < MIN_FINE_LAYER_DEPTH) continue;
-        const int lastLayer = sinkLayerIndex(SK.nrLayers, SK.layerDepth.data(), SK.thick.data(), maxDepth);
-        if (lastLayer == -9999) continue;
-        maxDepthOf[s] = maxDepth; lastLayerOf[s] = lastLayer;
-    }
+    std::vector<double> maxDepthOf;
+    std::vector<int32_t> lastLayerOf;
+    sinkCrackTables(nSoils, soils, SK.upperDepth.data(), SK.lowerDepth.data(), SK.computationSoilDepth, SK.nrLayers, SK.layerDepth.data(), SK.thick.data(), maxDepthOf,
+                    lastLayerOf);
     SK.crackMaxDepth = maxDepthOf; SK.crackLastLayer = lastLayerOf;
     SK.crackOn = true; SK.crackVer = ++sinkCrackVersions;
     return SF3D_OK;

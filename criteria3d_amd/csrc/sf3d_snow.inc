@@ -18,7 +18,13 @@
  *  - NODATA comparisons are isEqual (|a - b| < EPSILON), except the age test of snow.cpp:500 (==).
  * The application reuses one Crit3DSnow object across the cells of a thread (firstprivate): setPoint / setSnowInputData overwrite the
  * seven state members and the nine inputs, and every output member is written before it is read (computeSnowFall: _precSnow, _precRain;
- * the others are assigned, never accumulated), so nothing carries over from cell to cell. */
+ * the others are assigned, never accumulated), so nothing carries over from cell to cell.
+ * The per-cell text compiles for the host too (tests/snow_host.cpp defines SF3D_SNOW_HOST; snow_eq / snow_eqf also serve the host builds
+ * of sf3d_crop.inc, sf3d_root.inc and sf3d_sink.inc). */
+
+#ifndef SF3D_SNOW_HOST
+#define SF3D_SNOW_FN __device__ __forceinline__
+#endif
 
 #define SNOW_NODATA (-9999.0)
 #define SNOW_EPSILON 0.00001                 /* commonConstants.h:252 */
@@ -41,11 +47,11 @@
 #define SNOW_HEAT_CAPACITY_SNOW 2100000.
 #define SNOW_SWE_ENUM 56                     /* meteoVariable snowWaterEquivalent */
 
-__device__ __forceinline__ bool snow_eq(double a, double b) { return __builtin_fabs(a - b) < SNOW_EPSILON; }               /* isEqual(double, double) */
-__device__ __forceinline__ bool snow_eqf(float a, float b) { return __builtin_fabs((double)a - (double)b) < SNOW_EPSILON; }   /* isEqual(float, float) */
+SF3D_SNOW_FN bool snow_eq(double a, double b) { return __builtin_fabs(a - b) < SNOW_EPSILON; }               /* isEqual(double, double) */
+SF3D_SNOW_FN bool snow_eqf(float a, float b) { return __builtin_fabs((double)a - (double)b) < SNOW_EPSILON; }   /* isEqual(float, float) */
 
 /* tDewFromRelHum(double, double), agrolib/meteo/meteo.cpp:288-298 */
-__device__ __forceinline__ double snow_tdew(double RH, double T)
+SF3D_SNOW_FN double snow_tdew(double RH, double T)
 {
     if (snow_eq(RH, SNOW_NODATA) || snow_eq(T, SNOW_NODATA) || RH == 0) return SNOW_NODATA;
     RH = (100 < RH) ? 100 : RH;
@@ -56,7 +62,7 @@ __device__ __forceinline__ double snow_tdew(double RH, double T)
 }
 
 /* aerodynamicResistanceCampbell77(isSnow, 10, windSpeed, vegetativeHeight), snow.cpp:527-557 */
-__device__ __forceinline__ double snow_resistance(bool isSnow, double windSpeed, double vegetativeHeight)
+SF3D_SNOW_FN double snow_resistance(bool isSnow, double windSpeed, double vegetativeHeight)
 {
     const double zRefWind = 10, zRefTemp = 2;
     windSpeed = dmax(windSpeed, 0.05);
@@ -71,11 +77,9 @@ __device__ __forceinline__ double snow_resistance(bool isSnow, double windSpeed,
     return log1 * log2 / (SNOW_VON_KARMAN_CONST * SNOW_VON_KARMAN_CONST * windSpeed);
 }
 
-__global__ void __launch_bounds__(SF3D_BLOCK) k_snow_hour(SnowView v)
+/* one cell of the hour */
+SF3D_SNOW_FN void snow_cell(const SnowView& v, uint32_t c)
 {
-    fm_init();
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= v.nCells) return;
     const float flag = v.flag;
     if (v.mine && !v.mine[c]) {                 /* another rank's column: its state stays, the outputs say "not here" */
         for (int k = 0; k < 6; ++k) v.out[k][c] = flag;
@@ -255,6 +259,15 @@ __global__ void __launch_bounds__(SF3D_BLOCK) k_snow_hour(SnowView v)
     v.out[5][c] = liquid;
 }
 
+#ifndef SF3D_SNOW_HOST
+__global__ void __launch_bounds__(SF3D_BLOCK) k_snow_hour(SnowView v)
+{
+    fm_init();
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= v.nCells) return;
+    snow_cell(v, c);
+}
+
 /* ---- host side: the maps live in one device block of SNOW_MAPS x nCells floats; a call uploads, launches on the solver's stream, and
  * copies back only what it is asked for (the shared raster path at the end of sf3d_maps.inc). */
 sf3d_error_t DeviceSolver::snow_free()
@@ -342,3 +355,4 @@ static const float* snow_hour_input(const SnowCache& S, int k)
 static const float* snow_liquid_water(const SnowCache& S) { return S.base + (size_t)(SNOW_MAP_OUT + SNOW_OUT_LIQUID_WATER) * S.nCells; }
 
 double DeviceSolver::snow_kernel_ms() const { return impl_ ? impl_->snow.lastMs : 0.; }
+#endif

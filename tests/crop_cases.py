@@ -163,3 +163,159 @@ def small_raster_stages(r):
     want.update(crop.restate_crop_day(want, dem, idx, units, lat, DOY, DOY, flag))
     stages.append(dict(want))
     return stages
+
+
+# ---- scripts: a list of operations any backend (Restated, Device, HostRecorder) runs, and the host build of the per-cell text
+# (tests/crop_host.cpp)
+
+SEEDS = (21, 22, 23, 24)                        # of the random scripts, per shape; the device runs the first two
+SOUTH = -35.0
+
+
+def continuous_hour(dem, flag, rng, night=False):
+    """one hour of meteo maps drawn from continuous ranges, 3 % of each map at the flag; night: no radiation (net radiation <= 0)"""
+    shape = dem.shape
+    fl = np.float32(flag)
+    m = dict(airT=rng.uniform(-5.0, 35.0, shape), relHum=rng.uniform(20.0, 100.0, shape), windInt=rng.uniform(0.0, 10.0, shape),
+             globalRad=np.zeros(shape) if night else rng.uniform(50.0, 900.0, shape), transmissivity=rng.uniform(0.1, 0.9, shape))      # (above 0.75: min with 1)
+    m = {k: v.astype(np.float32) for k, v in m.items()}
+    for v in m.values():
+        v[rng.random(shape) < 0.03] = fl
+    return m
+
+
+def random_script(pin, shape, seed, continuous=True):
+    """(raster, ops) on a raster of any shape: small_raster's DEM and unit index (with a further 3 % of cells on no unit) and, with
+    `continuous`, degree days from -20 to 3000 and hours from continuous_hour (else small_raster's map and small_forcing's hours).
+    North (44.5): the degree-day map on day 310, a day hour, the daily update, a night hour, the next day's update.  South (-35): the
+    degree-day map on day 119, the days 119 to 152 (the leaf fall of the south: its first day, its 30 days and after) with a day or a
+    night hour each, then 181 to 183 (182: the year's first day empties the maps).  ops: ("initialize", latitude), ("set_degree_days", map,
+    doy), ("hour", meteo), ("day", dateDoy, currentDoy), ("checkpoint",)."""
+    r = small_raster(pin, shape, seed)
+    rng = np.random.default_rng(seed + 7000)
+    dem, flag = r["dem"], r["flag"]
+    if continuous:
+        r["dd0"] = np.where(rng.random(shape) < 0.95, rng.uniform(-20.0, 3000.0, shape), flag).astype(np.float32)
+        r["idx"][rng.random(shape) < 0.03] = -1
+    listed = small_forcing(shape, dem, flag)
+
+    def hour(k, night=False):
+        if continuous:
+            return continuous_hour(dem, flag, rng, night)
+        m = {n: v.copy() for n, v in listed[k % len(listed)].items()}
+        if night:
+            m["globalRad"] = np.where(m["globalRad"] == np.float32(flag), np.float32(flag), np.float32(0)).astype(np.float32)
+        return m
+    ops = [("initialize", r["latitude"]), ("set_degree_days", r["dd0"], DOY), ("checkpoint",), ("hour", hour(3)), ("checkpoint",), ("day", DOY, DOY), ("checkpoint",),
+           ("hour", hour(1, night=True)), ("checkpoint",), ("day", DOY + 1, DOY + 1), ("checkpoint",)]
+    ops += [("initialize", SOUTH), ("set_degree_days", r["dd0"], 119), ("checkpoint",)]
+    for doy in list(range(119, 153)) + [181, 182, 183]:
+        ops += [("hour", hour(doy, night=doy % 3 == 0)), ("day", doy, doy)]
+        if doy in (119, 120, 121, 150, 151, 152, 181, 182, 183):
+            ops.append(("checkpoint",))
+    return r, ops
+
+
+def as_pin(r, pin):
+    """a raster of small_raster under the keys Restated and Device read"""
+    return dict(dem=r["dem"], flag=r["flag"], unit_index=r["idx"], unit_list=r["units"], clear_sky=crop.CLEAR_SKY_TRANSMISSIVITY_DEFAULT)
+
+
+def run_script(backend, ops):
+    """the five maps at every checkpoint"""
+    out = []
+    for op in ops:
+        if op[0] == "initialize":
+            backend.initialize(op[1])
+        elif op[0] == "set_degree_days":
+            backend.set_degree_days(op[1], op[2])
+        elif op[0] == "hour":
+            backend.hour(op[1])
+        elif op[0] == "day":
+            backend.day(op[1], op[2])
+        elif op[0] == "set_state":
+            backend.set_state(op[1], op[2])
+        elif op[0] == "checkpoint":
+            out.append(backend.maps())
+    return out
+
+
+def pin_script(pin):
+    """the pin's calendar as a script.  A change of latitude keeps the four state maps (replay carries them over)"""
+    ops = []
+    for n, (op, a, b) in enumerate(pin["ops"]):
+        op, a, b = int(op), int(a), int(b)
+        if op == OP_LATITUDE:
+            ops.append(("initialize", a / 100.0, n > 0))
+        elif op == OP_HOUR:
+            ops.append(("hour", meteo(pin, a)))
+        elif op == OP_DAY:
+            ops.append(("day", a, b))
+        elif op == OP_SET_STATE:
+            ops.append(("set_state", crop.MAPS[a], pin["set_maps"][b]))
+        elif op == OP_SET_DEGREE_DAYS:
+            ops.append(("set_degree_days", pin["set_maps"][b], a))
+        elif op == OP_CHECKPOINT:
+            ops.append(("checkpoint",))
+    return ops
+
+
+def build_host(directory, sanitize=False):
+    from tests.raster_helpers import build_host_program
+    return build_host_program("crop", directory, sanitize)
+
+
+def run_host(exe, directory, name, p, ops):
+    """the host program on a script -> the five maps at every checkpoint.  p: the keys of as_pin.  ("initialize", latitude, True) keeps the
+    state maps"""
+    from tests.raster_helpers import Reader, run_host_program
+    import ctypes
+    dem = np.asarray(p["dem"], np.float32)
+    n, units = dem.size, p["unit_list"]
+    f32 = lambda a: np.asarray(a, np.float32).reshape(dem.shape)
+    parts = [np.array([n, len(units), len(ops)], np.int32), np.array([p["flag"], p["clear_sky"]], np.float32), dem, np.asarray(p["unit_index"], np.int32),
+             bytes(crop.unit_array(units))[:len(units) * ctypes.sizeof(crop.Unit)]]
+    code = lambda *v: np.array(v, np.int32)
+    checkpoints = 0
+    for op in ops:
+        if op[0] == "initialize":
+            parts += [code(OP_LATITUDE, int(len(op) > 2 and op[2]), 0), np.array([op[1]], np.float64)]
+        elif op[0] == "set_degree_days":
+            parts += [code(OP_SET_DEGREE_DAYS, op[2], 0), f32(op[1])]
+        elif op[0] == "hour":
+            parts += [code(OP_HOUR, 0, 0)] + [f32(op[1][k]) for k in crop.INPUT]
+        elif op[0] == "day":
+            parts.append(code(OP_DAY, op[1], op[2]))
+        elif op[0] == "set_state":
+            parts += [code(OP_SET_STATE, crop.STATE.index(op[1]), 0), f32(op[2])]
+        elif op[0] == "checkpoint":
+            parts.append(code(OP_CHECKPOINT, 0, 0))
+            checkpoints += 1
+    r = Reader(run_host_program(exe, directory, name, parts))
+    out = [{k: r.take(np.float32, *dem.shape) for k in crop.MAPS} for _ in range(checkpoints)]
+    assert r.done()
+    return out
+
+
+def edge_scripts(pin):
+    """(name, raster, ops) of valid inputs at the edges of the tables: CROP_MAX_UNITS land units with cells on the last one, and one row of
+    eight cells"""
+    r, ops = random_script(pin, (3, 11), SEEDS[0])
+    rng = np.random.default_rng(64)
+    r["units"] = [pin["unit_list"][k % len(pin["unit_list"])] for k in range(crop.MAX_UNITS)]
+    r["idx"] = rng.integers(-1, crop.MAX_UNITS, r["idx"].shape).astype(np.int32)
+    r["idx"].flat[5:9] = crop.MAX_UNITS - 1
+    yield "64-units", r, ops
+    r, ops = random_script(pin, (1, 8), SEEDS[1])
+    yield "1x8", r, ops
+
+
+def accepted(sf, p, latitude=44.5):
+    """sf3d_crop_initialize takes the raster: its validation passes (without a device the call then fails on the device, with another code)"""
+    crop.bind(sf)
+    dem, idx = np.ascontiguousarray(p["dem"], np.float32), np.ascontiguousarray(p["unit_index"], np.int32)
+    from criteria3d_amd import capi
+    code = sf.lib.sf3d_crop_initialize(dem.shape[0], dem.shape[1], dem.ctypes.data_as(crop.pf32), float(p["flag"]), idx.ctypes.data_as(crop.pi32), len(p["unit_list"]),
+                                       crop.unit_array(p["unit_list"]), latitude)
+    sf.lib.sf3d_crop_clean()
+    return code not in (capi.PARAMETER_ERROR, capi.INDEX_ERROR)

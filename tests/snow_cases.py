@@ -1,4 +1,5 @@
-"""Forcing shared by tests/test_gpu_snow.py, tests/test_snow_host.py and scripts/multirank_snow_worker.py (no tests here)."""
+"""Forcing shared by tests/test_gpu_snow.py, tests/test_snow_host.py and scripts/multirank_snow_worker.py, and the host build of the
+kernel's per-cell text (tests/snow_host.cpp) with its runner (no tests here)."""
 import numpy as np
 
 from criteria3d_amd import snow
@@ -70,3 +71,57 @@ def restated_run(dem, flag, hours, parameters=None):
         state = snow.restate_snow_hour(state, met, dem, flag, parameters)
         out.append(state)
     return out
+
+
+# ---- the host build of the per-cell text (tests/snow_host.cpp)
+
+SEEDS = (11, 12, 13, 14)                        # of continuous_forcing, per shape; the device runs the first two
+
+
+def continuous_forcing(shape, seed):
+    """small_forcing's six hours with every map drawn anew from continuous ranges of its own seed, plus a seventh hour whose surface water
+    lies between 0 and 120 mm on every cell: (dem, flag, hours).  The share of flag cells and of flags in the inputs is small_forcing's."""
+    dem, flag, hours = small_forcing(shape, seed)
+    rng = np.random.default_rng(seed + 5000)
+    fl = np.float32(flag)
+    glob = rng.uniform(0.0, 900.0, shape).astype(np.float32)
+    last = dict(airT=rng.uniform(-15.0, 20.0, shape).astype(np.float32), prec=rng.uniform(0.0, 8.0, shape).astype(np.float32),
+                relHum=rng.uniform(5.0, 110.0, shape).astype(np.float32), windInt=rng.uniform(0.0, 15.0, shape).astype(np.float32), globalRad=glob,
+                beamRad=(glob * rng.uniform(0.0, 1.0, shape).astype(np.float32)).astype(np.float32),
+                transmissivity=rng.uniform(0.0, 0.9, shape).astype(np.float32), clearSkyTransmissivity=0.75,
+                surfaceWater=rng.uniform(0.0, 120.0, shape).astype(np.float32))
+    for name in ("airT", "prec", "globalRad", "beamRad"):
+        last[name][rng.random(shape) < 0.04] = fl                    # an invalid point
+    return dem, flag, hours + [last]
+
+
+def build_host(directory, sanitize=False):
+    from tests.raster_helpers import build_host_program
+    return build_host_program("snow", directory, sanitize)
+
+
+def run_host(exe, directory, name, dem, flag, state, hours, parameters=None):
+    """the host program from `state` (the seven maps by name) over `hours` -> the thirteen maps after every hour, by name"""
+    from tests.raster_helpers import Reader, run_host_program
+    p = dict(snow.DEFAULT_PARAMETERS)
+    p.update(parameters or {})
+    n = dem.size
+    parts = [np.array([n, len(hours)], np.int32), np.array([flag], np.float32), np.array([p[k] for k in snow.PARAMETER_NAMES], np.float64), dem.astype(np.float32)]
+    parts += [np.asarray(state[k], np.float32) for k in snow.STATE]
+    for met in hours:
+        water = met.get("surfaceWater")
+        parts += [np.array([met["clearSkyTransmissivity"]], np.float64), np.array([water is not None], np.int32)]
+        parts += [np.asarray(met[k], np.float32) for k in snow.INPUT[:7]]
+        if water is not None:
+            parts.append(np.asarray(water, np.float32))
+    r = Reader(run_host_program(exe, directory, name, parts))
+    out = [{k: r.take(np.float32, *dem.shape) for k in snow.STATE + snow.OUTPUT} for _ in hours]
+    assert r.done()
+    return out
+
+
+def reset_state(dem, flag, parameters=None):
+    """the seven state maps of initializeSnowMaps / resetSnowModel"""
+    fl = np.float32(flag)
+    m = snow.restate_reset(np.where(dem == fl, fl, np.float32(0)), flag, parameters)
+    return {k: m[k] for k in snow.STATE}

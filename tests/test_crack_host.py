@@ -1,7 +1,8 @@
 """Soil cracking without a GPU: the restatement of Crit3DProject::computeSoilCracking inside the rain term (criteria3d_amd/sinks.py) against
 the compiled-reference pin tests/golden/soil_cracking.npz - node sinks, both actual maps, computeSoilCracking's return value and the crack
 water of every hour bit for bit, zero excluded; the fixture's arm table; the small rasters of tests/crack_cases.py reach every arm too;
-the per-soil tables of sf3d_sink_set_cracking against the recorded ones; its refusals and its off-switch, which need no device."""
+the per-soil tables of sf3d_sink_set_cracking against the recorded ones; its refusals and its off-switch, which need no device; and the host build of
+the kernel's per-cell text with cracking (tests/sink_host.cpp): equal to the pin and to the restatement bit for bit, clean under the sanitizers."""
 import ctypes as C
 
 import numpy as np
@@ -154,3 +155,73 @@ def test_soil_crack_table_reads_the_soils_of_load_all_soils():
     assert t == [dict(totalDepth=0.9, clay=[55.0, 20.0], silt=[30.0, 40.0], coarseFragments=[0.05, 0.0], organicMatter=[0.02, 0.01])]
     arr = sinks.crack_soil_array(t)
     assert arr[0].nrHorizons == 2 and arr[0].totalDepth == 0.9 and arr[0].silt[1] == 40.0 and C.sizeof(sinks.CrackSoil) == 16 + 32 * sinks.MAX_HORIZONS
+
+
+# ---- the host build of the per-cell text of k_sink_hour_crack behind sf3d_sink_set_cracking's table builder (tests/sink_host.cpp): the
+# text == the pin, the text == the restatement.  The edge cases of the tables run in tests/test_sink_host.py, with cracking.
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    from types import SimpleNamespace
+    d = tmp_path_factory.mktemp("crack_host")
+    return SimpleNamespace(dir=d, exes=sc.build_host(d), san=sc.build_host(d, sanitize=True))
+
+
+def test_host_text_equals_the_pin_on_every_hour_and_on_one_layer(pin, oracle, host):
+    """H, Se and the ponds come from the checker on the pin's potentials; no libm escape: the text carries its own exp"""
+    state = sc.node_state(oracle, pin)
+    assert np.array_equal(kc.bits(state["vwc"]), kc.bits(pin["vwc"]))
+    for k in range(len(pin["et0"])):
+        got = sc.run_host(host.exes, host.dir, "pin", pin, k, state, crack=True)
+        assert np.array_equal(kc.bits(got["max_depth"]), kc.bits(pin["crack_max_depth"])) and np.array_equal(got["last_layer"], pin["crack_last_layer"])
+        print(f"host text, hour {k}: values differ: {sc.compare_host(got['crack'], {n: pin[n][k] for n in kc.OUTPUTS}, kc.OUTPUTS, k)}")
+    for j, k in enumerate(int(v) for v in pin["one_layer_hours"]):
+        got = sc.run_host(host.exes, host.dir, "pin-one-layer", pin, k, state, one_layer=True, crack=True)
+        assert np.array_equal(got["last_layer"], pin["one_layer_crack_last_layer"])
+        print(f"host text, one layer, hour {k}: values differ: {sc.compare_host(got['crack'], {n: pin['one_layer_' + n][j] for n in kc.OUTPUTS}, kc.OUTPUTS, k)}")
+
+
+def test_host_text_equals_the_restatement_on_random_cases(pin, oracle, host):
+    from tests import tolerances
+    exact, why = tolerances.libm_probe()
+    print(why)
+    for name, case in sc.random_cases(pin, kc.small_case):
+        state, node_state = sc.node_state(oracle, case), sc.crack_state(oracle, case)
+        differ = 0
+        for k in range(len(case["et0"])):
+            got = sc.run_host(host.exes, host.dir, name, case, k, state, crack=True)
+            differ += sc.compare_host(got["crack"], kc.restated_case(case, k, node_state), kc.OUTPUTS, (name, k), exact)
+            differ += sc.compare_host(got["plain"], kc.restated_case(case, k, node_state, crack=False), kc.OUTPUTS[:3], (name, k, "off"), exact)
+        print(f"{name}: values differ: {differ}")
+
+
+def test_random_cases_reach_every_arm_of_the_pin(pin, oracle):
+    """the restatement's own counters over the union of the random cases: every arm the pin's census lists"""
+    union = {}
+    for name, case in sc.random_cases(pin, kc.small_case):
+        node_state = sc.crack_state(oracle, case)
+        filled = 0
+        for k in range(len(case["et0"])):
+            got = kc.restated_case(case, k, node_state, arms=union)
+            filled += np.count_nonzero((got["crack_water"] != float(case["flag"])) & (got["crack_water"] > 0))
+        assert filled > 0 or case["dem"].shape == kc.SHALLOW, name
+        kc.snow_arms(case, union)
+    unreachable = {}                                                 # arm -> why the random cases cannot reach it (the pin covers it); three at the most
+    missing = [str(arm) for arm in pin["arm_names"] if union.get(str(arm), 0) == 0 and str(arm) not in unreachable]
+    assert not missing and len(unreachable) <= 3, missing
+
+
+def test_sanitized_host_build_reports_nothing(pin, oracle, host):
+    """address and undefined-behaviour sanitizers on the pin and on every random case, with cracking: exit 0, nothing on stderr"""
+    state = sc.node_state(oracle, pin)
+    for k in range(len(pin["et0"])):
+        sc.run_host(host.san, host.dir, "san-pin", pin, k, state, crack=True)
+    for k in (int(v) for v in pin["one_layer_hours"]):
+        sc.run_host(host.san, host.dir, "san-pin-one-layer", pin, k, state, one_layer=True, crack=True)
+    runs = len(pin["et0"]) + len(pin["one_layer_hours"])
+    for name, case in sc.random_cases(pin, kc.small_case):
+        state = sc.node_state(oracle, case)
+        for k in range(len(case["et0"])):
+            sc.run_host(host.san, host.dir, "san-" + name, case, k, state, crack=True)
+            runs += 1
+    print(f"sink_host_san with cracking: {runs} runs, nothing reported")

@@ -1,7 +1,8 @@
 """Hourly ET0, daily extremes and the daily crop maps, the parts that need no GPU: the numpy restatements equal the compiled-reference
 pin tests/golden/crop_et0.npz bit for bit at every checkpoint, the pin reaches every arm, the small rasters of the GPU test hold ET0 and
 LAI on the shares of cells it asks for, the crop-table reader and isCrop on the
-Ravone project's crop rows, the C entry points of include/sf3d_crop.h and the binding table, the crop/ state folder."""
+Ravone project's crop rows, the C entry points of include/sf3d_crop.h and the binding table, the crop/ state folder; and the host build of the kernels' per-cell
+text (tests/crop_host.cpp): equal to the pin and to the restatement bit for bit, clean under the address and undefined-behaviour sanitizers."""
 import json
 import re
 import subprocess
@@ -14,7 +15,7 @@ import pytest
 from criteria3d_amd import build, capi, crop, esri, project3d as p3
 from tests import crop_cases as cc
 from tests import tolerances
-from tests.raster_helpers import bits as _bits
+from tests.raster_helpers import bits as _bits, differing
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -207,3 +208,92 @@ def test_state_directory_round_trip(tmp_path, pin):
     assert sorted(got) == sorted(crop.STATE)
     for n in crop.STATE:
         assert np.array_equal(_bits(got[n]), _bits(maps[n])), n
+
+
+# ---- the host build of the per-cell text of k_et0_hour and k_crop_day (tests/crop_host.cpp): the text == the pin, the text == the restatement
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("crop_host")
+    return SimpleNamespace(dir=d, exe=cc.build_host(d), san=cc.build_host(d, sanitize=True))
+
+
+def _random_scripts(pin):
+    for shape in cc.SHAPES:
+        for seed in cc.SEEDS:
+            for continuous in (False, True):
+                r, ops = cc.random_script(pin, shape, seed, continuous)
+                yield f"{'continuous' if continuous else 'lists'}-{shape[0]}x{shape[1]}-{seed}", r, ops
+
+
+def test_host_text_equals_the_pin_at_every_checkpoint(pin, host):
+    """no libm escape: the text carries its own exp, log and pow"""
+    got = cc.run_host(host.exe, host.dir, "pin", pin, cc.pin_script(pin))
+    assert len(got) == pin["maps"].shape[0]
+    for k, maps in enumerate(got):
+        for j, n in enumerate(crop.MAPS):
+            bad = differing(maps[n], pin["maps"][k][j])
+            print(f"host text, checkpoint {k} {n}: values differ: {int(bad.sum())}")
+            assert not bad.any(), (k, n, int(bad.sum()), maps[n][bad][:4], pin["maps"][k][j][bad][:4])
+
+
+def test_host_text_equals_the_restatement_on_random_scripts(pin, host):
+    """both hemispheres, the leaf fall of the south (days 119 to 152), the year's first day at 182, night hours; the value lists of
+    small_forcing and continuous ranges, four seeds per shape"""
+    exact, why = tolerances.libm_probe()
+    print(why)
+    for name, r, ops in _random_scripts(pin):
+        p = cc.as_pin(r, pin)
+        want, got = cc.run_script(cc.Restated(p), ops), cc.run_host(host.exe, host.dir, name, p, ops)
+        assert len(got) == len(want) == 15
+        differ = 0
+        for k, (g, w) in enumerate(zip(got, want)):
+            for n in crop.MAPS:
+                bad = differing(g[n], w[n])
+                differ += int(bad.sum())
+                if exact:
+                    assert not bad.any(), (name, k, n, int(bad.sum()), g[n][bad][:4], w[n][bad][:4])
+                else:           # another C library under the restatement: the tolerance of the restatement's own test above
+                    assert np.allclose(g[n], w[n], rtol=1e-6, atol=1e-6), (name, k, n)
+        print(f"{name}: values differ: {differ}")
+
+
+def test_random_scripts_are_not_vacuous(pin):
+    """the shares tests/test_gpu_crop.py asks of its small rasters, from the restatement; the south loses its leaves and starts its year"""
+    flag = np.float32(-9999.0)
+    for name, r, ops in _random_scripts(pin):
+        cps = cc.run_script(cc.Restated(cc.as_pin(r, pin)), ops)
+        after_dd, after_hour, after_day, after_night, after_next = cps[:5]
+        cells = r["dem_cells"]
+        assert np.count_nonzero(after_hour["et0"] > 0) > cc.ET0_SHARE * cells, name
+        assert np.count_nonzero(after_day["lai"] > 0) > cc.LAI_SHARE * cells and np.count_nonzero(after_next["lai"] > 0) > cc.LAI_SHARE * cells, name
+        assert np.count_nonzero(after_night["et0"] != flag) > 0 and np.count_nonzero(after_hour["dailyTmax"] != flag) > 0, name
+        south = cps[5:]
+        tree = (r["idx"] == 3) & (south[0]["lai"] != flag)
+        assert tree.sum() >= 3, name                                                      # the three lanes before the last hold a tree
+        day119, day120, day121, day150, day151, day152, day181, day182, day183 = south[1:]
+        # (a tree without a temperature that day keeps its LAI, so these are counts)
+        assert np.count_nonzero(day121["lai"][tree] < day120["lai"][tree]) > tree.sum() // 2, name      # the leaves fall from day 120 on
+        assert np.count_nonzero(day150["lai"][tree] > day151["lai"][tree]) > 0 and np.count_nonzero(day152["lai"][tree] == day151["lai"][tree]) > 0, name      # 30 days, then LAImin
+        held = lambda m: np.count_nonzero(m["degreeDays"] != flag)
+        assert held(day181) > 0 and np.all(day182["degreeDays"][day182["degreeDays"] != flag] <= 40.0), name      # day 182 starts the year: one day's degrees at the most
+        assert np.count_nonzero(day181["degreeDays"] > 40.0) > 0, name
+
+
+def test_sanitized_host_build_reports_nothing(pin, host):
+    """address and undefined-behaviour sanitizers on the pin, on every random script and on the edge cases: exit 0, nothing on stderr"""
+    cc.run_host(host.san, host.dir, "san-pin", pin, cc.pin_script(pin))
+    runs = 1
+    for name, r, ops in _random_scripts(pin):
+        cc.run_host(host.san, host.dir, "san-" + name, cc.as_pin(r, pin), ops)
+        runs += 1
+    sf = capi.load_product()
+    for name, r, ops in cc.edge_scripts(pin):
+        p = cc.as_pin(r, pin)
+        assert cc.accepted(sf, p), name
+        want, got = cc.run_script(cc.Restated(p), ops), cc.run_host(host.san, host.dir, "san-" + name, p, ops)
+        if tolerances.libm_probe()[0]:
+            assert all(not differing(g[n], w[n]).any() for g, w in zip(got, want) for n in crop.MAPS), name
+        runs += 1
+    assert np.count_nonzero(r["dem"] != np.float32(r["flag"])) > 0
+    print(f"crop_host_san: {runs} runs, nothing reported")

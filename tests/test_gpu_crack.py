@@ -3,7 +3,7 @@ tests/golden/soil_cracking.npz: node sinks, both actual maps and both cracking m
 state whose water content, maximum water content and pond equal the recorded ones; the nrLayers = 1 case; rasters with a partial block,
 less than a wave and a single row against the restatement, reaching every arm; cracking off after on; a column table changed between two
 hours; sf3d_sink_apply against the node-by-node setter with one computeStep against the CPU oracle given the same sinks; two ranks
-sharing the GPU."""
+sharing the GPU; the device against the host build of the same text (tests/sink_host.cpp) with cracking, bit for bit."""
 import numpy as np
 import pytest
 
@@ -228,3 +228,28 @@ def test_two_ranks_merge_to_the_single_rank_sinks_and_maps(product, pin, tmp_pat
             computed = (cell_owner == r) & (pin["columns"][0] >= 0)
             assert np.all(res[name][~computed] == flag), (name, r)      # another rank's cells: the flag
     _same(merged, {name: pin[name][which] for name in kc.OUTPUTS}, "merged ranks")
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("crack_host")
+    return d, sc.build_host(d)
+
+
+@pytest.mark.parametrize("shape", sc.SHAPES)
+def test_device_equals_the_host_build_of_the_same_text(product, pin, host, shape):
+    """k_sink_hour_crack against tests/sink_host.cpp, the same sink_cell<true> compiled for the CPU, on the continuous cases of two seeds
+    and on the edge cases of the tables, cracking on: node sinks, both actual maps, precSurfaceWater and crackWater of every hour, bit for
+    bit, on the H, Se and ponds the device holds.  tests/test_crack_host.py and tests/test_sink_host.py have run these cases under the
+    sanitizers and shown that they reach every arm."""
+    _need_glibc_set(product)
+    directory, exes = host
+    cases = [(f"{shape[1]}-{seed}", sc.continuous_case(kc.small_case(pin, shape, seed), seed), False) for seed in sc.SEEDS[:2]]
+    if shape == sc.SHAPES[0]:
+        cases += [(name, case, one_layer) for name, case, one_layer, crack in sc.edge_cases(sc.load_pin(), pin) if crack]
+    for name, case, one_layer in cases:
+        state, hours = sc.device_run(product, case, one_layer, crack=True)
+        for k, got in enumerate(hours):
+            want = sc.run_host(exes, directory, "gpu-" + name, case, k, state, one_layer=one_layer, crack=True)
+            print(f"{name}, hour {k}: values differ: {sc.compare_host(got, want['crack'], kc.OUTPUTS, (name, k))}")
+        assert any(np.count_nonzero(got["sinks"]) > 0 for got in hours), name                      # some sinks are non-zero

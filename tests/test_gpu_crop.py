@@ -2,7 +2,8 @@
 compiled-reference pin tests/golden/crop_et0.npz: all five maps at every checkpoint of the calendar bit for bit, zero cells excluded; a
 raster with a partial wave and a partial block, one of less than a wave and a single row of 300 cells against the restatement; the run interrupted through get_state / set_state and through
 the crop/ state folder; NULL inputs read what the snow hour uploaded; the solver does not notice the calls; two ranks sharing the GPU
-merge to the single-rank maps; the error codes."""
+merge to the single-rank maps; the error codes; the device against the host build of the same text (tests/crop_host.cpp) on random scripts
+over both hemispheres, bit for bit."""
 import numpy as np
 import pytest
 
@@ -10,7 +11,7 @@ from criteria3d_amd import capi, catchment as cm, crop, snow
 from tests import ranks as mr
 from tests import crop_cases as cc
 from tests.scenarios import ravone_project_model
-from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits as _bits, differing, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 
@@ -275,3 +276,36 @@ def test_error_paths(product, pin):
         crop.set_state(product, "lai", np.zeros((3, 3), np.float32))
     assert lib.sf3d_crop_clean() == capi.OK
     assert lib.sf3d_crop_get_state(0, n, p) == capi.MEMORY_ERROR                                    # after clean
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("crop_host")
+    return d, cc.build_host(d)
+
+
+@pytest.mark.parametrize("shape", cc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_device_equals_the_host_build_of_the_same_text(product, pin, host, shape):
+    """k_et0_hour and k_crop_day against tests/crop_host.cpp, the same crop_et0_cell and crop_day_cell compiled for the CPU, on the
+    continuous scripts of two seeds (the degree-day map, hours by day and by night, daily updates on both hemispheres) and on the edge
+    cases (64 land units, one row of eight cells): all five maps at every checkpoint, bit for bit.  tests/test_crop_host.py has run these
+    scripts under the sanitizers and shown that they are not vacuous."""
+    _need_glibc_set(product)
+    directory, exe = host
+    scripts = [(f"{shape[1]}-{seed}",) + cc.random_script(pin, shape, seed) for seed in cc.SEEDS[:2]]
+    if shape == cc.SHAPES[0]:
+        scripts += list(cc.edge_scripts(pin))
+    for name, r, ops in scripts:
+        p = cc.as_pin(r, pin)
+        want = cc.run_host(exe, directory, "gpu-" + name, p, ops)
+        got = cc.run_script(cc.Device(product, p), ops)
+        assert len(got) == len(want)
+        for k, (g, w) in enumerate(zip(got, want)):
+            for n in crop.MAPS:
+                bad = differing(g[n], w[n])
+                if bad.any() or k == len(got) - 1:
+                    print(f"{name} checkpoint {k} {n}: values differ: {int(bad.sum())}")
+                assert not bad.any(), (name, k, n, int(bad.sum()), g[n][bad][:4], w[n][bad][:4])
+        # (the share tests/test_crop_host.py asserts of the random scripts; the edge rasters hold a handful of cells)
+        assert np.count_nonzero(got[1]["et0"] > 0) > (cc.ET0_SHARE * r["dem_cells"] if r["dem"].shape == shape else 0)
+        crop.clean(product)

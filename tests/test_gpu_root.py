@@ -2,14 +2,15 @@
 k_root_gather) against the compiled-reference pin tests/golden/root_density.npz: every output of every degree-day map bit for bit, zero
 cells excluded; degreeDays == NULL reads the crop block's map; rasters with a partial block, less than a wave and a single row against
 the restatement; sf3d_clean and re-initialise; the solver does not notice the calls; two ranks sharing the GPU merge to the single-rank
-maps; the error codes."""
+maps; the error codes; the device against the host build of the same text (tests/root_host.cpp) on random rasters and on the edges of
+the tables, bit for bit."""
 import numpy as np
 import pytest
 
 from criteria3d_amd import capi, catchment as cm, crop, root
 from tests import ranks as mr
 from tests import root_cases as rc
-from tests.raster_helpers import need_glibc_set as _need_glibc_set
+from tests.raster_helpers import differing, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 
@@ -195,3 +196,41 @@ def test_error_paths(product, pin):
         root.compute(product, np.zeros((3, 3), np.float32))
     assert lib.sf3d_root_clean() == capi.OK
     assert lib.sf3d_root_get_length(n, d) == capi.MEMORY_ERROR                                       # after clean
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("root_host")
+    return d, rc.build_host(d)
+
+
+@pytest.mark.parametrize("shape", rc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_device_equals_the_host_build_of_the_same_text(product, pin, host, shape):
+    """k_root_table, k_root_cell and k_root_gather against tests/root_host.cpp, the same root_table_row, root_cell and root_gather_cell
+    compiled for the CPU behind the same table builder, on the continuous rasters of two seeds and on the edge cases of the tables: the
+    number of table rows, length, depth, first and last root layer, the key, the density of every layer (the rows of the table the cells
+    reach) and the one-layer gather of the layers 1, 5 and the last, bit for bit.  tests/test_root_host.py has run these cases under the
+    sanitizers and shown that they are not vacuous."""
+    _need_glibc_set(product)
+    directory, exe = host
+    cases = [(f"{shape[1]}-{seed}", rc.random_case(pin, shape, seed)) for seed in rc.SEEDS[:2]]
+    if shape == rc.SHAPES[0]:
+        cases += list(rc.edge_cases(pin))
+    for name, case in cases:
+        want = rc.run_host(exe, directory, "gpu-" + name, case)
+        nl = len(case["layer_depth"])
+        root.initialize(product, case["dem"], case["crop_index"], case["soil_index"], case["unit_list"], case["soil_list"], case["layer_depth"],
+                        case["layer_thickness"], float(case["flag"]))
+        assert root.table_rows(product) == want["rows"], name
+        for k, dd in enumerate(case["degree_days"]):
+            root.compute(product, dd)
+            got = dict(root.all_maps(product), key=root.get_keys(product))
+            for n in rc.OUTPUTS + ("key",):
+                g, w = np.asarray(got[n]), want["maps"][k][n]
+                bad = differing(g, w.astype(g.dtype))
+                print(f"{name} map {k} {n}: values differ: {int(bad.sum())}")
+                assert not bad.any(), (name, k, n, int(bad.sum()), g[bad][:4], w[bad][:4])
+            for layer in sorted({min(1, nl - 1), min(5, nl - 1), nl - 1}):                  # layer0 > 0, one layer
+                assert not differing(root.get_density(product, layer), want["maps"][k]["density"][layer]).any(), (name, k, layer)
+        assert np.count_nonzero(want["maps"][0]["length"] > 0) > 0
+        root.clean(product)

@@ -3,7 +3,8 @@ tests/golden/water_sinks.npz: node sinks and both actual maps of every hour bit 
 with NULL maps read from the crop and snow blocks; the nrLayers = 1 case; sf3d_sink_apply against the node-by-node setter and the compute
 call without apply against the run without it (C2's F20 hour); the crop, snow and root blocks undisturbed; two ranks sharing the GPU;
 rasters with a partial block, less than a wave and a single row against the restatement, a column table changed between two hours, and the
-output maps driven alternately with the sink hour under a table that changes."""
+output maps driven alternately with the sink hour under a table that changes; the device against the host build of the same text
+(tests/sink_host.cpp) on continuous cases and on the edges of the tables, bit for bit."""
 import numpy as np
 import pytest
 
@@ -299,3 +300,30 @@ def test_two_ranks_merge_to_the_single_rank_sinks(product, pin, tmp_path):
             assert np.all(res[name][~computed] == flag), (name, r)      # another rank's cells: the flag
     assert [a.shape for a in merged.values()] == [(n,), pin["dem"].shape, pin["dem"].shape] and all(a.dtype == np.float64 for a in merged.values())
     _same(merged, {name: pin[name][which] for name in ("sinks", "evaporation", "transpiration")}, "merged ranks")
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("sink_host")
+    return d, sc.build_host(d)
+
+
+@pytest.mark.parametrize("shape", sc.SHAPES)
+def test_device_equals_the_host_build_of_the_same_text(product, pin, host, shape):
+    """k_sink_hour (behind k_root_table, k_root_cell) against tests/sink_host.cpp fed by tests/root_host.cpp, the same sink_cell<false>
+    compiled for the CPU, on the continuous cases of two seeds and on the edge cases of the tables, cracking off: node sinks and both
+    actual maps of every hour, bit for bit, on the H and Se the device's getters return.  tests/test_sink_host.py has run these cases
+    under the sanitizers and shown that they reach every arm.  (The ownership mask is reached through the rank launcher only: the two-rank
+    tests hold it.)"""
+    _need_glibc_set(product)
+    from tests import crack_cases as kc
+    directory, exes = host
+    cases = [(f"{shape[1]}-{seed}", sc.continuous_case(sc.small_case(pin, shape, seed), seed), False) for seed in sc.SEEDS[:2]]
+    if shape == sc.SHAPES[0]:
+        cases += [(name, case, one_layer) for name, case, one_layer, crack in sc.edge_cases(pin, kc.load_pin())]
+    for name, case, one_layer in cases:
+        state, hours = sc.device_run(product, case, one_layer)
+        for k, got in enumerate(hours):
+            want = sc.run_host(exes, directory, "gpu-" + name, case, k, state, one_layer=one_layer)
+            print(f"{name}, hour {k}: values differ: {sc.compare_host(got, want['plain'], ('sinks', 'evaporation', 'transpiration'), (name, k))}")
+        assert any(np.count_nonzero(got["sinks"]) > 0 for got in hours), name                      # some sinks are non-zero

@@ -2,7 +2,8 @@
 all thirteen maps after every checkpoint hour bit for bit, zero cells excluded; the same run interrupted at hour 48 through get_state /
 set_state and through the application's snow/ state folder; the solver does not notice the calls; a melt hour's liquid water drives the
 product and the oracle to the same state; two ranks sharing the GPU merge to the single-rank maps; the error codes; rasters with a
-partial block, less than a wave and a single row, and a parameter set away from the defaults, against the restatement."""
+partial block, less than a wave and a single row, and a parameter set away from the defaults, against the restatement; and the device against the host build of the same
+text (tests/snow_host.cpp) on continuous forcing, bit for bit."""
 from pathlib import Path
 
 import numpy as np
@@ -14,7 +15,7 @@ from tests import tolerances
 from tests.scenarios import ravone_project_model
 from tests import snow_cases
 from tests.snow_cases import melt_forcing
-from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits as _bits, differing, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -277,3 +278,35 @@ def test_error_paths(product, pin):
     assert lib.sf3d_snow_clean() == capi.OK
     assert lib.sf3d_snow_get_state(0, n, p) == capi.MEMORY_ERROR                                    # after clean
     assert lib.sf3d_snow_compute_hour(n, *seven, None, 0.75) == capi.MEMORY_ERROR
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("snow_host")
+    return d, snow_cases.build_host(d)
+
+
+@pytest.mark.parametrize("shape", snow_cases.SHAPES)
+def test_device_equals_the_host_build_of_the_same_text(product, host, shape):
+    """k_snow_hour against tests/snow_host.cpp, the same snow_cell compiled for the CPU, on the continuous forcing of two seeds (seven hours,
+    the state carried along) under the default and the other parameters, and on one row of eight cells: all thirteen maps after every hour,
+    bit for bit.  tests/test_snow_host.py has run these cases under the sanitizers and shown that they are not vacuous."""
+    _need_glibc_set(product)
+    directory, exe = host
+    cases = [(seed, snow_cases.continuous_forcing(shape, seed), par) for seed in snow_cases.SEEDS[:2] for par in (None, snow_cases.OTHER_PARAMETERS)]
+    if shape == snow_cases.SHAPES[0]:
+        cases.append(("1x8", snow_cases.small_forcing((1, 8), 3), None))
+    for seed, (dem, flag, hours), par in cases:
+        snow.initialize(product, dem, flag, par)
+        start = {n: snow.get_state(product, n) for n in snow.STATE}
+        want = snow_cases.run_host(exe, directory, f"gpu-{shape[1]}-{seed}-{par is not None}", dem, flag, start, hours, par)
+        for h, met in enumerate(hours):
+            snow.compute_hour(product, met)
+            got = snow.all_maps(product)
+            for n in snow.STATE + snow.OUTPUT:
+                bad = differing(got[n], want[h][n])
+                if bad.any() or h == len(hours) - 1:
+                    print(f"raster {dem.shape}, seed {seed}, hour {h} {n}: values differ: {int(bad.sum())}")
+                assert not bad.any(), (shape, seed, h, n, int(bad.sum()), got[n][bad][:4], want[h][n][bad][:4])
+        assert np.count_nonzero(want[1]["swe"] > 0) > 0 and any(np.count_nonzero(w["liquid"] > 0) > 0 for w in want)
+        snow.clean(product)

@@ -1,18 +1,22 @@
 """Root length, depth and density maps, the parts that need no GPU: the ABI of include/sf3d_root.h against the binding, the error codes
 of the entry points, the Python restatement of computeRootLength3D / computeRootDensity3D equal to the compiled-reference pin
 tests/golden/root_density.npz bit for bit, the pin's arms, the root and soil table readers on the Ravone fixtures, the host lunette
-table against the values the pin recorded."""
+table against the values the pin recorded; and the host build of the kernels' text behind the entry point's table builder
+(tests/root_host.cpp): equal to the pin and to the restatement bit for bit, clean under the address and undefined-behaviour sanitizers on
+the edges of the tables."""
 import ctypes
 import json
 import re
 import subprocess
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 from criteria3d_amd import build, capi, crop, project3d as p3, root
 from tests import root_cases as rc
+from tests.raster_helpers import differing
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -193,3 +197,120 @@ def test_root_and_soil_table_readers():
     root.soil_array(soils)
     thick, _ = p3.soil_layers(0.95)
     assert len(thick) <= root.MAX_LAYERS
+
+
+# ---- the host build of the text of k_root_table, k_root_cell and k_root_gather behind sf3d_root_initialize's table builder
+# (tests/root_host.cpp): the text == the pin, the text == the restatement
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("root_host")
+    return SimpleNamespace(dir=d, exe=rc.build_host(d), san=rc.build_host(d, sanitize=True))
+
+
+def _pin_case(pin):
+    return rc.case_of(pin, pin["dem"], pin["crop_index"], pin["soil_index"], pin["degree_days"])
+
+
+def _random_cases(pin):
+    for shape in rc.SHAPES:
+        for seed in rc.SEEDS:
+            for continuous in (False, True):
+                yield f"{'continuous' if continuous else 'lists'}-{shape[0]}x{shape[1]}-{seed}", rc.random_case(pin, shape, seed, continuous)
+
+
+def test_host_text_equals_the_pin_on_every_map(pin, host):
+    """no libm escape: the text carries its own exp; atan2 of the lunette table is the C library's on both sides"""
+    got = rc.run_host(host.exe, host.dir, "pin", _pin_case(pin))
+    assert got["status"] == 0 and len(got["maps"]) == len(pin["degree_days"])
+    for k, maps in enumerate(got["maps"]):
+        for n in rc.OUTPUTS:
+            bad = differing(maps[n], pin[n][k])
+            print(f"host text, map {k} {n}: values differ: {int(bad.sum())}")
+            assert not bad.any(), (k, n, int(bad.sum()), maps[n][bad][:4], pin[n][k][bad][:4])
+    # the gathered layers from layer 3 on are the same maps
+    part = rc.run_host(host.exe, host.dir, "pin-3", _pin_case(pin), layer0=3)
+    for k, maps in enumerate(part["maps"]):
+        assert not differing(maps["density"], pin["density"][k][3:]).any() and not differing(maps["key"], got["maps"][k]["key"]).any(), k
+
+
+def _against_the_restatement(name, case, got, exact):
+    differ = 0
+    for k in range(len(case["degree_days"])):
+        want = rc.restated_case(case, k)
+        for n in rc.OUTPUTS:
+            g, w = got["maps"][k][n], want[n]
+            bad = differing(g, w.astype(g.dtype))
+            differ += int(bad.sum())
+            if exact or g.dtype.kind != "f":
+                assert not bad.any(), (name, k, n, int(bad.sum()), g[bad][:4], w[bad][:4])
+            else:           # another C library under the restatement's exp: the last places of a double
+                assert np.allclose(g, w, rtol=1e-12, atol=1e-12), (name, k, n)
+    print(f"{name}: values differ: {differ}")
+
+
+def test_host_text_equals_the_restatement_on_random_cases(pin, host):
+    from tests import tolerances
+    exact, why = tolerances.libm_probe()
+    print(why)
+    for name, case in _random_cases(pin):
+        got = rc.run_host(host.exe, host.dir, name, case)
+        assert got["status"] == 0
+        _against_the_restatement(name, case, got, exact)
+
+
+def test_random_cases_are_not_vacuous(pin):
+    """from the restatement: roots on ROOTED_SHARE of the cells, in every phase of the growth, with density in the layers"""
+    flag = float(pin["flag"])
+    no_growth = 0
+    for name, case in _random_cases(pin):
+        for k in range(2):
+            m = rc.restated_case(case, k)
+            rooted = (m["length"] > 0) & (m["first"] != int(flag))
+            assert np.count_nonzero(rooted) > rc.ROOTED_SHARE * rooted.size, (name, k)
+            assert np.count_nonzero(m["length"] == flag) > 0, (name, k)                                                 # no cell
+            no_growth += np.count_nonzero(m["length"] == 0)
+            assert np.count_nonzero(m["density"][1:][:, rooted] > 0) > np.count_nonzero(rooted), (name, k)              # more than one layer per rooted cell
+            assert m["length"].flat[-1] > 0, (name, k)                                                                  # the last lane computes
+    assert no_growth > 0                                                                                                # degree days <= 0 on a growing unit
+
+
+def test_sanitized_host_build_reports_nothing(pin, host):
+    """address and undefined-behaviour sanitizers on the pin, on every random case and on the edge cases of the tables (every table a heap
+    block of its own): exit 0, nothing on stderr; and the edge cases reach what they are made for"""
+    from tests import tolerances
+    exact = tolerances.libm_probe()[0]
+    rc.run_host(host.san, host.dir, "san-pin", _pin_case(pin))
+    rc.run_host(host.san, host.dir, "san-pin-3", _pin_case(pin), layer0=3)
+    runs = 2
+    for name, case in _random_cases(pin):
+        assert rc.run_host(host.san, host.dir, "san-" + name, case)["status"] == 0
+        runs += 1
+    sf = capi.load_product()
+    seen = {}
+    for name, case in rc.edge_cases(pin):
+        assert rc.accepted(sf, case), name                             # (a case the API refused would be dropped here)
+        got = rc.run_host(host.san, host.dir, "san-" + name, case)
+        assert got["status"] == 0, name
+        _against_the_restatement(name, case, got, exact)
+        seen[name] = (case, got)
+        runs += 1
+    nl = len(pin["layer_depth"])
+    case, got = seen["caps"]
+    m = got["maps"][0]
+    last_pair = (case["crop_index"] == root.MAX_UNITS - 1) & (case["soil_index"] == len(case["soil_list"]) - 1) & (m["key"] >= 0)
+    assert last_pair.sum() >= 3 and np.count_nonzero(m["key"] == got["rows"] - 1) > 0            # unit 63, the soil of 16 horizons, the last table row
+    assert len(case["soil_list"][-1]["upperDepth"]) == root.MAX_HORIZONS and np.count_nonzero(m["first"][last_pair] == 0) > 0      # firstRootLayer == 0
+    full = got["table"][:, got["rows"] - 1]                            # m = lunetteMax = 100 rooted atoms from the surface down
+    assert full.sum() > 0.9 and got["row_layers"][got["rows"] - 1][0] == 0
+    case, got = seen["clamp"]
+    tops = {k: round(u["rootDepthMin"] / 0.01) for k, u in enumerate(case["unit_list"])}
+    atoms = {k: int(s["totalDepth"] * 100) + 1 for k, s in enumerate(case["soil_list"])}
+    pairs = {(int(c), int(s)) for c, s, d in zip(case["crop_index"].flat, case["soil_index"].flat, case["dem"].flat) if d != np.float32(case["flag"])}
+    assert any(tops[c] >= atoms[s] for c, s in pairs) and any(0 < atoms[s] - tops[c] < round(case["soil_list"][s]["totalDepth"] / 0.01) for c, s in pairs)
+    case, got = seen["deep"]
+    assert np.count_nonzero(got["maps"][0]["last"] == nl - 1) > 0                                # lastRootLayer == nrLayers - 1
+    case, got = seen["one-layer"]
+    assert got["table"].shape[0] == 1 and not got["table"].any() and np.all(got["maps"][0]["first"][got["maps"][0]["key"] >= 0] == int(pin["flag"]))
+    assert seen["1x8"][0]["dem"].shape == (1, 8)
+    print(f"root_host_san: {runs} runs, nothing reported")

@@ -1,17 +1,19 @@
 """The hourly snow model, the parts that need no GPU: the C entry points of include/sf3d_snow.h and the binding table, the error codes a
 call gives before a raster exists, the fixture (a pin of the compiled reference) is not vacuous, the python restatement of the point
 model equals it bit for bit over all 96 hours, the small rasters' forcing of tests/snow_cases.py is not vacuous and reads every parameter,
-the per-node sources of assignPrecipitation, the snow/ state folder."""
+the per-node sources of assignPrecipitation, the snow/ state folder; and the host build of the kernel's per-cell text
+(tests/snow_host.cpp): equal to the pin and to the restatement bit for bit, clean under the address and undefined-behaviour sanitizers."""
 import re
 import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
+import pytest
 
 from criteria3d_amd import build, capi, esri, snow
 from tests import snow_cases
-from tests.raster_helpers import bits as _bits
+from tests.raster_helpers import bits as _bits, differing
 
 ROOT = Path(__file__).resolve().parent.parent
 PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
@@ -207,3 +209,113 @@ def test_state_directory_round_trip(tmp_path):
     assert sorted(got) == sorted(snow.STATE)
     for n in snow.STATE:
         assert np.array_equal(_bits(got[n]), _bits(maps[n])), n
+
+
+# ---- the host build of the per-cell text of k_snow_hour (tests/snow_host.cpp): the text == the pin, the text == the restatement
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("snow_host")
+    return SimpleNamespace(dir=d, exe=snow_cases.build_host(d), san=snow_cases.build_host(d, sanitize=True))
+
+
+def _pin_run():
+    """the pin's start (reset, the hand-edited SWE and surface temperature) and its 96 hours"""
+    z = np.load(PIN)
+    dem, flag = z["dem"], float(z["flag"])
+    state = snow_cases.reset_state(dem, flag)
+    for name, edit in (("swe", z["swe_edit"]), ("surfaceTemp", z["surface_temp_edit"])):
+        state[name] = np.where(edit == np.float32(flag), state[name], edit)
+    inp, clear_sky = z["inputs"], float(z["clear_sky"])
+    hours = [dict({n: inp[h, k] for k, n in enumerate(snow.INPUT)}, clearSkyTransmissivity=clear_sky) for h in range(96)]
+    return z, dem, flag, state, hours
+
+
+def _random_cases():
+    """(name, dem, flag, hours, parameters): small_forcing and continuous_forcing on every shape and seed, the first seed of each also under
+    OTHER_PARAMETERS"""
+    for shape in snow_cases.SHAPES:
+        for seed in snow_cases.SEEDS:
+            for kind, make in (("lists", snow_cases.small_forcing), ("continuous", snow_cases.continuous_forcing)):
+                dem, flag, hours = make(shape, seed)
+                yield f"{kind}-{shape[0]}x{shape[1]}-{seed}", dem, flag, hours, None
+                if seed == snow_cases.SEEDS[0]:
+                    yield f"{kind}-{shape[0]}x{shape[1]}-{seed}-other", dem, flag, hours, snow_cases.OTHER_PARAMETERS
+
+
+def test_host_text_equals_the_pin_at_every_checkpoint(host):
+    """no libm escape: the text carries its own exp, log and pow"""
+    z, dem, flag, state, hours = _pin_run()
+    got = snow_cases.run_host(host.exe, host.dir, "pin", dem, flag, state, hours)
+    names = [str(n) for n in z["map_names"]]
+    assert len(got) == 96
+    for k, cp in enumerate(int(c) for c in z["checkpoints"]):
+        for j, n in enumerate(names):
+            bad = differing(got[cp - 1][n], z["maps"][k][j])
+            print(f"host text, hour {cp} {n}: values differ: {int(bad.sum())}")
+            assert not bad.any(), (cp, n, int(bad.sum()))
+
+
+def _against_the_restatement(got, want, what, exact):
+    for h, (g, w) in enumerate(zip(got, want)):
+        for n in snow.STATE + snow.OUTPUT:
+            bad = differing(g[n], w[n])
+            if bad.any() or h == len(got) - 1:
+                print(f"{what}, hour {h} {n}: values differ: {int(bad.sum())}")
+            if exact:
+                assert not bad.any(), (what, h, n, int(bad.sum()), g[n][bad][:4], w[n][bad][:4])
+            else:           # another C library under the restatement: the last place of a double, far below the float the maps hold
+                assert np.allclose(g[n], w[n], rtol=1e-6, atol=1e-6), (what, h, n)
+
+
+def test_host_text_equals_the_restatement_on_the_pin_and_on_random_cases(host):
+    from tests import tolerances
+    exact, why = tolerances.libm_probe()
+    print(why)
+    z, dem, flag, state, hours = _pin_run()
+    want, s = [], dict(state)
+    for met in hours:
+        s = snow.restate_snow_hour(s, met, dem, flag)
+        want.append(s)
+    _against_the_restatement(snow_cases.run_host(host.exe, host.dir, "pin", dem, flag, state, hours), want, "pin", exact)
+    for name, dem, flag, hours, par in _random_cases():
+        got = snow_cases.run_host(host.exe, host.dir, name, dem, flag, snow_cases.reset_state(dem, flag, par), hours, par)
+        _against_the_restatement(got, snow_cases.restated_run(dem, flag, hours, par), name, exact)
+
+
+def test_continuous_forcing_is_not_vacuous():
+    """the shares tests/test_small_forcing_is_not_vacuous asks of the value lists hold for the continuous hours too, and the seventh hour
+    reaches the invalid point, the free water and both sides of every precipitation threshold"""
+    for shape in snow_cases.SHAPES:
+        for seed in snow_cases.SEEDS:
+            dem, flag, hours = snow_cases.continuous_forcing(shape, seed)
+            fl = np.float32(flag)
+            valid = dem != fl
+            assert len(hours) == 7 and dem.size // 2 < valid.sum() < dem.size
+            run = snow_cases.restated_run(dem, flag, hours)
+            assert all(np.isfinite(m).all() for maps in run for m in maps.values())
+            assert np.count_nonzero(run[1]["swe"][valid] > 0) > valid.sum() // 2 and np.count_nonzero(run[3]["snowMelt"][valid] > 0) > valid.sum() // 2
+            last, out = hours[6], run[6]
+            free = valid & (last["surfaceWater"] > 100)
+            invalid = valid & ((last["airT"] == fl) | (last["prec"] == fl) | (last["globalRad"] == fl) | (last["beamRad"] == fl))
+            assert free.sum() > 0 and invalid.sum() > 0 and np.all(out["swe"][free | invalid] == fl)
+            computed = valid & ~free & ~invalid & (run[5]["swe"] != fl)
+            assert computed.sum() > dem.size // 2 and np.all(out["swe"][computed] != fl)
+            fall, prec = out["snowFall"][computed], last["prec"][computed]
+            assert np.count_nonzero(fall == 0) > 0 and np.count_nonzero((fall > 0) & (fall == prec)) > 0             # all rain, all snow
+            mixed, prec2 = run[2]["snowFall"][valid], hours[2]["prec"][valid]
+            assert np.count_nonzero((mixed > 0) & (mixed < prec2)) > valid.sum() // 2                                   # the third hour: mixed
+            assert np.count_nonzero(last["relHum"][computed] > 100) > 0 and np.count_nonzero(last["windInt"][computed] > 10) > 0
+
+
+def test_sanitized_host_build_reports_nothing(host):
+    """address and undefined-behaviour sanitizers on the pin and on every random case: exit 0, nothing on stderr (run_host_program)"""
+    z, dem, flag, state, hours = _pin_run()
+    snow_cases.run_host(host.san, host.dir, "san-pin", dem, flag, state, hours)
+    runs = 1
+    for name, dem, flag, hours, par in _random_cases():
+        snow_cases.run_host(host.san, host.dir, "san-" + name, dem, flag, snow_cases.reset_state(dem, flag, par), hours, par)
+        runs += 1
+    dem, flag, hours = snow_cases.small_forcing((1, 8), 3)              # one row of eight cells
+    snow_cases.run_host(host.san, host.dir, "san-1x8", dem, flag, snow_cases.reset_state(dem, flag), hours)
+    print(f"snow_host_san: {runs + 1} runs, nothing reported")
