@@ -616,6 +616,34 @@ struct TopoCall {       /* what sf3d_topodist_interpolate adds to a MeteoCall: h
     int32_t kh;
 };
 
+/* ---- air and dew-point temperature with local detrending on the meteo block's raster (sf3d_localdetrend.inc,
+ * include/sf3d_localdetrend.h): one wave per cell, the station table and the cell's selected list in LDS ---- */
+#define LOCALDETREND_MAX_PARAMETERS 6   /* SF3D_LOCALDETREND_MAX_PARAMETERS: lapseRatePiecewise_three_free */
+#define LOCALDETREND_MAX_FIRST_GUESS 31 /* SF3D_LOCALDETREND_MAX_FIRST_GUESS: the most calculateFirstGuessCombinations produces */
+#define LOCALDETREND_TABLE_DOUBLES ((3 + LOCALDETREND_MAX_FIRST_GUESS) * LOCALDETREND_MAX_PARAMETERS)
+struct LocalDetrendSetup {      /* what a call fixes for every cell */
+    const double* table;                /* parametersMin, parametersMax, parametersDelta (LOCALDETREND_MAX_PARAMETERS each), then the first-guess
+                                         * combinations, LOCALDETREND_MAX_PARAMETERS a row */
+    int32_t function, nFirstGuess, minPointsLocal, method, useDetrending;
+    uint32_t minPoints, minPointsStep;  /* unsigned(minPointsLocalDetrending * 1.2f), unsigned(minPoints * 0.8) */
+    float stdDevThreshold, radiusAll, area;     /* radiusAll: computeShepardInitialRadius(area, nStations, minPoints), the host's */
+};
+struct LocalDetrendView {       /* k_localdetrend: k_meteo_idw's view, the stations' heights and the per-cell outcome */
+    MeteoView m;
+    LocalDetrendSetup s;
+    const float* sh;
+    double* parameters;                 /* [nCells][LOCALDETREND_MAX_PARAMETERS] */
+    uint32_t* count;
+    float* radius;
+    float* r2;
+    uint8_t* significant;
+};
+struct LocalDetrendCall {       /* what sf3d_localdetrend_interpolate adds to a MeteoCall: host pointers */
+    LocalDetrendSetup setup;
+    const double* table;                /* LOCALDETREND_TABLE_DOUBLES doubles */
+    const float* height;
+};
+
 /* ---- hourly evaporation, transpiration and rain sinks (sf3d_sink.inc, include/sf3d_sink.h): one thread per raster cell walks its column ---- */
 #define SINK_HORIZON_VALUES 5           /* per horizon: waterContentHH, FC, WP, SAT, getSoilFraction() */
 enum { SINK_H_HH = 0, SINK_H_FC = 1, SINK_H_WP = 2, SINK_H_SAT = 3, SINK_H_FRACTION = 4 };

@@ -110,6 +110,12 @@ struct MeteoCache {
     float* topoMatrix = nullptr;
     uint32_t topoPoints = 0, topoMatrixCap = 0;
     double topoMs[3] = {0., 0., 0.};    /* k_topodist_maps, k_meteo_idw_td, k_topodist_matrix */
+    /* local detrending (sf3d_localdetrend.inc): the per-cell outcome of the last call (parameters: doubles; count: uint32; radius, R2:
+     * floats; significant: bytes - a map each, in this order) and the call's tables (the fit table, then the stations' heights) */
+    char* localFit = nullptr;
+    char* localTables = nullptr;
+    bool localDone = false;
+    double localMs = 0.;
 };
 
 /* hourly radiation maps (sf3d_rad.inc): the five outputs, the static maps of include/sf3d_rad.h and the hour's transmissivity; they belong to

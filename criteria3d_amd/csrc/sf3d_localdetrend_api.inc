@@ -1,0 +1,109 @@
+/* part of sf3d_api.cpp (included after sf3d_topodist_api.inc; it uses the raster and the call checks of sf3d_meteo_api.inc) - the C entry
+ * points of include/sf3d_localdetrend.h.  The host checks the call against the scope of the block before any device work, lays the fit's
+ * ranges and first guesses out as the table the kernel reads, and evaluates what needs the C library's sqrt once per call (the radius of
+ * localSelection where every station is selected); the selection, the fits and the interpolation live on the device
+ * (sf3d_localdetrend.inc). */
+#include "sf3d_localdetrend.h"
+
+static_assert(SF3D_LOCALDETREND_MAX_PARAMETERS == LOCALDETREND_MAX_PARAMETERS && SF3D_LOCALDETREND_MAX_FIRST_GUESS == LOCALDETREND_MAX_FIRST_GUESS,
+              "sf3d_localdetrend.h and sf3d_device.h disagree");
+static_assert(sizeof(sf3d_localdetrend_fit_t) == 24 + (3 + SF3D_LOCALDETREND_MAX_FIRST_GUESS) * SF3D_LOCALDETREND_MAX_PARAMETERS * sizeof(double),
+              "sf3d_localdetrend_fit_t has no padding");
+
+namespace {
+
+/* the number of parameters of a function, 0: unknown */
+int localParameters(int function)
+{
+    return function == SF3D_LOCALDETREND_PIECEWISE_TWO ? 4 : function == SF3D_LOCALDETREND_PIECEWISE_THREE_FREE ? 6 : function == SF3D_LOCALDETREND_PIECEWISE_THREE ? 5 : 0;
+}
+
+/* the checks that need no raster */
+bool localCallOk(int variable, uint32_t nStations, const double* x, const double* y, const float* height, const sf3d_meteo_settings_t* settings,
+                 const sf3d_localdetrend_fit_t* fit)
+{
+    if (!settings || !fit) return false;
+    if (variable != SF3D_METEO_AIR_TEMPERATURE && variable != SF3D_METEO_AIR_DEW_TEMPERATURE) return false;     /* getUseDetrendingVar, project.cpp:3160 */
+    if (!settings->useMultipleDetrending || !settings->useLocalDetrending) return false;
+    if (settings->useTopographicDistance || settings->useKriging || settings->useSupplementalStations || settings->useCrossValidationIndex || settings->updateMinMax)
+        return false;
+    if (settings->nProxies < 0 || settings->nProxies > SF3D_METEO_MAX_PROXIES) return false;
+    int active = 0;
+    for (int p = 0; p < settings->nProxies; ++p) {
+        if (!settings->proxy[p].active) continue;
+        if (!settings->proxy[p].isHeight) return false;
+        ++active;
+    }
+    if (active != 1) return false;
+    const int np = localParameters(fit->function);
+    if (np == 0 || fit->nParameters != np) return false;
+    if (fit->nFirstGuess < 1 || fit->nFirstGuess > SF3D_LOCALDETREND_MAX_FIRST_GUESS || fit->minPointsLocalDetrending < 1) return false;
+    if (std::isnan(fit->stdDevThreshold)) return false;
+    for (int j = 0; j < np; ++j) {
+        if (!std::isfinite(fit->parametersMin[j]) || !std::isfinite(fit->parametersMax[j]) || !std::isfinite(fit->parametersDelta[j])) return false;
+        for (int k = 0; k < fit->nFirstGuess; ++k)
+            if (!std::isfinite(fit->firstGuess[k][j])) return false;
+    }
+    if (nStations > SF3D_METEO_MAX_STATIONS || (nStations > 0 && (!x || !y || !height))) return false;
+    for (uint32_t k = 0; k < nStations; ++k)
+        if (!std::isfinite(x[k]) || !std::isfinite(y[k]) || !std::isfinite(height[k])) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+sf3d_error_t sf3d_localdetrend_interpolate(int variable, int method, uint32_t nStations, const double* x, const double* y, const float* height, const float* value,
+                                           float boundingBoxArea, const sf3d_meteo_settings_t* settings, const sf3d_localdetrend_fit_t* fit, float* out)
+{
+    if (!localCallOk(variable, nStations, x, y, height, settings, fit)) return SF3D_PARAMETER_ERROR;
+    /* the rest of the call is sf3d_meteo_interpolate's, which knows neither option */
+    sf3d_meteo_settings_t plain = *settings;
+    plain.useMultipleDetrending = 0; plain.useLocalDetrending = 0;
+    MeteoCall call;
+    const sf3d_error_t e = meteoPrepare(variable, method, nStations, x, y, value, boundingBoxArea, &plain, false, call);
+    if (e != SF3D_OK) return e;
+    double table[LOCALDETREND_TABLE_DOUBLES] = {0.};
+    const int P = SF3D_LOCALDETREND_MAX_PARAMETERS;
+    for (int j = 0; j < fit->nParameters; ++j) {
+        table[j] = fit->parametersMin[j]; table[P + j] = fit->parametersMax[j]; table[2 * P + j] = fit->parametersDelta[j];
+        for (int k = 0; k < fit->nFirstGuess; ++k) table[(3 + k) * P + j] = fit->firstGuess[k][j];
+    }
+    LocalDetrendCall local{};
+    local.table = table; local.height = height;
+    LocalDetrendSetup& s = local.setup;
+    s.function = fit->function; s.nFirstGuess = fit->nFirstGuess; s.minPointsLocal = fit->minPointsLocalDetrending;
+    s.minPoints = unsigned(fit->minPointsLocalDetrending * 1.2f);           /* interpolation.cpp:1092-1093 */
+    s.minPointsStep = unsigned(s.minPoints * 0.8);                          /* :1150 */
+    s.stdDevThreshold = fit->stdDevThreshold; s.area = boundingBoxArea;
+    /* computeShepardInitialRadius(area, N, minPoints), :1098 with :800-803 */
+    s.radiusAll = float(std::sqrt((s.minPoints * boundingBoxArea) / (float(3.1415926535898) * nStations)));
+    return rasterFail("localdetrend interpolate", dev().localdetrend_interpolate(call, local, mapsOwnedCells((size_t)MT.nRows * MT.nCols), out));
+}
+
+sf3d_error_t sf3d_localdetrend_get_fit(uint32_t nrCells, uint8_t* significant, float* r2, double* parameters)
+{
+    if (!MT.on) return SF3D_MEMORY_ERROR;
+    if (nrCells != MT.nRows * MT.nCols || !dev().localdetrend_done()) return SF3D_PARAMETER_ERROR;
+    return rasterFail("localdetrend get fit", dev().localdetrend_fit(significant, r2, parameters));
+}
+
+sf3d_error_t sf3d_localdetrend_get_selection(uint32_t nrCells, uint32_t* count, float* radius)
+{
+    if (!MT.on) return SF3D_MEMORY_ERROR;
+    if (nrCells != MT.nRows * MT.nCols || !dev().localdetrend_done()) return SF3D_PARAMETER_ERROR;
+    return rasterFail("localdetrend get selection", dev().localdetrend_selection(count, radius));
+}
+
+double sf3d_localdetrend_kernel_ms(void) { return dev().localdetrend_kernel_ms(); }
+
+uint64_t sf3d_localdetrend_bytes(void) { return MT.on ? dev().localdetrend_bytes() : 0; }
+
+sf3d_error_t sf3d_localdetrend_clean(void)
+{
+    (void)dev().localdetrend_free();
+    return SF3D_OK;
+}
+
+} /* extern "C" */

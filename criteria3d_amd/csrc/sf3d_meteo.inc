@@ -68,8 +68,9 @@ template <class Dist> SF3D_METEO_FN float meteo_idw(const Dist& dist, const floa
     return (sumWeights > 0.0) ? (float)(sum / sumWeights) : (float)METEO_NODATA;
 }
 
-/* shepardSearchNeighbour, then shepardIdw (modified == false) or modifiedShepardIdw with radius == NODATA on entry */
-template <class Dist> SF3D_METEO_FN float meteo_shepard(const Dist& dist, const double* sx, const double* sy, const float* sv, uint32_t nStations, float x, float y, float radius0, bool modified)
+/* shepardSearchNeighbour, then shepardIdw (modified == false) or modifiedShepardIdw with radius == NODATA on entry.  sx, sy, sv: the
+ * station table (pointers here; sf3d_localdetrend.inc hands in a cell's selected list, indexed the same way) */
+template <class Dist, class Coord, class Value> SF3D_METEO_FN float meteo_shepard(const Dist& dist, Coord sx, Coord sy, Value sv, uint32_t nStations, float x, float y, float radius0, bool modified)
 {
     float ld[METEO_LIST];
     uint32_t li[METEO_LIST];
@@ -275,7 +276,8 @@ sf3d_error_t DeviceSolver::meteo_free()
 {
     if (!impl_) return SF3D_OK;
     raster_unbind(FEED_METEO);
-    raster_release({impl_->meteo.base, impl_->meteo.stations, impl_->meteo.topoMaps, impl_->meteo.topoTables, impl_->meteo.topoMatrix});       /* the topographic distance maps go with their raster */
+    raster_release({impl_->meteo.base, impl_->meteo.stations, impl_->meteo.topoMaps, impl_->meteo.topoTables, impl_->meteo.topoMatrix,
+                    impl_->meteo.localFit, impl_->meteo.localTables});       /* the topographic distance maps and the local detrending's outcome go with their raster */
     impl_->meteo = MeteoCache();
     return SF3D_OK;
 }

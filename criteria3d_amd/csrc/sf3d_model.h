@@ -255,6 +255,16 @@ public:
     sf3d_error_t topo_matrix(uint32_t nPoints, const double* x, const double* y, const double* z, const int32_t* mapIndex, float* matrix);
     sf3d_error_t topo_free();
     double topo_kernel_ms(int which) const;
+    /* air and dew-point temperature with local detrending on the meteo block's raster (sf3d_localdetrend.inc; the caller has checked that
+     * the raster is there and the call against the caps): the map into the meteo block's slot of the variable, and the per-cell outcome of
+     * the last call (localdetrend_done: it is there).  The outcome goes with the raster (meteo_free). */
+    sf3d_error_t localdetrend_interpolate(const MeteoCall& call, const LocalDetrendCall& local, const uint8_t* mine, float* out);
+    bool localdetrend_done() const;
+    sf3d_error_t localdetrend_fit(uint8_t* significant, float* r2, double* parameters);
+    sf3d_error_t localdetrend_selection(uint32_t* count, float* radius);
+    uint64_t localdetrend_bytes() const;
+    sf3d_error_t localdetrend_free();
+    double localdetrend_kernel_ms() const;
     /* hourly r.sun radiation maps (sf3d_rad.inc): the five outputs and the static maps, independent of the node model as the other raster
      * blocks; transmissivity == nullptr: k_rad_hour reads the map the meteo block holds (the caller asks meteo_produced first) */
     sf3d_error_t rad_alloc(const RadSetup& setup);

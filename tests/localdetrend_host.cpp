@@ -1,0 +1,100 @@
+/* host build of the per-cell text of k_localdetrend (criteria3d_amd/csrc/sf3d_meteo.inc and sf3d_localdetrend.inc: the text the device
+ * compiles, here with one lane) for tests/test_localdetrend_host.py: the pin is checked on a CPU before any device runs the kernel, and
+ * the same program is built once with -fsanitize=address,undefined.
+ *
+ *   localdetrend_host <input> <output>
+ * input : int32 nRows, nCols, nCases; float flag; double xll, yll, cellSize; float dem[nCells];
+ *         per case: int32 var, method, function, nParameters, nFirstGuess, minPointsLocalDetrending, useDetrending, nStations;
+ *                   float stdDevThreshold, area; double table[(3 + 31) * 6] (min, max, delta, the first guesses: six a row);
+ *                   double x[nStations], y[nStations]; float height[nStations], value[nStations].
+ * output: per case float map[nCells]; uint32 count[nCells]; float radius[nCells]; int32 significant[nCells]; float r2[nCells];
+ *         double parameters[nCells][6]. */
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "sf3d_device.h"
+
+#define SF3D_METEO_HOST
+#define SF3D_METEO_FN static inline
+#define SF3D_METEO_MEMBER inline
+#include "sf3d_meteo.inc"
+#include "sf3d_localdetrend.inc"
+
+template <class T> static std::vector<T> readv(FILE* f, size_t n)
+{
+    std::vector<T> v(n);
+    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "localdetrend_host: short input\n"); exit(2); }
+    return v;
+}
+
+template <class T> static void writev(FILE* f, const std::vector<T>& v)
+{
+    if (v.size() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "localdetrend_host: short output\n"); exit(3); }
+}
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) return 2;
+    FILE* in = fopen(argv[1], "rb");
+    FILE* out = fopen(argv[2], "wb");
+    if (!in || !out) return 2;
+    const std::vector<int32_t> dims = readv<int32_t>(in, 3);
+    const float flag = readv<float>(in, 1)[0];
+    const std::vector<double> geo = readv<double>(in, 3);
+    const uint32_t nRows = (uint32_t)dims[0], nCols = (uint32_t)dims[1];
+    const int nCases = dims[2];
+    const size_t n = (size_t)nRows * nCols;
+    const std::vector<float> dem = readv<float>(in, n);
+
+    MeteoView v{};
+    v.dem = dem.data();
+    v.xll = geo[0]; v.yll = geo[1]; v.cellSize = geo[2];
+    v.nCells = (uint32_t)n; v.nRows = nRows; v.nCols = nCols; v.flag = flag;
+
+    for (int k = 0; k < nCases; ++k) {
+        const std::vector<int32_t> iv = readv<int32_t>(in, 8);
+        const std::vector<float> fv = readv<float>(in, 2);
+        const std::vector<double> table = readv<double>(in, LOCALDETREND_TABLE_DOUBLES);
+        const uint32_t m = (uint32_t)iv[7];
+        const std::vector<double> sx = readv<double>(in, m), sy = readv<double>(in, m);
+        const std::vector<float> sh = readv<float>(in, m), sv = readv<float>(in, m);
+        if (m > METEO_MAX_STATIONS || iv[4] < 1 || iv[4] > LOCALDETREND_MAX_FIRST_GUESS) return 2;
+
+        LocalDetrendSetup s{};
+        s.table = table.data();
+        s.function = iv[2]; s.nFirstGuess = iv[4]; s.minPointsLocal = iv[5]; s.method = iv[1]; s.useDetrending = iv[6];
+        s.minPoints = unsigned(iv[5] * 1.2f);
+        s.minPointsStep = unsigned(s.minPoints * 0.8);
+        s.stdDevThreshold = fv[0]; s.area = fv[1];
+        s.radiusAll = float(std::sqrt((s.minPoints * fv[1]) / (float(3.1415926535898) * m)));
+
+        /* the wave's room */
+        std::vector<uint16_t> idx(m + 1);
+        std::vector<float> d(m + 1), val(m + 1), lanes(LD_LANES);
+        std::vector<double> wt(m + 1), fit((size_t)LD_MAX_FIRST_GUESS * LD_FIT_STRIDE);
+        float* h = reinterpret_cast<float*>(wt.data());                /* as in the kernel: weight[i] takes the room of the heights and weights */
+        LdList L{idx.data(), d.data(), h, h + (m + 1), val.data(), wt.data(), lanes.data(), fit.data()};
+        const LdStations st{sx.data(), sy.data(), sh.data(), sv.data(), m};
+
+        std::vector<float> map(n, flag), radius(n, (float)LD_NODATA), r2(n, (float)LD_NODATA);
+        std::vector<uint32_t> count(n, 0);
+        std::vector<int32_t> significant(n, 0);
+        std::vector<double> parameters(n * LD_MAX_PARAMETERS, (double)LD_NODATA);
+        for (uint32_t c = 0; c < n; ++c) {
+            const float z = dem[c];
+            if (meteo_eqf(z, flag)) continue;
+            float x, y;
+            meteo_cell_xy(v, c, x, y);
+            LdOutcome o;
+            map[c] = ld_cell(s, st, L, z, x, y, o);
+            count[c] = o.count; radius[c] = o.radius; significant[c] = o.significant; r2[c] = o.r2;
+            for (int j = 0; j < LD_MAX_PARAMETERS; ++j) parameters[(size_t)c * LD_MAX_PARAMETERS + j] = o.parameters[j];
+        }
+        writev(out, map); writev(out, count); writev(out, radius); writev(out, significant); writev(out, r2); writev(out, parameters);
+    }
+    fclose(in);
+    return fclose(out) == 0 ? 0 : 3;
+}
