@@ -644,6 +644,32 @@ struct LocalDetrendCall {       /* what sf3d_localdetrend_interpolate adds to a 
     const float* height;
 };
 
+/* ---- local detrending with every active proxy (sf3d_localproxies.inc, include/sf3d_localproxies.h): k_localdetrend's mapping, the
+ * stations' values of the other proxies in LDS, the two lists of multipleDetrendingOtherProxiesFitting as membership bits ---- */
+#define LOCALPROXIES_MAX_OTHERS 7       /* SF3D_LOCALPROXIES_MAX_OTHERS: the active proxies that are not the height */
+struct LocalProxiesSetup {      /* what a call fixes for every cell beyond LocalDetrendSetup */
+    int32_t heightSlot;                 /* the slot of the active height proxy, -1: the height is not active */
+    int32_t nOthers;                    /* the active proxies that are not the height */
+    int32_t slot[LOCALPROXIES_MAX_OTHERS];              /* their slots, ascending */
+    float stdDevThreshold[LOCALPROXIES_MAX_OTHERS];
+    double range[LOCALPROXIES_MAX_OTHERS][4];           /* getFittingParametersRange(): min slope, min intercept, max slope, max intercept */
+};
+struct LocalProxiesView {       /* k_localdetrend_proxies: k_localdetrend's view and the block's own */
+    LocalDetrendView d;
+    LocalProxiesSetup p;
+    const float* rows;                  /* [nOthers][METEO_MAX_STATIONS]: the stations' values of the other proxies */
+    double* proxyLine;                  /* [nCells][METEO_MAX_PROXIES][2]: slope, intercept */
+    uint32_t* interpolated;             /* the length of the interpolated list */
+    uint8_t* proxySignificant;          /* [nCells][METEO_MAX_PROXIES] */
+};
+struct LocalProxiesCall {       /* what sf3d_localproxies_interpolate adds to a MeteoCall: host pointers */
+    LocalDetrendSetup setup;
+    LocalProxiesSetup proxies;
+    const double* table;                /* LOCALDETREND_TABLE_DOUBLES doubles */
+    const float* height;                /* the height proxy's row; zeros where the height is not active */
+    const float* rows[LOCALPROXIES_MAX_OTHERS];
+};
+
 /* ---- hourly evaporation, transpiration and rain sinks (sf3d_sink.inc, include/sf3d_sink.h): one thread per raster cell walks its column ---- */
 #define SINK_HORIZON_VALUES 5           /* per horizon: waterContentHH, FC, WP, SAT, getSoilFraction() */
 enum { SINK_H_HH = 0, SINK_H_FC = 1, SINK_H_WP = 2, SINK_H_SAT = 3, SINK_H_FRACTION = 4 };

@@ -116,6 +116,12 @@ struct MeteoCache {
     char* localTables = nullptr;
     bool localDone = false;
     double localMs = 0.;
+    /* local detrending with every proxy (sf3d_localproxies.inc): per cell the proxies' lines (doubles), the interpolated count (uint32)
+     * and the proxies' significance (bytes), in this order; the call's tables (the fit table, the height row, the other proxies' rows) */
+    char* proxiesFit = nullptr;
+    char* proxiesTables = nullptr;
+    bool proxiesDone = false;
+    double proxiesMs = 0.;
 };
 
 /* hourly radiation maps (sf3d_rad.inc): the five outputs, the static maps of include/sf3d_rad.h and the hour's transmissivity; they belong to

@@ -425,16 +425,11 @@ SF3D_METEO_FN uint32_t ld_select(const LdSetup& s, const LdStations& st, const L
     return nrValid;
 }
 
-/* one DEM cell of height z at the float (x, y): the map value; `o`: what the getters return of the cell */
-SF3D_METEO_FN float ld_cell(const LdSetup& s, const LdStations& st, const LdList& L, float z, float x, float y, LdOutcome& o)
+/* multipleDetrendingElevationFitting (interpolation.cpp:1862-1953) and detrendingElevation over the list: proxyValidity (:1418-1457) and
+ * the minimum of elevation points (:1885), then the fit.  Returns whether the height proxy is significant; par: the cell's parameters,
+ * NODATA where it is not; R2: NODATA where no fit ran.  k_localdetrend_proxies (sf3d_localproxies.inc) runs the same text */
+SF3D_METEO_FN bool ld_elevation(const LdSetup& s, const LdList& L, uint32_t n, double* par, double& R2)
 {
-    float radius;
-    const uint32_t n = ld_select(s, st, L, x, y, radius);
-    o.count = n; o.radius = radius; o.significant = 0; o.r2 = (float)LD_NODATA;
-#pragma unroll
-    for (int j = 0; j < LD_MAX_PARAMETERS; ++j) o.parameters[j] = LD_NODATA;
-
-    /* proxyValidity (interpolation.cpp:1418-1457) and the minimum of elevation points (:1885) */
     uint32_t nrData = 0;
     double sum = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -454,17 +449,51 @@ SF3D_METEO_FN float ld_cell(const LdSetup& s, const LdStations& st, const LdList
     }
     valid = valid && nrData >= (uint32_t)s.minPointsLocal;
 
-    double par[LD_MAX_PARAMETERS];
 #pragma unroll
     for (int j = 0; j < LD_MAX_PARAMETERS; ++j) par[j] = LD_NODATA;
-    double R2 = LD_NODATA;
+    R2 = LD_NODATA;
     bool significant = false;
     if (valid) {
         if (s.function == LD_PIECEWISE_TWO) significant = ld_fit<LD_PIECEWISE_TWO, 4>(s, L, n, nrData, par, R2);
         else if (s.function == LD_PIECEWISE_THREE) significant = ld_fit<LD_PIECEWISE_THREE, 5>(s, L, n, nrData, par, R2);
         else significant = ld_fit<LD_PIECEWISE_THREE_FREE, 6>(s, L, n, nrData, par, R2);
-        o.r2 = (float)R2;
     }
+    return significant;
+}
+
+/* the methods of interpolate() (interpolation.cpp:2511-2528) over a list of n stations; radius: localRadius */
+SF3D_METEO_FN float ld_methods(const LdSetup& s, const LdStations& st, const LdList& L, uint32_t n, float radius, float x, float y)
+{
+    if (s.method == METEO_IDW) return meteo_idw(LdListDistance{L.d}, L.val, n);
+    if (s.method == METEO_SHEPARD) {
+        /* computeShepardInitialRadius(area, nrPoints, SHEPARD_AVG_NRPOINTS) with the list's size (interpolation.cpp:812-813) */
+        const float radius0 = __builtin_sqrtf(((float)8u * s.area) / ((float)3.1415926535898 * (float)n));
+        return meteo_shepard(LdListDistance{L.d}, LdCoord{st.sx, L.idx}, LdCoord{st.sy, L.idx}, (const float*)L.val, n, x, y, radius0, false);
+    }
+    return ld_shepard_modified(st, L, n, radius, x, y);
+}
+
+/* the elevation function of the call at the height z */
+SF3D_METEO_FN double ld_height_function(const LdSetup& s, double z, double* par)
+{
+    if (s.function == LD_PIECEWISE_TWO) return ld_func<LD_PIECEWISE_TWO>(z, par);
+    if (s.function == LD_PIECEWISE_THREE) return ld_func<LD_PIECEWISE_THREE>(z, par);
+    return ld_func<LD_PIECEWISE_THREE_FREE>(z, par);
+}
+
+/* one DEM cell of height z at the float (x, y): the map value; `o`: what the getters return of the cell */
+SF3D_METEO_FN float ld_cell(const LdSetup& s, const LdStations& st, const LdList& L, float z, float x, float y, LdOutcome& o)
+{
+    float radius;
+    const uint32_t n = ld_select(s, st, L, x, y, radius);
+    o.count = n; o.radius = radius; o.significant = 0;
+#pragma unroll
+    for (int j = 0; j < LD_MAX_PARAMETERS; ++j) o.parameters[j] = LD_NODATA;
+
+    double par[LD_MAX_PARAMETERS];
+    double R2;
+    const bool significant = ld_elevation(s, L, n, par, R2);
+    o.r2 = (float)R2;
     if (significant) {
         o.significant = 1;
 #pragma unroll
@@ -472,22 +501,14 @@ SF3D_METEO_FN float ld_cell(const LdSetup& s, const LdStations& st, const LdList
     }
 
     /* interpolate() over the list */
-    float result;
-    if (s.method == METEO_IDW) result = meteo_idw(LdListDistance{L.d}, L.val, n);
-    else if (s.method == METEO_SHEPARD) {
-        /* computeShepardInitialRadius(area, nrPoints, SHEPARD_AVG_NRPOINTS) with the list's size (interpolation.cpp:812-813) */
-        const float radius0 = __builtin_sqrtf(((float)8u * s.area) / ((float)3.1415926535898 * (float)n));
-        result = meteo_shepard(LdListDistance{L.d}, LdCoord{st.sx, L.idx}, LdCoord{st.sy, L.idx}, (const float*)L.val, n, x, y, radius0, false);
-    } else result = ld_shepard_modified(st, L, n, radius, x, y);
+    float result = ld_methods(s, st, L, n, radius, x, y);
     if (meteo_eqf(result, (float)LD_NODATA)) return (float)LD_NODATA;
     if (s.useDetrending) {
         /* retrend, interpolation.cpp:1298-1313: float(functionSum(...)) of the cell's height with the cell's parameters */
         double retrendValue = 0.;
         if (significant) {
             double sumOfFunctions = 0.0;
-            if (s.function == LD_PIECEWISE_TWO) sumOfFunctions += ld_func<LD_PIECEWISE_TWO>((double)z, par);
-            else if (s.function == LD_PIECEWISE_THREE) sumOfFunctions += ld_func<LD_PIECEWISE_THREE>((double)z, par);
-            else sumOfFunctions += ld_func<LD_PIECEWISE_THREE_FREE>((double)z, par);
+            sumOfFunctions += ld_height_function(s, (double)z, par);
             retrendValue = (float)sumOfFunctions;
         }
         result += (float)retrendValue;
@@ -559,7 +580,7 @@ sf3d_error_t DeviceSolver::localdetrend_interpolate(const MeteoCall& call, const
     LocalDetrendView v{};
     sf3d_error_t e = meteo_view(call, mine, v.m);
     if (e != SF3D_OK) return e;
-    K.localDone = false;
+    K.localDone = false; K.proxiesDone = false;             /* the outcome of a call of sf3d_localproxies.inc is overwritten */
     if (!K.localFit) RASTER_TRY(hipMalloc((void**)&K.localFit, n * LD_CELL_BYTES));
     if (!K.localTables) RASTER_TRY(hipMalloc((void**)&K.localTables, LD_TABLE_BYTES));
     double* table = (double*)K.localTables;

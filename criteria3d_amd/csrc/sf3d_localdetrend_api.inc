@@ -18,9 +18,9 @@ int localParameters(int function)
     return function == SF3D_LOCALDETREND_PIECEWISE_TWO ? 4 : function == SF3D_LOCALDETREND_PIECEWISE_THREE_FREE ? 6 : function == SF3D_LOCALDETREND_PIECEWISE_THREE ? 5 : 0;
 }
 
-/* the checks that need no raster */
+/* the checks that need no raster; heightOnly: the proxy rule of sf3d_localdetrend.h (sf3d_localproxies_api.inc has its own) */
 bool localCallOk(int variable, uint32_t nStations, const double* x, const double* y, const float* height, const sf3d_meteo_settings_t* settings,
-                 const sf3d_localdetrend_fit_t* fit)
+                 const sf3d_localdetrend_fit_t* fit, bool heightOnly = true)
 {
     if (!settings || !fit) return false;
     if (variable != SF3D_METEO_AIR_TEMPERATURE && variable != SF3D_METEO_AIR_DEW_TEMPERATURE) return false;     /* getUseDetrendingVar, project.cpp:3160 */
@@ -29,12 +29,12 @@ bool localCallOk(int variable, uint32_t nStations, const double* x, const double
         return false;
     if (settings->nProxies < 0 || settings->nProxies > SF3D_METEO_MAX_PROXIES) return false;
     int active = 0;
-    for (int p = 0; p < settings->nProxies; ++p) {
+    for (int p = 0; heightOnly && p < settings->nProxies; ++p) {
         if (!settings->proxy[p].active) continue;
         if (!settings->proxy[p].isHeight) return false;
         ++active;
     }
-    if (active != 1) return false;
+    if (heightOnly && active != 1) return false;
     const int np = localParameters(fit->function);
     if (np == 0 || fit->nParameters != np) return false;
     if (fit->nFirstGuess < 1 || fit->nFirstGuess > SF3D_LOCALDETREND_MAX_FIRST_GUESS || fit->minPointsLocalDetrending < 1) return false;
@@ -48,6 +48,22 @@ bool localCallOk(int variable, uint32_t nStations, const double* x, const double
     for (uint32_t k = 0; k < nStations; ++k)
         if (!std::isfinite(x[k]) || !std::isfinite(y[k]) || !std::isfinite(height[k])) return false;
     return true;
+}
+
+/* the table the kernel reads (LOCALDETREND_TABLE_DOUBLES doubles, zeroed by the caller) and what the call fixes for every cell */
+void localSetup(const sf3d_localdetrend_fit_t* fit, uint32_t nStations, float boundingBoxArea, double* table, LocalDetrendSetup& s)
+{
+    const int P = SF3D_LOCALDETREND_MAX_PARAMETERS;
+    for (int j = 0; j < fit->nParameters; ++j) {
+        table[j] = fit->parametersMin[j]; table[P + j] = fit->parametersMax[j]; table[2 * P + j] = fit->parametersDelta[j];
+        for (int k = 0; k < fit->nFirstGuess; ++k) table[(3 + k) * P + j] = fit->firstGuess[k][j];
+    }
+    s.function = fit->function; s.nFirstGuess = fit->nFirstGuess; s.minPointsLocal = fit->minPointsLocalDetrending;
+    s.minPoints = unsigned(fit->minPointsLocalDetrending * 1.2f);           /* interpolation.cpp:1092-1093 */
+    s.minPointsStep = unsigned(s.minPoints * 0.8);                          /* :1150 */
+    s.stdDevThreshold = fit->stdDevThreshold; s.area = boundingBoxArea;
+    /* computeShepardInitialRadius(area, N, minPoints), :1098 with :800-803 */
+    s.radiusAll = float(std::sqrt((s.minPoints * boundingBoxArea) / (float(3.1415926535898) * nStations)));
 }
 
 }  // namespace
@@ -65,20 +81,9 @@ sf3d_error_t sf3d_localdetrend_interpolate(int variable, int method, uint32_t nS
     const sf3d_error_t e = meteoPrepare(variable, method, nStations, x, y, value, boundingBoxArea, &plain, false, call);
     if (e != SF3D_OK) return e;
     double table[LOCALDETREND_TABLE_DOUBLES] = {0.};
-    const int P = SF3D_LOCALDETREND_MAX_PARAMETERS;
-    for (int j = 0; j < fit->nParameters; ++j) {
-        table[j] = fit->parametersMin[j]; table[P + j] = fit->parametersMax[j]; table[2 * P + j] = fit->parametersDelta[j];
-        for (int k = 0; k < fit->nFirstGuess; ++k) table[(3 + k) * P + j] = fit->firstGuess[k][j];
-    }
     LocalDetrendCall local{};
     local.table = table; local.height = height;
-    LocalDetrendSetup& s = local.setup;
-    s.function = fit->function; s.nFirstGuess = fit->nFirstGuess; s.minPointsLocal = fit->minPointsLocalDetrending;
-    s.minPoints = unsigned(fit->minPointsLocalDetrending * 1.2f);           /* interpolation.cpp:1092-1093 */
-    s.minPointsStep = unsigned(s.minPoints * 0.8);                          /* :1150 */
-    s.stdDevThreshold = fit->stdDevThreshold; s.area = boundingBoxArea;
-    /* computeShepardInitialRadius(area, N, minPoints), :1098 with :800-803 */
-    s.radiusAll = float(std::sqrt((s.minPoints * boundingBoxArea) / (float(3.1415926535898) * nStations)));
+    localSetup(fit, nStations, boundingBoxArea, table, local.setup);
     return rasterFail("localdetrend interpolate", dev().localdetrend_interpolate(call, local, mapsOwnedCells((size_t)MT.nRows * MT.nCols), out));
 }
 

@@ -265,6 +265,17 @@ public:
     uint64_t localdetrend_bytes() const;
     sf3d_error_t localdetrend_free();
     double localdetrend_kernel_ms() const;
+    /* the same with every active proxy (sf3d_localproxies.inc): the elevation's outcome goes where localdetrend_interpolate leaves its
+     * own, the interpolated count and the proxies' lines (slope, intercept per slot) are this block's; meteo_has_map: the block holds a
+     * raster for the proxy slot */
+    sf3d_error_t localproxies_interpolate(const MeteoCall& call, const LocalProxiesCall& local, const uint8_t* mine, float* out);
+    bool localproxies_done() const;
+    bool meteo_has_map(uint32_t proxy) const;
+    sf3d_error_t localproxies_interpolated(uint32_t* count);
+    sf3d_error_t localproxies_fit(uint8_t* significant, double* lines);
+    uint64_t localproxies_bytes() const;
+    sf3d_error_t localproxies_free();
+    double localproxies_kernel_ms() const;
     /* hourly r.sun radiation maps (sf3d_rad.inc): the five outputs and the static maps, independent of the node model as the other raster
      * blocks; transmissivity == nullptr: k_rad_hour reads the map the meteo block holds (the caller asks meteo_produced first) */
     sf3d_error_t rad_alloc(const RadSetup& setup);

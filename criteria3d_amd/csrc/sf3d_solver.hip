@@ -53,6 +53,7 @@
 #include "sf3d_meteo.inc"
 #include "sf3d_topodist.inc"
 #include "sf3d_localdetrend.inc"
+#include "sf3d_localproxies.inc"
 #include "sf3d_sink.inc"
 #include "sf3d_rad.inc"
 #include "sf3d_transmissivity.inc"

@@ -1,0 +1,205 @@
+"""What tests/test_localproxies_host.py, tests/test_gpu_localproxies.py, tests/golden/make_localproxies.py and
+scripts/multirank_localproxies_worker.py share (no tests here): the pin tests/golden/localproxies.npz decoded into its two rasters with
+their proxy rasters, cases and recorded outcomes; the file format of the host build of the per-cell text (tests/localproxies_host.cpp),
+which the pin's driver reads and writes too; and the calls of a case through the binding and through the restatement.
+
+A raster carries SLOTS proxy slots: slot 0 is the height (no raster of its own: the DEM), slots 1 .. 7 hold the synthetic rasters.  A
+case says which slots are active, the stations' value of every slot, and range and threshold of every slot that is not the height."""
+import json
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+from criteria3d_amd import localdetrend as ld, localproxies as lp, meteo
+from tests import localdetrend_cases as lc
+
+ROOT = Path(__file__).resolve().parent.parent
+PIN = ROOT / "tests" / "golden" / "localproxies.npz"
+RASTERS = ("relief", "tiny")
+SLOTS = meteo.MAX_PROXIES
+PORT = 29803                                    # the two-rank test's (clear of tests/ranks.py's table and of the other blocks' ports)
+QUANTITIES = ("value", "count", "interpolated", "radius", "significant", "r2", "parameters", "proxy_significant", "slope", "intercept")
+bits = lc.bits
+
+
+def proxies_of(c) -> list:
+    return [dict(active=int(a), isHeight=int(k == 0)) for k, a in enumerate(c["active"])]
+
+
+def maps_of(r) -> list:
+    """the rasters of meteo.initialize: None in the height's slot"""
+    return [None] + [r["maps"][k] for k in range(1, SLOTS)]
+
+
+def load_pin():
+    z = np.load(PIN)
+    p = {k: z[k] for k in z.files}
+    out = dict(flag=np.float32(p["flag"]), arms=dict(zip((str(n) for n in p["arm_names"]), (int(c) for c in p["arm_counts"]))), notes=json.loads(str(p["notes"])))
+    for name in RASTERS:
+        geo = p[f"{name}_geo"]
+        r = dict(name=name, dem=p[f"{name}_dem"], maps=p[f"{name}_maps"], xll=float(geo[0]), yll=float(geo[1]), cell_size=float(geo[2]), flag=out["flag"], cases=[])
+        for k, c in enumerate(json.loads(str(p[f"{name}_cases"]))):
+            g = lambda key: p[f"{name}_c{k}_{key}"]
+            n_par = len(c["fit"]["min"])
+            par = np.full(r["dem"].shape + (ld.MAX_PARAMETERS,), ld.NODATA, np.float64)
+            par[..., :n_par] = g("par")
+            c.update(x=g("x"), y=g("y"), proxy_values=g("pv"), value=g("v"), area=np.float32(c["area"]),
+                     want=dict(value=g("map"), count=g("count").astype(np.uint32), interpolated=g("interp").astype(np.uint32), radius=g("radius"),
+                               significant=g("sig").astype(bool), r2=g("r2"), parameters=par, proxy_significant=g("psig").astype(bool), slope=g("slope"),
+                               intercept=g("icpt")))
+            r["cases"].append(c)
+        out[name] = r
+    return out
+
+
+def case_name(c) -> str:
+    active = "".join(str(int(a)) for a in c["active"])
+    return f"{c['label']}-{meteo.VARIABLES[c['var']]}-{meteo.METHODS[c['method']]}-{ld.FUNCTIONS[c['fit']['function']]}-min{c['fit']['minPointsLocalDetrending']}-{active}"
+
+
+def same(got: dict, want: dict, what: str, quantities=QUANTITIES) -> None:
+    """every recorded quantity bit for bit; NaN in R2 is compared as 'both NaN'"""
+    for q in quantities:
+        a, b = np.asarray(got[q]), np.asarray(want[q])
+        assert a.shape == b.shape, (what, q, a.shape, b.shape)
+        if q == "r2":
+            bad = (bits(a) != bits(b)) & ~(np.isnan(a) & np.isnan(b))
+        elif q in ("parameters", "slope", "intercept"):
+            bad = (a.view(np.uint64) != b.view(np.uint64)) & ~(np.isnan(a) & np.isnan(b))
+        elif q in ("count", "interpolated", "significant", "proxy_significant"):
+            bad = a != b
+        else:
+            bad = bits(a) != bits(b)
+        assert not bad.any(), (what, q, int(bad.sum()), np.argwhere(bad)[:4].tolist(), a[bad][:4], b[bad][:4])
+
+
+def restated(r, c, mine=None, arms=None) -> dict:
+    return lp.restate_interpolate(r["dem"], r["xll"], r["yll"], r["cell_size"], maps_of(r), c["var"], c["method"], c["x"], c["y"], c["value"], c["proxy_values"],
+                                  c["area"], c["fit"], proxies_of(c), c["others"], dict(useDetrending=c["useDetrending"]), float(r["flag"]), mine, arms)
+
+
+def initialize(sf, r) -> None:
+    meteo.initialize(sf, r["dem"], r["xll"], r["yll"], r["cell_size"], maps_of(r), float(r["flag"]))
+
+
+def interpolate(sf, c, download=True):
+    return lp.interpolate(sf, c["var"], c["method"], c["x"], c["y"], c["value"], c["proxy_values"], c["area"], c["fit"], proxies_of(c), c["others"],
+                          dict(useDetrending=c["useDetrending"]), download)
+
+
+def outcome(sf, value) -> dict:
+    """the map with what the getters return of the last call, by the names of QUANTITIES"""
+    return dict(value=value, interpolated=lp.get_interpolated(sf), **ld.get_selection(sf), **ld.get_fit(sf), **lp.get_proxy_fit(sf))
+
+
+def default_others(threshold=ld.NODATA) -> list:
+    """the reference's default range of a proxy without one ({-1, -40, 1, 50}, interpolationSettings.cpp:251) in every slot beside the height's"""
+    return lp.make_others([None] + [dict(range=[-1.0, -40.0, 1.0, 50.0], stdDevThreshold=threshold)] * (SLOTS - 1))
+
+
+def synthetic_rasters(shape, rng) -> np.ndarray:
+    """SLOTS rasters on `shape` (slot 0 unused): a plane, a patchy 0 / fraction map with flag holes, a bounded index, and four more of the
+    three kinds"""
+    rows, cols = shape
+    r, c = np.mgrid[0:rows, 0:cols]
+    maps = np.zeros((SLOTS,) + shape, np.float32)
+    maps[1] = np.round(2.0 + 0.45 * c + 0.3 * r, 2)                                           # sea distance [km]: a plane
+    urban = np.where(rng.uniform(size=shape) < 0.45, np.round(rng.uniform(0.05, 1.0, shape), 2), 0.0)
+    maps[2] = urban
+    maps[3] = np.round(np.sin(0.7 * c) * np.cos(0.9 * r), 3)                                  # a bounded index
+    maps[4] = np.round(1.0 / (1.0 + np.exp(-(c - cols / 2.0) / 3.0)), 3)                       # water index
+    maps[5] = np.round(30.0 - 0.6 * c + 0.8 * r, 2)                                           # another plane
+    maps[6] = np.where(rng.uniform(size=shape) < 0.3, np.round(rng.uniform(0.1, 1.0, shape), 2), 0.0)
+    maps[7] = np.round(np.cos(0.4 * c + 0.5 * r), 3)
+    return maps.astype(np.float32)
+
+
+def synthetic(n_stations: int, min_points_local: int, method: int, n_others: int, seed: int = 11) -> tuple:
+    """(raster, case) away from the pin: the 3 x 11 raster of localdetrend_cases.synthetic with proxy rasters, `n_stations` stations and
+    `n_others` other proxies active beside the height; the stations' proxy values have trends in them, some are 0 and a few NODATA"""
+    r, c = lc.synthetic(n_stations, min_points_local, method)
+    rng = np.random.default_rng(seed + n_stations + n_others)
+    r["maps"] = synthetic_rasters(r["dem"].shape, rng)
+    r["maps"][2][0, 3] = r["flag"]
+    pv = np.zeros((SLOTS, n_stations), np.float32)
+    pv[0] = c.pop("height")
+    t = c["value"].astype(np.float64)
+    for k in range(1, SLOTS):
+        if k in (2, 6):
+            v = np.where(rng.uniform(size=n_stations) < 0.5, np.round(rng.uniform(0.05, 1.0, n_stations), 2), 0.0)
+        else:
+            v = np.round(rng.uniform(0.0, 40.0, n_stations), 2)
+        pv[k] = v
+        t = t + (0.03 * k) * v * (1 if k % 2 else -1)
+    pv[1][5::17] = np.float32(ld.NODATA)
+    pv[3][2::23] = np.float32(ld.NODATA)
+    c["value"] = np.round(t, 1).astype(np.float32)
+    c["proxy_values"] = pv
+    c["active"] = [1] + [1] * n_others + [0] * (SLOTS - 1 - n_others)
+    c["others"] = default_others()
+    return r, c
+
+
+# ---- the file format of tests/localproxies_host.cpp (its header comment)
+
+def write_input(path, r, cases) -> None:
+    with open(path, "wb") as f:
+        np.array([r["dem"].shape[0], r["dem"].shape[1], len(cases)], np.int32).tofile(f)
+        np.array([r["flag"]], np.float32).tofile(f)
+        np.array([r["xll"], r["yll"], r["cell_size"]], np.float64).tofile(f)
+        r["dem"].astype(np.float32).tofile(f)
+        np.asarray(r["maps"], np.float32).tofile(f)
+        for c in cases:
+            fit = c["fit"]
+            np.array([c["var"], c["method"], fit["function"], len(fit["min"]), len(fit["first_guess"]), fit["minPointsLocalDetrending"], c["useDetrending"], len(c["x"])],
+                     np.int32).tofile(f)
+            np.array(c["active"], np.int32).tofile(f)
+            np.array([fit["stdDevThreshold"], c["area"]], np.float32).tofile(f)
+            np.array([o["stdDevThreshold"] for o in c["others"]], np.float32).tofile(f)
+            np.array([list(o["min"]) + list(o["max"]) for o in c["others"]], np.float64).tofile(f)
+            lc.fit_table(fit).tofile(f)
+            np.asarray(c["x"], np.float64).tofile(f)
+            np.asarray(c["y"], np.float64).tofile(f)
+            np.asarray(c["proxy_values"], np.float32).tofile(f)
+            np.asarray(c["value"], np.float32).tofile(f)
+
+
+def read_output(path, r, cases) -> list:
+    raw = np.fromfile(path, np.uint8)
+    shape, cells = r["dem"].shape, r["dem"].size
+    pos, out = 0, []
+
+    def take(count, dtype, tail=()):
+        nonlocal pos
+        size = count * np.dtype(dtype).itemsize
+        a = raw[pos:pos + size].view(dtype).copy()
+        pos += size
+        return a.reshape(shape + tail)
+    for _ in cases:
+        out.append(dict(value=take(cells, np.float32), count=take(cells, np.uint32), interpolated=take(cells, np.uint32), radius=take(cells, np.float32),
+                        significant=take(cells, np.int32).astype(bool), r2=take(cells, np.float32),
+                        parameters=take(cells * ld.MAX_PARAMETERS, np.float64, (ld.MAX_PARAMETERS,)),
+                        proxy_significant=take(cells * SLOTS, np.int32, (SLOTS,)).astype(bool), slope=take(cells * SLOTS, np.float64, (SLOTS,)),
+                        intercept=take(cells * SLOTS, np.float64, (SLOTS,))))
+    assert pos == raw.size, (pos, raw.size)
+    return out
+
+
+def build_host(directory, sanitize=False) -> Path:
+    """tests/localproxies_host.cpp with the flags of the product's host side (no FMA contraction); sanitize: address and undefined behaviour"""
+    exe = Path(directory) / ("localproxies_host_san" if sanitize else "localproxies_host")
+    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wno-unknown-pragmas", *extra, f"-I{ROOT / 'include'}", f"-I{ROOT / 'criteria3d_amd' / 'csrc'}",
+                    str(ROOT / "tests" / "localproxies_host.cpp"), "-o", str(exe), "-lm"], check=True)
+    return exe
+
+
+def run_host(exe, r, directory, cases=None) -> list:
+    """the host program on one raster -> the outcome of every case"""
+    cases = r["cases"] if cases is None else cases
+    src, dst = Path(directory) / f"{r['name']}.in", Path(directory) / f"{r['name']}.out"
+    write_input(src, r, cases)
+    res = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True)
+    assert res.returncode == 0 and not res.stderr, (res.returncode, res.stderr[-2000:])
+    return read_output(dst, r, cases)

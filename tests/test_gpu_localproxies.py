@@ -1,0 +1,141 @@
+"""Local detrending with every proxy on the device (include/sf3d_localproxies.h) against the compiled-reference pin
+tests/golden/localproxies.npz and the restatement of criteria3d_amd/localproxies.py: every case of the pin in every cell and every
+recorded quantity, the cases of the pin of the height alone through the new entry point, the meteo block's slot, the same bits twice, the
+life of the per-cell outcome, two ranks, and lists longer than a wave."""
+import numpy as np
+import pytest
+
+from criteria3d_amd import capi, hour, localdetrend as ld, localproxies as lp, meteo
+from tests import localdetrend_cases as lc
+from tests import localproxies_cases as pc
+from tests import ranks as mr
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return pc.load_pin()
+
+
+def _same(got, want, what):
+    bad = pc.bits(got) != pc.bits(want)
+    assert not bad.any(), (what, int(bad.sum()), np.asarray(got)[bad][:4], np.asarray(want)[bad][:4])
+
+
+@pytest.mark.parametrize("name", pc.RASTERS)
+def test_every_case_equals_the_pin_in_every_cell_and_quantity(product, pin, name):
+    r = pin[name]
+    pc.initialize(product, r)
+    flag = r["flag"]
+    for k, c in enumerate(r["cases"]):
+        what = f"{name} {k} {pc.case_name(c)}"
+        got = pc.interpolate(product, c)
+        pc.same(pc.outcome(product, got), c["want"], what)
+        _same(meteo.get_map(product, c["var"]), c["want"]["value"], f"{what}: the meteo block's slot")
+        assert (got[r["dem"] == flag] == flag).all()
+    assert lp.bytes_held(product) > r["dem"].size * (meteo.MAX_PROXIES * 17 + 4)
+    lp.clean(product)
+    assert lp.bytes_held(product) == 0
+    meteo.clean(product)
+
+
+@pytest.mark.parametrize("name", lc.RASTERS)
+def test_the_pin_of_the_height_alone_through_the_new_entry_point(product, name):
+    """the cases of tests/golden/localdetrend.npz with no other proxy active: k_localdetrend_proxies gives the bits k_localdetrend is held to"""
+    r = lc.load_pin()[name]
+    lc.initialize(product, r)
+    for k, c in enumerate(r["cases"]):
+        got = lp.interpolate(product, c["var"], c["method"], c["x"], c["y"], c["value"], c["height"][None, :], c["area"], c["fit"], [dict(active=1, isHeight=1)],
+                             pc.default_others()[:1], dict(useDetrending=c["useDetrending"]))
+        lc.same(dict(value=got, **ld.get_selection(product), **ld.get_fit(product)), c["want"], f"{name} {k} {lc.case_name(c)}")
+        assert (lp.get_interpolated(product) == c["want"]["count"]).all() and not lp.get_proxy_fit(product)["proxy_significant"].any()
+    meteo.clean(product)
+
+
+def test_two_calls_give_the_same_bits(product, pin):
+    r = pin["relief"]
+    pc.initialize(product, r)
+    c = next(c for c in r["cases"] if c["label"] == "cap")
+    first = pc.outcome(product, pc.interpolate(product, c))
+    other = next(c for c in r["cases"] if c["label"] == "two")
+    pc.interpolate(product, other)                                          # another call in between leaves nothing behind
+    second = pc.outcome(product, pc.interpolate(product, c))
+    pc.same(second, first, "the second call")
+    meteo.clean(product)
+
+
+def test_the_map_counts_as_produced_and_the_outcome_goes_with_the_raster(product, pin):
+    r = pin["tiny"]                                                         # its maps are temperatures the humidity formula takes
+    pc.initialize(product, r)
+    hour.bind(product)
+    with pytest.raises(capi.SF3DError):                                     # neither temperature map has been produced yet
+        hour.relative_humidity(product)
+    with pytest.raises(capi.SF3DError):                                     # no call yet: nothing to get
+        lp.get_proxy_fit(product)
+    air_case = next(c for c in r["cases"] if c["label"] == "four")
+    dew_case = next(c for c in r["cases"] if c["label"] == "one")
+    assert pc.interpolate(product, air_case, download=False) is None
+    dew = pc.interpolate(product, dew_case)
+    _same(meteo.get_map(product, "airT"), air_case["want"]["value"], "the air temperature stayed in its slot")
+    rh = hour.relative_humidity(product)                                    # reads both slots in place: accepted as produced
+    _same(rh, hour.restate_relative_humidity(air_case["want"]["value"], dew, float(r["flag"])), "relative humidity from the two slots")
+    # a call of the height alone overwrites the elevation's outcome: the proxies' getters are refused until the next call of this block
+    ld.interpolate(product, "airT", air_case["method"], air_case["x"], air_case["y"], air_case["proxy_values"][0], air_case["value"], air_case["area"], air_case["fit"])
+    with pytest.raises(capi.SF3DError):
+        lp.get_interpolated(product)
+    # an active proxy without a raster is refused
+    meteo.initialize(product, r["dem"], r["xll"], r["yll"], r["cell_size"], [None, None] + pc.maps_of(r)[2:], float(r["flag"]))
+    with pytest.raises(capi.SF3DError):
+        pc.interpolate(product, next(c for c in r["cases"] if c["label"] == "one"))
+    # after sf3d_meteo_clean the getters and the call are refused, not launched on a freed pointer
+    pc.initialize(product, r)
+    pc.interpolate(product, air_case)
+    meteo.clean(product)
+    assert lp.bytes_held(product) == 0
+    for refused in (lambda: lp.get_proxy_fit(product), lambda: lp.get_interpolated(product), lambda: ld.get_fit(product), lambda: pc.interpolate(product, air_case)):
+        with pytest.raises(capi.SF3DError):
+            refused()
+    # a second sf3d_meteo_initialize drops the outcome too
+    pc.initialize(product, r)
+    pc.interpolate(product, air_case)
+    pc.initialize(product, r)
+    with pytest.raises(capi.SF3DError):
+        lp.get_interpolated(product)
+    pc.same(pc.outcome(product, pc.interpolate(product, air_case)), air_case["want"], "on the new raster")
+    meteo.clean(product)
+
+
+def test_two_ranks_merge_to_the_single_rank_map(product, pin, tmp_path):
+    r = pin["relief"]
+    which = next(k for k, c in enumerate(r["cases"]) if c["label"] == "four")
+    ranks = mr.run("scripts/multirank_localproxies_worker.py", 2, pc.PORT, [which], tmp_path)
+    rows, cols = r["dem"].shape
+    idx = np.arange(rows * cols).reshape(rows, cols)                        # the surface node of every cell of catchment_model(cols, rows, 4)
+    cell_owner = mr.cell_owner(ranks, idx, rows * cols * 4)
+    flag = np.float32(r["flag"])
+    want = r["cases"][which]["want"]
+    for k, res in enumerate(ranks):
+        _same(res["got"], res["map"], f"rank {k} getter")
+        other = (cell_owner != k) & (cell_owner >= 0)
+        assert (res["map"][other] == flag).all() and (res["interpolated"][other] == 0).all() and (res["slope"][other] == ld.NODATA).all(), \
+            f"rank {k}: another rank's cells hold the flag"
+    _same(mr.merge([res["map"] for res in ranks], cell_owner, flag, others=flag, what="map"), want["value"], "merged ranks")
+    merged = mr.merge([res["interpolated"].astype(np.float32) for res in ranks], cell_owner, np.float32(0), others=np.float32(0), what="interpolated")
+    assert (merged == want["interpolated"]).all()
+
+
+@pytest.mark.parametrize("others", [2, lp.MAX_OTHERS], ids=lambda v: f"others{v}")
+@pytest.mark.parametrize("stations,min_points_local", [(70, 60), (150, 60)], ids=lambda v: str(v))
+def test_lists_longer_than_a_wave_against_the_restatement(product, stations, min_points_local, others):
+    """70 stations, all selected: lists of 70, the prunings' compaction over two ballots; 150: rings that select more than 64 stations.  Two
+    other proxies: five matrix entries and two gradients, a lane each; the cap: 119 entries, two a lane.  33 cells: a last block of one wave"""
+    r, c = pc.synthetic(stations, min_points_local, meteo.SHEPARD_MODIFIED, others)
+    pc.initialize(product, r)
+    got = pc.outcome(product, pc.interpolate(product, c))
+    want = pc.restated(r, c)
+    pc.same(got, want, f"{stations} stations, {others} other proxies")
+    inside = r["dem"] != r["flag"]
+    assert want["count"][inside].min() > 64 and want["proxy_significant"][inside].sum() >= others * inside.sum() // 2
+    assert (want["interpolated"][inside] < want["count"][inside]).all() and want["interpolated"][inside].min() > 32
+    meteo.clean(product)
