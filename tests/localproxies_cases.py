@@ -1,7 +1,10 @@
 """What tests/test_localproxies_host.py, tests/test_gpu_localproxies.py, tests/golden/make_localproxies.py and
 scripts/multirank_localproxies_worker.py share (no tests here): the pin tests/golden/localproxies.npz decoded into its two rasters with
 their proxy rasters, cases and recorded outcomes; the file format of the host build of the per-cell text (tests/localproxies_host.cpp),
-which the pin's driver reads and writes too; and the calls of a case through the binding and through the restatement.
+which the pin's driver reads and writes too; the calls of a case through the binding and through the restatement; and, away from the pin,
+`synthetic` with the table OFF_PIN of its arguments: one to seven other proxies all significant (5, 14, 27, 44, 65, 90, 119 entries of the
+normal matrix and the gradient) on lists of 14 to 31 and of 70, the three-piece functions and an inactive height under them, and mixed
+significance on lists of 70 and of 122 to 131.
 
 A raster carries SLOTS proxy slots: slot 0 is the height (no raster of its own: the DEM), slots 1 .. 7 hold the synthetic rasters.  A
 case says which slots are active, the stations' value of every slot, and range and threshold of every slot that is not the height."""
@@ -115,10 +118,13 @@ def synthetic_rasters(shape, rng) -> np.ndarray:
     return maps.astype(np.float32)
 
 
-def synthetic(n_stations: int, min_points_local: int, method: int, n_others: int, seed: int = 11) -> tuple:
-    """(raster, case) away from the pin: the 3 x 11 raster of localdetrend_cases.synthetic with proxy rasters, `n_stations` stations and
-    `n_others` other proxies active beside the height; the stations' proxy values have trends in them, some are 0 and a few NODATA"""
-    r, c = lc.synthetic(n_stations, min_points_local, method)
+def synthetic(n_stations: int, min_points_local: int, method: int, n_others: int, seed: int = 11, function: int = ld.PIECEWISE_TWO, guesses: int | None = 2,
+              height_seed: int = 7, height_active: bool = True, thresholds=None, spoil=None) -> tuple:
+    """(raster, case) away from the pin: the 3 x 11 raster of localdetrend_cases.synthetic(.., function, guesses, height_seed) with proxy
+    rasters, `n_stations` stations and `n_others` other proxies active beside the height; the stations' proxy values have trends in them,
+    some are 0 and a few NODATA.  thresholds: {slot: stdDevThreshold}; spoil: {slot: "nodata" (four stations keep a value: too few for
+    proxyValidity) or "constant" (one value everywhere: with a threshold, no deviation)}"""
+    r, c = lc.synthetic(n_stations, min_points_local, method, function, guesses, height_seed)
     rng = np.random.default_rng(seed + n_stations + n_others)
     r["maps"] = synthetic_rasters(r["dem"].shape, rng)
     r["maps"][2][0, 3] = r["flag"]
@@ -134,10 +140,52 @@ def synthetic(n_stations: int, min_points_local: int, method: int, n_others: int
         t = t + (0.03 * k) * v * (1 if k % 2 else -1)
     pv[1][5::17] = np.float32(ld.NODATA)
     pv[3][2::23] = np.float32(ld.NODATA)
+    for k, how in (spoil or {}).items():
+        if how == "nodata":
+            pv[k][4:] = np.float32(ld.NODATA)
+        else:
+            pv[k][:] = np.float32(3.25)
     c["value"] = np.round(t, 1).astype(np.float32)
     c["proxy_values"] = pv
-    c["active"] = [1] + [1] * n_others + [0] * (SLOTS - 1 - n_others)
+    c["active"] = [int(height_active)] + [1] * n_others + [0] * (SLOTS - 1 - n_others)
     c["others"] = default_others()
+    for k, threshold in (thresholds or {}).items():
+        c["others"][k] = dict(c["others"][k], stdDevThreshold=float(threshold))
+    return r, c
+
+
+def _off_pin() -> tuple:
+    """(label, the arguments of `synthetic` by name).  k significant other proxies make NP (NP + 1) / 2 + NP entries of the normal matrix
+    and the gradient with NP = 2 k: 5, 14, 27, 44, 65, 90, 119 - a lane of the wave owns the entries lane and lane + 64, so k = 5 is the one
+    shape in which lane 0 alone owns a second entry"""
+    I, M = meteo.IDW, meteo.SHEPARD_MODIFIED
+    out = []
+    # every k, all significant in every cell: a list within a wave, and a list of 70 whose interpolated list ends around 64
+    for n, mpl in ((40, 12), (70, 60)):
+        for k in range(1, lp.MAX_OTHERS + 1):
+            out.append((f"all{n}-k{k}", dict(n_stations=n, min_points_local=mpl, method=I, n_others=k)))
+    # the three-piece functions under the proxies, more than two busy fit lanes
+    out.append(("three70-k5", dict(n_stations=70, min_points_local=60, method=M, n_others=5, function=ld.PIECEWISE_THREE, guesses=3)))
+    out.append(("free70-k5", dict(n_stations=70, min_points_local=60, method=I, n_others=5, function=ld.PIECEWISE_THREE_FREE, guesses=4)))
+    out.append(("three70-k6", dict(n_stations=70, min_points_local=60, method=I, n_others=6, function=ld.PIECEWISE_THREE, guesses=4)))
+    out.append(("free70-k6", dict(n_stations=70, min_points_local=60, method=M, n_others=6, function=ld.PIECEWISE_THREE_FREE, guesses=3)))
+    out.append(("noheight70-k3", dict(n_stations=70, min_points_local=60, method=M, n_others=3, height_active=False)))
+    out.append(("modified40-k5", dict(n_stations=40, min_points_local=12, method=M, n_others=5)))
+    # mixed significance on long lists: thresholds, a slot with four values, a constant slot - the significant slots have gaps
+    out.append(("mixed70", dict(n_stations=70, min_points_local=60, method=M, n_others=7, thresholds={2: 1.0, 5: 100.0}, spoil={4: "nodata"})))
+    out.append(("mixed150", dict(n_stations=150, min_points_local=60, method=I, n_others=6, thresholds={1: 11.65, 2: 0.5, 3: 11.1, 6: 0.335}, spoil={2: "constant"})))
+    out.append(("none70", dict(n_stations=70, min_points_local=60, method=I, n_others=4, thresholds={1: 100.0, 2: 100.0, 3: 100.0, 4: 100.0})))
+    return tuple(out)
+
+
+OFF_PIN = _off_pin()
+# the restatement takes more than 5 s on these: held host build against device only (the same functions at k = 6 are restated)
+HOST_ONLY = ("three70-k5", "free70-k5")
+
+
+def off_pin(label: str) -> tuple:
+    r, c = synthetic(**dict(OFF_PIN)[label])
+    r["name"], c["label"] = label, label
     return r, c
 
 

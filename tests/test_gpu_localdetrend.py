@@ -1,7 +1,8 @@
 """Air and dew-point temperature with local detrending on the device (include/sf3d_localdetrend.h) against the compiled-reference pin
 tests/golden/localdetrend.npz and the restatement of criteria3d_amd/localdetrend.py: every case of the pin in every cell and every
-recorded quantity, the meteo block's slot, the same bits twice, the life of the per-cell outcome, two ranks, and selected lists longer
-than a wave up to the 1 024-station cap."""
+recorded quantity, the meteo block's slot, the same bits twice, the life of the per-cell outcome, two ranks, selected lists longer
+than a wave up to the 1 024-station cap, and the cases of localdetrend_cases.OFF_PIN - list lengths at the wave's edges, full first-guess
+lists, every function and method above 64 stations, small block shapes - against the host build of the kernel's own text."""
 import numpy as np
 import pytest
 
@@ -15,6 +16,13 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def pin():
     return lc.load_pin()
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    """the host build of the kernel's per-cell text (tests/localdetrend_host.cpp), built once in a temporary directory"""
+    d = tmp_path_factory.mktemp("localdetrend_host")
+    return lc.build_host(d), d
 
 
 def _same(got, want, what):
@@ -122,4 +130,21 @@ def test_lists_longer_than_a_wave_against_the_restatement(product, stations, min
         with pytest.raises(capi.SF3DError):                                 # one station beyond the cap
             ld.interpolate(product, "airT", method, np.append(c["x"], 0.0), np.append(c["y"], 0.0), np.append(c["height"], 0.0), np.append(c["value"], 0.0),
                            c["area"], c["fit"])
+    meteo.clean(product)
+
+
+@pytest.mark.parametrize("label", [label for label, _ in lc.OFF_PIN])
+def test_off_the_pin_the_device_equals_the_host_build_of_its_text(product, host, label):
+    """lc.OFF_PIN: lists of 1, 4, 5, 63, 64, 65, 128 and 129 entries with every method, ring-selected lists of 122 to 131 with 16, 30 and 31
+    first guesses, the dew point without retrend, equal values, a height that is not significant, the iteration cap, and rasters of one
+    block, a block and a wave (the flag in the first cell) and two blocks - every cell and quantity bit for bit, R2 NaN as "both NaN".
+    The host build is held to the restatement in tests/test_localdetrend_host.py, except the cases of lc.HOST_ONLY"""
+    r, c = lc.off_pin(label)
+    want = lc.run_host(host[0], r, host[1], [c])[0]
+    lc.initialize(product, r)
+    got = lc.interpolate(product, c)
+    lc.same(lc.outcome(product, got), want, label)
+    _same(meteo.get_map(product, c["var"]), want["value"], f"{label}: the meteo block's slot")
+    out = r["dem"] == r["flag"]
+    assert out.sum() == 1 and (got[out] == r["flag"]).all() and (ld.get_selection(product)["count"][out] == 0).all() and (want["count"][~out] > 0).all()
     meteo.clean(product)

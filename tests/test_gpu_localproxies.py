@@ -1,7 +1,9 @@
 """Local detrending with every proxy on the device (include/sf3d_localproxies.h) against the compiled-reference pin
 tests/golden/localproxies.npz and the restatement of criteria3d_amd/localproxies.py: every case of the pin in every cell and every
 recorded quantity, the cases of the pin of the height alone through the new entry point, the meteo block's slot, the same bits twice, the
-life of the per-cell outcome, two ranks, and lists longer than a wave."""
+life of the per-cell outcome, two ranks, lists longer than a wave, and the cases of localproxies_cases.OFF_PIN (every number of
+significant other proxies from 0 to 7 on lists above and below a wave) and of localdetrend_cases.OFF_PIN (the height alone) against the
+host builds of the kernels' own text."""
 import numpy as np
 import pytest
 
@@ -16,6 +18,13 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def pin():
     return pc.load_pin()
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    """the host builds of the two kernels' per-cell text (tests/localproxies_host.cpp, tests/localdetrend_host.cpp), built once"""
+    d = tmp_path_factory.mktemp("localproxies_host")
+    return pc.build_host(d), lc.build_host(d), d
 
 
 def _same(got, want, what):
@@ -138,4 +147,37 @@ def test_lists_longer_than_a_wave_against_the_restatement(product, stations, min
     inside = r["dem"] != r["flag"]
     assert want["count"][inside].min() > 64 and want["proxy_significant"][inside].sum() >= others * inside.sum() // 2
     assert (want["interpolated"][inside] < want["count"][inside]).all() and want["interpolated"][inside].min() > 32
+    meteo.clean(product)
+
+
+@pytest.mark.parametrize("label", [label for label, _ in pc.OFF_PIN])
+def test_off_the_pin_the_device_equals_the_host_build_of_its_text(product, host, label):
+    """pc.OFF_PIN: 1 to 7 significant other proxies (5, 14, 27, 44, 65, 90, 119 entries of matrix and gradient) on lists within a wave and
+    on lists of 70 whose interpolated list ends at 63 or 66, the three-piece functions and an inactive height under them, and thresholds
+    and spoilt slots that leave gaps in the significant set and 2 to 5 significant proxies within one raster on lists of 122 to 131 -
+    every cell and quantity bit for bit, NaN as "both NaN".  The host build is held to the restatement in tests/test_localproxies_host.py,
+    except the cases of pc.HOST_ONLY"""
+    r, c = pc.off_pin(label)
+    want = pc.run_host(host[0], r, host[2], [c])[0]
+    pc.initialize(product, r)
+    got = pc.interpolate(product, c)
+    pc.same(pc.outcome(product, got), want, label)
+    _same(meteo.get_map(product, c["var"]), want["value"], f"{label}: the meteo block's slot")
+    out = r["dem"] == r["flag"]
+    assert out.sum() == 1 and (got[out] == r["flag"]).all() and (ld.get_selection(product)["count"][out] == 0).all() and (lp.get_interpolated(product)[out] == 0).all()
+    meteo.clean(product)
+
+
+@pytest.mark.parametrize("label", [label for label, _ in lc.OFF_PIN])
+def test_the_height_alone_off_the_pin_through_the_new_entry_point(product, host, label):
+    """lc.OFF_PIN with no other proxy active: k_localdetrend_proxies gives the bits k_localdetrend is held to, those of the host build of
+    k_localdetrend's text"""
+    r, c = lc.off_pin(label)
+    want = lc.run_host(host[1], r, host[2], [c])[0]
+    lc.initialize(product, r)
+    got = lp.interpolate(product, c["var"], c["method"], c["x"], c["y"], c["value"], c["height"][None, :], c["area"], c["fit"], [dict(active=1, isHeight=1)],
+                         pc.default_others()[:1], dict(useDetrending=c["useDetrending"]))
+    lc.same(dict(value=got, **ld.get_selection(product), **ld.get_fit(product)), want, label)
+    _same(meteo.get_map(product, c["var"]), want["value"], f"{label}: the meteo block's slot")
+    assert (lp.get_interpolated(product) == want["count"]).all() and not lp.get_proxy_fit(product)["proxy_significant"].any()
     meteo.clean(product)

@@ -2,8 +2,10 @@
 the product library and absent from sf3d.h and the shim; the refusals that come before any device work (and sf3d_meteo_interpolate's
 own, which stay); the pin's arm list and size; the per-cell text of k_localdetrend compiled for the host (tests/localdetrend_host.cpp)
 equal to the compiled-reference pin tests/golden/localdetrend.npz in every recorded quantity, and once more as a stand-alone program under
-the address and undefined-behaviour sanitizers; the Python restatement equal to the pin on every cell of `tiny`; and the restated range
-and first-guess list equal to what the pin recorded from the reference."""
+the address and undefined-behaviour sanitizers; the Python restatement equal to the pin on every cell of `tiny`; the restated range
+and first-guess list equal to what the pin recorded from the reference; and off the pin (localdetrend_cases.OFF_PIN) the host build equal to
+the restatement in every cell and quantity, the sanitizer program on the same inputs, and the list lengths, functions, methods, guess
+counts and arms that the table is there for, asserted on the two references."""
 import ctypes
 import re
 import subprocess
@@ -28,6 +30,29 @@ def host(pin, tmp_path_factory):
     d = tmp_path_factory.mktemp("localdetrend_host")
     exe = lc.build_host(d)
     return {name: lc.run_host(exe, pin[name], d) for name in lc.RASTERS}
+
+
+@pytest.fixture(scope="module")
+def off_pin(tmp_path_factory):
+    """label -> (raster, case, the host build's outcome) of every case of lc.OFF_PIN"""
+    d = tmp_path_factory.mktemp("localdetrend_off_pin")
+    exe = lc.build_host(d)
+    out = {}
+    for label, _ in lc.OFF_PIN:
+        r, c = lc.off_pin(label)
+        out[label] = (r, c, lc.run_host(exe, r, d, [c])[0])
+    return out
+
+
+@pytest.fixture(scope="module")
+def off_pin_restated(off_pin):
+    """label -> (the restatement's outcome, its arms) of the cases that are not in lc.HOST_ONLY, computed once"""
+    out = {}
+    for label, (r, c, _) in off_pin.items():
+        if label not in lc.HOST_ONLY:
+            arms = {}
+            out[label] = (lc.restated(r, c, arms=arms), arms)
+    return out
 
 
 def test_header_and_binding_table_agree():
@@ -172,13 +197,15 @@ def test_host_build_of_the_kernels_text_equals_the_pin_in_every_quantity(pin, ho
     assert sum(int(c["want"]["significant"].sum()) for c in r["cases"]) > 100                 # not vacuous
 
 
-def test_host_build_under_the_sanitizers_reports_nothing(pin, host, tmp_path):
-    """a stand-alone program with its own main: nothing is loaded into Python"""
+def test_host_build_under_the_sanitizers_reports_nothing(pin, host, off_pin, tmp_path):
+    """a stand-alone program with its own main: nothing is loaded into Python.  The pin, then the inputs of lc.OFF_PIN"""
     exe = lc.build_host(tmp_path, sanitize=True)
     for name in lc.RASTERS:
         got = lc.run_host(exe, pin[name], tmp_path)                    # asserts exit status 0 and an empty stderr
         for k, (a, b) in enumerate(zip(got, host[name])):
             lc.same(a, b, f"{name} {k} under the sanitizers")
+    for label, (r, c, want) in off_pin.items():
+        lc.same(lc.run_host(exe, r, tmp_path, [c])[0], want, f"{label} under the sanitizers")
 
 
 def test_restatement_equals_the_pin_on_every_cell_of_tiny(pin):
@@ -202,3 +229,55 @@ def test_restated_range_and_first_guesses_equal_the_reference(pin):
     fit = ld.make_fit("piecewiseThree", pin["ranges"][0]["configured"] if pin["ranges"][0]["function"] == 2 else
                       [-350.0, 0.0, 300.0, 0.002, -0.01, 2500.0, 0.0, 1000.0, 0.007, -0.0015], [0, 1, 1, 1, 1], (3.0, 21.0), 8, 5.0)
     assert fit["function"] == ld.PIECEWISE_THREE and len(fit["min"]) == 5 and fit["min"][1] == 1.0 and fit["max"][1] == 27.0 and len(fit["first_guess"]) == 30
+
+
+@pytest.mark.parametrize("label", [label for label, _ in lc.OFF_PIN if label not in lc.HOST_ONLY])
+def test_host_build_equals_the_restatement_off_the_pin(off_pin, off_pin_restated, label):
+    """every cell and every quantity of lc.QUANTITIES, bit for bit.  The cases of lc.HOST_ONLY - the full first-guess lists of the
+    three-piece functions, 10 to 30 s a case in the restatement - are held host build against device only (tests/test_gpu_localdetrend.py);
+    the long-ring case here is rings150-two-16"""
+    r, c, got = off_pin[label]
+    want = off_pin_restated[label][0]
+    lc.same(got, want, label)
+    out = r["dem"] == r["flag"]
+    assert out.sum() == 1 and (got["value"][out] == r["flag"]).all() and (got["count"][out] == 0).all() and (got["count"][~out] > 0).all()
+
+
+def test_the_off_pin_table_reaches_what_it_claims(pin, off_pin, off_pin_restated):
+    """asserted on the two references, so that an edit of the table cannot hollow it out.  All four arms occur above 64 stations: the cap
+    and the later guess through cap70 (a first guess below its range, as the pin's `cap`), bestR2 < 0 through equal70"""
+    assert len(lc.OFF_PIN) == len(dict(lc.OFF_PIN)) == len(off_pin) and set(lc.HOST_ONLY) < set(off_pin) and "rings150-two-16" in off_pin_restated
+    lengths, functions, methods, guesses, shapes = set(), set(), set(), set(), set()
+    for label, (r, c, got) in off_pin.items():
+        inside = r["dem"] != r["flag"]
+        counts = set(got["count"][inside].tolist())
+        lengths |= counts
+        guesses.add(len(c["fit"]["first_guess"]))
+        shapes.add((r["dem"].shape, bool(r["dem"][0, 0] == r["flag"])))
+        if min(counts) > 64:
+            functions.add(c["fit"]["function"])
+            methods.add(c["method"])
+        if c["method"] == meteo.SHEPARD:
+            assert not lc.ties(r, c), label
+            if label in off_pin_restated:
+                assert not off_pin_restated[label][0]["ties"].any(), label
+    assert {63, 64, 65, 128, 129} <= lengths and {1, 4, 5} <= lengths
+    rings = off_pin["rings150-free-31"]
+    assert len(rings[1]["x"]) == 150 > rings[2]["count"].max() > 128                         # a ring-selected list above 128
+    assert functions == {0, 1, 2} and methods == {0, 1, 2} and ld.MAX_FIRST_GUESS in guesses and {16, 30} <= guesses
+    assert shapes >= {((3, 11), False), ((1, 4), False), ((1, 5), True), ((2, 4), False)}
+    # the positions of the 31-guess list are a configuration the pin recorded from the reference, with the synthetic range's configured values
+    for function, position in lc.POSITION_31.items():
+        assert any(e["function"] == function and e["position"] == position and len(e["want_combinations"]) == ld.MAX_FIRST_GUESS for e in pin["ranges"])
+    for arm in ("the fit ends on the iteration cap", "a later first guess replaces the best fit", "bestR2 < 0: the fit is repeated from the RMSE index",
+                "a parameter clamped to its range"):
+        assert any(arms.get(arm, 0) > 0 and off_pin[label][2]["count"][off_pin[label][0]["dem"] != off_pin[label][0]["flag"]].min() > 64
+                   for label, (_, arms) in off_pin_restated.items()), arm
+    # the arms at more than 64 stations that the pin has below a wave only
+    r, c, got = off_pin["dew70-undetrended"]
+    assert c["var"] == meteo.AIR_DEW_TEMPERATURE and c["useDetrending"] == 0 and got["significant"][r["dem"] != r["flag"]].all()
+    r, c, got = off_pin["equal70"]
+    assert not np.isfinite(got["r2"][r["dem"] != r["flag"]]).any() and np.isfinite(got["value"]).all()
+    r, c, got = off_pin["flat70"]
+    assert not got["significant"].any() and (got["count"][r["dem"] != r["flag"]] == 70).all()
+    assert off_pin_restated["flat70"][1]["height not significant: standard deviation below the threshold"] == 32

@@ -3,7 +3,10 @@ points exported by the product library and absent from sf3d.h and the shim; the 
 list; the per-cell text of k_localdetrend_proxies compiled for the host (tests/localproxies_host.cpp) equal to the compiled-reference pin
 tests/golden/localproxies.npz in every recorded quantity on both rasters, and once more as a stand-alone program under the address and
 undefined-behaviour sanitizers; the same host text with no other proxy active equal to the pin of the height alone
-(tests/golden/localdetrend.npz); and the Python restatement equal to the pin on every cell of `tiny`."""
+(tests/golden/localdetrend.npz); the Python restatement equal to the pin on every cell of `tiny`; and off the pin
+(localproxies_cases.OFF_PIN) the host build equal to the restatement in every cell and quantity, the sanitizer program on the same inputs,
+and what the table is there for asserted on the references: every number of significant other proxies from 0 to 7 on lists above a wave,
+gaps in the significant set, cells of one raster that differ in it, a list above 64 whose interpolated list is not."""
 import ctypes
 import re
 import subprocess
@@ -41,6 +44,28 @@ def exe(tmp_path_factory):
 def host(pin, exe, tmp_path_factory):
     d = tmp_path_factory.mktemp("localproxies_run")
     return {name: pc.run_host(exe, pin[name], d) for name in pc.RASTERS}
+
+
+@pytest.fixture(scope="module")
+def off_pin(exe, tmp_path_factory):
+    """label -> (raster, case, the host build's outcome) of every case of pc.OFF_PIN"""
+    d = tmp_path_factory.mktemp("localproxies_off_pin")
+    out = {}
+    for label, _ in pc.OFF_PIN:
+        r, c = pc.off_pin(label)
+        out[label] = (r, c, pc.run_host(exe, r, d, [c])[0])
+    return out
+
+
+@pytest.fixture(scope="module")
+def off_pin_restated(off_pin):
+    """label -> (the restatement's outcome, its arms) of the cases that are not in pc.HOST_ONLY, computed once"""
+    out = {}
+    for label, (r, c, _) in off_pin.items():
+        if label not in pc.HOST_ONLY:
+            arms = {}
+            out[label] = (pc.restated(r, c, arms=arms), arms)
+    return out
 
 
 def test_header_and_binding_table_agree():
@@ -190,13 +215,15 @@ def test_host_build_of_the_kernels_text_equals_the_pin_in_every_quantity(pin, ho
     assert sum(int(c["want"]["proxy_significant"].sum()) for c in r["cases"]) > 100                 # not vacuous
 
 
-def test_host_build_under_the_sanitizers_reports_nothing(pin, host, tmp_path):
-    """a stand-alone program with its own main: nothing is loaded into Python"""
+def test_host_build_under_the_sanitizers_reports_nothing(pin, host, off_pin, tmp_path):
+    """a stand-alone program with its own main: nothing is loaded into Python.  The pin, then the inputs of pc.OFF_PIN"""
     san = pc.build_host(tmp_path, sanitize=True)
     for name in pc.RASTERS:
         got = pc.run_host(san, pin[name], tmp_path)                     # asserts exit status 0 and an empty stderr
         for k, (a, b) in enumerate(zip(got, host[name])):
             pc.same(a, b, f"{name} {k} under the sanitizers")
+    for label, (r, c, want) in off_pin.items():
+        pc.same(pc.run_host(san, r, tmp_path, [c])[0], want, f"{label} under the sanitizers")
 
 
 @pytest.mark.parametrize("name", lc.RASTERS)
@@ -222,6 +249,50 @@ def test_restatement_equals_the_pin_on_every_cell_of_tiny(pin):
     for must in MUST:
         if must.startswith(("method", "variable", "interpolated count")):
             continue
+        assert arms.get(must, 0) > 0, must
+
+
+@pytest.mark.parametrize("label", [label for label, _ in pc.OFF_PIN if label not in pc.HOST_ONLY])
+def test_host_build_equals_the_restatement_off_the_pin(off_pin, off_pin_restated, label):
+    """every cell and every quantity of pc.QUANTITIES, bit for bit.  The two cases of pc.HOST_ONLY (a three-piece function under five other
+    proxies: more than 5 s in the restatement) are held host build against device only (tests/test_gpu_localproxies.py)"""
+    r, c, got = off_pin[label]
+    pc.same(got, off_pin_restated[label][0], label)
+    out = r["dem"] == r["flag"]
+    assert out.sum() == 1 and (got["value"][out] == r["flag"]).all() and (got["count"][out] == 0).all() and (got["count"][~out] > 0).all()
+
+
+def test_the_off_pin_table_reaches_what_it_claims(off_pin, off_pin_restated):
+    """asserted on the two references, so that an edit of the table cannot hollow it out"""
+    assert len(pc.OFF_PIN) == len(dict(pc.OFF_PIN)) == len(off_pin) and set(pc.HOST_ONLY) < set(off_pin)
+    k_any, k_long, functions_long, gaps, across, differ = set(), set(), set(), 0, 0, 0
+    for label, (r, c, got) in off_pin.items():
+        inside = r["dem"] != r["flag"]
+        k = got["proxy_significant"][inside].sum(axis=1)
+        count, interpolated = got["count"][inside], got["interpolated"][inside]
+        k_any |= set(k.tolist())
+        k_long |= set(k[count > 64].tolist())
+        if count.min() > 64 and k.min() >= 5:
+            functions_long.add(c["fit"]["function"])
+        across += int(((count > 64) & (interpolated <= 64)).sum())
+        differ += len(set(k.tolist())) > 1 and count.min() > 64
+        active = [p for p in range(1, pc.SLOTS) if c["active"][p]]
+        for row in got["proxy_significant"][inside]:
+            significant = [p for p in active if row[p]]
+            gaps += significant != active[:len(significant)]
+        assert c["method"] != meteo.SHEPARD, label                          # no shepardIdw case, so no order left open by std::sort
+        assert not got["proxy_significant"][..., [p for p in range(pc.SLOTS) if p == 0 or not c["active"][p]]].any(), label
+    assert k_any == set(range(lp.MAX_OTHERS + 1)) and k_long == set(range(lp.MAX_OTHERS + 1))         # 3, 5 and 6 (65 entries at 5) on lists above a wave
+    assert functions_long == {0, 1, 2} and gaps > 0 and across > 0 and differ >= 1
+    assert {len(c["fit"]["first_guess"]) for _, c, _ in off_pin.values()} >= {2, 3, 4}
+    r, c, got = off_pin["noheight70-k3"]
+    assert not c["active"][0] and not got["significant"].any() and (got["proxy_significant"][r["dem"] != r["flag"]].sum(axis=1) == 3).all()
+    arms = {}
+    for _, a in off_pin_restated.values():
+        for name, n in a.items():
+            arms[name] = arms.get(name, 0) + n
+    for must in ("a proxy fails the first pass for count", "a proxy fails the first pass for deviation", "a proxy fails only the second pass",
+                 "a proxy passes only the second pass", "every proxy fails the first pass: the list untouched", "the height not active", "a station pruned for NODATA"):
         assert arms.get(must, 0) > 0, must
 
 
