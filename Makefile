@@ -13,13 +13,13 @@ all: product shim
 
 product: $(CSRC)/libsf3d_hip.so
 # every part of the translation unit (the .inc files hold nearly all kernel and host code) and every header is a prerequisite
-$(CSRC)/libsf3d_hip.so: $(CSRC)/sf3d_solver.hip $(CSRC)/sf3d_api.cpp $(wildcard $(CSRC)/*.inc $(CSRC)/*.h) include/sf3d.h include/sf3d_maps.h include/sf3d_snow.h include/sf3d_crop.h include/sf3d_root.h include/sf3d_meteo.h include/sf3d_topodist.h include/sf3d_localdetrend.h include/sf3d_localproxies.h include/sf3d_sink.h include/sf3d_rad.h include/sf3d_transmissivity.h include/sf3d_hour.h
+$(CSRC)/libsf3d_hip.so: $(CSRC)/sf3d_solver.hip $(CSRC)/sf3d_api.cpp $(wildcard $(CSRC)/*.inc $(CSRC)/*.h include/*.h)
 	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(CSRC) -x hip $(CSRC)/sf3d_solver.hip $(CSRC)/sf3d_api.cpp -o $@
 
 # the same product with the 0.50-ulp elementary functions of rounds 1-4 instead of the C library's: the build the oracle's
 # fast-math twin (make -C oracle oracle-fm) is a twin of; load it with SF3D_PRODUCT_LIB=build_variants/libsf3d_hip_fm.so SF3D_TEST_RTOL=1e-6
 product-fm: build_variants/libsf3d_hip_fm.so
-build_variants/libsf3d_hip_fm.so: $(CSRC)/sf3d_solver.hip $(CSRC)/sf3d_api.cpp $(wildcard $(CSRC)/*.inc $(CSRC)/*.h) include/sf3d.h include/sf3d_maps.h include/sf3d_snow.h include/sf3d_crop.h include/sf3d_root.h include/sf3d_meteo.h include/sf3d_topodist.h include/sf3d_localdetrend.h include/sf3d_localproxies.h include/sf3d_sink.h include/sf3d_rad.h include/sf3d_transmissivity.h include/sf3d_hour.h
+build_variants/libsf3d_hip_fm.so: $(CSRC)/sf3d_solver.hip $(CSRC)/sf3d_api.cpp $(wildcard $(CSRC)/*.inc $(CSRC)/*.h include/*.h)
 	mkdir -p build_variants
 	$(HIPCC) $(HIPFLAGS) -DSF3D_LIBM_GLIBC=0 -Iinclude -I$(CSRC) -x hip $(CSRC)/sf3d_solver.hip $(CSRC)/sf3d_api.cpp -o $@
 

@@ -40,7 +40,7 @@ def _stale(target: Path, sources) -> bool:
 def build_product(force: bool = False) -> Path:
     """hipcc --offload-arch=gfx950: kernels + C ABI -> criteria3d_amd/csrc/libsf3d_hip.so"""
     srcs = [CSRC / "sf3d_solver.hip", CSRC / "sf3d_api.cpp"]
-    deps = srcs + sorted(CSRC.glob("*.inc")) + sorted(CSRC.glob("*.h")) + [INCLUDE / "sf3d.h", INCLUDE / "sf3d_maps.h", INCLUDE / "sf3d_snow.h", INCLUDE / "sf3d_crop.h", INCLUDE / "sf3d_root.h", INCLUDE / "sf3d_meteo.h", INCLUDE / "sf3d_topodist.h", INCLUDE / "sf3d_localdetrend.h", INCLUDE / "sf3d_localproxies.h", INCLUDE / "sf3d_sink.h", INCLUDE / "sf3d_rad.h", INCLUDE / "sf3d_transmissivity.h", INCLUDE / "sf3d_hour.h"]      # every part of the translation unit (the Makefile rule uses the same wildcard)
+    deps = srcs + sorted(CSRC.glob("*.inc")) + sorted(CSRC.glob("*.h")) + sorted(INCLUDE.glob("*.h"))      # every part of the translation unit and every public header (the Makefile rule uses the same wildcards)
     if force or _stale(PRODUCT_LIB, deps):
         extra = os.environ.get("SF3D_EXTRA_HIPFLAGS", "").split()      # tuning experiments, e.g. -DSF3D_PROPS_WAVES=4
         cmd = [HIPCC, *HIP_FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-x", "hip", *map(str, srcs), "-o", str(PRODUCT_LIB)]

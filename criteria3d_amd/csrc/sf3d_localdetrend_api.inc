@@ -1,9 +1,9 @@
 /* part of sf3d_api.cpp (included after sf3d_topodist_api.inc; it uses the raster and the call checks of sf3d_meteo_api.inc) - the C entry
- * points of include/sf3d_localdetrend.h.  The host checks the call against the scope of the block before any device work, lays the fit's
- * ranges and first guesses out as the table the kernel reads, and evaluates what needs the C library's sqrt once per call (the radius of
- * localSelection where every station is selected); the selection, the fits and the interpolation live on the device
- * (sf3d_localdetrend.inc). */
+ * points of include/sf3d_localdetrend.h.  The host checks the call against the scope of the block before any device work and sets it up
+ * with sf3d_localdetrend_setup.inc (the table the kernel reads, the numbers every cell shares); the selection, the fits and the
+ * interpolation live on the device (sf3d_localdetrend.inc). */
 #include "sf3d_localdetrend.h"
+#include "sf3d_localdetrend_setup.inc"
 
 static_assert(SF3D_LOCALDETREND_MAX_PARAMETERS == LOCALDETREND_MAX_PARAMETERS && SF3D_LOCALDETREND_MAX_FIRST_GUESS == LOCALDETREND_MAX_FIRST_GUESS,
               "sf3d_localdetrend.h and sf3d_device.h disagree");
@@ -11,12 +11,6 @@ static_assert(sizeof(sf3d_localdetrend_fit_t) == 24 + (3 + SF3D_LOCALDETREND_MAX
               "sf3d_localdetrend_fit_t has no padding");
 
 namespace {
-
-/* the number of parameters of a function, 0: unknown */
-int localParameters(int function)
-{
-    return function == SF3D_LOCALDETREND_PIECEWISE_TWO ? 4 : function == SF3D_LOCALDETREND_PIECEWISE_THREE_FREE ? 6 : function == SF3D_LOCALDETREND_PIECEWISE_THREE ? 5 : 0;
-}
 
 /* the checks that need no raster; heightOnly: the proxy rule of sf3d_localdetrend.h (sf3d_localproxies_api.inc has its own) */
 bool localCallOk(int variable, uint32_t nStations, const double* x, const double* y, const float* height, const sf3d_meteo_settings_t* settings,
@@ -48,22 +42,6 @@ bool localCallOk(int variable, uint32_t nStations, const double* x, const double
     for (uint32_t k = 0; k < nStations; ++k)
         if (!std::isfinite(x[k]) || !std::isfinite(y[k]) || !std::isfinite(height[k])) return false;
     return true;
-}
-
-/* the table the kernel reads (LOCALDETREND_TABLE_DOUBLES doubles, zeroed by the caller) and what the call fixes for every cell */
-void localSetup(const sf3d_localdetrend_fit_t* fit, uint32_t nStations, float boundingBoxArea, double* table, LocalDetrendSetup& s)
-{
-    const int P = SF3D_LOCALDETREND_MAX_PARAMETERS;
-    for (int j = 0; j < fit->nParameters; ++j) {
-        table[j] = fit->parametersMin[j]; table[P + j] = fit->parametersMax[j]; table[2 * P + j] = fit->parametersDelta[j];
-        for (int k = 0; k < fit->nFirstGuess; ++k) table[(3 + k) * P + j] = fit->firstGuess[k][j];
-    }
-    s.function = fit->function; s.nFirstGuess = fit->nFirstGuess; s.minPointsLocal = fit->minPointsLocalDetrending;
-    s.minPoints = unsigned(fit->minPointsLocalDetrending * 1.2f);           /* interpolation.cpp:1092-1093 */
-    s.minPointsStep = unsigned(s.minPoints * 0.8);                          /* :1150 */
-    s.stdDevThreshold = fit->stdDevThreshold; s.area = boundingBoxArea;
-    /* computeShepardInitialRadius(area, N, minPoints), :1098 with :800-803 */
-    s.radiusAll = float(std::sqrt((s.minPoints * boundingBoxArea) / (float(3.1415926535898) * nStations)));
 }
 
 }  // namespace

@@ -1,49 +1,12 @@
 /* part of sf3d_api.cpp (included after sf3d_localdetrend_api.inc, whose call checks and set-up it uses) - the C entry points of
  * include/sf3d_localproxies.h.  The host checks the call against the scope of the block before any device work and lays the active
- * proxies out as the kernel reads them: the height's slot, the other proxies in slot order with their station rows, ranges and
- * thresholds; everything else lives on the device (sf3d_localproxies.inc). */
+ * proxies out as the kernel reads them (proxiesCallOk of sf3d_localdetrend_setup.inc); everything else lives on the device
+ * (sf3d_localproxies.inc). */
 #include "sf3d_localproxies.h"
 
 static_assert(SF3D_LOCALPROXIES_MAX_OTHERS == LOCALPROXIES_MAX_OTHERS && SF3D_LOCALPROXIES_MAX_OTHERS == SF3D_METEO_MAX_PROXIES - 1,
               "sf3d_localproxies.h and sf3d_device.h disagree");
 static_assert(sizeof(sf3d_localproxies_proxy_t) == 40 && sizeof(sf3d_localproxies_others_t) == 40 * SF3D_METEO_MAX_PROXIES, "sf3d_localproxies_others_t has no padding");
-
-namespace {
-
-/* the checks that need no raster, beyond localCallOk's; fills the proxies of the call */
-bool proxiesCallOk(uint32_t nStations, uint32_t nProxies, const float* proxyValues, const sf3d_meteo_settings_t* settings, const sf3d_localproxies_others_t* others,
-                   LocalProxiesSetup& ps, const float** rows, const float** height)
-{
-    if (!others || nProxies != (uint32_t)settings->nProxies || (nStations > 0 && nProxies > 0 && !proxyValues)) return false;
-    int heights = 0;
-    ps.heightSlot = -1; ps.nOthers = 0;
-    *height = nullptr;
-    for (int p = 0; p < settings->nProxies; ++p) {
-        const float* row = proxyValues ? proxyValues + (size_t)p * nStations : nullptr;
-        if (settings->proxy[p].isHeight) {
-            if (++heights > 1) return false;
-            if (settings->proxy[p].active) { ps.heightSlot = p; *height = row; }
-        }
-        if (!settings->proxy[p].active) continue;
-        for (uint32_t k = 0; k < nStations; ++k)
-            if (!std::isfinite(row[k])) return false;
-        if (settings->proxy[p].isHeight) continue;
-        if (ps.nOthers == SF3D_LOCALPROXIES_MAX_OTHERS) return false;
-        const sf3d_localproxies_proxy_t& o = others->proxy[p];
-        if (std::isnan(o.stdDevThreshold)) return false;
-        for (int t = 0; t < 2; ++t) {
-            if (!std::isfinite(o.min[t]) || !std::isfinite(o.max[t]) || o.min[t] > o.max[t]) return false;
-            ps.range[ps.nOthers][t] = o.min[t]; ps.range[ps.nOthers][2 + t] = o.max[t];
-        }
-        ps.stdDevThreshold[ps.nOthers] = o.stdDevThreshold;
-        ps.slot[ps.nOthers] = p;
-        rows[ps.nOthers] = row;
-        ++ps.nOthers;
-    }
-    return true;
-}
-
-}  // namespace
 
 extern "C" {
 

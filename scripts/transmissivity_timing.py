@@ -18,6 +18,7 @@ sys.path.insert(0, str(ROOT))
 import numpy as np                                                          # noqa: E402
 from criteria3d_amd import capi, radiation as rad, transmissivity as tr    # noqa: E402
 from tests import transmissivity_cases as tc                               # noqa: E402
+from tests.raster_helpers import build_host_program                          # noqa: E402
 
 WHEN, STEP = (2021, 3, 20, 8, 0, 0), 3600
 SETS, WIDTHS = (40, 200, 1024), (13, 23)
@@ -71,7 +72,7 @@ def main():
     rad.clean(sf)
     # the host build of the same text on one CPU: every call `repeat` times, the seconds without reading and writing
     with tempfile.TemporaryDirectory() as tmp:
-        exe = tc.build_host(tmp)
+        exe = build_host_program("transmissivity", tmp)
         for run, call in zip(runs, calls):
             tc.write_host_input(Path(tmp) / "in.bin", dem, flag, (xll, yll, cs), [call])
             repeat = 5

@@ -95,11 +95,6 @@ def outputs(sf, n):
     return dict(sinks=sinks.get_node_sinks(sf, n), evaporation=e, transpiration=t, prec_surface_water=p, crack_water=w)
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64)
-
-
 # ---- a raster of any shape on the pin's tables
 
 PREC = (0.0, 0.05, 0.6, 3.0, 14.0, 60.0)       # [mm]: none, below the smallest pond, between the ponds, ordinary, more than a crack of 0.6 m takes

@@ -260,11 +260,6 @@ def pin_script(pin):
     return ops
 
 
-def build_host(directory, sanitize=False):
-    from tests.raster_helpers import build_host_program
-    return build_host_program("crop", directory, sanitize)
-
-
 def run_host(exe, directory, name, p, ops):
     """the host program on a script -> the five maps at every checkpoint.  p: the keys of as_pin.  ("initialize", latitude, True) keeps the
     state maps"""

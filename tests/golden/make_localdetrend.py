@@ -30,6 +30,7 @@ HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE.parent.parent))
 from criteria3d_amd import localdetrend as ld, meteo  # noqa: E402
 from tests import localdetrend_cases as lc  # noqa: E402
+from tests.raster_helpers import same  # noqa: E402
 
 OUT = HERE / "localdetrend.npz"
 FLAG = np.float32(-9999.0)
@@ -439,7 +440,7 @@ def main():
                 for k, (c, g) in enumerate(zip(cases, got)):
                     t0 = time.time()
                     mine = lc.restated(r, c, arms=arms)
-                    lc.same(mine, g, f"restatement {k} {lc.case_name(c)}")
+                    same(mine, g, f"restatement {k} {lc.case_name(c)}", lc.QUANTITIES)
                     if c["method"] == meteo.SHEPARD:
                         assert not mine["ties"].any(), "two selected stations at one float distance in a shepardIdw case: move a station"
                     print(f"  restatement {k}: equal ({time.time() - t0:.1f} s)")

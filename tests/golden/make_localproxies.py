@@ -32,6 +32,7 @@ sys.path.insert(0, str(HERE.parent.parent))
 sys.path.insert(0, str(HERE))
 from criteria3d_amd import localdetrend as ld, localproxies as lp, meteo  # noqa: E402
 from tests import localproxies_cases as pc  # noqa: E402
+from tests.raster_helpers import same  # noqa: E402
 import make_localdetrend as base  # noqa: E402
 
 OUT = HERE / "localproxies.npz"
@@ -405,7 +406,7 @@ def main():
                 for k, (c, g) in enumerate(zip(cases, got)):
                     t0 = time.time()
                     mine = pc.restated(r, c, arms=arms)
-                    pc.same(mine, g, f"restatement {k} {pc.case_name(c)}")
+                    same(mine, g, f"restatement {k} {pc.case_name(c)}", pc.QUANTITIES)
                     if c["method"] == meteo.SHEPARD:
                         assert not mine["ties"].any(), "two listed stations at one float distance in a shepardIdw case: move a station"
                     print(f"  restatement {k}: equal ({time.time() - t0:.1f} s)")

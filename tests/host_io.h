@@ -1,5 +1,5 @@
-/* shared by the host programs of the raster blocks (tests/snow_host.cpp, crop_host.cpp, root_host.cpp, sink_host.cpp): binary input and
- * output, and the elementary functions of the kernels' text on a CPU.
+/* shared by every host program that reads an input file (tests/<block>_host.cpp for snow, crop, root, sink, rad, transmissivity, hour,
+ * topodist, localdetrend and localproxies): binary input and output, and the elementary functions of the kernels' text on a CPU.
  *
  * Every array a program hands to the kernels' text is a std::vector of exactly the size the text may index (one heap block per map or
  * table), so that the address sanitizer sees a read one element past its end. */

@@ -2,7 +2,6 @@
 tests/golden/relhum_dew.npz and pond_day.npz, the host build of the per-cell text (tests/hour_host.cpp), and a small "world" - every raster
 block and a node model on one small raster - with the hour driven through it in two ways: every stage's maps downloaded and handed to the
 next stage through the host-pointer entry points, and in place through include/sf3d_hour.h."""
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -30,39 +29,18 @@ def load_pond_pin():
     return p
 
 
-def bits(a, dtype=np.float32):
-    return np.ascontiguousarray(a, dtype).view(np.uint32 if dtype == np.float32 else np.uint64)
-
-
-def build_host(directory, sanitize=False):
-    exe = Path(directory) / ("hour_host_san" if sanitize else "hour_host")
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-Wall", "-Werror", "-Wno-unused-function", *extra,
-                    f"-I{ROOT / 'criteria3d_amd' / 'csrc'}", str(ROOT / "tests" / "hour_host.cpp"), "-o", str(exe), "-lm"], check=True)
-    return exe
-
-
 def run_host(exe, tmp_path, rh, pd, case, tag="x"):
     """the pins' inputs through the host program -> (relHum of the pairs, the raster's map, the pond map of `case` (0: computeCrop on, 1: off))"""
-    src, dst = Path(tmp_path) / f"in_{tag}.bin", Path(tmp_path) / f"out_{tag}.bin"
-    with open(src, "wb") as f:
-        np.array([rh["dew_t"].size, rh["map_air_t"].size], np.int32).tofile(f)
-        np.array([rh["flag"]], np.float32).tofile(f)
-        for name in ("dew_t", "air_t", "map_air_t", "map_dew_t"):
-            np.ascontiguousarray(rh[name], np.float32).tofile(f)
-        np.array([pd["slope"].size, len(pd["maximum_pond"]), int(pd["compute_crop"][case])], np.int32).tofile(f)
-        np.array([pd["slope_flag"], pd["flag"]], np.float32).tofile(f)
-        np.ascontiguousarray(pd["slope"], np.float32).tofile(f)
-        np.ascontiguousarray(pd["unit"], np.int32).tofile(f)
-        np.ascontiguousarray(pd["lai"], np.float32).tofile(f)
-        np.stack([pd["maximum_pond"], pd["lai_max"]], axis=1).astype(np.float64).tofile(f)
-        np.ascontiguousarray(pd["is_crop"], np.int32).tofile(f)
-    r = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
-    raw = np.fromfile(dst, np.float32)
-    n0, n1 = rh["dew_t"].size, rh["map_air_t"].size
-    assert raw.size == n0 + n1 + pd["slope"].size
-    return raw[:n0], raw[n0:n0 + n1].reshape(rh["map_air_t"].shape), raw[n0 + n1:].reshape(pd["slope"].shape)
+    from tests.raster_helpers import Reader, run_host_program
+    parts = [np.array([rh["dew_t"].size, rh["map_air_t"].size], np.int32), np.array([rh["flag"]], np.float32)]
+    parts += [np.asarray(rh[name], np.float32) for name in ("dew_t", "air_t", "map_air_t", "map_dew_t")]
+    parts += [np.array([pd["slope"].size, len(pd["maximum_pond"]), int(pd["compute_crop"][case])], np.int32), np.array([pd["slope_flag"], pd["flag"]], np.float32),
+              np.asarray(pd["slope"], np.float32), np.asarray(pd["unit"], np.int32), np.asarray(pd["lai"], np.float32),
+              np.stack([pd["maximum_pond"], pd["lai_max"]], axis=1).astype(np.float64), np.asarray(pd["is_crop"], np.int32)]
+    out = Reader(run_host_program(exe, tmp_path, tag, parts))
+    got = out.take(np.float32, rh["dew_t"].size), out.take(np.float32, *rh["map_air_t"].shape), out.take(np.float32, *pd["slope"].shape)
+    assert out.done()
+    return got
 
 
 def pond_restated(pd, case, surface_index=None, mine=None):

@@ -7,30 +7,13 @@
  *         int32 nPond, nUnits, computeCrop; float slopeFlag, laiFlag; float slopeDegree[nPond]; int32 unit[nPond]; float lai[nPond];
  *         per unit double maximumPond, laiMax; int32 isCrop[nUnits].
  * output: float relHum[nPairs] (relHumFromTdew), float map[nCells] (the map loop's rule), float pond[nPond] (-9999: skipped). */
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "sf3d_device.h"
-
-#define SF3D_GL_FN static inline
-#define SF3D_GL_TABLE static const
-#include "sf3d_glibcmath.inc"
+#include "host_io.h"
 
 #define SF3D_HOUR_HOST
 #define SF3D_HOUR_FN static inline
 #define hour_exp(x) sf3d_gl_exp(x)
 #define hour_pow(x, y) sf3d_gl_pow(x, y)
 #include "sf3d_hour.inc"
-
-template <class T> static std::vector<T> readv(FILE* f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "hour_host: short input\n"); exit(2); }
-    return v;
-}
 
 int main(int argc, char** argv)
 {
@@ -39,7 +22,7 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) return 2;
     const std::vector<int32_t> dims = readv<int32_t>(in, 2);
-    const float flag = readv<float>(in, 1)[0];
+    const float flag = read1<float>(in);
     const size_t nPairs = (size_t)dims[0], nCells = (size_t)dims[1];
     const std::vector<float> dewT = readv<float>(in, nPairs), airT = readv<float>(in, nPairs), mapAirT = readv<float>(in, nCells), mapDewT = readv<float>(in, nCells);
     std::vector<float> rh(nPairs), map(nCells);
@@ -63,7 +46,7 @@ int main(int argc, char** argv)
         const double tanSlope = std::tan(slope[c] * 0.01745329252);                           /* the host's, as in sf3d_hour_api.inc */
         pond[c] = hour_pond_cell(tanSlope, table[2 * (size_t)u], table[2 * (size_t)u + 1], computeCrop && isCrop[u], lai[c], laiFlag);
     }
-    if (fwrite(rh.data(), 4, nPairs, out) != nPairs || fwrite(map.data(), 4, nCells, out) != nCells || fwrite(pond.data(), 4, nPond, out) != nPond) return 3;
+    writev(out, rh); writev(out, map); writev(out, pond);
     fclose(in);
     return fclose(out) == 0 ? 0 : 3;
 }

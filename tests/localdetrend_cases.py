@@ -6,20 +6,18 @@ with the table OFF_PIN of its arguments: selected lists of exactly 1, 4, 5, 63, 
 to 131 with the full first-guess lists (16, 30 and the 31 of POSITION_31), the arms the pin has below a wave only, and rasters of one
 block, a block and a wave, and two blocks.  HOST_ONLY names the cases the restatement is too slow for."""
 import json
-import subprocess
 from pathlib import Path
 
 import numpy as np
 
 from criteria3d_amd import localdetrend as ld, meteo
-from tests import meteo_cases as mc
 
 ROOT = Path(__file__).resolve().parent.parent
 PIN = ROOT / "tests" / "golden" / "localdetrend.npz"
 RASTERS = ("relief", "tiny")
 PORT = 29801                                    # the two-rank test's (clear of tests/ranks.py's table and of the other blocks' ports)
-QUANTITIES = ("value", "count", "radius", "significant", "r2", "parameters")
-bits = mc.bits
+# the rule of tests/raster_helpers.py same for every recorded quantity: the parameters as raw 64-bit patterns, a NaN in R2 equal to any NaN
+QUANTITIES = dict(value="bits", count="value", radius="bits", significant="value", r2="nan", parameters="bits")
 
 
 def load_pin():
@@ -48,23 +46,6 @@ def case_name(c) -> str:
 
 def settings_of(c) -> dict:
     return ld.local_settings(dict(useDetrending=c["useDetrending"]))
-
-
-def same(got: dict, want: dict, what: str, quantities=QUANTITIES) -> None:
-    """every recorded quantity bit for bit; NaN in R2 is compared as "both NaN" (the bits of a NaN are the compiler's choice)"""
-    for q in quantities:
-        a, b = np.asarray(got[q]), np.asarray(want[q])
-        assert a.shape == b.shape, (what, q, a.shape, b.shape)
-        if q == "r2":
-            nan = np.isnan(a) & np.isnan(b)
-            bad = (bits(a) != bits(b)) & ~nan
-        elif q == "parameters":
-            bad = a.view(np.uint64) != b.view(np.uint64)
-        elif q in ("count", "significant"):
-            bad = a != b
-        else:
-            bad = bits(a) != bits(b)
-        assert not bad.any(), (what, q, int(bad.sum()), a[bad][:4], b[bad][:4])
 
 
 def restated(r, c, mine=None, arms=None) -> dict:
@@ -193,55 +174,42 @@ def fit_table(fit: dict) -> np.ndarray:
     return t
 
 
+def case_head(c) -> np.ndarray:
+    fit = c["fit"]
+    return np.array([c["var"], c["method"], fit["function"], len(fit["min"]), len(fit["first_guess"]), fit["minPointsLocalDetrending"], c["useDetrending"], len(c["x"])], np.int32)
+
+
+def input_parts(r, cases) -> list:
+    parts = [np.array([r["dem"].shape[0], r["dem"].shape[1], len(cases)], np.int32), np.array([r["flag"]], np.float32),
+             np.array([r["xll"], r["yll"], r["cell_size"]], np.float64), r["dem"].astype(np.float32)]
+    for c in cases:
+        parts += [case_head(c), np.array([c["fit"]["stdDevThreshold"], c["area"]], np.float32), fit_table(c["fit"])]
+        parts += [np.asarray(a, t) for a, t in ((c["x"], np.float64), (c["y"], np.float64), (c["height"], np.float32), (c["value"], np.float32))]
+    return parts
+
+
+def output_of(raw: bytes, r, cases) -> list:
+    from tests.raster_helpers import Reader
+    shape, out, o = r["dem"].shape, Reader(raw), []
+    for _ in cases:
+        o.append(dict(value=out.take(np.float32, *shape), count=out.take(np.uint32, *shape), radius=out.take(np.float32, *shape),
+                      significant=out.take(np.int32, *shape).astype(bool), r2=out.take(np.float32, *shape), parameters=out.take(np.float64, *shape, ld.MAX_PARAMETERS)))
+    assert out.done()
+    return o
+
+
 def write_input(path, r, cases) -> None:
-    with open(path, "wb") as f:
-        np.array([r["dem"].shape[0], r["dem"].shape[1], len(cases)], np.int32).tofile(f)
-        np.array([r["flag"]], np.float32).tofile(f)
-        np.array([r["xll"], r["yll"], r["cell_size"]], np.float64).tofile(f)
-        r["dem"].astype(np.float32).tofile(f)
-        for c in cases:
-            fit = c["fit"]
-            np.array([c["var"], c["method"], fit["function"], len(fit["min"]), len(fit["first_guess"]), fit["minPointsLocalDetrending"], c["useDetrending"], len(c["x"])],
-                     np.int32).tofile(f)
-            np.array([fit["stdDevThreshold"], c["area"]], np.float32).tofile(f)
-            fit_table(fit).tofile(f)
-            for a, t in ((c["x"], np.float64), (c["y"], np.float64), (c["height"], np.float32), (c["value"], np.float32)):
-                np.asarray(a, t).tofile(f)
+    """for the pin's driver (tests/golden/make_localdetrend.py), which reads and writes the program's format"""
+    from tests.raster_helpers import write_parts
+    write_parts(path, input_parts(r, cases))
 
 
 def read_output(path, r, cases) -> list:
-    raw = np.fromfile(path, np.uint8)
-    shape, cells = r["dem"].shape, r["dem"].size
-    pos, out = 0, []
-
-    def take(count, dtype):
-        nonlocal pos
-        size = count * np.dtype(dtype).itemsize
-        a = raw[pos:pos + size].view(dtype).copy()
-        pos += size
-        return a
-    for _ in cases:
-        out.append(dict(value=take(cells, np.float32).reshape(shape), count=take(cells, np.uint32).reshape(shape), radius=take(cells, np.float32).reshape(shape),
-                        significant=take(cells, np.int32).reshape(shape).astype(bool), r2=take(cells, np.float32).reshape(shape),
-                        parameters=take(cells * ld.MAX_PARAMETERS, np.float64).reshape(shape + (ld.MAX_PARAMETERS,))))
-    assert pos == raw.size, (pos, raw.size)
-    return out
-
-
-def build_host(directory, sanitize=False) -> Path:
-    """tests/localdetrend_host.cpp with the flags of the product's host side (no FMA contraction); sanitize: address and undefined behaviour"""
-    exe = Path(directory) / ("localdetrend_host_san" if sanitize else "localdetrend_host")
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wno-unknown-pragmas", *extra, f"-I{ROOT / 'include'}", f"-I{ROOT / 'criteria3d_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "localdetrend_host.cpp"), "-o", str(exe), "-lm"], check=True)
-    return exe
+    return output_of(Path(path).read_bytes(), r, cases)
 
 
 def run_host(exe, r, directory, cases=None) -> list:
     """the host program on one raster -> the outcome of every case"""
+    from tests.raster_helpers import run_host_program
     cases = r["cases"] if cases is None else cases
-    src, dst = Path(directory) / f"{r['name']}.in", Path(directory) / f"{r['name']}.out"
-    write_input(src, r, cases)
-    res = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True)
-    assert res.returncode == 0 and not res.stderr, (res.returncode, res.stderr[-2000:])
-    return read_output(dst, r, cases)
+    return output_of(run_host_program(exe, directory, r["name"], input_parts(r, cases)), r, cases)

@@ -1,6 +1,7 @@
 /* host build of the per-cell text of k_localdetrend (criteria3d_amd/csrc/sf3d_meteo.inc and sf3d_localdetrend.inc: the text the device
- * compiles, here with one lane) for tests/test_localdetrend_host.py: the pin is checked on a CPU before any device runs the kernel, and
- * the same program is built once with -fsanitize=address,undefined.
+ * compiles, here with one lane) behind the set-up of sf3d_localdetrend_interpolate (sf3d_localdetrend_setup.inc) for
+ * tests/test_localdetrend_host.py: the pin is checked on a CPU before any device runs the kernel, and the same program is built once with
+ * -fsanitize=address,undefined.
  *
  *   localdetrend_host <input> <output>
  * input : int32 nRows, nCols, nCases; float flag; double xll, yll, cellSize; float dem[nCells];
@@ -9,31 +10,14 @@
  *                   double x[nStations], y[nStations]; float height[nStations], value[nStations].
  * output: per case float map[nCells]; uint32 count[nCells]; float radius[nCells]; int32 significant[nCells]; float r2[nCells];
  *         double parameters[nCells][6]. */
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "sf3d_device.h"
+#include "host_io.h"
+#include "sf3d_localdetrend_setup.inc"
 
 #define SF3D_METEO_HOST
 #define SF3D_METEO_FN static inline
 #define SF3D_METEO_MEMBER inline
 #include "sf3d_meteo.inc"
 #include "sf3d_localdetrend.inc"
-
-template <class T> static std::vector<T> readv(FILE* f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "localdetrend_host: short input\n"); exit(2); }
-    return v;
-}
-
-template <class T> static void writev(FILE* f, const std::vector<T>& v)
-{
-    if (v.size() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "localdetrend_host: short output\n"); exit(3); }
-}
 
 int main(int argc, char** argv)
 {
@@ -42,7 +26,7 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) return 2;
     const std::vector<int32_t> dims = readv<int32_t>(in, 3);
-    const float flag = readv<float>(in, 1)[0];
+    const float flag = read1<float>(in);
     const std::vector<double> geo = readv<double>(in, 3);
     const uint32_t nRows = (uint32_t)dims[0], nCols = (uint32_t)dims[1];
     const int nCases = dims[2];
@@ -65,11 +49,8 @@ int main(int argc, char** argv)
 
         LocalDetrendSetup s{};
         s.table = table.data();
-        s.function = iv[2]; s.nFirstGuess = iv[4]; s.minPointsLocal = iv[5]; s.method = iv[1]; s.useDetrending = iv[6];
-        s.minPoints = unsigned(iv[5] * 1.2f);
-        s.minPointsStep = unsigned(s.minPoints * 0.8);
-        s.stdDevThreshold = fv[0]; s.area = fv[1];
-        s.radiusAll = float(std::sqrt((s.minPoints * fv[1]) / (float(3.1415926535898) * m)));
+        s.method = iv[1]; s.useDetrending = iv[6];
+        localNumbers(iv[2], iv[4], iv[5], fv[0], m, fv[1], s);
 
         /* the wave's room */
         std::vector<uint16_t> idx(m + 1);

@@ -9,7 +9,6 @@ significance on lists of 70 and of 122 to 131.
 A raster carries SLOTS proxy slots: slot 0 is the height (no raster of its own: the DEM), slots 1 .. 7 hold the synthetic rasters.  A
 case says which slots are active, the stations' value of every slot, and range and threshold of every slot that is not the height."""
 import json
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -22,8 +21,9 @@ PIN = ROOT / "tests" / "golden" / "localproxies.npz"
 RASTERS = ("relief", "tiny")
 SLOTS = meteo.MAX_PROXIES
 PORT = 29803                                    # the two-rank test's (clear of tests/ranks.py's table and of the other blocks' ports)
-QUANTITIES = ("value", "count", "interpolated", "radius", "significant", "r2", "parameters", "proxy_significant", "slope", "intercept")
-bits = lc.bits
+# the rule of tests/raster_helpers.py same for every recorded quantity: a NaN equal to any NaN in R2 and in the doubles of the fits
+QUANTITIES = dict(value="bits", count="value", interpolated="value", radius="bits", significant="value", r2="nan", parameters="nan", proxy_significant="value",
+                  slope="nan", intercept="nan")
 
 
 def proxies_of(c) -> list:
@@ -59,22 +59,6 @@ def load_pin():
 def case_name(c) -> str:
     active = "".join(str(int(a)) for a in c["active"])
     return f"{c['label']}-{meteo.VARIABLES[c['var']]}-{meteo.METHODS[c['method']]}-{ld.FUNCTIONS[c['fit']['function']]}-min{c['fit']['minPointsLocalDetrending']}-{active}"
-
-
-def same(got: dict, want: dict, what: str, quantities=QUANTITIES) -> None:
-    """every recorded quantity bit for bit; NaN in R2 is compared as 'both NaN'"""
-    for q in quantities:
-        a, b = np.asarray(got[q]), np.asarray(want[q])
-        assert a.shape == b.shape, (what, q, a.shape, b.shape)
-        if q == "r2":
-            bad = (bits(a) != bits(b)) & ~(np.isnan(a) & np.isnan(b))
-        elif q in ("parameters", "slope", "intercept"):
-            bad = (a.view(np.uint64) != b.view(np.uint64)) & ~(np.isnan(a) & np.isnan(b))
-        elif q in ("count", "interpolated", "significant", "proxy_significant"):
-            bad = a != b
-        else:
-            bad = bits(a) != bits(b)
-        assert not bad.any(), (what, q, int(bad.sum()), np.argwhere(bad)[:4].tolist(), a[bad][:4], b[bad][:4])
 
 
 def restated(r, c, mine=None, arms=None) -> dict:
@@ -191,63 +175,41 @@ def off_pin(label: str) -> tuple:
 
 # ---- the file format of tests/localproxies_host.cpp (its header comment)
 
+def input_parts(r, cases) -> list:
+    parts = [np.array([r["dem"].shape[0], r["dem"].shape[1], len(cases)], np.int32), np.array([r["flag"]], np.float32),
+             np.array([r["xll"], r["yll"], r["cell_size"]], np.float64), r["dem"].astype(np.float32), np.asarray(r["maps"], np.float32)]
+    for c in cases:
+        parts += [lc.case_head(c), np.array(c["active"], np.int32), np.array([c["fit"]["stdDevThreshold"], c["area"]], np.float32),
+                  np.array([o["stdDevThreshold"] for o in c["others"]], np.float32), np.array([list(o["min"]) + list(o["max"]) for o in c["others"]], np.float64),
+                  lc.fit_table(c["fit"]), np.asarray(c["x"], np.float64), np.asarray(c["y"], np.float64), np.asarray(c["proxy_values"], np.float32),
+                  np.asarray(c["value"], np.float32)]
+    return parts
+
+
+def output_of(raw: bytes, r, cases) -> list:
+    from tests.raster_helpers import Reader
+    shape, out, o = r["dem"].shape, Reader(raw), []
+    for _ in cases:
+        o.append(dict(value=out.take(np.float32, *shape), count=out.take(np.uint32, *shape), interpolated=out.take(np.uint32, *shape), radius=out.take(np.float32, *shape),
+                      significant=out.take(np.int32, *shape).astype(bool), r2=out.take(np.float32, *shape), parameters=out.take(np.float64, *shape, ld.MAX_PARAMETERS),
+                      proxy_significant=out.take(np.int32, *shape, SLOTS).astype(bool), slope=out.take(np.float64, *shape, SLOTS),
+                      intercept=out.take(np.float64, *shape, SLOTS)))
+    assert out.done()
+    return o
+
+
 def write_input(path, r, cases) -> None:
-    with open(path, "wb") as f:
-        np.array([r["dem"].shape[0], r["dem"].shape[1], len(cases)], np.int32).tofile(f)
-        np.array([r["flag"]], np.float32).tofile(f)
-        np.array([r["xll"], r["yll"], r["cell_size"]], np.float64).tofile(f)
-        r["dem"].astype(np.float32).tofile(f)
-        np.asarray(r["maps"], np.float32).tofile(f)
-        for c in cases:
-            fit = c["fit"]
-            np.array([c["var"], c["method"], fit["function"], len(fit["min"]), len(fit["first_guess"]), fit["minPointsLocalDetrending"], c["useDetrending"], len(c["x"])],
-                     np.int32).tofile(f)
-            np.array(c["active"], np.int32).tofile(f)
-            np.array([fit["stdDevThreshold"], c["area"]], np.float32).tofile(f)
-            np.array([o["stdDevThreshold"] for o in c["others"]], np.float32).tofile(f)
-            np.array([list(o["min"]) + list(o["max"]) for o in c["others"]], np.float64).tofile(f)
-            lc.fit_table(fit).tofile(f)
-            np.asarray(c["x"], np.float64).tofile(f)
-            np.asarray(c["y"], np.float64).tofile(f)
-            np.asarray(c["proxy_values"], np.float32).tofile(f)
-            np.asarray(c["value"], np.float32).tofile(f)
+    """for the pin's driver (tests/golden/make_localproxies.py), which reads and writes the program's format"""
+    from tests.raster_helpers import write_parts
+    write_parts(path, input_parts(r, cases))
 
 
 def read_output(path, r, cases) -> list:
-    raw = np.fromfile(path, np.uint8)
-    shape, cells = r["dem"].shape, r["dem"].size
-    pos, out = 0, []
-
-    def take(count, dtype, tail=()):
-        nonlocal pos
-        size = count * np.dtype(dtype).itemsize
-        a = raw[pos:pos + size].view(dtype).copy()
-        pos += size
-        return a.reshape(shape + tail)
-    for _ in cases:
-        out.append(dict(value=take(cells, np.float32), count=take(cells, np.uint32), interpolated=take(cells, np.uint32), radius=take(cells, np.float32),
-                        significant=take(cells, np.int32).astype(bool), r2=take(cells, np.float32),
-                        parameters=take(cells * ld.MAX_PARAMETERS, np.float64, (ld.MAX_PARAMETERS,)),
-                        proxy_significant=take(cells * SLOTS, np.int32, (SLOTS,)).astype(bool), slope=take(cells * SLOTS, np.float64, (SLOTS,)),
-                        intercept=take(cells * SLOTS, np.float64, (SLOTS,))))
-    assert pos == raw.size, (pos, raw.size)
-    return out
-
-
-def build_host(directory, sanitize=False) -> Path:
-    """tests/localproxies_host.cpp with the flags of the product's host side (no FMA contraction); sanitize: address and undefined behaviour"""
-    exe = Path(directory) / ("localproxies_host_san" if sanitize else "localproxies_host")
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wno-unknown-pragmas", *extra, f"-I{ROOT / 'include'}", f"-I{ROOT / 'criteria3d_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "localproxies_host.cpp"), "-o", str(exe), "-lm"], check=True)
-    return exe
+    return output_of(Path(path).read_bytes(), r, cases)
 
 
 def run_host(exe, r, directory, cases=None) -> list:
     """the host program on one raster -> the outcome of every case"""
+    from tests.raster_helpers import run_host_program
     cases = r["cases"] if cases is None else cases
-    src, dst = Path(directory) / f"{r['name']}.in", Path(directory) / f"{r['name']}.out"
-    write_input(src, r, cases)
-    res = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True)
-    assert res.returncode == 0 and not res.stderr, (res.returncode, res.stderr[-2000:])
-    return read_output(dst, r, cases)
+    return output_of(run_host_program(exe, directory, r["name"], input_parts(r, cases)), r, cases)

@@ -1,6 +1,8 @@
 /* host build of the per-cell text of k_localdetrend_proxies (criteria3d_amd/csrc/sf3d_meteo.inc, sf3d_localdetrend.inc and
- * sf3d_localproxies.inc: the text the device compiles, here with one lane) for tests/test_localproxies_host.py: the pin is checked on a
- * CPU before any device runs the kernel, and the same program is built once with -fsanitize=address,undefined.
+ * sf3d_localproxies.inc: the text the device compiles, here with one lane) behind the checks and the set-up of
+ * sf3d_localproxies_interpolate (sf3d_localdetrend_setup.inc; a case they refuse ends the program with status 2) for
+ * tests/test_localproxies_host.py: the pin is checked on a CPU before any device runs the kernel, and the same program is built once with
+ * -fsanitize=address,undefined.
  *
  *   localproxies_host <input> <output>
  * input : int32 nRows, nCols, nCases; float flag; double xll, yll, cellSize; float dem[nCells]; float maps[8][nCells] (slot 0 unused:
@@ -11,13 +13,8 @@
  *                   double x[nStations], y[nStations]; float proxyValues[8][nStations]; float value[nStations].
  * output: per case float map[nCells]; uint32 count[nCells], interpolated[nCells]; float radius[nCells]; int32 significant[nCells];
  *         float r2[nCells]; double parameters[nCells][6]; int32 proxySignificant[nCells][8]; double slope[nCells][8], intercept[nCells][8]. */
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "sf3d_device.h"
+#include "host_io.h"
+#include "sf3d_localdetrend_setup.inc"
 
 #define SF3D_METEO_HOST
 #define SF3D_METEO_FN static inline
@@ -26,18 +23,6 @@
 #include "sf3d_localdetrend.inc"
 #include "sf3d_localproxies.inc"
 
-template <class T> static std::vector<T> readv(FILE* f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "localproxies_host: short input\n"); exit(2); }
-    return v;
-}
-
-template <class T> static void writev(FILE* f, const std::vector<T>& v)
-{
-    if (v.size() && fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "localproxies_host: short output\n"); exit(3); }
-}
-
 int main(int argc, char** argv)
 {
     if (argc != 3) return 2;
@@ -45,7 +30,7 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) return 2;
     const std::vector<int32_t> dims = readv<int32_t>(in, 3);
-    const float flag = readv<float>(in, 1)[0];
+    const float flag = read1<float>(in);
     const std::vector<double> geo = readv<double>(in, 3);
     const uint32_t nRows = (uint32_t)dims[0], nCols = (uint32_t)dims[1];
     const int nCases = dims[2];
@@ -74,24 +59,26 @@ int main(int argc, char** argv)
 
         LocalDetrendSetup s{};
         s.table = table.data();
-        s.function = iv[2]; s.nFirstGuess = iv[4]; s.minPointsLocal = iv[5]; s.method = iv[1]; s.useDetrending = iv[6];
-        s.minPoints = unsigned(iv[5] * 1.2f);
-        s.minPointsStep = unsigned(s.minPoints * 0.8);
-        s.stdDevThreshold = fv[0]; s.area = fv[1];
-        s.radiusAll = float(std::sqrt((s.minPoints * fv[1]) / (float(3.1415926535898) * m)));
+        s.method = iv[1]; s.useDetrending = iv[6];
+        localNumbers(iv[2], iv[4], iv[5], fv[0], m, fv[1], s);
 
-        /* the proxies of the call, as sf3d_localproxies_api.inc lays them out */
-        LocalProxiesSetup ps{};
-        ps.heightSlot = active[0] ? 0 : -1;
-        std::vector<float> rows((size_t)LP_MAX_OTHERS * METEO_MAX_STATIONS, 0.f);
-        for (int p = 1; p < S; ++p) {
-            if (!active[p]) continue;
-            const int r = ps.nOthers++;
-            ps.slot[r] = p; ps.stdDevThreshold[r] = threshold[p];
-            for (int t = 0; t < 4; ++t) ps.range[r][t] = range[(size_t)p * 4 + t];
-            for (uint32_t i = 0; i < m; ++i) rows[(size_t)r * METEO_MAX_STATIONS + i] = pv[(size_t)p * m + i];
+        /* the proxies of the call as the entry point takes them (slot 0 is the height), through its check and lay-out */
+        sf3d_meteo_settings_t settings{};
+        sf3d_localproxies_others_t others{};
+        settings.nProxies = S;
+        for (int p = 0; p < S; ++p) {
+            settings.proxy[p].active = active[p]; settings.proxy[p].isHeight = p == 0;
+            others.proxy[p].stdDevThreshold = threshold[p];
+            for (int t = 0; t < 2; ++t) { others.proxy[p].min[t] = range[(size_t)p * 4 + t]; others.proxy[p].max[t] = range[(size_t)p * 4 + 2 + t]; }
         }
-        const std::vector<float> sh(pv.begin(), pv.begin() + m);
+        LocalProxiesSetup ps{};
+        const float* row[LP_MAX_OTHERS] = {nullptr};
+        const float* height = nullptr;
+        if (!proxiesCallOk(m, (uint32_t)S, pv.data(), &settings, &others, ps, row, &height)) { fprintf(stderr, "localproxies_host: case %d is refused\n", k); return 2; }
+        std::vector<float> rows((size_t)LP_MAX_OTHERS * METEO_MAX_STATIONS, 0.f);          /* the kernel's: METEO_MAX_STATIONS a row */
+        for (int r = 0; r < ps.nOthers; ++r)
+            for (uint32_t i = 0; i < m; ++i) rows[(size_t)r * METEO_MAX_STATIONS + i] = row[r][i];
+        const std::vector<float> sh = height ? std::vector<float>(height, height + m) : std::vector<float>(m, 0.f);      /* zeros where the height is not active */
 
         /* the wave's room */
         std::vector<uint16_t> idx(m + 1);

@@ -48,10 +48,6 @@ def interpolate(sf, c, download=True):
     return meteo.interpolate(sf, c["var"], c["method"], c["x"], c["y"], c["value"], c["area"], c["settings"], download)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def cap_raster(pin):
     """257 x 3 = 771 cells (three blocks and three lanes) with SF3D_METEO_MAX_STATIONS stations on a jittered lattice around it: the LDS
     staging loop runs four times per thread and the tail block computes; the height proxy with inversion and a second raster"""

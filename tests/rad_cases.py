@@ -49,12 +49,6 @@ def pin_geo(pin, raster):
     return tuple(pin["geo"][raster]) if pin["geo"].ndim == 2 else tuple(pin["geo"])
 
 
-def same_bits(a, b):
-    """equal float32 maps: the same bits, a nan equals a nan (the sign and payload of a nan are not promised, sf3d_glibcmath.inc)"""
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
 def pin_chains(pin):
     """the pin's cases as chains of hours that share their maps: [(raster, [case, ...]), ...]"""
     chains = []

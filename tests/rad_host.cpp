@@ -1,6 +1,7 @@
 /* host build of the radiation block's point function (criteria3d_amd/csrc/sf3d_rad.inc with sf3d_trig.inc and sf3d_rad_setup.inc: the text
  * the device compiles) for tests/test_rad_point_host.py: runs rad_point over every cell of a raster for a list of hours and writes the
- * five maps after each, so that the pin is checked on a CPU before any device runs the kernel.
+ * five maps after each, so that the pin is checked on a CPU before any device runs the kernel; the same program is built once with
+ * -fsanitize=address,undefined.
  *
  *   rad_host <input> <output>
  * input : int32 nRows, nCols; float flag; double xll, yll, cellSize; float maps dem, lat, lon, slope, aspect; int32 nCases; per case:
@@ -8,16 +9,7 @@
  *         albedo, tilt, aspect, clearSky; int32 year, month, day, hour, minute, second, keep; float map transmissivity.
  *         keep = 0: the five maps start at the flag (a fresh sf3d_rad_initialize); 1: they are the previous case's.
  * output: per case int32 status (0, or 1: S_solpos refuses the date) and the five maps. */
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "sf3d_device.h"
-
-#define SF3D_GL_FN static inline
-#define SF3D_GL_TABLE static const
-#include "sf3d_glibcmath.inc"
+#include "host_io.h"
 
 #define SF3D_RAD_HOST
 #define SF3D_RAD_FN static inline
@@ -28,13 +20,6 @@
 #include "sf3d_rad.inc"
 #include "sf3d_rad_setup.inc"
 
-template <class T> static std::vector<T> readv(FILE* f, size_t n)
-{
-    std::vector<T> v(n);
-    if (fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "rad_host: short input\n"); exit(2); }
-    return v;
-}
-
 int main(int argc, char** argv)
 {
     if (argc != 3) return 2;
@@ -42,7 +27,7 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) return 2;
     const std::vector<int32_t> dims = readv<int32_t>(in, 2);
-    const float flag = readv<float>(in, 1)[0];
+    const float flag = read1<float>(in);
     const std::vector<double> geo = readv<double>(in, 3);
     const int nRows = dims[0], nCols = dims[1];
     const size_t n = (size_t)nRows * nCols;
@@ -54,7 +39,7 @@ int main(int argc, char** argv)
     bool first = true;
     for (size_t c = 0; c < n; ++c)
         if (!isFlag(dem[c], flag) && !isFlag(dem[c], -9999.f)) { if (first || dem[c] > g.demMax) g.demMax = dem[c]; first = false; }
-    const int nCases = readv<int32_t>(in, 1)[0];
+    const int nCases = read1<int32_t>(in);
     std::vector<float> maps[5];
     for (int k = 0; k < nCases; ++k) {
         const std::vector<int32_t> si = readv<int32_t>(in, 8);
@@ -79,9 +64,9 @@ int main(int argc, char** argv)
                 for (int m = 0; m < 5; ++m) maps[m][c] = o[m];
             }
         }
-        fwrite(&status, 4, 1, out);
-        for (auto& m : maps) fwrite(m.data(), 4, n, out);
+        writev(out, std::vector<int32_t>{status});
+        for (auto& m : maps) writev(out, m);
     }
-    fclose(out);
-    return 0;
+    fclose(in);
+    return fclose(out) == 0 ? 0 : 3;
 }

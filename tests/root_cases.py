@@ -35,11 +35,6 @@ def initialize(sf, pin, dem=None, crop_index=None, soil_index=None):
                     float(pin["flag"]))
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
 def small_raster(pin, shape, seed):
     """a raster of any shape on the pin's tables: DEM with flag cells, random unit and soil indices (some missing), degree days over all phases"""
     rng = np.random.default_rng(seed)
@@ -149,11 +144,6 @@ def accepted(sf, case):
                                        root.unit_array(case["unit_list"]), len(case["soil_list"]), root.soil_array(case["soil_list"]))
     sf.lib.sf3d_root_clean()
     return code not in (capi.PARAMETER_ERROR, capi.INDEX_ERROR)
-
-
-def build_host(directory, sanitize=False):
-    from tests.raster_helpers import build_host_program
-    return build_host_program("root", directory, sanitize)
 
 
 def run_host(exe, directory, name, case, layer0=0):

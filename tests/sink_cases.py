@@ -77,10 +77,6 @@ def hour(sf, pin, k, null=()):
     sinks.compute_hour(sf, **given)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
 # ---- a raster of any shape on the pin's tables
 
 SHAPES = ((7, 37), (3, 11), (1, 300))          # 259 cells: one block and three lanes; 33: less than a wave; 300: a partial second block
@@ -322,10 +318,7 @@ def device_run(sf, case, one_layer=False, crack=False):
     return state, out
 
 
-def build_host(directory, sanitize=False):
-    """(the root program, the sink program): the sink program takes the root program's outputs"""
-    from tests.raster_helpers import build_host_program
-    return rc.build_host(directory, sanitize), build_host_program("sink", directory, sanitize)
+HOST_PROGRAMS = ("root", "sink")                # run_host's `exes`, in this order: the sink program takes the root program's outputs
 
 
 def run_host(exes, directory, name, case, k, state, one_layer=False, crack=False):

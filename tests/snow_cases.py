@@ -95,11 +95,6 @@ def continuous_forcing(shape, seed):
     return dem, flag, hours + [last]
 
 
-def build_host(directory, sanitize=False):
-    from tests.raster_helpers import build_host_program
-    return build_host_program("snow", directory, sanitize)
-
-
 def run_host(exe, directory, name, dem, flag, state, hours, parameters=None):
     """the host program from `state` (the seven maps by name) over `hours` -> the thirteen maps after every hour, by name"""
     from tests.raster_helpers import Reader, run_host_program

@@ -2,7 +2,6 @@
 product library (and by the oracle), the C++ shim exports exactly the reference's 70 mangled
 names, and the host-side API logic of the PRODUCT (validation rules, error codes, sentinels -
 soilFluxes3D.cpp) behaves like the reference's.  No compute call is made."""
-import re
 import subprocess
 from pathlib import Path
 
@@ -11,19 +10,13 @@ import pytest
 
 from criteria3d_amd import build, capi
 from tests import checkers
+from tests.raster_helpers import declared_entry_points, exported_names as exported
 
 ROOT = Path(__file__).resolve().parent.parent
 
 
 def declared_symbols():
-    text = (ROOT / "include" / "sf3d.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sf3d_[a-z0-9_]+)\s*\(", text)))
-
-
-def exported(lib: Path):
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+    return declared_entry_points("sf3d.h", "sf3d_")
 
 
 def test_header_and_binding_table_agree():

@@ -12,6 +12,7 @@ from criteria3d_amd import capi, sinks
 from tests import crack_cases as kc
 from tests import sink_cases as sc
 from tests.golden import make_soil_cracking as gen
+from tests.raster_helpers import bits, build_host_program
 
 
 @pytest.fixture(scope="module")
@@ -28,13 +29,13 @@ def restated(pin):
 def test_restatement_equals_the_pin(pin, restated):
     for k, got in enumerate(restated[0]):
         for name in ("sinks_et",) + kc.OUTPUTS:
-            bad = kc.bits(got[name]) != kc.bits(pin[name][k])
+            bad = bits(got[name]) != bits(pin[name][k])
             assert not bad.any(), (k, name, int(bad.sum()))
         plain = sinks.restate_sink_hour(pin["dem"], float(pin["flag"]), float(pin["cell_size"]), pin["columns"], pin["vwc"], pin["crop_index"], pin["soil_index"],
                                         pin["sink_units"], pin["sink_soils"], pin["layer_depth"], pin["layer_thickness"], float(pin["computation_depth"]),
                                         pin["et0"][k], pin["lai"][k], pin["sink_degree_days"][k], pin["liquid_water"][k], sc.roots_of(pin, k), len(pin["vwc"]))
         assert np.count_nonzero(plain["sinks"] != got["sinks"]) > 100, k                  # cracking changes the hour
-        assert np.array_equal(kc.bits(plain["sinks_et"]), kc.bits(got["sinks_et"]))
+        assert np.array_equal(bits(plain["sinks_et"]), bits(got["sinks_et"]))
     ns = pin["dem"].size
     flag = float(pin["flag"])
     assert np.all(pin["crack_water"][:, pin["columns"][0] < 0] == flag) and np.all(pin["prec_surface_water"][:, pin["columns"][0] < 0] == np.float32(flag))
@@ -46,10 +47,10 @@ def test_one_layer_case(pin):
     for j, k in enumerate(int(v) for v in pin["one_layer_hours"]):
         got = kc.restated(pin, k, one_layer=True)
         for name in kc.OUTPUTS:
-            assert np.array_equal(kc.bits(got[name]), kc.bits(pin["one_layer_" + name][j])), (k, name)
+            assert np.array_equal(bits(got[name]), bits(pin["one_layer_" + name][j])), (k, name)
         w = pin["one_layer_crack_water"][j]
         assert not pin["one_layer_sinks"][j][pin["dem"].size:].any() and np.all(w[w != float(pin["flag"])] == 0)
-        assert np.array_equal(kc.bits(pin["one_layer_prec_surface_water"][j]), kc.bits(np.where(pin["columns"][0] < 0, np.float32(pin["flag"]), pin["liquid_water"][k])))
+        assert np.array_equal(bits(pin["one_layer_prec_surface_water"][j]), bits(np.where(pin["columns"][0] < 0, np.float32(pin["flag"]), pin["liquid_water"][k])))
 
 
 def test_no_arm_is_empty(pin, restated):
@@ -71,7 +72,7 @@ def test_no_arm_is_empty(pin, restated):
     assert snow == {k: recorded[k] for k in outside[:2]}
     for k in range(len(pin["et0"])):
         want = kc.liquid_water(pin["precipitation"][k], pin["snow_fall"][k], pin["snow_melt"][k], bool(pin["snow"][k]), pin["flag"])
-        assert np.array_equal(kc.bits(want), kc.bits(pin["liquid_water"][k]))
+        assert np.array_equal(bits(want), bits(pin["liquid_water"][k]))
 
 
 def test_small_cases_reach_every_arm(pin, oracle):
@@ -98,17 +99,17 @@ def test_small_cases_reach_every_arm(pin, oracle):
 def test_crack_tables_equal_the_recorded_ones(pin):
     reasons = []
     md, ll = sinks.crack_tables(pin["sink_soils"], pin["crack_soils"], pin["layer_depth"], pin["layer_thickness"], float(pin["computation_depth"]), reasons)
-    assert np.array_equal(kc.bits(md), kc.bits(pin["crack_max_depth"])) and np.array_equal(ll, pin["crack_last_layer"])      # lastLayer: the compiled getSoilLayerIndex
+    assert np.array_equal(bits(md), bits(pin["crack_max_depth"])) and np.array_equal(ll, pin["crack_last_layer"])      # lastLayer: the compiled getSoilLayerIndex
     assert (ll == -9999).sum() == 3 and len(set(reasons)) == 6 and md[0] == 0.6 and md[1] == 0.4
     sf = capi.load_product()
     sc.initialize(sf, pin)                                        # no device needed
     sinks.set_cracking(sf, pin["crack_soils"])
     md2, ll2 = sinks.get_crack_tables(sf)
-    assert np.array_equal(kc.bits(md2), kc.bits(pin["crack_max_depth"])) and np.array_equal(ll2, pin["crack_last_layer"])
+    assert np.array_equal(bits(md2), bits(pin["crack_max_depth"])) and np.array_equal(ll2, pin["crack_last_layer"])
     sc.initialize(sf, pin, one_layer=True)
     sinks.set_cracking(sf, pin["crack_soils"])
     md1, ll1 = sinks.get_crack_tables(sf)
-    assert np.array_equal(kc.bits(md1), kc.bits(pin["one_layer_crack_max_depth"])) and np.array_equal(ll1, pin["one_layer_crack_last_layer"]) and np.all(ll1 == -9999)
+    assert np.array_equal(bits(md1), bits(pin["one_layer_crack_max_depth"])) and np.array_equal(ll1, pin["one_layer_crack_last_layer"]) and np.all(ll1 == -9999)
     sinks.clean(sf)
 
 
@@ -164,16 +165,16 @@ def test_soil_crack_table_reads_the_soils_of_load_all_soils():
 def host(tmp_path_factory):
     from types import SimpleNamespace
     d = tmp_path_factory.mktemp("crack_host")
-    return SimpleNamespace(dir=d, exes=sc.build_host(d), san=sc.build_host(d, sanitize=True))
+    return SimpleNamespace(dir=d, exes=[build_host_program(b, d) for b in sc.HOST_PROGRAMS], san=[build_host_program(b, d, sanitize=True) for b in sc.HOST_PROGRAMS])
 
 
 def test_host_text_equals_the_pin_on_every_hour_and_on_one_layer(pin, oracle, host):
     """H, Se and the ponds come from the checker on the pin's potentials; no libm escape: the text carries its own exp"""
     state = sc.node_state(oracle, pin)
-    assert np.array_equal(kc.bits(state["vwc"]), kc.bits(pin["vwc"]))
+    assert np.array_equal(bits(state["vwc"]), bits(pin["vwc"]))
     for k in range(len(pin["et0"])):
         got = sc.run_host(host.exes, host.dir, "pin", pin, k, state, crack=True)
-        assert np.array_equal(kc.bits(got["max_depth"]), kc.bits(pin["crack_max_depth"])) and np.array_equal(got["last_layer"], pin["crack_last_layer"])
+        assert np.array_equal(bits(got["max_depth"]), bits(pin["crack_max_depth"])) and np.array_equal(got["last_layer"], pin["crack_last_layer"])
         print(f"host text, hour {k}: values differ: {sc.compare_host(got['crack'], {n: pin[n][k] for n in kc.OUTPUTS}, kc.OUTPUTS, k)}")
     for j, k in enumerate(int(v) for v in pin["one_layer_hours"]):
         got = sc.run_host(host.exes, host.dir, "pin-one-layer", pin, k, state, one_layer=True, crack=True)

@@ -5,7 +5,6 @@ Ravone project's crop rows, the C entry points of include/sf3d_crop.h and the bi
 text (tests/crop_host.cpp): equal to the pin and to the restatement bit for bit, clean under the address and undefined-behaviour sanitizers."""
 import json
 import re
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -15,7 +14,7 @@ import pytest
 from criteria3d_amd import build, capi, crop, esri, project3d as p3
 from tests import crop_cases as cc
 from tests import tolerances
-from tests.raster_helpers import bits as _bits, differing
+from tests.raster_helpers import bits as _bits, build_host_program, declared_entry_points, differing, exported_names, header_text
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -26,8 +25,7 @@ def pin():
 
 
 def test_crop_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_crop.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_crop_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_crop.h"), declared_entry_points("sf3d_crop.h", "sf3d_crop_")
     assert declared == sorted(crop.SIGNATURES)
     assert not set(declared) & set(capi.SIGNATURES)          # sf3d.h (the drop-in ABI) is unchanged
     for k, n in enumerate(("DEGREE_DAYS", "LAI", "DAILY_TMIN", "DAILY_TMAX")):
@@ -38,9 +36,7 @@ def test_crop_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_crop_entry_points():
-    lib = build.build_product()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(crop.SIGNATURES) <= names
 
 
@@ -215,7 +211,7 @@ def test_state_directory_round_trip(tmp_path, pin):
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("crop_host")
-    return SimpleNamespace(dir=d, exe=cc.build_host(d), san=cc.build_host(d, sanitize=True))
+    return SimpleNamespace(dir=d, exe=build_host_program("crop", d), san=build_host_program("crop", d, sanitize=True))
 
 
 def _random_scripts(pin):

@@ -12,7 +12,7 @@ from tests import crack_cases as kc
 from tests import ranks as mr
 from tests import sink_cases as sc
 from tests.golden import make_soil_cracking as gen
-from tests.raster_helpers import need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits, build_host_program, need_glibc_set as _need_glibc_set
 from tests.tolerances import assert_water_nodes
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +33,7 @@ def _model(lib, case, columns=True):
 
 def _same(got, want, what):
     for name in want:
-        bad = kc.bits(got[name]) != kc.bits(want[name])
+        bad = bits(got[name]) != bits(want[name])
         print(f"{what} {name}: {int(bad.sum())} values differ")
         assert not bad.any(), (what, name, int(bad.sum()), np.asarray(got[name])[bad][:4], np.asarray(want[name])[bad][:4])
 
@@ -42,7 +42,7 @@ def test_every_hour_equals_the_pin(product, pin):
     _need_glibc_set(product)
     m = _model(product, pin)
     for got, name in zip(kc.node_state(product, m.n), ("vwc", "max_vwc", "pond_mm")):              # the state the reference read
-        assert np.array_equal(kc.bits(got), kc.bits(pin[name])), name
+        assert np.array_equal(bits(got), bits(pin[name])), name
     kc.initialize(product, pin)
     for k in range(len(pin["et0"])):
         sc.hour(product, pin, k)
@@ -192,7 +192,7 @@ def test_a_changed_column_table_leaves_no_crack_water_behind_and_apply_is_the_se
     _same(hour_b, _wanted(case, 0, state, columns), "hour B")
     assert not stale.any() and np.count_nonzero(hour_b["sinks"][m.ns:] > 0) > 50
     sinks.apply(product)
-    assert np.array_equal(kc.bits(sinks.get_node_sinks(product, m.n)), kc.bits(hour_b["sinks"]))
+    assert np.array_equal(bits(sinks.get_node_sinks(product, m.n)), bits(hour_b["sinks"]))
     dt0 = product.lib.sf3d_compute_step(3600.0)
     s0 = cm.snapshot(product, m)
     q = hour_b["sinks"]
@@ -233,7 +233,7 @@ def test_two_ranks_merge_to_the_single_rank_sinks_and_maps(product, pin, tmp_pat
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("crack_host")
-    return d, sc.build_host(d)
+    return d, [build_host_program(b, d) for b in sc.HOST_PROGRAMS]
 
 
 @pytest.mark.parametrize("shape", sc.SHAPES)

@@ -11,7 +11,7 @@ from criteria3d_amd import capi, catchment as cm, crop, snow
 from tests import ranks as mr
 from tests import crop_cases as cc
 from tests.scenarios import ravone_project_model
-from tests.raster_helpers import bits as _bits, differing, need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits as _bits, build_host_program, differing, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 
@@ -281,7 +281,7 @@ def test_error_paths(product, pin):
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("crop_host")
-    return d, cc.build_host(d)
+    return d, build_host_program("crop", d)
 
 
 @pytest.mark.parametrize("shape", cc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")

@@ -9,6 +9,7 @@ import pytest
 from criteria3d_amd import capi, hour, localdetrend as ld, meteo
 from tests import localdetrend_cases as lc
 from tests import ranks as mr
+from tests.raster_helpers import bits, build_host_program, same
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +23,11 @@ def pin():
 def host(tmp_path_factory):
     """the host build of the kernel's per-cell text (tests/localdetrend_host.cpp), built once in a temporary directory"""
     d = tmp_path_factory.mktemp("localdetrend_host")
-    return lc.build_host(d), d
+    return build_host_program("localdetrend", d), d
 
 
 def _same(got, want, what):
-    bad = lc.bits(got) != lc.bits(want)
+    bad = bits(got) != bits(want)
     assert not bad.any(), (what, int(bad.sum()), np.asarray(got)[bad][:4], np.asarray(want)[bad][:4])
 
 
@@ -38,7 +39,7 @@ def test_every_case_equals_the_pin_in_every_cell_and_quantity(product, pin, name
     for k, c in enumerate(r["cases"]):
         what = f"{name} {k} {lc.case_name(c)}"
         got = lc.interpolate(product, c)
-        lc.same(lc.outcome(product, got), c["want"], what)
+        same(lc.outcome(product, got), c["want"], what, lc.QUANTITIES)
         _same(meteo.get_map(product, c["var"]), c["want"]["value"], f"{what}: the meteo block's slot")
         assert (got[r["dem"] != flag] != flag).all() and (got[r["dem"] == flag] == flag).all()
     assert ld.bytes_held(product) > r["dem"].size * (ld.MAX_PARAMETERS * 8 + 13)
@@ -55,7 +56,7 @@ def test_two_calls_give_the_same_bits(product, pin):
     other = next(c for c in r["cases"] if c["label"] == "vee")
     lc.interpolate(product, other)                                          # another call in between leaves nothing behind
     second = lc.outcome(product, lc.interpolate(product, c))
-    lc.same(second, first, "the second call")
+    same(second, first, "the second call", lc.QUANTITIES)
     meteo.clean(product)
 
 
@@ -89,7 +90,7 @@ def test_the_map_counts_as_produced_and_the_outcome_goes_with_the_raster(product
     lc.initialize(product, r)
     with pytest.raises(capi.SF3DError):
         ld.get_selection(product)
-    lc.same(lc.outcome(product, lc.interpolate(product, air_case)), air_case["want"], "on the new raster")
+    same(lc.outcome(product, lc.interpolate(product, air_case)), air_case["want"], "on the new raster", lc.QUANTITIES)
     meteo.clean(product)
 
 
@@ -119,7 +120,7 @@ def test_lists_longer_than_a_wave_against_the_restatement(product, stations, min
     lc.initialize(product, r)
     got = lc.outcome(product, lc.interpolate(product, c))
     want = lc.restated(r, c)
-    lc.same(got, want, f"{stations} stations, {meteo.METHODS[method]}")
+    same(got, want, f"{stations} stations, {meteo.METHODS[method]}", lc.QUANTITIES)
     inside = r["dem"] != r["flag"]
     assert want["count"][inside].min() >= min(stations, ld.min_points(min_points_local)) > 20 and want["significant"][inside].all()
     if stations != 1024:
@@ -143,7 +144,7 @@ def test_off_the_pin_the_device_equals_the_host_build_of_its_text(product, host,
     want = lc.run_host(host[0], r, host[1], [c])[0]
     lc.initialize(product, r)
     got = lc.interpolate(product, c)
-    lc.same(lc.outcome(product, got), want, label)
+    same(lc.outcome(product, got), want, label, lc.QUANTITIES)
     _same(meteo.get_map(product, c["var"]), want["value"], f"{label}: the meteo block's slot")
     out = r["dem"] == r["flag"]
     assert out.sum() == 1 and (got[out] == r["flag"]).all() and (ld.get_selection(product)["count"][out] == 0).all() and (want["count"][~out] > 0).all()

@@ -11,6 +11,7 @@ from criteria3d_amd import capi, hour, localdetrend as ld, localproxies as lp, m
 from tests import localdetrend_cases as lc
 from tests import localproxies_cases as pc
 from tests import ranks as mr
+from tests.raster_helpers import bits, build_host_program, same
 
 pytestmark = pytest.mark.gpu
 
@@ -24,11 +25,11 @@ def pin():
 def host(tmp_path_factory):
     """the host builds of the two kernels' per-cell text (tests/localproxies_host.cpp, tests/localdetrend_host.cpp), built once"""
     d = tmp_path_factory.mktemp("localproxies_host")
-    return pc.build_host(d), lc.build_host(d), d
+    return build_host_program("localproxies", d), build_host_program("localdetrend", d), d
 
 
 def _same(got, want, what):
-    bad = pc.bits(got) != pc.bits(want)
+    bad = bits(got) != bits(want)
     assert not bad.any(), (what, int(bad.sum()), np.asarray(got)[bad][:4], np.asarray(want)[bad][:4])
 
 
@@ -40,7 +41,7 @@ def test_every_case_equals_the_pin_in_every_cell_and_quantity(product, pin, name
     for k, c in enumerate(r["cases"]):
         what = f"{name} {k} {pc.case_name(c)}"
         got = pc.interpolate(product, c)
-        pc.same(pc.outcome(product, got), c["want"], what)
+        same(pc.outcome(product, got), c["want"], what, pc.QUANTITIES)
         _same(meteo.get_map(product, c["var"]), c["want"]["value"], f"{what}: the meteo block's slot")
         assert (got[r["dem"] == flag] == flag).all()
     assert lp.bytes_held(product) > r["dem"].size * (meteo.MAX_PROXIES * 17 + 4)
@@ -57,7 +58,7 @@ def test_the_pin_of_the_height_alone_through_the_new_entry_point(product, name):
     for k, c in enumerate(r["cases"]):
         got = lp.interpolate(product, c["var"], c["method"], c["x"], c["y"], c["value"], c["height"][None, :], c["area"], c["fit"], [dict(active=1, isHeight=1)],
                              pc.default_others()[:1], dict(useDetrending=c["useDetrending"]))
-        lc.same(dict(value=got, **ld.get_selection(product), **ld.get_fit(product)), c["want"], f"{name} {k} {lc.case_name(c)}")
+        same(dict(value=got, **ld.get_selection(product), **ld.get_fit(product)), c["want"], f"{name} {k} {lc.case_name(c)}", lc.QUANTITIES)
         assert (lp.get_interpolated(product) == c["want"]["count"]).all() and not lp.get_proxy_fit(product)["proxy_significant"].any()
     meteo.clean(product)
 
@@ -70,7 +71,7 @@ def test_two_calls_give_the_same_bits(product, pin):
     other = next(c for c in r["cases"] if c["label"] == "two")
     pc.interpolate(product, other)                                          # another call in between leaves nothing behind
     second = pc.outcome(product, pc.interpolate(product, c))
-    pc.same(second, first, "the second call")
+    same(second, first, "the second call", pc.QUANTITIES)
     meteo.clean(product)
 
 
@@ -111,7 +112,7 @@ def test_the_map_counts_as_produced_and_the_outcome_goes_with_the_raster(product
     pc.initialize(product, r)
     with pytest.raises(capi.SF3DError):
         lp.get_interpolated(product)
-    pc.same(pc.outcome(product, pc.interpolate(product, air_case)), air_case["want"], "on the new raster")
+    same(pc.outcome(product, pc.interpolate(product, air_case)), air_case["want"], "on the new raster", pc.QUANTITIES)
     meteo.clean(product)
 
 
@@ -143,7 +144,7 @@ def test_lists_longer_than_a_wave_against_the_restatement(product, stations, min
     pc.initialize(product, r)
     got = pc.outcome(product, pc.interpolate(product, c))
     want = pc.restated(r, c)
-    pc.same(got, want, f"{stations} stations, {others} other proxies")
+    same(got, want, f"{stations} stations, {others} other proxies", pc.QUANTITIES)
     inside = r["dem"] != r["flag"]
     assert want["count"][inside].min() > 64 and want["proxy_significant"][inside].sum() >= others * inside.sum() // 2
     assert (want["interpolated"][inside] < want["count"][inside]).all() and want["interpolated"][inside].min() > 32
@@ -161,7 +162,7 @@ def test_off_the_pin_the_device_equals_the_host_build_of_its_text(product, host,
     want = pc.run_host(host[0], r, host[2], [c])[0]
     pc.initialize(product, r)
     got = pc.interpolate(product, c)
-    pc.same(pc.outcome(product, got), want, label)
+    same(pc.outcome(product, got), want, label, pc.QUANTITIES)
     _same(meteo.get_map(product, c["var"]), want["value"], f"{label}: the meteo block's slot")
     out = r["dem"] == r["flag"]
     assert out.sum() == 1 and (got[out] == r["flag"]).all() and (ld.get_selection(product)["count"][out] == 0).all() and (lp.get_interpolated(product)[out] == 0).all()
@@ -177,7 +178,7 @@ def test_the_height_alone_off_the_pin_through_the_new_entry_point(product, host,
     lc.initialize(product, r)
     got = lp.interpolate(product, c["var"], c["method"], c["x"], c["y"], c["value"], c["height"][None, :], c["area"], c["fit"], [dict(active=1, isHeight=1)],
                          pc.default_others()[:1], dict(useDetrending=c["useDetrending"]))
-    lc.same(dict(value=got, **ld.get_selection(product), **ld.get_fit(product)), want, label)
+    same(dict(value=got, **ld.get_selection(product), **ld.get_fit(product)), want, label, lc.QUANTITIES)
     _same(meteo.get_map(product, c["var"]), want["value"], f"{label}: the meteo block's slot")
     assert (lp.get_interpolated(product) == want["count"]).all() and not lp.get_proxy_fit(product)["proxy_significant"].any()
     meteo.clean(product)

@@ -11,6 +11,7 @@ from criteria3d_amd import capi, crop, meteo, snow
 from tests import ranks as mr
 from tests import crop_cases as cc
 from tests import meteo_cases as mc
+from tests.raster_helpers import bits
 from tests.snow_cases import melt_forcing
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,10 @@ def pin():
 
 
 def _same(got, want, what):
-    bad = mc.bits(got) != mc.bits(want)
+    bad = bits(got) != bits(want)
     if bad.any():
         print(f"{what}: {int(bad.sum())} values differ")
-    assert np.array_equal(mc.bits(got), mc.bits(want)), (what, int(bad.sum()), got[bad][:4], want[bad][:4])
+    assert np.array_equal(bits(got), bits(want)), (what, int(bad.sum()), got[bad][:4], want[bad][:4])
 
 
 def test_every_cell_of_every_case_equals_the_pin(product, pin):
@@ -122,7 +123,7 @@ def test_300_stations_on_small_rasters_against_the_restatement(product, pin, sha
     got = meteo.interpolate(product, "airT", method, r["x"], r["y"], r["value"], r["area"], r["settings"])
     want = meteo.restate_interpolate(r["dem"], r["xll"], r["yll"], r["cell_size"], r["proxy_maps"], "airT", method, r["x"], r["y"], r["value"], r["area"],
                                      r["settings"], float(flag))
-    print(f"{shape} {method}: {int((mc.bits(got) != mc.bits(want)).sum())} values differ")
+    print(f"{shape} {method}: {int((bits(got) != bits(want)).sum())} values differ")
     _same(got, want, f"300 stations on {shape}, {method}")
     assert got.flat[0] == flag and got.flat[-1] != flag and np.count_nonzero(got != flag) == r["dem"].size - 2
     meteo.clean(product)

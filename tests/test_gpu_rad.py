@@ -18,6 +18,7 @@ import pytest
 from criteria3d_amd import capi, catchment as cm, meteo, radiation as rad
 from tests import ranks as mr
 from tests import rad_cases
+from tests.raster_helpers import differing
 from tests.test_trig_host import acos_ranges, build_trig_host, ptr, trig_ranges
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,7 @@ def pin():
 
 
 def _same(got, want, what):
-    same = rad_cases.same_bits(got, want)
+    same = ~differing(got, want)
     assert same.all(), (what, int((~same).sum()), np.argwhere(~same)[:4].tolist(), np.asarray(got)[~same][:4], np.asarray(want)[~same][:4])
 
 

@@ -10,7 +10,7 @@ import pytest
 from criteria3d_amd import capi, catchment as cm, crop, root
 from tests import ranks as mr
 from tests import root_cases as rc
-from tests.raster_helpers import differing, need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits, build_host_program, differing, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +22,7 @@ def pin():
 
 def _same(got, want, what):
     for n in rc.OUTPUTS:
-        bad = rc.bits(got[n]) != rc.bits(want[n])
+        bad = bits(got[n]) != bits(want[n])
         print(f"{what} {n}: {int(bad.sum())} values differ")
         assert not bad.any(), (what, n, int(bad.sum()), got[n][bad][:4], want[n][bad][:4])
 
@@ -38,7 +38,7 @@ def test_every_output_of_every_map_equals_the_pin(product, pin):
         got = root.all_maps(product)
         _same(got, {n: pin[n][k] for n in rc.OUTPUTS}, f"map {k}")
         for layer in (0, 5, len(pin["layer_depth"]) - 1):                   # the one-layer getter
-            assert np.array_equal(rc.bits(root.get_density(product, layer)), rc.bits(pin["density"][k][layer])), (k, layer)
+            assert np.array_equal(bits(root.get_density(product, layer)), bits(pin["density"][k][layer])), (k, layer)
         keys = root.get_keys(product)
         assert np.array_equal(keys >= 0, pin["length"][k] != flag) and keys.max() < root.table_rows(product)
     # the keyed form: far fewer distinct density vectors than computed cells
@@ -201,7 +201,7 @@ def test_error_paths(product, pin):
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("root_host")
-    return d, rc.build_host(d)
+    return d, build_host_program("root", d)
 
 
 @pytest.mark.parametrize("shape", rc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")

@@ -14,7 +14,7 @@ from tests import crop_cases as cc
 from tests import root_cases as rc
 from tests import sink_cases as sc
 from tests.snow_cases import melt_forcing
-from tests.raster_helpers import bits as _bits, need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits as _bits, build_host_program, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +34,7 @@ def _model(product, pin):
 
 def _same(got, want, what):
     for name in want:
-        bad = sc.bits(got[name]) != sc.bits(want[name])
+        bad = _bits(got[name]) != _bits(want[name])
         print(f"{what} {name}: {int(bad.sum())} values differ")
         assert not bad.any(), (what, name, int(bad.sum()), np.asarray(got[name])[bad][:4], np.asarray(want[name])[bad][:4])
 
@@ -47,7 +47,7 @@ def _outputs(product, n):
 def test_every_hour_equals_the_pin(product, pin):
     _need_glibc_set(product)
     m = _model(product, pin)
-    assert np.array_equal(sc.bits(product.water_content(0, m.n)), sc.bits(pin["vwc"]))             # the state the fixture's water contents were read from
+    assert np.array_equal(_bits(product.water_content(0, m.n)), _bits(pin["vwc"]))             # the state the fixture's water contents were read from
     rc.initialize(product, pin)
     sc.initialize(product, pin)
     for k in range(len(pin["et0"])):
@@ -195,7 +195,7 @@ def test_a_changed_column_table_leaves_no_sinks_behind(product, pin):
     assert not stale.any() and np.count_nonzero(hour_b["sinks"]) > 300
     # the hand-over: apply leaves the array as it is, and the solver steps as after the node-by-node setter
     sinks.apply(product)
-    assert np.array_equal(sc.bits(sinks.get_node_sinks(product, m.n)), sc.bits(hour_b["sinks"]))
+    assert np.array_equal(_bits(sinks.get_node_sinks(product, m.n)), _bits(hour_b["sinks"]))
     dt0 = product.lib.sf3d_compute_step(3600.0)
     s0 = cm.snapshot(product, m)
     q = hour_b["sinks"]
@@ -305,7 +305,7 @@ def test_two_ranks_merge_to_the_single_rank_sinks(product, pin, tmp_path):
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("sink_host")
-    return d, sc.build_host(d)
+    return d, [build_host_program(b, d) for b in sc.HOST_PROGRAMS]
 
 
 @pytest.mark.parametrize("shape", sc.SHAPES)

@@ -15,7 +15,7 @@ from tests import tolerances
 from tests.scenarios import ravone_project_model
 from tests import snow_cases
 from tests.snow_cases import melt_forcing
-from tests.raster_helpers import bits as _bits, differing, need_glibc_set as _need_glibc_set
+from tests.raster_helpers import bits as _bits, build_host_program, differing, need_glibc_set as _need_glibc_set
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -283,7 +283,7 @@ def test_error_paths(product, pin):
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("snow_host")
-    return d, snow_cases.build_host(d)
+    return d, build_host_program("snow", d)
 
 
 @pytest.mark.parametrize("shape", snow_cases.SHAPES)

@@ -8,6 +8,7 @@ from criteria3d_amd import capi, hour, meteo, topodist
 from tests import meteo_cases as mc
 from tests import ranks as mr
 from tests import topodist_cases as tc
+from tests.raster_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,7 @@ def pin():
 
 
 def _same(got, want, what):
-    bad = tc.bits(got) != tc.bits(want)
+    bad = bits(got) != bits(want)
     assert not bad.any(), (what, int(bad.sum()), np.asarray(got)[bad][:4], np.asarray(want)[bad][:4])
 
 
@@ -61,7 +62,7 @@ def test_set_get_and_drop_map(product, pin):
     _same(topodist.get_map(product, hand + 1), r["maps"][hand + 1], "the neighbouring map is untouched")
     after = tc.interpolate(product, r, case, every)
     _same(after, case["want"], "the hand-made map")
-    assert (tc.bits(before) != tc.bits(after)).any()
+    assert (bits(before) != bits(after)).any()
     # a dropped map: the station is map-less; naming it is refused, -1 in its place gives the walk
     topodist.drop_map(product, hand)
     with pytest.raises(capi.SF3DError):
@@ -178,7 +179,7 @@ def test_1024_stations_on_257_x_3_cells_against_the_restatement(product, method)
     _same(got, want, f"1024 stations, {method}")
     assert got.flat[0] == r["flag"] and got.flat[-1] != r["flag"] and np.count_nonzero(got != r["flag"]) == r["dem"].size - 2
     plain = meteo.interpolate(product, "airT", method, r["x"], r["y"], r["value"], r["area"], dict(r["settings"], useTopographicDistance=0))
-    assert (tc.bits(plain) != tc.bits(got)).any()                         # the topographic distance changes the map
+    assert (bits(plain) != bits(got)).any()                         # the topographic distance changes the map
     with pytest.raises(capi.SF3DError):                                   # one point beyond the cap
         topodist.compute(product, np.append(r["x"], 0.0), np.append(r["y"], 0.0), np.append(r["z"], 0.0))
     meteo.clean(product)

@@ -4,7 +4,6 @@ tests/golden/relhum_dew.npz and pond_day.npz bit for bit, the pins' arms, the pe
 the host (tests/hour_host.cpp) equal to the pins on every value - and once more as a stand-alone program under the address and
 undefined-behaviour sanitizers -, the order of restate_totals, and every refusal of the entry points through the C ABI without a device."""
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 from criteria3d_amd import build, capi, catchment as cm, hour, sinks
 from tests import hour_cases as hc
 from tests import sink_cases as sc
+from tests.raster_helpers import bits, build_host_program, declared_entry_points, exported_names, header_text
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -28,8 +28,7 @@ def pd():
 
 
 def test_hour_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_hour.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_hour_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_hour.h"), declared_entry_points("sf3d_hour.h", "sf3d_hour_")
     assert declared == sorted(hour.SIGNATURES)
     for k, n in enumerate(("RELHUM", "TOTALS", "POND")):
         assert re.search(rf"SF3D_HOUR_KERNEL_{n} = {k}\b", text) and getattr(hour, "KERNEL_" + n) == k
@@ -39,13 +38,11 @@ def test_hour_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_hour_entry_points_and_the_drop_in_abi_does_not():
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_product())], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(hour.SIGNATURES) <= names
     assert "sf3d_hour" not in (ROOT / "include" / "sf3d.h").read_text()
     assert not any("sf3d_hour" in n for n in capi.SIGNATURES)
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_shim())], capture_output=True, text=True, check=True).stdout
-    assert "sf3d_hour" not in out
+    assert not any("sf3d_hour" in n for n in exported_names(build.build_shim()))
 
 
 def test_the_pins_reach_every_arm(rh, pd):
@@ -66,17 +63,17 @@ def test_the_pins_reach_every_arm(rh, pd):
 
 
 def test_restatements_equal_the_pins(rh, pd):
-    assert np.array_equal(hc.bits(hour.rel_hum_from_tdew(rh["dew_t"], rh["air_t"])), hc.bits(rh["rel_hum"]))
-    assert np.array_equal(hc.bits(hour.restate_relative_humidity(rh["map_air_t"], rh["map_dew_t"], float(rh["flag"]))), hc.bits(rh["map_rel_hum"]))
+    assert np.array_equal(bits(hour.rel_hum_from_tdew(rh["dew_t"], rh["air_t"])), bits(rh["rel_hum"]))
+    assert np.array_equal(bits(hour.restate_relative_humidity(rh["map_air_t"], rh["map_dew_t"], float(rh["flag"]))), bits(rh["map_rel_hum"]))
     for case in range(2):
         cell = hc.pond_restated(pd, case)
-        assert np.array_equal(hc.bits(cell), hc.bits(pd["cell_pond"][case])), case
+        assert np.array_equal(bits(cell), bits(pd["cell_pond"][case])), case
         # dailyUpdatePond: the node of a cell takes the value unless it is NODATA; the others keep theirs
         on_nodes = hc.pond_restated(pd, case, surface_index=pd["index"])
         node = pd["initial_pond"].copy()
         put = on_nodes != np.float32(-9999.0)
         node[pd["index"][put]] = on_nodes[put].astype(np.float64)
-        assert np.array_equal(hc.bits(node, np.float64), hc.bits(pd["node_pond"][case], np.float64)), case
+        assert np.array_equal(bits(node), bits(pd["node_pond"][case])), case
         assert np.count_nonzero(node != pd["initial_pond"]) > 200 and np.count_nonzero(node == pd["initial_pond"]) > 10
     assert not np.array_equal(pd["cell_pond"][0], pd["cell_pond"][1])
 
@@ -84,26 +81,26 @@ def test_restatements_equal_the_pins(rh, pd):
 def test_other_ranks_cells_keep_the_flag_in_the_restatements(rh, pd):
     mine = (np.arange(rh["map_air_t"].size).reshape(rh["map_air_t"].shape) % 3) != 0
     got = hour.restate_relative_humidity(rh["map_air_t"], rh["map_dew_t"], float(rh["flag"]), mine)
-    assert np.all(got[~mine] == rh["flag"]) and np.array_equal(hc.bits(got[mine]), hc.bits(rh["map_rel_hum"][mine]))
+    assert np.all(got[~mine] == rh["flag"]) and np.array_equal(bits(got[mine]), bits(rh["map_rel_hum"][mine]))
     pond = hc.pond_restated(pd, 0, mine=mine)
-    assert np.all(pond[~mine] == np.float32(-9999.0)) and np.array_equal(hc.bits(pond[mine]), hc.bits(pd["cell_pond"][0][mine]))
+    assert np.all(pond[~mine] == np.float32(-9999.0)) and np.array_equal(bits(pond[mine]), bits(pd["cell_pond"][0][mine]))
 
 
 def test_host_build_of_the_kernels_text_equals_the_pins(rh, pd, tmp_path):
-    exe = hc.build_host(tmp_path)
+    exe = build_host_program("hour", tmp_path)
     for case in range(2):
         pairs, raster, pond = hc.run_host(exe, tmp_path, rh, pd, case, tag=str(case))
-        assert np.array_equal(hc.bits(pairs), hc.bits(rh["rel_hum"]))
-        assert np.array_equal(hc.bits(raster), hc.bits(rh["map_rel_hum"]))
-        assert np.array_equal(hc.bits(pond), hc.bits(pd["cell_pond"][case])), case
+        assert np.array_equal(bits(pairs), bits(rh["rel_hum"]))
+        assert np.array_equal(bits(raster), bits(rh["map_rel_hum"]))
+        assert np.array_equal(bits(pond), bits(pd["cell_pond"][case])), case
 
 
 def test_host_build_runs_clean_under_the_sanitizers(rh, pd, tmp_path):
     """the program has its own main and is not loaded into python; a sanitizer report ends it with a non-zero status"""
-    exe = hc.build_host(tmp_path, sanitize=True)
+    exe = build_host_program("hour", tmp_path, sanitize=True)
     for case in range(2):
         pairs, _, pond = hc.run_host(exe, tmp_path, rh, pd, case, tag=f"san{case}")
-        assert np.array_equal(hc.bits(pairs), hc.bits(rh["rel_hum"])) and np.array_equal(hc.bits(pond), hc.bits(pd["cell_pond"][case]))
+        assert np.array_equal(bits(pairs), bits(rh["rel_hum"])) and np.array_equal(bits(pond), bits(pd["cell_pond"][case]))
 
 
 def test_restate_totals_is_the_sequential_sum_of_the_terms():

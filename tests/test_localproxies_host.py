@@ -9,7 +9,6 @@ and what the table is there for asserted on the references: every number of sign
 gaps in the significant set, cells of one raster that differ in it, a list above 64 whose interpolated list is not."""
 import ctypes
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -18,6 +17,7 @@ import pytest
 from criteria3d_amd import build, capi, localdetrend as ld, localproxies as lp, meteo
 from tests import localdetrend_cases as lc
 from tests import localproxies_cases as pc
+from tests.raster_helpers import build_host_program, declared_entry_points, exported_names, header_text, same
 
 ROOT = Path(__file__).resolve().parent.parent
 MUST = ("0 other proxies active", "1 other proxies active", "2 other proxies active", "4 other proxies active", "7 other proxies active", "the height not active",
@@ -37,7 +37,7 @@ def pin():
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    return pc.build_host(tmp_path_factory.mktemp("localproxies_host"))
+    return build_host_program("localproxies", tmp_path_factory.mktemp("localproxies_host"))
 
 
 @pytest.fixture(scope="module")
@@ -69,8 +69,7 @@ def off_pin_restated(off_pin):
 
 
 def test_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_localproxies.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_localproxies_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_localproxies.h"), declared_entry_points("sf3d_localproxies.h", "sf3d_localproxies_")
     assert declared == sorted(lp.SIGNATURES)
     assert re.search(rf"#define SF3D_LOCALPROXIES_MAX_OTHERS {lp.MAX_OTHERS}\b", text) and lp.MAX_OTHERS == meteo.MAX_PROXIES - 1 == 7
     device = (ROOT / "criteria3d_amd" / "csrc" / "sf3d_device.h").read_text()
@@ -80,13 +79,11 @@ def test_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_entry_points_and_the_drop_in_abi_does_not():
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_product())], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(lp.SIGNATURES) <= names
     assert "localproxies" not in (ROOT / "include" / "sf3d.h").read_text()
     assert not any("localproxies" in n.lower() for n in capi.SIGNATURES) and not any("localproxies" in n.lower() for n in capi.REFERENCE_API)
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_shim())], capture_output=True, text=True, check=True).stdout
-    assert "localproxies" not in out.lower()
+    assert not any("localproxies" in n.lower() for n in exported_names(build.build_shim()))
 
 
 def _fit(**change) -> dict:
@@ -211,19 +208,19 @@ def test_the_pin_holds_the_arms_the_issue_lists(pin):
 def test_host_build_of_the_kernels_text_equals_the_pin_in_every_quantity(pin, host, name):
     r = pin[name]
     for k, (c, got) in enumerate(zip(r["cases"], host[name])):
-        pc.same(got, c["want"], f"{name} {k} {pc.case_name(c)}")
+        same(got, c["want"], f"{name} {k} {pc.case_name(c)}", pc.QUANTITIES)
     assert sum(int(c["want"]["proxy_significant"].sum()) for c in r["cases"]) > 100                 # not vacuous
 
 
 def test_host_build_under_the_sanitizers_reports_nothing(pin, host, off_pin, tmp_path):
     """a stand-alone program with its own main: nothing is loaded into Python.  The pin, then the inputs of pc.OFF_PIN"""
-    san = pc.build_host(tmp_path, sanitize=True)
+    san = build_host_program("localproxies", tmp_path, sanitize=True)
     for name in pc.RASTERS:
         got = pc.run_host(san, pin[name], tmp_path)                     # asserts exit status 0 and an empty stderr
         for k, (a, b) in enumerate(zip(got, host[name])):
-            pc.same(a, b, f"{name} {k} under the sanitizers")
+            same(a, b, f"{name} {k} under the sanitizers", pc.QUANTITIES)
     for label, (r, c, want) in off_pin.items():
-        pc.same(pc.run_host(san, r, tmp_path, [c])[0], want, f"{label} under the sanitizers")
+        same(pc.run_host(san, r, tmp_path, [c])[0], want, f"{label} under the sanitizers", pc.QUANTITIES)
 
 
 @pytest.mark.parametrize("name", lc.RASTERS)
@@ -237,7 +234,7 @@ def test_host_text_with_no_other_proxy_equals_the_pin_of_the_height_alone(exe, t
         pv[0] = c["height"]
         cases.append(dict(c, proxy_values=pv, active=[1] + [0] * (pc.SLOTS - 1), others=pc.default_others()))
     for k, (c, got) in enumerate(zip(cases, pc.run_host(exe, r, tmp_path, cases))):
-        lc.same(got, c["want"], f"{name} {k} {lc.case_name(c)}")
+        same(got, c["want"], f"{name} {k} {lc.case_name(c)}", lc.QUANTITIES)
         assert (got["interpolated"] == got["count"]).all() and not got["proxy_significant"].any()
 
 
@@ -245,7 +242,7 @@ def test_restatement_equals_the_pin_on_every_cell_of_tiny(pin):
     r = pin["tiny"]
     arms = {}
     for k, c in enumerate(r["cases"]):
-        pc.same(pc.restated(r, c, arms=arms), c["want"], f"tiny {k} {pc.case_name(c)}")
+        same(pc.restated(r, c, arms=arms), c["want"], f"tiny {k} {pc.case_name(c)}", pc.QUANTITIES)
     for must in MUST:
         if must.startswith(("method", "variable", "interpolated count")):
             continue
@@ -257,7 +254,7 @@ def test_host_build_equals_the_restatement_off_the_pin(off_pin, off_pin_restated
     """every cell and every quantity of pc.QUANTITIES, bit for bit.  The two cases of pc.HOST_ONLY (a three-piece function under five other
     proxies: more than 5 s in the restatement) are held host build against device only (tests/test_gpu_localproxies.py)"""
     r, c, got = off_pin[label]
-    pc.same(got, off_pin_restated[label][0], label)
+    same(got, off_pin_restated[label][0], label, pc.QUANTITIES)
     out = r["dem"] == r["flag"]
     assert out.sum() == 1 and (got["value"][out] == r["flag"]).all() and (got["count"][out] == 0).all() and (got["count"][~out] > 0).all()
 

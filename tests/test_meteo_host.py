@@ -4,7 +4,6 @@ pin's arms and cases, the neighbourhood sizes and the distinct distances of the 
 points absent from sf3d.h and the drop-in shim."""
 import ctypes
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 from criteria3d_amd import build, capi, meteo
 from tests import meteo_cases as mc
+from tests.raster_helpers import bits, declared_entry_points, exported_names, header_text
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -22,8 +22,7 @@ def pin():
 
 
 def test_meteo_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_meteo.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_meteo_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_meteo.h"), declared_entry_points("sf3d_meteo.h", "sf3d_meteo_")
     assert declared == sorted(meteo.SIGNATURES)
     assert re.search(rf"#define SF3D_METEO_MAX_STATIONS {meteo.MAX_STATIONS}\b", text) and re.search(rf"#define SF3D_METEO_MAX_PROXIES {meteo.MAX_PROXIES}\b", text)
     for k, n in enumerate(("AIR_TEMPERATURE", "PRECIPITATION", "AIR_REL_HUMIDITY", "WIND_SCALAR_INTENSITY", "GLOBAL_IRRADIANCE", "ATM_TRANSMISSIVITY",
@@ -41,17 +40,14 @@ def test_meteo_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_meteo_entry_points():
-    lib = build.build_product()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(meteo.SIGNATURES) <= names
 
 
 def test_meteo_entry_points_are_not_part_of_the_drop_in_abi():
     assert "sf3d_meteo" not in (ROOT / "include" / "sf3d.h").read_text()
     assert not any("meteo" in n.lower() for n in capi.SIGNATURES) and not any("meteo" in n.lower() for n in capi.REFERENCE_API)
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_shim())], capture_output=True, text=True, check=True).stdout
-    assert "meteo" not in out.lower()
+    assert not any("meteo" in n.lower() for n in exported_names(build.build_shim()))
 
 
 def test_the_pin_reaches_every_arm_and_case(pin):
@@ -124,10 +120,10 @@ def test_restatement_equals_the_compiled_reference_in_every_cell_of_every_case(p
     computed = 0
     for k, c in enumerate(pin["cases"]):
         got = mc.restated(pin, c)
-        bad = mc.bits(got) != mc.bits(c["want"])
+        bad = bits(got) != bits(c["want"])
         if bad.any():
             print(f"case {k} {mc.case_name(c)}: {int(bad.sum())} values differ")
-        assert np.array_equal(mc.bits(got), mc.bits(c["want"])), (k, mc.case_name(c), int(bad.sum()), got[bad][:4], c["want"][bad][:4])
+        assert np.array_equal(bits(got), bits(c["want"])), (k, mc.case_name(c), int(bad.sum()), got[bad][:4], c["want"][bad][:4])
         computed += int((got != flag).sum())
     assert computed > 30000                                                 # not vacuous
     # the methods differ from each other where they should

@@ -6,7 +6,6 @@ and both retention curves, and the factor of safety of a hand-placed column with
 import json
 import math
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -17,22 +16,20 @@ from criteria3d_amd import project3d as p3
 from tests import map_cases as mpc
 from tests import sink_cases as sc
 from tests.kernel_notes import kernel_resources
+from tests.raster_helpers import declared_entry_points, exported_names
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden"
 
 
 def test_maps_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_maps.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_[a-z0-9_]+)\s*\(", text)))
+    declared = declared_entry_points("sf3d_maps.h", "sf3d_")
     assert declared == sorted(maps.SIGNATURES)
     assert not set(declared) & set(capi.SIGNATURES)          # sf3d.h (the drop-in ABI the oracle exports too) is unchanged
 
 
 def test_product_library_exports_the_map_entry_points():
-    lib = build.build_product()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(maps.SIGNATURES) <= names
 
 

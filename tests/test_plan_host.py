@@ -28,22 +28,16 @@ from pathlib import Path
 
 import pytest
 
+from tests.raster_helpers import build_host_program
+
 ROOT = Path(__file__).resolve().parent.parent
 GROUPS = ["box 64 x 6 x 2", "refusal", "neither", "box 128 x 8 x 3", "box 192 x 6 x 2", "masked 70 x 7", "cost model", "step plan"]
-
-
-def build_host(directory, sanitize=False):
-    exe = Path(directory) / ("plan_host_san" if sanitize else "plan_host")
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-pthread", *extra, f"-I{ROOT / 'include'}",
-                    f"-I{ROOT / 'criteria3d_amd' / 'csrc'}", str(ROOT / "tests" / "plan_host.cpp"), "-o", str(exe)], check=True)
-    return exe
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_every_stage_holds_its_claims_against_the_link_data(tmp_path, sanitize):
     """the program has its own main and is not loaded into python; a failed claim or a sanitizer report ends it with a non-zero status"""
-    run = subprocess.run([str(build_host(tmp_path, sanitize))], capture_output=True, text=True)
+    run = subprocess.run([str(build_host_program("plan", tmp_path, sanitize))], capture_output=True, text=True)
     assert run.returncode == 0, run.stderr
     assert run.stdout.splitlines() == [f"ok {g}" for g in GROUPS]
 

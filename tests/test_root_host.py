@@ -7,7 +7,6 @@ the edges of the tables."""
 import ctypes
 import json
 import re
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -16,7 +15,7 @@ import pytest
 
 from criteria3d_amd import build, capi, crop, project3d as p3, root
 from tests import root_cases as rc
-from tests.raster_helpers import differing
+from tests.raster_helpers import bits, build_host_program, declared_entry_points, differing, exported_names, header_text
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -27,8 +26,7 @@ def pin():
 
 
 def test_root_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_root.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_root_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_root.h"), declared_entry_points("sf3d_root.h", "sf3d_root_")
     assert declared == sorted(root.SIGNATURES)
     assert not set(declared) & set(capi.SIGNATURES) and not set(declared) & set(crop.SIGNATURES)          # sf3d.h and sf3d_crop.h are unchanged
     for name, value in (("SOILS", root.MAX_SOILS), ("HORIZONS", root.MAX_HORIZONS), ("LAYERS", root.MAX_LAYERS), ("ATOMS", root.MAX_ATOMS)):
@@ -51,9 +49,7 @@ def test_root_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_root_entry_points():
-    lib = build.build_product()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(root.SIGNATURES) <= names
 
 
@@ -134,7 +130,7 @@ def test_restatement_equals_the_compiled_reference_on_every_map(pin):
     for k in range(len(pin["degree_days"])):
         got = rc.restated(pin, k)
         for n in rc.OUTPUTS:
-            bad = rc.bits(got[n]) != rc.bits(pin[n][k])
+            bad = bits(got[n]) != bits(pin[n][k])
             print(f"map {k} {n}: {int(bad.sum())} values differ")
             assert not bad.any(), (k, n, int(bad.sum()), got[n][bad][:4], pin[n][k][bad][:4])
         computed += int((got["length"] != float(pin["flag"])).sum())
@@ -205,7 +201,7 @@ def test_root_and_soil_table_readers():
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("root_host")
-    return SimpleNamespace(dir=d, exe=rc.build_host(d), san=rc.build_host(d, sanitize=True))
+    return SimpleNamespace(dir=d, exe=build_host_program("root", d), san=build_host_program("root", d, sanitize=True))
 
 
 def _pin_case(pin):

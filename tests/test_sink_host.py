@@ -11,6 +11,7 @@ import pytest
 from criteria3d_amd import capi, catchment as cm, sinks
 from tests import sink_cases as sc
 from tests.golden import make_water_sinks as gen
+from tests.raster_helpers import bits, build_host_program
 
 
 @pytest.fixture(scope="module")
@@ -28,7 +29,7 @@ def test_restatement_equals_the_pin(pin, restated):
     for k, got in enumerate(restated[0]):
         for name in sc.OUTPUTS:
             want = pin[name][k]
-            bad = sc.bits(got[name]) != sc.bits(want)
+            bad = bits(got[name]) != bits(want)
             assert not bad.any(), (k, name, int(bad.sum()))
         assert np.count_nonzero(pin["sinks_et"][k]) > 1000 and np.isfinite(pin["sinks"][k]).all()
     flag = float(pin["flag"])
@@ -39,10 +40,10 @@ def test_restatement_equals_the_pin(pin, restated):
 def test_one_layer_case(pin):
     for j, k in enumerate(pin["one_layer_hours"]):
         got = sc.restated(pin, int(k), one_layer=True)
-        assert np.array_equal(sc.bits(got["sinks_et"]), sc.bits(pin["one_layer_sinks_et"][j])) and np.array_equal(sc.bits(got["sinks"]), sc.bits(pin["one_layer_sinks"][j]))
-        assert np.array_equal(sc.bits(got["evaporation"]), sc.bits(pin["one_layer_evaporation"][j]))
+        assert np.array_equal(bits(got["sinks_et"]), bits(pin["one_layer_sinks_et"][j])) and np.array_equal(bits(got["sinks"]), bits(pin["one_layer_sinks"][j]))
+        assert np.array_equal(bits(got["evaporation"]), bits(pin["one_layer_evaporation"][j]))
         t = pin["one_layer_transpiration"][j]
-        assert np.array_equal(sc.bits(got["transpiration"]), sc.bits(t)) and np.all(t[t != float(pin["flag"])] == 0)
+        assert np.array_equal(bits(got["transpiration"]), bits(t)) and np.all(t[t != float(pin["flag"])] == 0)
         ns = pin["dem"].size
         assert not pin["one_layer_sinks"][j][ns:].any() and np.count_nonzero(pin["one_layer_sinks"][j][:ns] < 0) > 0 and np.count_nonzero(pin["one_layer_sinks"][j][:ns] > 0) > 0
 
@@ -79,13 +80,13 @@ def test_small_cases_reach_every_arm(pin, oracle):
 
 def test_host_tables_equal_the_recorded_ones(pin):
     ec, lec, last = sinks.evaporation_coefficients(pin["layer_depth"], pin["layer_thickness"], float(pin["computation_depth"]))
-    assert last == int(pin["last_evap_layer"]) and np.array_equal(sc.bits(ec), sc.bits(pin["evap_coeff"])) and np.array_equal(sc.bits(lec), sc.bits(pin["layer_evap_coeff"]))
+    assert last == int(pin["last_evap_layer"]) and np.array_equal(bits(ec), bits(pin["evap_coeff"])) and np.array_equal(bits(lec), bits(pin["layer_evap_coeff"]))
     assert np.array_equal(sinks.horizon_table(pin["sink_soils"], pin["layer_depth"]), pin["horizon"]) and (pin["horizon"] == -9999).any()
     sf = capi.load_product()
     sc.initialize(sf, pin)                                        # no device needed
     t = sinks.get_tables(sf)
     assert t["last_evap_layer"] == int(pin["last_evap_layer"]) and np.array_equal(t["horizon"], pin["horizon"])
-    assert np.array_equal(sc.bits(t["evap_coeff"]), sc.bits(pin["evap_coeff"])) and np.array_equal(sc.bits(t["layer_evap_coeff"]), sc.bits(pin["layer_evap_coeff"]))
+    assert np.array_equal(bits(t["evap_coeff"]), bits(pin["evap_coeff"])) and np.array_equal(bits(t["layer_evap_coeff"]), bits(pin["layer_evap_coeff"]))
     sc.initialize(sf, pin, one_layer=True)
     assert sinks.get_tables(sf)["last_evap_layer"] == int(pin["one_layer_last_evap_layer"]) == 0
     sinks.clean(sf)
@@ -169,13 +170,13 @@ PLAIN = ("sinks", "evaporation", "transpiration")
 def host(tmp_path_factory):
     from types import SimpleNamespace
     d = tmp_path_factory.mktemp("sink_host")
-    return SimpleNamespace(dir=d, exes=sc.build_host(d), san=sc.build_host(d, sanitize=True))
+    return SimpleNamespace(dir=d, exes=[build_host_program(b, d) for b in sc.HOST_PROGRAMS], san=[build_host_program(b, d, sanitize=True) for b in sc.HOST_PROGRAMS])
 
 
 def test_host_text_equals_the_pin_on_every_hour_and_on_one_layer(pin, oracle, host):
     """H and Se come from the checker's getters on the pin's potentials; no libm escape: the text carries its own exp"""
     state = sc.node_state(oracle, pin)
-    assert np.array_equal(sc.bits(state["vwc"]), sc.bits(pin["vwc"]))
+    assert np.array_equal(bits(state["vwc"]), bits(pin["vwc"]))
     for k in range(len(pin["et0"])):
         got = sc.run_host(host.exes, host.dir, "pin", pin, k, state)
         assert got["status"] == 0 and got["last_evap_layer"] == int(pin["last_evap_layer"])

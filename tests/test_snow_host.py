@@ -4,7 +4,6 @@ model equals it bit for bit over all 96 hours, the small rasters' forcing of tes
 the per-node sources of assignPrecipitation, the snow/ state folder; and the host build of the kernel's per-cell text
 (tests/snow_host.cpp): equal to the pin and to the restatement bit for bit, clean under the address and undefined-behaviour sanitizers."""
 import re
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -13,15 +12,14 @@ import pytest
 
 from criteria3d_amd import build, capi, esri, snow
 from tests import snow_cases
-from tests.raster_helpers import bits as _bits, differing
+from tests.raster_helpers import bits as _bits, build_host_program, declared_entry_points, differing, exported_names, header_text
 
 ROOT = Path(__file__).resolve().parent.parent
 PIN = ROOT / "tests" / "golden" / "snow_brooks.npz"
 
 
 def test_snow_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_snow.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_snow_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_snow.h"), declared_entry_points("sf3d_snow.h", "sf3d_snow_")
     assert declared == sorted(snow.SIGNATURES)
     assert not set(declared) & set(capi.SIGNATURES)          # sf3d.h (the drop-in ABI) is unchanged
     for k, n in enumerate(("SWE", "ICE_CONTENT", "LW_CONTENT", "INTERNAL_ENERGY", "SURFACE_ENERGY", "SURFACE_TEMP", "AGE_OF_SNOW")):
@@ -31,10 +29,7 @@ def test_snow_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_snow_entry_points():
-    lib = build.build_product()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert set(snow.SIGNATURES) <= names
+    assert set(snow.SIGNATURES) <= exported_names(build.build_product())
 
 
 def test_error_codes_without_a_raster_and_default_parameters():
@@ -216,7 +211,7 @@ def test_state_directory_round_trip(tmp_path):
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     d = tmp_path_factory.mktemp("snow_host")
-    return SimpleNamespace(dir=d, exe=snow_cases.build_host(d), san=snow_cases.build_host(d, sanitize=True))
+    return SimpleNamespace(dir=d, exe=build_host_program("snow", d), san=build_host_program("snow", d, sanitize=True))
 
 
 def _pin_run():

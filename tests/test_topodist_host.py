@@ -5,7 +5,6 @@ once more as a stand-alone program under the address and undefined-behaviour san
 interpolation, the station matrix, the Kh search) equal to the pin; and the application's file names."""
 import ctypes
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 
 from criteria3d_amd import build, capi, esri, meteo, topodist
 from tests import topodist_cases as tc
+from tests.raster_helpers import bits, build_host_program, declared_entry_points, exported_names, header_text
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -25,13 +25,12 @@ def pin():
 @pytest.fixture(scope="module")
 def host(pin, tmp_path_factory):
     d = tmp_path_factory.mktemp("topodist_host")
-    exe = tc.build_host(d)
+    exe = build_host_program("topodist", d)
     return {name: tc.run_host(exe, pin[name], pin, d) for name in tc.RASTERS}
 
 
 def test_header_and_binding_table_agree():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "sf3d_topodist.h").read_text(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sf3d_topodist_[a-z0-9_]+)\s*\(", text)))
+    text, declared = header_text("sf3d_topodist.h"), declared_entry_points("sf3d_topodist.h", "sf3d_topodist_")
     assert declared == sorted(topodist.SIGNATURES)
     assert re.search(rf"#define SF3D_TOPODIST_MAX_STEPS {topodist.MAX_STEPS}\b", text) and topodist.MAX_STEPS == 65536
     assert topodist.MAX_STATIONS == meteo.MAX_STATIONS == 1024
@@ -43,13 +42,11 @@ def test_header_and_binding_table_agree():
 
 
 def test_product_library_exports_the_entry_points_and_the_drop_in_abi_does_not():
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_product())], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_names(build.build_product())
     assert set(topodist.SIGNATURES) <= names
     assert "topodist" not in (ROOT / "include" / "sf3d.h").read_text()
     assert not any("topodist" in n.lower() for n in capi.SIGNATURES) and not any("topodist" in n.lower() for n in capi.REFERENCE_API)
-    out = subprocess.run(["nm", "-D", "--defined-only", str(build.build_shim())], capture_output=True, text=True, check=True).stdout
-    assert "topodist" not in out.lower()
+    assert not any("topodist" in n.lower() for n in exported_names(build.build_shim()))
 
 
 def test_refusals_come_before_any_device_work():
@@ -128,21 +125,21 @@ def test_the_pin_holds_what_the_issue_lists(pin):
 def test_host_build_of_the_kernels_text_equals_the_pin_on_every_value(pin, host, name):
     r = pin[name]
     maps, case_maps, matrices = host[name]
-    assert np.array_equal(tc.bits(maps), tc.bits(r["maps"]))
+    assert np.array_equal(bits(maps), bits(r["maps"]))
     for k, c in enumerate(r["cases"]):
-        bad = tc.bits(case_maps[k]) != tc.bits(c["want"])
+        bad = bits(case_maps[k]) != bits(c["want"])
         assert not bad.any(), (k, tc.case_name(c), int(bad.sum()), case_maps[k][bad][:4], c["want"][bad][:4])
-    assert np.array_equal(tc.bits(matrices), tc.bits(r["matrices"]))
+    assert np.array_equal(bits(matrices), bits(r["matrices"]))
     assert (maps[r["dem"][None].repeat(len(maps), 0) != pin["flag"]] > 0).sum() > 100         # not vacuous
 
 
 def test_host_build_under_the_sanitizers_reports_nothing(pin, host, tmp_path):
     """a stand-alone program with its own main: nothing is loaded into Python"""
-    exe = tc.build_host(tmp_path, sanitize=True)
+    exe = build_host_program("topodist", tmp_path, sanitize=True)
     for name in tc.RASTERS:
         got = tc.run_host(exe, pin[name], pin, tmp_path)              # asserts exit status 0 and an empty stderr
         for a, b in zip(got, host[name]):
-            assert np.array_equal(tc.bits(a), tc.bits(b))
+            assert np.array_equal(bits(a), bits(b))
 
 
 @pytest.mark.parametrize("name", tc.RASTERS)
@@ -150,11 +147,11 @@ def test_restated_maps_and_matrices_equal_the_pin(pin, name):
     r = pin[name]
     for i in range(len(r["x"])):
         got = topodist.restate_map(r["dem"], r["xll"], r["yll"], r["cell_size"], r["x"][i], r["y"][i], r["z"][i], float(r["flag"]))
-        assert np.array_equal(tc.bits(got), tc.bits(r["maps"][i])), i
+        assert np.array_equal(bits(got), bits(r["maps"][i])), i
     for k, mode in enumerate(pin["modes"]):
         held, index = tc.mode_maps(r, mode)
         got = topodist.restate_station_matrix(r["dem"], r["xll"], r["yll"], r["cell_size"], float(r["flag"]), r["x"], r["y"], r["z"], held, index)
-        assert np.array_equal(tc.bits(got), tc.bits(r["matrices"][k])), mode
+        assert np.array_equal(bits(got), bits(r["matrices"][k])), mode
     # on the tiny raster the look-up is not the cell's own index: reading the station's map at the cell itself gives other values
     if name == "tiny":
         cx, cy = meteo.cell_centres(r["dem"].shape, r["xll"], r["yll"], r["cell_size"])
@@ -168,7 +165,7 @@ def test_restated_interpolation_equals_the_pin_in_every_cell_of_every_case(pin, 
     r = pin[name]
     for k, c in enumerate(r["cases"]):
         got = tc.restated(r, c)
-        bad = tc.bits(got) != tc.bits(c["want"])
+        bad = bits(got) != bits(c["want"])
         assert not bad.any(), (k, tc.case_name(c), int(bad.sum()), got[bad][:4], c["want"][bad][:4])
     if name == "relief":                                             # Kh, the maps and the hand-made map change the result
         by = {tc.case_name(c): c["want"] for c in r["cases"]}
@@ -184,7 +181,7 @@ def test_kh_zero_and_precipitation_equal_the_plain_interpolation(pin):
         if tc.effective_kh(c) == 0:
             plain = meteo.restate_interpolate(r["dem"], r["xll"], r["yll"], r["cell_size"], [None], c["var"], c["method"], r["x"], r["y"], c["value"], c["area"],
                                               dict(c["settings"], useTopographicDistance=0), float(r["flag"]))
-            assert np.array_equal(tc.bits(plain), tc.bits(c["want"])), tc.case_name(c)
+            assert np.array_equal(bits(plain), bits(c["want"])), tc.case_name(c)
             seen += 1
     assert seen >= 12
 
@@ -202,8 +199,8 @@ def test_kh_search_equals_the_reference(pin):
         kh, series = topodist.optimize_kh(o["var"], o["method"], r["x"][s], r["y"][s], r["z"][s], o["value"], o["observed"], matrix, np.float32(o["area"]), settings,
                                           pin["max_kh"], pv, inside)
         assert kh == o["kh"] and isinstance(kh, int)
-        assert np.array_equal(tc.bits([p[0] for p in series]), tc.bits(o["series_kh"]))
-        assert np.array_equal(tc.bits([p[1] for p in series]), tc.bits(o["series_error"]))
+        assert np.array_equal(bits([p[0] for p in series]), bits(o["series_kh"]))
+        assert np.array_equal(bits([p[1] for p in series]), bits(o["series_error"]))
     assert len({o["kh"] for o in pin["opt"]}) >= 2
 
 
@@ -217,6 +214,6 @@ def test_maps_round_trip_through_the_applications_files(pin, tmp_path):
     back = topodist.load_maps(tmp_path / "TD", "DEM_Ravone", ids + ["missing"])
     assert back[3] is None
     for a, b in zip(back[:3], r["maps"][:3]):
-        assert np.array_equal(tc.bits(a), tc.bits(b))
+        assert np.array_equal(bits(a), bits(b))
     got, h = esri.read_grid(paths[0])
     assert h["ncols"] == 37 and h["nrows"] == 7 and h["cellsize"] == r["cell_size"] and h["nodata"] == float(r["flag"])

@@ -7,13 +7,13 @@ library's, and here radPoint.global is summed as a double: equality of the host 
 construction; a (case, station) that differs would be listed in ONE_ULP below at one float ulp, at most three - none is."""
 import ctypes
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from criteria3d_amd import build, capi, radiation as rad, transmissivity as tr
+from tests import raster_helpers as rh
 from tests import transmissivity_cases as tc
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -27,7 +27,7 @@ def pin():
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    return tc.build_host(tmp_path_factory.mktemp("transmissivity_host"))
+    return rh.build_host_program("transmissivity", tmp_path_factory.mktemp("transmissivity_host"))
 
 
 def test_header_and_binding_agree():
@@ -46,10 +46,9 @@ def test_header_and_binding_agree():
 
 
 def test_product_library_exports_the_entry_points_outside_the_drop_in_abi():
-    lib = build.build_product()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
+    functions = rh.exported_names(build.build_product(), "T")
     for name in tr.SIGNATURES:
-        assert re.search(rf" T {name}$", out, re.M), name
+        assert name in functions, name
     assert not any("transmissivity" in n for n in capi.SIGNATURES)
 
 
@@ -167,7 +166,7 @@ def test_restatement_equals_the_compiled_reference_in_every_case_and_station(pin
         st = pin[f"stations{k}"]
         if c["mode"] == tc.POINTS:
             got, n_valid, arms, model, _ = tr.restate_points(grid, c["settings"], c["when"], c["width"], c["step"], st, pin[f"measured{k}"])
-            assert tc.same_bits(got, pin[f"result{k}"]).all(), c["name"]
+            assert not rh.differing(got, pin[f"result{k}"]).any(), c["name"]
             assert (n_valid > 0) == bool(c["ret"]), c["name"]
         else:
             res = [tr.restate_window(grid, c["settings"], c["when"], p, c["step"]) for p in st]
@@ -190,7 +189,7 @@ def test_host_build_of_the_kernels_text_equals_the_pin(pin, host, tmp_path):
             if c["mode"] == tc.WINDOW:
                 assert got["result"].tolist() == pin[f"result{k}"].tolist(), c["name"]
             else:
-                same = tc.same_bits(got["result"], pin[f"result{k}"])
+                same = ~rh.differing(got["result"], pin[f"result{k}"])
                 differing += [(c["name"], int(s), float(got["result"][s]), float(pin[f"result{k}"][s])) for s in np.nonzero(~same)[0]]
             checked += 1
     assert checked == len(pin["cases"]) >= 40
@@ -211,10 +210,10 @@ def test_host_build_equals_the_restatement_off_the_pin_and_the_small_sets_reach_
     union = 0
     for shape, g in zip(tc.SHAPES, got):
         want, _, arms, evals = ref[shape]
-        assert tc.same_bits(g["result"], want).all(), shape
+        assert not rh.differing(g["result"], want).any(), shape
         for p, slots in enumerate(evals):                                   # the double global and the elevation of every evaluation
             for s, (written, elev, glob) in slots.items():
-                assert g["written"][p, s] == written and tc.same_bits(g["elev"][p, s], elev).all(), (shape, p, s)
+                assert g["written"][p, s] == written and not rh.differing(g["elev"][p, s], np.float32(elev)).any(), (shape, p, s)
                 # the restatement's sin / cos / tan are the C library's, the kernel text's are faithful routines (within an ulp): the double
                 # differs in its last places at most, through a handful of well-conditioned operations
                 assert written == 0 or abs(g["glob"][p, s] - glob) <= 1e-12 * abs(glob), (shape, p, s, g["glob"][p, s], glob)
@@ -231,9 +230,9 @@ def test_host_build_equals_the_restatement_off_the_pin_and_the_small_sets_reach_
 
 def test_host_build_runs_clean_under_asan_and_ubsan_as_a_stand_alone_program(pin, tmp_path):
     """the program has its own main and is not loaded into python; a sanitizer report ends it with a non-zero status"""
-    exe = tc.build_host(tmp_path, sanitize=True)
+    exe = rh.build_host_program("transmissivity", tmp_path, sanitize=True)
     dem, flag, geo = tc.raster_of(pin, 1)
     idx, calls = tc.pin_calls(pin, 1)
     got = tc.run_host(exe, tmp_path, dem, flag, geo, calls, tag="san")
     k0 = idx[0]
-    assert tc.same_bits(got[0]["result"], pin[f"result{k0}"]).all()
+    assert not rh.differing(got[0]["result"], pin[f"result{k0}"]).any()

@@ -2,19 +2,16 @@
 tests/golden/topodist.npz decoded into its two rasters with their stations, maps, cases, station matrices and Kh searches; the host
 build of the per-cell text (tests/topodist_host.cpp); and the small and the cap rasters of tests/meteo_cases.py with station heights."""
 import json
-import subprocess
 from pathlib import Path
 
 import numpy as np
 
 from criteria3d_amd import meteo, topodist
-from tests import meteo_cases as mc
 
 ROOT = Path(__file__).resolve().parent.parent
 PIN = ROOT / "tests" / "golden" / "topodist.npz"
 RASTERS = ("relief", "tiny")
 PORT = 29799                                    # the two-rank test's (clear of tests/ranks.py's table and of test_gpu_multirank.py's ports)
-bits = mc.bits
 
 
 def load_pin():
@@ -81,42 +78,24 @@ def interpolate(sf, r, c, index, download=True):
     return topodist.interpolate(sf, c["var"], c["method"], r["x"], r["y"], r["z"], c["value"], index, c["area"], c["settings"], c["kh"], download)
 
 
-def build_host(directory, sanitize=False) -> Path:
-    """tests/topodist_host.cpp with the flags of the product's host side (no FMA contraction); sanitize: address and undefined behaviour"""
-    exe = Path(directory) / ("topodist_host_san" if sanitize else "topodist_host")
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wno-unknown-pragmas", *extra, f"-I{ROOT / 'include'}", f"-I{ROOT / 'criteria3d_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "topodist_host.cpp"), "-o", str(exe), "-lm"], check=True)
-    return exe
-
-
 def run_host(exe, r, pin, directory):
     """the host program on one raster of the pin -> (maps, case maps, matrices per mode)"""
-    src, dst = Path(directory) / f"{r['name']}.in", Path(directory) / f"{r['name']}.out"
-    n, cells = len(r["x"]), r["dem"].size
-    with open(src, "wb") as f:
-        np.array([r["dem"].shape[0], r["dem"].shape[1], n, len(r["cases"]), len(pin["modes"]), r["hand"]], np.int32).tofile(f)
-        np.array([r["flag"]], np.float32).tofile(f)
-        np.array([r["xll"], r["yll"], r["cell_size"]], np.float64).tofile(f)
-        r["dem"].astype(np.float32).tofile(f)
-        for a in (r["x"], r["y"], r["z"]):
-            a.astype(np.float64).tofile(f)
-        r["hand_map"].astype(np.float32).tofile(f)
-        for c in r["cases"]:
-            st = c["settings"]
-            np.array([c["var"], c["method"], effective_kh(c), int(c["mode"] == "hand"), st["proxies"][0]["active"], st["useDetrending"]], np.int32).tofile(f)
-            np.array([st["rainfallThreshold"], meteo.shepard_initial_radius(c["area"], n), st["proxies"][0]["slope"]], np.float32).tofile(f)
-            mode_maps(r, c["mode"])[1].tofile(f)
-            c["value"].astype(np.float32).tofile(f)
-        for mode in pin["modes"]:
-            np.array([int(mode == "hand")], np.int32).tofile(f)
-            mode_maps(r, mode)[1].tofile(f)
-    res = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True)
-    assert res.returncode == 0 and not res.stderr, (res.returncode, res.stderr[-2000:])
-    raw = np.fromfile(dst, np.float32)
-    assert raw.size == n * cells + len(r["cases"]) * cells + len(pin["modes"]) * n * n
-    a, b = n * cells, n * cells + len(r["cases"]) * cells
-    return raw[:a].reshape(n, *r["dem"].shape), raw[a:b].reshape(len(r["cases"]), *r["dem"].shape), raw[b:].reshape(len(pin["modes"]), n, n)
+    from tests.raster_helpers import Reader, run_host_program
+    n = len(r["x"])
+    parts = [np.array([r["dem"].shape[0], r["dem"].shape[1], n, len(r["cases"]), len(pin["modes"]), r["hand"]], np.int32), np.array([r["flag"]], np.float32),
+             np.array([r["xll"], r["yll"], r["cell_size"]], np.float64), r["dem"].astype(np.float32)]
+    parts += [a.astype(np.float64) for a in (r["x"], r["y"], r["z"])] + [r["hand_map"].astype(np.float32)]
+    for c in r["cases"]:
+        st = c["settings"]
+        parts += [np.array([c["var"], c["method"], effective_kh(c), int(c["mode"] == "hand"), st["proxies"][0]["active"], st["useDetrending"]], np.int32),
+                  np.array([st["rainfallThreshold"], meteo.shepard_initial_radius(c["area"], n), st["proxies"][0]["slope"]], np.float32),
+                  mode_maps(r, c["mode"])[1], c["value"].astype(np.float32)]
+    for mode in pin["modes"]:
+        parts += [np.array([int(mode == "hand")], np.int32), mode_maps(r, mode)[1]]
+    out = Reader(run_host_program(exe, directory, r["name"], parts))
+    got = out.take(np.float32, n, *r["dem"].shape), out.take(np.float32, len(r["cases"]), *r["dem"].shape), out.take(np.float32, len(pin["modes"]), n, n)
+    assert out.done()
+    return got
 
 
 def with_heights(r, seed):

@@ -10,26 +10,13 @@
  *         per matrix: int32 useHand; int32 mapIndex[nStations].
  * output: float maps[nStations][nCells]; float caseMap[nCases][nCells]; float matrix[nMatrices][nStations][nStations].
  * useHand: map `hand` is handMap in the place of the computed one. */
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "sf3d_device.h"
+#include "host_io.h"
 
 #define SF3D_METEO_HOST
 #define SF3D_METEO_FN static inline
 #define SF3D_METEO_MEMBER inline
 #include "sf3d_meteo.inc"
 #include "sf3d_topodist.inc"
-
-template <class T> static std::vector<T> readv(FILE* f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "topodist_host: short input\n"); exit(2); }
-    return v;
-}
 
 int main(int argc, char** argv)
 {
@@ -38,7 +25,7 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) return 2;
     const std::vector<int32_t> dims = readv<int32_t>(in, 6);
-    const float flag = readv<float>(in, 1)[0];
+    const float flag = read1<float>(in);
     const std::vector<double> geo = readv<double>(in, 3);
     const uint32_t nRows = (uint32_t)dims[0], nCols = (uint32_t)dims[1], m = (uint32_t)dims[2];
     const int nCases = dims[3], nMatrices = dims[4], hand = dims[5];
@@ -56,7 +43,7 @@ int main(int argc, char** argv)
     for (uint32_t p = 0; p < m; ++p)
         for (uint32_t c = 0; c < n; ++c)
             if (!meteo_eqf(dem[c], flag)) maps[(size_t)p * n + c] = topo_map_cell(g, c, dem[c], sx[p], sy[p], sz[p]);
-    if (fwrite(maps.data(), 4, maps.size(), out) != maps.size()) return 3;
+    writev(out, maps);
     std::vector<float> withHand = maps;
     if (hand >= 0 && (uint32_t)hand < m) for (size_t c = 0; c < n; ++c) withHand[(size_t)hand * n + c] = handMap[c];
 
@@ -90,18 +77,18 @@ int main(int argc, char** argv)
             dist.x = x; dist.y = y; dist.z = z; dist.kh = iv[2];
             map[c] = meteo_cell(v, c, z, x, y, dist, sx.data(), sy.data(), value.data(), m);
         }
-        if (fwrite(map.data(), 4, n, out) != n) return 3;
+        writev(out, map);
     }
 
     /* k_topodist_matrix */
     for (int k = 0; k < nMatrices; ++k) {
-        const int32_t useHand = readv<int32_t>(in, 1)[0];
+        const int32_t useHand = read1<int32_t>(in);
         const std::vector<int32_t> mapIndex = readv<int32_t>(in, m);
         const float* held = useHand ? withHand.data() : maps.data();
         std::vector<float> matrix((size_t)m * m);
         for (uint32_t j = 0; j < m; ++j)
             for (uint32_t i = 0; i < m; ++i) matrix[(size_t)j * m + i] = topo_matrix_entry(g, held, n, sx.data(), sy.data(), sz.data(), mapIndex.data(), j, i);
-        if (fwrite(matrix.data(), 4, matrix.size(), out) != matrix.size()) return 3;
+        writev(out, matrix);
     }
     fclose(in);
     return fclose(out) == 0 ? 0 : 3;

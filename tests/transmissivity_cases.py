@@ -8,7 +8,6 @@ the pin's scaled window; the stations are seeded over the raster stretched by a 
 series walk through the kinds of the pin, and the times and settings are chosen so that the runs together reach every arm of the pin."""
 import functools
 import json
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -37,64 +36,37 @@ def raster_of(pin, r):
     return pin[f"dem{r}"], float(pin["flag"]), tuple(pin["rasters"][r]["geo"])
 
 
-def same_bits(a, b, dtype=np.float32):
-    a, b = np.ascontiguousarray(a, dtype), np.ascontiguousarray(b, dtype)
-    u = np.uint32 if dtype == np.float32 else np.uint64
-    return (a.view(u) == b.view(u)) | (np.isnan(a) & np.isnan(b))
-
-
-def build_host(directory, sanitize=False):
-    exe = Path(directory) / ("transmissivity_host_san" if sanitize else "transmissivity_host")
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-Wall", "-Werror", "-Wno-unused-function", *extra,
-                    f"-I{ROOT / 'criteria3d_amd' / 'csrc'}", str(ROOT / "tests" / "transmissivity_host.cpp"), "-o", str(exe), "-lm"], check=True)
-    return exe
+def host_input(dem, flag, geo, calls) -> list:
+    """the input of tests/transmissivity_host.cpp, part by part; calls: [(settings, when, mode, width, step, stations [n, 5], measured
+    [n, width] or None)]"""
+    parts = [np.array(dem.shape, np.int32), np.array([flag], np.float32), np.array(geo, np.float64), np.asarray(dem, np.float32), np.array([len(calls)], np.int32)]
+    for settings, when, mode, width, step, stations, measured in calls:
+        full = rad.settings_dict(settings)
+        parts += [np.array([full[k] for k in SETTING_INTS], np.int32),
+                  np.array([full["linke"], *full["linkeMonthly"], full["albedo"], full["tilt"], full["aspect"], full["clearSky"]], np.float32),
+                  np.array([*when, mode, width, step, len(stations)], np.int32), np.asarray(stations, np.float64)]
+        if mode == POINTS:
+            parts.append(np.asarray(measured, np.float32))
+    return parts
 
 
 def write_host_input(path, dem, flag, geo, calls):
-    """calls: [(settings, when, mode, width, step, stations [n, 5], measured [n, width] or None)]"""
-    with open(path, "wb") as f:
-        np.array(dem.shape, np.int32).tofile(f)
-        np.array([flag], np.float32).tofile(f)
-        np.array(geo, np.float64).tofile(f)
-        np.ascontiguousarray(dem, np.float32).tofile(f)
-        np.array([len(calls)], np.int32).tofile(f)
-        for settings, when, mode, width, step, stations, measured in calls:
-            full = rad.settings_dict(settings)
-            np.array([full[k] for k in SETTING_INTS], np.int32).tofile(f)
-            np.array([full["linke"], *full["linkeMonthly"], full["albedo"], full["tilt"], full["aspect"], full["clearSky"]], np.float32).tofile(f)
-            np.array([*when, mode, width, step, len(stations)], np.int32).tofile(f)
-            np.ascontiguousarray(stations, np.float64).tofile(f)
-            if mode == POINTS:
-                np.ascontiguousarray(measured, np.float32).tofile(f)
-
-
-def read_host_output(path, calls):
-    """[dict(status, result, written, elev, glob)] per call"""
-    raw = np.fromfile(path, np.uint8)
-    at, out = 0, []
-
-    def take(count, dtype):
-        nonlocal at
-        size = count * np.dtype(dtype).itemsize
-        v = raw[at:at + size].view(dtype).copy()
-        at += size
-        return v
-    for _, _, mode, width, _, stations, _ in calls:
-        n = len(stations)
-        slots = tr.WINDOW_SLOTS if mode == WINDOW else width
-        status = take(n, np.int32)
-        result = take(n, np.float32 if mode == POINTS else np.int32)
-        out.append(dict(status=status, result=result, written=take(n * slots, np.uint8).reshape(n, slots), elev=take(n * slots, np.float32).reshape(n, slots),
-                        glob=take(n * slots, np.float64).reshape(n, slots)))
-    assert at == raw.size
-    return out
+    """for scripts/transmissivity_timing.py, which runs the program itself (with a repeat count)"""
+    from tests.raster_helpers import write_parts
+    write_parts(path, host_input(dem, flag, geo, calls))
 
 
 def run_host(exe, tmp_path, dem, flag, geo, calls, tag="x"):
-    write_host_input(tmp_path / f"in_{tag}.bin", dem, flag, geo, calls)
-    subprocess.run([str(exe), str(tmp_path / f"in_{tag}.bin"), str(tmp_path / f"out_{tag}.bin")], check=True)
-    return read_host_output(tmp_path / f"out_{tag}.bin", calls)
+    """[dict(status, result, written, elev, glob)] per call"""
+    from tests.raster_helpers import Reader, run_host_program
+    r, out = Reader(run_host_program(exe, tmp_path, tag, host_input(dem, flag, geo, calls))), []
+    for _, _, mode, width, _, stations, _ in calls:
+        n = len(stations)
+        slots = tr.WINDOW_SLOTS if mode == WINDOW else width
+        out.append(dict(status=r.take(np.int32, n), result=r.take(np.float32 if mode == POINTS else np.int32, n), written=r.take(np.uint8, n, slots),
+                        elev=r.take(np.float32, n, slots), glob=r.take(np.float64, n, slots)))
+    assert r.done()
+    return out
 
 
 def pin_calls(pin, r):

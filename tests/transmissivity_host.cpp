@@ -12,16 +12,8 @@
  *         uint8 written[nPoints][slots], float elevationRefr[nPoints][slots], double global[nPoints][slots]; slots = width, or 24 in mode 1.
  * repeat: evaluate every case that many times and print the seconds of all but the reading and writing (scripts/transmissivity_timing.py). */
 #include <chrono>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 
-#include "sf3d_device.h"
-
-#define SF3D_GL_FN static inline
-#define SF3D_GL_TABLE static const
-#include "sf3d_glibcmath.inc"
+#include "host_io.h"
 
 #define SF3D_RAD_HOST
 #define SF3D_RAD_FN static inline
@@ -32,13 +24,6 @@
 #include "sf3d_rad.inc"
 #include "sf3d_rad_setup.inc"
 #include "sf3d_transmissivity.inc"
-
-template <class T> static std::vector<T> readv(FILE* f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "transmissivity_host: short input\n"); exit(2); }
-    return v;
-}
 
 struct Case {
     std::vector<int32_t> si, call;
@@ -113,7 +98,7 @@ int main(int argc, char** argv)
     if (!in) return 2;
     const int repeat = argc > 3 ? atoi(argv[3]) : 1;
     const std::vector<int32_t> dims = readv<int32_t>(in, 2);
-    const float flag = readv<float>(in, 1)[0];
+    const float flag = read1<float>(in);
     const std::vector<double> geo = readv<double>(in, 3);
     const size_t n = (size_t)dims[0] * dims[1];
     const std::vector<float> dem = readv<float>(in, n);
@@ -124,7 +109,7 @@ int main(int argc, char** argv)
     bool first = true;
     for (size_t c = 0; c < n; ++c)
         if (!isFlag(dem[c], flag) && !isFlag(dem[c], -9999.f)) { if (first || dem[c] > g.demMax) g.demMax = dem[c]; first = false; }
-    const int nCases = readv<int32_t>(in, 1)[0];
+    const int nCases = read1<int32_t>(in);
     std::vector<Case> cases((size_t)nCases);
     for (Case& c : cases) {
         c.si = readv<int32_t>(in, 8);
@@ -144,13 +129,10 @@ int main(int argc, char** argv)
     FILE* out = fopen(argv[2], "wb");
     if (!out) return 2;
     for (const Case& c : cases) {
-        fwrite(c.status.data(), 4, c.status.size(), out);
-        if (c.call[6] == TR_MODE_POINTS) fwrite(c.result.data(), 4, c.result.size(), out);
-        else fwrite(c.steps.data(), 4, c.steps.size(), out);
-        fwrite(c.written.data(), 1, c.written.size(), out);
-        fwrite(c.elev.data(), 4, c.elev.size(), out);
-        fwrite(c.global.data(), 8, c.global.size(), out);
+        writev(out, c.status);
+        if (c.call[6] == TR_MODE_POINTS) writev(out, c.result);
+        else writev(out, c.steps);
+        writev(out, c.written); writev(out, c.elev); writev(out, c.global);
     }
-    fclose(out);
-    return 0;
+    return fclose(out) == 0 ? 0 : 3;
 }
