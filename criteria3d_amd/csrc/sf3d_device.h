@@ -670,6 +670,64 @@ struct LocalProxiesCall {       /* what sf3d_localproxies_interpolate adds to a 
     const float* rows[LOCALPROXIES_MAX_OTHERS];
 };
 
+/* ---- glocal detrending (sf3d_glocal.inc, include/sf3d_glocal.h): a fit per macro area (k_glocal_areas, one wave an area), then every
+ * cell blended over the areas that cover it (k_glocal_cells, one thread a cell) ---- */
+struct GlocalAreaDev {          /* what k_glocal_areas records of an area and k_glocal_cells reads */
+    double parameters[LOCALDETREND_MAX_PARAMETERS];     /* the height's, NODATA where it is not significant */
+    double line[METEO_MAX_PROXIES][2];                  /* slope, intercept of the significant other proxies (mask), packed in slot order; the rest NODATA */
+    float r2;                           /* float(R2) of the height's fit, NODATA where none ran */
+    int32_t significant;                /* the height */
+    uint32_t fitted;                    /* the area's stations with a point this hour: the fitting subset and the rebuilt one */
+    uint32_t kept;                      /* what detrendingOtherProxies leaves of the rebuilt subset */
+    uint32_t mask;                      /* bit r: other proxy r of the call is significant */
+    uint8_t proxySignificant[METEO_MAX_PROXIES];
+    uint32_t reserved;
+};
+struct GlocalAreasView {        /* k_glocal_areas */
+    LocalDetrendSetup s;                /* minPointsLocal 0: neither minimum-points rule */
+    LocalProxiesSetup p;
+    const uint32_t* stationOffset;      /* [nAreas + 1] into the areas' station lists */
+    const int32_t* listPoint;           /* per list entry: the station's place in the call's point table, -1: no point this hour */
+    const float* sv;                    /* the call's point table: values */
+    const float* sh;                    /* heights */
+    const float* rows;                  /* [nOthers][METEO_MAX_STATIONS] */
+    GlocalAreaDev* area;                /* [nAreas] */
+    float* detrended;                   /* per list entry: the rebuilt subset's detrended value, NODATA where the entry is not in it */
+    uint8_t* keptBit;                   /* per list entry */
+    uint16_t* keptPoint;                /* per area from stationOffset[a]: the kept stations' places in the point table, subset order */
+    float* keptValue;                   /* and their detrended values */
+    uint32_t nAreas;
+};
+struct GlocalCellsView {        /* k_glocal_cells: k_meteo_idw's view, the cell-major pair table and what k_glocal_areas left */
+    MeteoView m;
+    LocalDetrendSetup s;
+    LocalProxiesSetup p;
+    const uint32_t* pairOffset;         /* [nCells + 1] */
+    const uint32_t* pairArea;           /* per pair, ascending within a cell */
+    const float* pairWeight;
+    const uint32_t* stationOffset;
+    const GlocalAreaDev* area;
+    const uint16_t* keptPoint;
+    const float* keptValue;
+    uint32_t* failed;                   /* one word: an interpolate() gave NODATA */
+    uint32_t nPairs;
+};
+struct GlocalStatic {           /* what sf3d_glocal_set_areas hands to DeviceSolver::glocal_set: host pointers */
+    uint32_t nAreas, nList, nPairs;
+    const uint32_t* stationOffset;
+    const uint32_t* pairOffset;
+    const uint32_t* pairArea;
+    const float* pairWeight;
+};
+struct GlocalCall {             /* what sf3d_glocal_interpolate adds to a MeteoCall: host pointers */
+    LocalDetrendSetup setup;
+    LocalProxiesSetup proxies;
+    const double* table;                /* LOCALDETREND_TABLE_DOUBLES doubles */
+    const float* height;
+    const float* rows[LOCALPROXIES_MAX_OTHERS];
+    const int32_t* listPoint;           /* nList entries */
+};
+
 /* ---- hourly evaporation, transpiration and rain sinks (sf3d_sink.inc, include/sf3d_sink.h): one thread per raster cell walks its column ---- */
 #define SINK_HORIZON_VALUES 5           /* per horizon: waterContentHH, FC, WP, SAT, getSoilFraction() */
 enum { SINK_H_HH = 0, SINK_H_FC = 1, SINK_H_WP = 2, SINK_H_SAT = 3, SINK_H_FRACTION = 4 };

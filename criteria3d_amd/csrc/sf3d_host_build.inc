@@ -122,6 +122,16 @@ struct MeteoCache {
     char* proxiesTables = nullptr;
     bool proxiesDone = false;
     double proxiesMs = 0.;
+    /* glocal detrending (sf3d_glocal.inc): one block for the areas' tables and what k_glocal_areas records (GL_T_*, at glocalOff), sized
+     * when the areas are set; the call's tables (the fit table, the height row, the other proxies' rows); the proxies of the last call */
+    char* glocalBlock = nullptr;
+    char* glocalTables = nullptr;
+    size_t glocalOff[11] = {0};
+    size_t glocalBytes = 0;
+    uint32_t glocalAreas = 0, glocalList = 0, glocalPairs = 0;
+    bool glocalDone = false;
+    double glocalMs[2] = {0., 0.};      /* k_glocal_areas, k_glocal_cells */
+    LocalProxiesSetup glocalProxies = {};
 };
 
 /* hourly radiation maps (sf3d_rad.inc): the five outputs, the static maps of include/sf3d_rad.h and the hour's transmissivity; they belong to

@@ -10,42 +10,6 @@ static_assert(SF3D_LOCALDETREND_MAX_PARAMETERS == LOCALDETREND_MAX_PARAMETERS &&
 static_assert(sizeof(sf3d_localdetrend_fit_t) == 24 + (3 + SF3D_LOCALDETREND_MAX_FIRST_GUESS) * SF3D_LOCALDETREND_MAX_PARAMETERS * sizeof(double),
               "sf3d_localdetrend_fit_t has no padding");
 
-namespace {
-
-/* the checks that need no raster; heightOnly: the proxy rule of sf3d_localdetrend.h (sf3d_localproxies_api.inc has its own) */
-bool localCallOk(int variable, uint32_t nStations, const double* x, const double* y, const float* height, const sf3d_meteo_settings_t* settings,
-                 const sf3d_localdetrend_fit_t* fit, bool heightOnly = true)
-{
-    if (!settings || !fit) return false;
-    if (variable != SF3D_METEO_AIR_TEMPERATURE && variable != SF3D_METEO_AIR_DEW_TEMPERATURE) return false;     /* getUseDetrendingVar, project.cpp:3160 */
-    if (!settings->useMultipleDetrending || !settings->useLocalDetrending) return false;
-    if (settings->useTopographicDistance || settings->useKriging || settings->useSupplementalStations || settings->useCrossValidationIndex || settings->updateMinMax)
-        return false;
-    if (settings->nProxies < 0 || settings->nProxies > SF3D_METEO_MAX_PROXIES) return false;
-    int active = 0;
-    for (int p = 0; heightOnly && p < settings->nProxies; ++p) {
-        if (!settings->proxy[p].active) continue;
-        if (!settings->proxy[p].isHeight) return false;
-        ++active;
-    }
-    if (heightOnly && active != 1) return false;
-    const int np = localParameters(fit->function);
-    if (np == 0 || fit->nParameters != np) return false;
-    if (fit->nFirstGuess < 1 || fit->nFirstGuess > SF3D_LOCALDETREND_MAX_FIRST_GUESS || fit->minPointsLocalDetrending < 1) return false;
-    if (std::isnan(fit->stdDevThreshold)) return false;
-    for (int j = 0; j < np; ++j) {
-        if (!std::isfinite(fit->parametersMin[j]) || !std::isfinite(fit->parametersMax[j]) || !std::isfinite(fit->parametersDelta[j])) return false;
-        for (int k = 0; k < fit->nFirstGuess; ++k)
-            if (!std::isfinite(fit->firstGuess[k][j])) return false;
-    }
-    if (nStations > SF3D_METEO_MAX_STATIONS || (nStations > 0 && (!x || !y || !height))) return false;
-    for (uint32_t k = 0; k < nStations; ++k)
-        if (!std::isfinite(x[k]) || !std::isfinite(y[k]) || !std::isfinite(height[k])) return false;
-    return true;
-}
-
-}  // namespace
-
 extern "C" {
 
 sf3d_error_t sf3d_localdetrend_interpolate(int variable, int method, uint32_t nStations, const double* x, const double* y, const float* height, const float* value,

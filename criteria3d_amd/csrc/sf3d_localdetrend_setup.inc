@@ -39,6 +39,39 @@ static inline void localSetup(const sf3d_localdetrend_fit_t* fit, uint32_t nStat
     localNumbers(fit->function, fit->nFirstGuess, fit->minPointsLocalDetrending, fit->stdDevThreshold, nStations, boundingBoxArea, s);
 }
 
+/* the checks of a call that need no raster; heightOnly: the proxy rule of sf3d_localdetrend.h (proxiesCallOk below has its own); local: local
+ * detrending - without it (sf3d_glocal.h) useLocalDetrending must be 0 and minPointsLocalDetrending is not read */
+static inline bool localCallOk(int variable, uint32_t nStations, const double* x, const double* y, const float* height, const sf3d_meteo_settings_t* settings,
+                 const sf3d_localdetrend_fit_t* fit, bool heightOnly = true, bool local = true)
+{
+    if (!settings || !fit) return false;
+    if (variable != SF3D_METEO_AIR_TEMPERATURE && variable != SF3D_METEO_AIR_DEW_TEMPERATURE) return false;     /* getUseDetrendingVar, project.cpp:3160 */
+    if (!settings->useMultipleDetrending || (settings->useLocalDetrending != 0) != local) return false;
+    if (settings->useTopographicDistance || settings->useKriging || settings->useSupplementalStations || settings->useCrossValidationIndex || settings->updateMinMax)
+        return false;
+    if (settings->nProxies < 0 || settings->nProxies > SF3D_METEO_MAX_PROXIES) return false;
+    int active = 0;
+    for (int p = 0; heightOnly && p < settings->nProxies; ++p) {
+        if (!settings->proxy[p].active) continue;
+        if (!settings->proxy[p].isHeight) return false;
+        ++active;
+    }
+    if (heightOnly && active != 1) return false;
+    const int np = localParameters(fit->function);
+    if (np == 0 || fit->nParameters != np) return false;
+    if (fit->nFirstGuess < 1 || fit->nFirstGuess > SF3D_LOCALDETREND_MAX_FIRST_GUESS || (local && fit->minPointsLocalDetrending < 1)) return false;
+    if (std::isnan(fit->stdDevThreshold)) return false;
+    for (int j = 0; j < np; ++j) {
+        if (!std::isfinite(fit->parametersMin[j]) || !std::isfinite(fit->parametersMax[j]) || !std::isfinite(fit->parametersDelta[j])) return false;
+        for (int k = 0; k < fit->nFirstGuess; ++k)
+            if (!std::isfinite(fit->firstGuess[k][j])) return false;
+    }
+    if (nStations > SF3D_METEO_MAX_STATIONS || (nStations > 0 && (!x || !y || !height))) return false;
+    for (uint32_t k = 0; k < nStations; ++k)
+        if (!std::isfinite(x[k]) || !std::isfinite(y[k]) || !std::isfinite(height[k])) return false;
+    return true;
+}
+
 /* the checks of sf3d_localproxies_interpolate that need no raster, beyond localCallOk's; fills the proxies of the call: rows[r] is the
  * station row of ps.slot[r], *height the active height's row (nullptr: the height is not active) */
 static inline bool proxiesCallOk(uint32_t nStations, uint32_t nProxies, const float* proxyValues, const sf3d_meteo_settings_t* settings,

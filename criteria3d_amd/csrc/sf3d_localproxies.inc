@@ -268,6 +268,24 @@ SF3D_METEO_FN uint32_t lp_compact(const LdList& L, const uint8_t* member, uint32
     return kept;
 }
 
+/* detrendingOtherProxies (interpolation.cpp:2173-2236) with the lines of vec[LP_P] over the entries that are in the interpolated list: a
+ * station with an incomplete significant proxy (X.mask) leaves it.  k_glocal_areas (sf3d_glocal.inc) runs the same text */
+SF3D_METEO_FN void lp_detrend(const LdList& L, const LpCtx& X, uint32_t n)
+{
+    for (uint32_t i = ld_lane(); i < n; i += LD_LANES) {
+        if (!(X.member[i] & LP_INTERP)) continue;
+        const uint32_t at = L.idx[i];
+        bool proxyComplete = true;
+        for (uint32_t r = 0; r < X.nOthers; ++r)
+            if (((X.mask >> r) & 1u) && meteo_eqf(X.rows[(size_t)r * METEO_MAX_STATIONS + at], (float)LD_NODATA)) proxyComplete = false;
+        if (proxyComplete) {
+            const float detrendValue = (float)lp_sum(X, at, X.vec + LP_P * LP_NP, -1);
+            L.val[i] -= detrendValue;
+        } else X.member[i] = (uint8_t)(X.member[i] & ~LP_INTERP);
+    }
+    ld_sync();
+}
+
 /* multipleDetrendingOtherProxiesFitting and detrendingOtherProxies over the selected list of n entries (their values detrended by the
  * elevation already).  Returns the length of the interpolated list, compacted; X.mask: the significant proxies; their slope and
  * intercept are left in vec[LP_P], two per significant proxy in slot order */
@@ -324,19 +342,7 @@ SF3D_METEO_FN uint32_t lp_others(const LdSetup& s, const LpSetup& ps, const LdLi
         ld_sync();
         lp_marquardt(L, X, n, NP);
         ld_sync();
-        /* detrendingOtherProxies: a station with an incomplete significant proxy leaves the interpolated list */
-        for (uint32_t i = lane; i < n; i += LD_LANES) {
-            if (!(X.member[i] & LP_INTERP)) continue;
-            const uint32_t at = L.idx[i];
-            bool proxyComplete = true;
-            for (uint32_t r = 0; r < X.nOthers; ++r)
-                if (((second >> r) & 1u) && meteo_eqf(X.rows[(size_t)r * METEO_MAX_STATIONS + at], (float)LD_NODATA)) proxyComplete = false;
-            if (proxyComplete) {
-                const float detrendValue = (float)lp_sum(X, at, X.vec + LP_P * LP_NP, -1);
-                L.val[i] -= detrendValue;
-            } else X.member[i] = (uint8_t)(X.member[i] & ~LP_INTERP);
-        }
-        ld_sync();
+        lp_detrend(L, X, n);
     }
     return lp_compact(L, X.member, n);
 }
@@ -346,6 +352,35 @@ struct LpOutcome {
     uint32_t interpolated;              /* the length of the interpolated list */
     uint32_t mask;                      /* bit r: other proxy r is significant; its slope and intercept are in vec[LP_P] */
 };
+
+/* retrend (:1298-1313) through getMultipleDetrendingValues (:2563-2617) on cell c: the height first (significant: with par), then the
+ * significant proxies (mask) in slot order, slope and intercept of each in `lines`; a NODATA among the cell's values of them: 0.
+ * k_glocal_cells (sf3d_glocal.inc) runs the same text */
+SF3D_METEO_FN float lp_retrend(const MeteoView& m, const LdSetup& s, const LpSetup& ps, uint32_t nOthers, uint32_t mask, const double* lines, uint32_t c, float z,
+                               bool significant, double* par)
+{
+    double retrendValue = 0.;
+    bool complete = true;
+    double zh = 0;
+    if (significant) {
+        zh = lp_cell_proxy(m, c, z, ps.heightSlot);
+        complete = zh != LD_NODATA;
+    }
+    for (uint32_t r = 0; r < nOthers; ++r)
+        if (((mask >> r) & 1u) && lp_cell_proxy(m, c, z, ps.slot[r]) == LD_NODATA) complete = false;
+    if (complete && (significant || mask != 0)) {
+        double sumOfFunctions = 0.0;
+        if (significant) sumOfFunctions += ld_height_function(s, zh, par);
+        int j = 0;
+        for (uint32_t r = 0; r < nOthers; ++r) {
+            if (!((mask >> r) & 1u)) continue;
+            sumOfFunctions += lines[j] * lp_cell_proxy(m, c, z, ps.slot[r]) + lines[j + 1];
+            j += 2;
+        }
+        retrendValue = (float)sumOfFunctions;
+    }
+    return (float)retrendValue;
+}
 
 /* one DEM cell c of height z at the float (x, y): the map value */
 SF3D_METEO_FN float lp_cell(const MeteoView& m, const LdSetup& s, const LpSetup& ps, const LdStations& st, const LdList& L, LpCtx& X, uint32_t c, float z, float x,
@@ -376,31 +411,7 @@ SF3D_METEO_FN float lp_cell(const MeteoView& m, const LdSetup& s, const LpSetup&
     /* interpolate() over what is left of the list; modifiedShepardIdw still takes the localRadius of the selection */
     float result = ld_methods(s, st, L, nInterpolated, radius, x, y);
     if (meteo_eqf(result, (float)LD_NODATA)) return (float)LD_NODATA;
-    if (s.useDetrending) {
-        /* retrend (:1298-1313) through getMultipleDetrendingValues (:2563-2617): the height first, then the significant proxies in slot
-         * order; a NODATA among the cell's values of them: 0 */
-        double retrendValue = 0.;
-        bool complete = true;
-        double zh = 0;
-        if (significant) {
-            zh = lp_cell_proxy(m, c, z, ps.heightSlot);
-            complete = zh != LD_NODATA;
-        }
-        for (uint32_t r = 0; r < X.nOthers; ++r)
-            if (((X.mask >> r) & 1u) && lp_cell_proxy(m, c, z, ps.slot[r]) == LD_NODATA) complete = false;
-        if (complete && (significant || X.mask != 0)) {
-            double sumOfFunctions = 0.0;
-            if (significant) sumOfFunctions += ld_height_function(s, zh, par);
-            int j = 0;
-            for (uint32_t r = 0; r < X.nOthers; ++r) {
-                if (!((X.mask >> r) & 1u)) continue;
-                sumOfFunctions += X.vec[LP_P * LP_NP + j] * lp_cell_proxy(m, c, z, ps.slot[r]) + X.vec[LP_P * LP_NP + j + 1];
-                j += 2;
-            }
-            retrendValue = (float)sumOfFunctions;
-        }
-        result += (float)retrendValue;
-    }
+    if (s.useDetrending) result += lp_retrend(m, s, ps, X.nOthers, X.mask, X.vec + LP_P * LP_NP, c, z, significant, par);
     return result;
 }
 

@@ -276,6 +276,18 @@ public:
     uint64_t localproxies_bytes() const;
     sf3d_error_t localproxies_free();
     double localproxies_kernel_ms() const;
+    /* glocal detrending (sf3d_glocal.inc): the macro areas' tables belong to the meteo block's raster and go with it (meteo_free);
+     * glocal_interpolate runs k_glocal_areas and k_glocal_cells into the meteo block's slot of the variable - SF3D_MISSING_DATA_ERROR
+     * where an interpolate() gave NODATA, and the slot is then not produced; glocal_records: what k_glocal_areas left of the last call and
+     * the proxies it ran with.  which of glocal_kernel_ms: 0 k_glocal_areas, 1 k_glocal_cells */
+    sf3d_error_t glocal_set(const GlocalStatic& g);
+    bool glocal_areas_set() const;
+    sf3d_error_t glocal_interpolate(const MeteoCall& call, const GlocalCall& g, const uint8_t* mine, float* out);
+    bool glocal_done() const;
+    sf3d_error_t glocal_records(GlocalAreaDev* area, float* detrended, uint8_t* kept, LocalProxiesSetup* proxies);
+    uint64_t glocal_bytes() const;
+    sf3d_error_t glocal_free();
+    double glocal_kernel_ms(int which) const;
     /* hourly r.sun radiation maps (sf3d_rad.inc): the five outputs and the static maps, independent of the node model as the other raster
      * blocks; transmissivity == nullptr: k_rad_hour reads the map the meteo block holds (the caller asks meteo_produced first) */
     sf3d_error_t rad_alloc(const RadSetup& setup);

@@ -18,7 +18,7 @@
  * The values are the reference's to the bit (tests/golden/localproxies.npz: a pin of the compiled reference).
  *
  * With the caller: what sf3d_localdetrend.h leaves there except the other proxies - the point list, the height's range, delta and first
- * guesses, lapse-rate codes (every station is primary), glocal detrending, output points - and multipleDetrending without
+ * guesses, lapse-rate codes (every station is primary), output points - and multipleDetrending without
  * localDetrending.
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.  The block
