@@ -4,7 +4,9 @@ k_glocal_cells compiled for the host (tests/glocal_host.cpp) equal to the compil
 and every area quantity on both rasters, and once more as a stand-alone program under the address and undefined-behaviour sanitizers;
 the Python restatement equal to the pin on `tiny`; `areas_from_maps` against a hand-made three-area layout; every refusal of
 sf3d_glocal_set_areas and sf3d_glocal_interpolate through the HIP-free check functions the entry points share with the host program;
-and off the pin (glocal_cases.OFF_PIN) the host build equal to the restatement, with the flag an interpolate() raises when it gives NODATA."""
+and off the pin (glocal_cases.OFF_PIN, and OFF_PIN_EDGES with the property of every row) the host build equal to the restatement, with the
+flag an interpolate() raises when it gives NODATA: IDW on the stations' own place, both Shepard methods over one station."""
+import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -101,6 +103,12 @@ def test_sanitized_host_program_runs_clean_on_the_pin_and_off_it(pin, host, tmp_
     r, c = gc.off_pin("lists65-130")
     assert gc.run_host(san, r, tmp_path, [c])[0]["status"] == 0
     r, c = gc.failing_area()
+    assert gc.run_host(san, r, tmp_path, [c])[0]["status"] == 1
+    # entries without a point, a chunk without one, lists of METEO_MAX_STATIONS entries, an area with no point at all
+    for label in ("holes-third", "holes-run64-idw", "lists-cap", "empty-area"):
+        r, c = gc.off_pin(label)
+        assert gc.run_host(san, r, tmp_path, [c])[0]["status"] == 0, label
+    r, c = gc.failing_single_station(meteo.SHEPARD)
     assert gc.run_host(san, r, tmp_path, [c])[0]["status"] == 1
 
 
@@ -248,3 +256,76 @@ def test_an_interpolate_that_gives_nodata_raises_the_flag(exe, tmp_path):
     g = gc.run_host(exe, r, tmp_path, [c])[0]
     assert g["status"] == 1 and g["kept"][1] == 6
     assert gc.restated(r, c)["failed"]
+
+
+# sha256 of glocal_cases.input_parts of the five cases of OFF_PIN as they stood before `synthetic` took use_detrending, var, empty_areas and missing
+OFF_PIN_INPUTS = {"lists65-130": "4063fcca8a6b5481d6a3e77c5450ce43c44fa52092c7776dffd372822af7df5b",
+                  "lists-modified": "925b240b42fc5736b9b948946921adce7656c78e672d2f78cdebb9a9511414ae",
+                  "guesses31-three": "1f65c2a61ca51cf9aedaa439e74a637d4d94805f4a5cddaf522e924d37234040",
+                  "guesses31-free": "14ae3b9ce6027bcfc437858170efa6dec75ecd1f7ae848e9969724e28b0ddeb5",
+                  "five-deep": "1bd36a9df686377e1ef6623473fd8ac2d8b0ceee73df3c6c159552327f9959f9"}
+
+
+def test_the_new_arguments_of_synthetic_leave_the_five_off_pin_cases_as_they_were():
+    assert [label for label, _ in gc.OFF_PIN] == list(OFF_PIN_INPUTS)
+    for label, want in OFF_PIN_INPUTS.items():
+        r, c = gc.off_pin(label)
+        h = hashlib.sha256()
+        for part in gc.input_parts(r, [c]):
+            h.update(np.ascontiguousarray(part).tobytes())
+        assert h.hexdigest() == want, label
+
+
+def test_without_points_cuts_the_call_and_leaves_the_areas():
+    r, c = gc.off_pin("lists65-130")
+    keep = gc.missing_points(r, c, ("every", 3))
+    q = gc.without_points(c, keep)
+    assert len(q["point_index"]) == 140 - 47 and q["proxy_values"].shape == (gc.SLOTS, 93) and len(c["point_index"]) == 140
+    for key in ("point_index", "x", "y", "value"):
+        assert np.array_equal(q[key], c[key][keep]) and len(q[key]) == 93
+    assert np.array_equal(q["proxy_values"], c["proxy_values"][:, keep]) and q["fit"] is c["fit"] and q["area"] == c["area"]
+    keep = gc.missing_points(r, c, ("entries", 1, 0, 64))
+    assert keep.sum() == 140 - 64 and not np.isin(r["areas"][1]["stations"][:64], c["point_index"][keep]).any()
+
+
+@pytest.mark.parametrize("label", gc.EDGE_LABELS)
+def test_edge_rows_host_build_equals_the_restatement_and_shows_the_row_s_property(exe, tmp_path, label):
+    """glocal_cases.OFF_PIN_EDGES: every quantity of the host build equal to the restatement's, and the outcome shows what the row is
+    there for (its third column)"""
+    _, arguments, must = next(row for row in gc.OFF_PIN_EDGES if row[0] == label)
+    r, c = gc.off_pin(label)
+    g = gc.run_host(exe, r, tmp_path, [c])[0]
+
+    def again(**changed):
+        q, qc = gc.synthetic(**dict(arguments, **changed))
+        q["name"], qc["label"] = f"{label}-again", label
+        return gc.run_host(exe, q, tmp_path, [qc])[0]
+    must(r, c, g, again)
+    mine = gc.restated(r, c)
+    assert g["status"] == 0 and not mine["failed"]
+    same(g, mine, label, gc.QUANTITIES)
+    inside = r["dem"] != r["flag"]
+    assert (g["value"][inside] != r["flag"]).any()
+
+
+def test_the_sparse_hour_on_the_cap_s_areas_is_legal_and_fits_the_last_chunk_alone(exe, tmp_path):
+    """what tests/test_gpu_glocal.py calls between two full hours: of the list of 1024 only entries of the last chunk have a point"""
+    r, c = gc.off_pin("lists-cap")
+    q = gc.without_points(c, gc.missing_points(r, c, gc.CAP_TAIL))
+    g = gc.run_host(exe, r, tmp_path, [q])[0]
+    assert g["status"] == 0 and g["fitted"][0] == 64 and (g["fitted"][1:] > 0).all() and (g["fitted"] < np.array(gc.lengths(r)) // 4).all()
+    kept = g["station_kept"][gc.entries(r, 0)]
+    assert kept.any() and not kept[:meteo.MAX_STATIONS - 64].any()
+    mine = gc.restated(r, q)
+    assert not mine["failed"]
+    same(g, mine, "cap-tail", gc.QUANTITIES)
+
+
+@pytest.mark.parametrize("method", (meteo.SHEPARD, meteo.SHEPARD_MODIFIED))
+def test_both_shepard_methods_give_nodata_for_an_area_of_one_station(exe, tmp_path, method):
+    r, c = gc.failing_single_station(method)
+    g = gc.run_host(exe, r, tmp_path, [c])[0]
+    assert g["status"] == 1 and g["fitted"].tolist() == [1, 30] and g["kept"][0] == 1
+    mine = gc.restated(r, c)
+    assert mine["failed"]
+    same(g, mine, r["name"], gc.QUANTITIES)

@@ -1,8 +1,10 @@
 """Glocal detrending on the device (include/sf3d_glocal.h) against the compiled-reference pin tests/golden/glocal.npz: every case of the
 pin in every cell and every area quantity on both rasters, the meteo block's slot, the same bits twice, the slot counted as produced and
 read on the device by the hour block (its humidity pass and its ET0 hour), the life of the block, two ranks, and off the pin
-(glocal_cases.OFF_PIN: area lists of 65 and 130 stations, five areas, 31 first guesses, cells under five areas) the device against the
-host build of its own text, with the error an interpolate() that gives NODATA must bring back."""
+(glocal_cases.OFF_PIN: area lists of 65 and 130 stations, five areas, 31 first guesses, cells under five areas; OFF_PIN_EDGES: list
+entries without a point this hour, lists of 2 to 1024 stations, one to ten areas, an area with no point, no retrend) the device against
+the host build of its own text, a sparse hour between two full ones on one set of areas, and the error an interpolate() that gives
+NODATA must bring back."""
 import numpy as np
 import pytest
 
@@ -162,11 +164,14 @@ def test_two_ranks_merge_to_the_single_rank_map(product, pin, tmp_path):
     _same(mr.merge([res["map"] for res in ranks], cell_owner, flag, others=flag, what="map"), want["value"], "merged ranks")
 
 
-@pytest.mark.parametrize("label", [label for label, _ in gc.OFF_PIN])
+@pytest.mark.parametrize("label", [label for label, _ in gc.OFF_PIN] + list(gc.EDGE_LABELS))
 def test_off_the_pin_the_device_equals_the_host_build_of_its_text(product, host, label):
     """gc.OFF_PIN: an area list of 65 and one of 130 stations (one and two wave widths crossed) among five areas (the second block has
-    one wave idle), 31 first guesses of both three-piece functions (lanes 0 to 30 busy), every cell under five areas - every cell and
-    area quantity bit for bit, NaN as "both NaN".  The host build is held to the restatement in tests/test_glocal_host.py"""
+    one wave idle), 31 first guesses of both three-piece functions (lanes 0 to 30 busy), every cell under five areas; gc.OFF_PIN_EDGES:
+    list entries without a point this hour (a ballot with gaps, a chunk whose ballot is 0, a list whose first two chunks are empty),
+    lists of 63 to 129 and of 255 to 1024 stations, lists of 2 to 11, one, eight, nine and ten areas, an area with no point, no retrend,
+    the dew point - every cell and area quantity bit for bit, NaN as "both NaN".  The host build is held to the restatement, and every
+    row of OFF_PIN_EDGES to its property, in tests/test_glocal_host.py"""
     r, c = gc.off_pin(label)
     want = gc.run_host(host[0], r, host[1], [c])[0]
     assert want["status"] == 0
@@ -179,25 +184,45 @@ def test_off_the_pin_the_device_equals_the_host_build_of_its_text(product, host,
     meteo.clean(product)
 
 
-def test_an_interpolate_that_gives_nodata_brings_the_error_back(product, host):
-    """glocal_cases.failing_area: every station of an area on the centre of its one cell.  The host build raises its flag; the device
-    returns SF3D_MISSING_DATA_ERROR, the variable's slot does not count as produced, the areas' records are there, and the next good
-    call works.  (No input erases a whole rebuilt subset: tests/glocal_cases.py says why.)"""
-    r, c = gc.failing_area()
-    want = gc.run_host(host[0], r, host[1], [c])[0]
-    assert want["status"] == 1
+def test_an_hour_with_fewer_stations_reads_nothing_the_fuller_hour_left(product, host):
+    """the areas of `lists-cap` set once, then four hours: every list whole (1024, 1023, 257, 256, 255 fitted), every fifth point gone, of
+    the list of 1024 only entries of the last chunk with a point (64 fitted, fifteen chunks whose ballot is 0), every list whole again.
+    What an hour leaves in keptPoint, keptValue, detrended and keptBit beyond its own counts is the fuller hour's: each call equals the
+    host build of that call alone, and the last the first"""
+    r, c = gc.off_pin("lists-cap")
+    hours = [c, gc.without_points(c, gc.missing_points(r, c, ("every", 5))), gc.without_points(c, gc.missing_points(r, c, gc.CAP_TAIL)), c]
+    want = gc.run_host(host[0], r, host[1], hours)
+    assert [w["status"] for w in want] == [0] * 4 and [int(w["fitted"][0]) for w in want] == [1024, 819, 64, 1024]
     gc.initialize(product, r)
-    hour.bind(product)
-    good = dict(c, x=c["x"] + 37.0)                                         # the same stations, off the centre
-    meteo.set_map(product, "dewT", np.where(r["dem"] != r["flag"], np.float32(2.0), r["flag"]).astype(np.float32))
-    gc.interpolate(product, good)
-    hour.relative_humidity(product)                                         # produced
-    with pytest.raises(capi.SF3DError) as failure:
-        gc.interpolate(product, c)
-    assert capi.ERROR_NAMES[capi.MISSING_DATA_ERROR] in str(failure.value)
-    same(gl.get_area_fit(product), want, "the areas of the failed call", gc.AREA_QUANTITIES)
-    with pytest.raises(capi.SF3DError):                                     # the overwritten slot no longer counts as produced
-        hour.relative_humidity(product)
-    gc.interpolate(product, good)
-    hour.relative_humidity(product)
+    got = [gc.outcome(product, gc.interpolate(product, q)) for q in hours]
+    for k in range(4):
+        same(got[k], want[k], f"hour {k}", gc.QUANTITIES)
+    same(got[3], got[0], "the full hour again", gc.QUANTITIES)
     meteo.clean(product)
+
+
+def test_an_interpolate_that_gives_nodata_brings_the_error_back(product, host):
+    """glocal_cases.failing_area: every station of an area on the centre of its one cell (IDW); failing_single_station: an area of one
+    station that covers cells alone (both Shepard methods).  The host build raises its flag; the device returns SF3D_MISSING_DATA_ERROR,
+    the variable's slot does not count as produced, the areas' records are there, and the next good call works.  (No input erases a
+    whole rebuilt subset: tests/glocal_cases.py says why.)"""
+    for which in (meteo.IDW, meteo.SHEPARD, meteo.SHEPARD_MODIFIED):
+        r, c = gc.failing_area() if which == meteo.IDW else gc.failing_single_station(which)
+        want = gc.run_host(host[0], r, host[1], [c])[0]
+        assert want["status"] == 1
+        gc.initialize(product, r)
+        hour.bind(product)
+        # the same stations off the centre; the same stations by IDW, which one station is enough for
+        good = dict(c, x=c["x"] + 37.0) if which == meteo.IDW else dict(c, method=meteo.IDW)
+        meteo.set_map(product, "dewT", np.where(r["dem"] != r["flag"], np.float32(2.0), r["flag"]).astype(np.float32))
+        gc.interpolate(product, good)
+        hour.relative_humidity(product)                                     # produced
+        with pytest.raises(capi.SF3DError) as failure:
+            gc.interpolate(product, c)
+        assert capi.ERROR_NAMES[capi.MISSING_DATA_ERROR] in str(failure.value), r["name"]
+        same(gl.get_area_fit(product), want, f"{r['name']}: the areas of the failed call", gc.AREA_QUANTITIES)
+        with pytest.raises(capi.SF3DError):                                 # the overwritten slot no longer counts as produced
+            hour.relative_humidity(product)
+        gc.interpolate(product, good)
+        hour.relative_humidity(product)
+        meteo.clean(product)
