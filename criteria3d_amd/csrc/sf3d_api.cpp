@@ -1195,6 +1195,7 @@ sf3d_error_t sf3d_device_pow(uint32_t count, const double* x, const double* y, d
 #include "sf3d_localdetrend_api.inc"
 #include "sf3d_localproxies_api.inc"
 #include "sf3d_glocal_api.inc"
+#include "sf3d_multidetrend_api.inc"
 #include "sf3d_sink_api.inc"
 #include "sf3d_rad_api.inc"
 #include "sf3d_transmissivity_api.inc"

@@ -728,6 +728,65 @@ struct GlocalCall {             /* what sf3d_glocal_interpolate adds to a MeteoC
     const int32_t* listPoint;           /* nList entries */
 };
 
+/* ---- multiple detrending without areas (sf3d_multidetrend.inc, include/sf3d_multidetrend.h): one fit over all the call's stations
+ * (k_multidetrend_fit, one wave), then every cell (k_multidetrend_cells) or every point of a list (k_multidetrend_points, a thread each)
+ * interpolated over the stations the fit kept ---- */
+struct MultiDetrendRecord {     /* what k_multidetrend_fit records of the call and the two other kernels read */
+    double parameters[LOCALDETREND_MAX_PARAMETERS];     /* the height's, NODATA where it is not significant */
+    double line[METEO_MAX_PROXIES][2];                  /* slope, intercept of the significant other proxies (mask), packed in slot order; the rest NODATA */
+    float r2;                           /* float(R2) of the height's fit, NODATA where none ran */
+    int32_t significant;                /* the height */
+    uint32_t fitted;                    /* the call's stations */
+    uint32_t kept;                      /* what the prunings and detrendingOtherProxies leave of them */
+    uint32_t mask;                      /* bit r: other proxy r of the call is significant */
+    uint32_t reserved;
+};
+struct MultiDetrendFitView {    /* k_multidetrend_fit */
+    LocalDetrendSetup s;                /* minPointsLocal 0: neither minimum-points rule */
+    LocalProxiesSetup p;
+    const double* sx;                   /* the call's station table, in device memory */
+    const double* sy;
+    const float* sv;
+    const float* sh;                    /* heights */
+    const float* rows;                  /* [nOthers][METEO_MAX_STATIONS] */
+    MultiDetrendRecord* record;         /* one */
+    float* detrended;                   /* per station: its detrended value, NODATA where it is not kept */
+    uint8_t* keptBit;                   /* per station */
+    double* keptX;                      /* the kept stations in call order: x, y */
+    double* keptY;
+    float* keptValue;                   /* and their detrended values */
+    uint32_t nStations;
+};
+struct MultiDetrendCellsView {  /* k_multidetrend_cells: k_meteo_idw's view and what k_multidetrend_fit left */
+    MeteoView m;
+    LocalDetrendSetup s;
+    LocalProxiesSetup p;
+    const MultiDetrendRecord* record;
+    const double* keptX;
+    const double* keptY;
+    const float* keptValue;
+};
+struct MultiDetrendPointsView { /* k_multidetrend_points: the last call's kept stations and fit, and the points of this call */
+    LocalDetrendSetup s;
+    LocalProxiesSetup p;
+    const MultiDetrendRecord* record;
+    const double* keptX;                /* the kept stations of the last interpolate */
+    const double* keptY;
+    const float* keptValue;
+    const float* px;                    /* the points: float x, y as interpolate() takes them */
+    const float* py;
+    const float* pv;                    /* [nProxies][nPoints]: every slot's value at the point, NODATA where it has none */
+    float* out;                         /* [nPoints] */
+    uint32_t nPoints, nProxies;
+};
+struct MultiDetrendCall {       /* what sf3d_multidetrend_interpolate adds to a MeteoCall: host pointers */
+    LocalDetrendSetup setup;
+    LocalProxiesSetup proxies;
+    const double* table;                /* LOCALDETREND_TABLE_DOUBLES doubles */
+    const float* height;
+    const float* rows[LOCALPROXIES_MAX_OTHERS];
+};
+
 /* ---- hourly evaporation, transpiration and rain sinks (sf3d_sink.inc, include/sf3d_sink.h): one thread per raster cell walks its column ---- */
 #define SINK_HORIZON_VALUES 5           /* per horizon: waterContentHH, FC, WP, SAT, getSoilFraction() */
 enum { SINK_H_HH = 0, SINK_H_FC = 1, SINK_H_WP = 2, SINK_H_SAT = 3, SINK_H_FRACTION = 4 };

@@ -132,6 +132,17 @@ struct MeteoCache {
     bool glocalDone = false;
     double glocalMs[2] = {0., 0.};      /* k_glocal_areas, k_glocal_cells */
     LocalProxiesSetup glocalProxies = {};
+    /* multiple detrending without areas (sf3d_multidetrend.inc): one block of fixed size for the call's tables and what
+     * k_multidetrend_fit leaves (MD_OFF_*), allocated by the first call; the points of sf3d_multidetrend_points, grown as needed; the
+     * set-up and the proxies of the last call, which the points are evaluated with */
+    char* multiBlock = nullptr;
+    char* multiPoints = nullptr;
+    size_t multiPointsCap = 0;
+    uint32_t multiStations = 0;
+    bool multiDone = false;
+    double multiMs[3] = {0., 0., 0.};   /* k_multidetrend_fit, k_multidetrend_cells, k_multidetrend_points */
+    LocalDetrendSetup multiSetup = {};
+    LocalProxiesSetup multiProxies = {};
 };
 
 /* hourly radiation maps (sf3d_rad.inc): the five outputs, the static maps of include/sf3d_rad.h and the hour's transmissivity; they belong to

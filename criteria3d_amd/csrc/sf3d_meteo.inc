@@ -278,7 +278,8 @@ sf3d_error_t DeviceSolver::meteo_free()
     raster_unbind(FEED_METEO);
     raster_release({impl_->meteo.base, impl_->meteo.stations, impl_->meteo.topoMaps, impl_->meteo.topoTables, impl_->meteo.topoMatrix,
                     impl_->meteo.localFit, impl_->meteo.localTables, impl_->meteo.proxiesFit, impl_->meteo.proxiesTables,
-                    impl_->meteo.glocalBlock, impl_->meteo.glocalTables});       /* the topographic distance maps, the local detrending's outcome and the macro areas go with their raster */
+                    impl_->meteo.glocalBlock, impl_->meteo.glocalTables, impl_->meteo.multiBlock,
+                    impl_->meteo.multiPoints});       /* the topographic distance maps, the local detrending's outcome, the macro areas and the one fit go with their raster */
     impl_->meteo = MeteoCache();
     return SF3D_OK;
 }

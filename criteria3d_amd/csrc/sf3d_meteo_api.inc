@@ -20,8 +20,9 @@ struct MeteoHost {
 
 void topoHostClear();                          /* sf3d_topodist_api.inc: the topographic distance maps go with their raster */
 void glocalHostClear();                        /* sf3d_glocal_api.inc: so do the macro areas */
+void multidetrendHostClear();                  /* sf3d_multidetrend_api.inc: and the one fit of the last call */
 
-void meteoClear() { MT = MeteoHost(); topoHostClear(); glocalHostClear(); (void)dev().meteo_free(); }
+void meteoClear() { MT = MeteoHost(); topoHostClear(); glocalHostClear(); multidetrendHostClear(); (void)dev().meteo_free(); }
 
 /* computeShepardInitialRadius(area, nrPoints, SHEPARD_AVG_NRPOINTS), interpolation.cpp:800-803: float products, PI of commonConstants.h:249 */
 float meteoInitialRadius(float area, uint32_t allPointsNr)

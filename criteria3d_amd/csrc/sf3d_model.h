@@ -288,6 +288,17 @@ public:
     uint64_t glocal_bytes() const;
     sf3d_error_t glocal_free();
     double glocal_kernel_ms(int which) const;
+    /* multiple detrending without areas (sf3d_multidetrend.inc): multidetrend_interpolate runs k_multidetrend_fit and, behind it on the
+     * same stream, k_multidetrend_cells into the meteo block's slot of the variable; multidetrend_points evaluates the last call's fit
+     * and kept stations at a list of points (k_multidetrend_points); multidetrend_records: what k_multidetrend_fit left of the last
+     * call, its station count and the proxies it ran with.  which of multidetrend_kernel_ms: 0 fit, 1 cells, 2 points */
+    sf3d_error_t multidetrend_interpolate(const MeteoCall& call, const MultiDetrendCall& g, const uint8_t* mine, float* out);
+    bool multidetrend_done() const;
+    sf3d_error_t multidetrend_points(uint32_t nPoints, uint32_t nProxies, const float* x, const float* y, const float* proxyValues, float* out);
+    sf3d_error_t multidetrend_records(MultiDetrendRecord* record, float* detrended, uint8_t* kept, LocalProxiesSetup* proxies);
+    uint64_t multidetrend_bytes() const;
+    sf3d_error_t multidetrend_free();
+    double multidetrend_kernel_ms(int which) const;
     /* hourly r.sun radiation maps (sf3d_rad.inc): the five outputs and the static maps, independent of the node model as the other raster
      * blocks; transmissivity == nullptr: k_rad_hour reads the map the meteo block holds (the caller asks meteo_produced first) */
     sf3d_error_t rad_alloc(const RadSetup& setup);

@@ -55,6 +55,7 @@
 #include "sf3d_localdetrend.inc"
 #include "sf3d_localproxies.inc"
 #include "sf3d_glocal.inc"
+#include "sf3d_multidetrend.inc"
 #include "sf3d_sink.inc"
 #include "sf3d_rad.inc"
 #include "sf3d_transmissivity.inc"

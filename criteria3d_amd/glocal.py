@@ -15,8 +15,8 @@ Four parts:
     an `arms` counter - the checkers of the CPU tests against the compiled-reference pin (tests/golden/glocal.npz).  Checkers, never a
     fallback.  `marquardt_unweighted` is the reference's unweighted text; the device runs the weighted text with every weight 1.
 
-With the caller stay lapse-rate codes, topographic distance inside an area, the meteo-grid variant, cross validation, output points and
-multipleDetrending without areas."""
+With the caller stay lapse-rate codes, topographic distance inside an area, the meteo-grid variant, cross validation and output points.
+multipleDetrending without areas is `multidetrend`."""
 from __future__ import annotations
 
 import ctypes as C

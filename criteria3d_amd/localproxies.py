@@ -14,7 +14,7 @@ Three parts:
     the reference's types and operation order - `marquardt_others` keeps the reference's P[k][j], which the kernel does not - the
     checkers of the CPU tests against the compiled-reference pin (tests/golden/localproxies.npz).  Checkers, never a fallback.
 
-With the caller stay lapse-rate codes, output points and multipleDetrending without localDetrending."""
+With the caller stay lapse-rate codes and output points.  multipleDetrending without localDetrending is `multidetrend`."""
 from __future__ import annotations
 
 import ctypes as C

@@ -17,7 +17,7 @@
  *
  * With the caller: the point list and its indices, the height's range (setMultipleDetrendingHeightTemperatureRange), delta and first
  * guesses as in sf3d_localdetrend.h, the weight maps (loadGlocalWeightMaps), lapse-rate codes (every station is primary), topographic
- * distance inside an area, the meteo-grid variant (areaCellsGrid), cross validation, output points, and multipleDetrending without areas.
+ * distance inside an area, the meteo-grid variant (areaCellsGrid), cross validation and output points.  multipleDetrending without areas, with its points, is sf3d_multidetrend.h.
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.  The block
  * belongs to the meteo block's raster: sf3d_meteo_initialize comes first, and sf3d_glocal_clean, sf3d_meteo_clean, a second

@@ -17,7 +17,7 @@
  * With the caller: the point list (quality control, checkAndPassDataToInterpolation); the parameter range after
  * setMultipleDetrendingHeightTemperatureRange (:1506-1553), parametersDelta = (max - min) / 800 (:1671) and the list of
  * calculateFirstGuessCombinations (:1556-1622) - criteria3d_amd/localdetrend.py restates the three; other proxies (sf3d_localproxies.h
- * is this block with every active proxy; sf3d_glocal.h is glocal detrending), lapse-rate codes (every station is primary), output points; and everything
+ * is this block with every active proxy; sf3d_glocal.h is glocal detrending, sf3d_multidetrend.h multiple detrending with neither), lapse-rate codes (every station is primary), output points; and everything
  * sf3d_meteo.h leaves with the caller.
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.  The block

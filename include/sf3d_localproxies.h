@@ -18,8 +18,8 @@
  * The values are the reference's to the bit (tests/golden/localproxies.npz: a pin of the compiled reference).
  *
  * With the caller: what sf3d_localdetrend.h leaves there except the other proxies - the point list, the height's range, delta and first
- * guesses, lapse-rate codes (every station is primary), output points - and multipleDetrending without
- * localDetrending.
+ * guesses, lapse-rate codes (every station is primary), output points.  multipleDetrending without localDetrending is
+ * sf3d_multidetrend.h.
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.  The block
  * belongs to the meteo block's raster: sf3d_meteo_initialize comes first, and sf3d_localproxies_clean, sf3d_meteo_clean, a second

@@ -15,7 +15,8 @@
  * regressions and detrendPoints (once per variable and hour, on N points): the calls take detrended values and the fitted slopes.  Also
  * multiple and local detrending, topographic distance, kriging, supplemental stations (every station is primary), the cross-validation
  * index and updateMinMaxRasterGrid: a settings struct that asks for one of them is refused (SF3D_PARAMETER_ERROR).  Topographic distance
- * has entry points of its own on this block's raster: sf3d_topodist.h.
+ * has entry points of its own on this block's raster: sf3d_topodist.h; so have multiple detrending with local detrending (sf3d_localdetrend.h,
+ * sf3d_localproxies.h), with glocal detrending (sf3d_glocal.h) and with neither (sf3d_multidetrend.h).
  *
  * This header extends the product library only (libsf3d_hip.so); it is not part of the soilFluxes3D drop-in ABI of sf3d.h.  The meteo
  * state belongs to the raster as the snow, crop and root maps do: it does not need sf3d_initialize and survives it, uses the device
